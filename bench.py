@@ -13,8 +13,10 @@ process touches the GPU; the parent only relays rank 0's line);  under `python -
 per GPU, RCCL ("nccl") only for the barrier / max-over-ranks timing.  `--force-dist` takes that same
 torch.distributed code path with world size 1 (so the RCCL branch runs on a one-GPU box too).
 
-Timing: exactly K steps per timed region, each region bracketed by barrier + synchronize, MAX over ranks;
-the region is repeated until >= 1 s has been timed and the MEDIAN region is reported (min / max beside it).
+Timing: exactly K steps (--steps) are timed, in one region bracketed by barrier + synchronize, MAX over ranks; `ms_per_step`
+is that region's time over K.  `--min-timed-s S` repeats the K-step region until >= S s have been timed and reports the MEDIAN
+region (min / max beside it).  `--dump-outputs DIR` writes the audio the last timed step produced (rank 0's channels) as .npy
+files after the timing: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 After the timing, at EVERY world size: a parity bit on every rank (a fresh bank, two steps from the zero state, >= 64
 channels of the rank's own shard against the oracle; the flags are gathered into `parity`), every rank's shader clock
 and socket power while all GPUs run the headline launch together (`extra.power_clock.per_gpu`), the name of the kernel
@@ -44,7 +46,8 @@ HBM_PEAK_GBS = 8000.0            # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E
 # the kernel this workload is expected to run (rocprofv3 --kernel-trace name); the line quotes what the library REPORTS it
 # launched (fmd_demod_last_kernel) and flags a difference
 KERNEL_EXPECTED = "fmd_tk::fmd_demod_tile_kernel<5, 2>"
-MIN_TIMED_S = 1.0                # repeat the K-step region until this much has been timed
+MIN_TIMED_S = 0.0                # 0: one region of exactly --steps timed steps; > 0: repeat the region until this much has been timed
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: at most this much in all (a fixed, seeded sample of channels beyond it)
 MAX_REGIONS = 4000
 PMC_SUMMARY = os.path.join("profiles", "r06_pmc_summary.json")
 BOUNDS = os.path.join("profiles", "r06_bounds.json")   # per-row pipe utilisation from the committed PMC passes (scripts/summarize_bounds.py)
@@ -669,6 +672,27 @@ def extra_power_clock(torch, dev_index, step, seconds=2.0):
     return res
 
 
+def dump_outputs(path, audio, lens, lo):
+    """--dump-outputs: what a caller of the timed path receives from one step -- every channel's audio (s16, as float32),
+    its length and its global channel id -- as DIR/audio.npy (the rows concatenated in channel order), DIR/audio_len.npy
+    and DIR/channel.npy.  Beyond DUMP_MAX_BYTES in all, a fixed, seeded sample of channels (same on every run)."""
+    import numpy as np
+    nch = len(lens)
+    per = 4 * lens.astype(np.int64) + 16                    # audio + length + channel id, bytes per channel
+    keep = np.arange(nch)
+    budget = DUMP_MAX_BYTES - 3 * 4096                       # the three .npy headers
+    if per.sum() > budget:
+        order = np.random.default_rng(0).permutation(nch)
+        keep = np.sort(order[:max(1, int(np.searchsorted(np.cumsum(per[order]), budget, side="right")))])
+    os.makedirs(path, exist_ok=True)
+    rows = [audio[c, :int(lens[c])].astype(np.float32) for c in keep]
+    np.save(os.path.join(path, "audio.npy"), np.concatenate(rows) if rows else np.zeros(0, np.float32))
+    np.save(os.path.join(path, "audio_len.npy"), lens[keep].astype(np.float64))
+    np.save(os.path.join(path, "channel.npy"), (keep + lo).astype(np.float64))
+    return {"dir": path, "files": ["audio.npy", "audio_len.npy", "channel.npy"], "channels": int(len(keep)), "of_channels": nch,
+            "sampled": bool(len(keep) < nch)}
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes (this process has not touched
     the GPU and never will), relay rank 0's JSON line, fail if any rank fails.  A rank that dies -- rank 0, which hosts
@@ -727,7 +751,11 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the side lines (extra.*), the per-GPU clock / power sample included")
     ap.add_argument("--power-only", action="store_true", help="of the side lines keep only extra.power_clock (every rank samples its own GPU)")
     ap.add_argument("--cpu-seconds", type=float, default=4.0, help="oracle time spent on the all-threads CPU baseline (rank 0); + 1 s + 2 s for the two single-thread figures")
-    ap.add_argument("--min-timed-s", type=float, default=MIN_TIMED_S, help="repeat the K-step region until this much has been timed")
+    ap.add_argument("--min-timed-s", type=float, default=MIN_TIMED_S,
+                    help="repeat the K-step region until this much has been timed (default 0: exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) to DIR/*.npy; reproducible run to run "
+                         "as long as the number of timed steps is (--min-timed-s 0)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for the barrier / max-over-ranks timing (nccl = RCCL); with gloo "
                          "ranks may share a GPU (launch-path check on a single-GPU box)")
@@ -838,6 +866,9 @@ def main():
     reps = min(MAX_REGIONS, max(1, int(math.ceil(1.3 * args.min_timed_s / regions[0][0]))))
     for _ in range(reps - 1):
         regions.append(timed_region())
+    dumped = None
+    if args.dump_outputs and rank == 0:                                     # the last timed step's audio, before anything else runs
+        dumped = dump_outputs(args.dump_outputs, out.cpu().numpy(), bank.last_out_len(), lo)
     walls = sorted(r[0] for r in regions)
     elapsed = walls[len(walls) // 2]                                        # median region
     own_med = sorted(r[1] for r in regions)[len(regions) // 2]
@@ -938,6 +969,7 @@ def main():
                        "torch_distributed": None if dist is None else {"backend": args.backend, "world_size": world,
                                                                       "collectives": "barrier per fence, all_reduce(MAX) per region, all_gather of the per-GPU rates"}},
             "timing": {"regions": len(regions), "steps_per_region": args.steps, "statistic": "median region, max over ranks",
+                       "timed_steps": len(regions) * args.steps,
                        "ms_per_step_min": round(walls[0] / args.steps * 1e3, 4),
                        "ms_per_step_max": round(walls[-1] / args.steps * 1e3, 4),
                        "timed_ms_total": round(sum(walls) * 1e3, 2)},
@@ -961,6 +993,8 @@ def main():
             sys.stderr.write("bench.py: the library launched %r, expected %r\n" % (launched, KERNEL_EXPECTED))
         if par is not None:
             res["parity"] = par
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if pc is not None:
             res["extra"] = {"power_clock": pc}
         if world == 1 and not args.no_extra and not args.power_only:
