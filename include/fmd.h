@@ -310,6 +310,51 @@ int fmd_firdemod_tiling(const fmd_firdemod *f, uint32_t *audio_per_tile, uint32_
 /* Name of the kernel this handle launches, as `rocprofv3 --kernel-trace` prints it (see fmd_demod_last_kernel). */
 int fmd_firdemod_kernel_name(const fmd_firdemod *f, char *name, size_t cap);
 
+/* ---- station bank: many FM stations out of one wideband stream --------------------------------------------- */
+/* NEW SURFACE (the reference demodulates ONE station per stream, the one offset tuning puts at -Fs/4, simple_fm.rs:194-195).
+ * A bank runs K digital down-converters per input stream -- mix by the station's offset, filter, decimate -- each followed by
+ * the reference's own fm_demod (:355-367) and low_pass_real (:408-426).  Definition (integers only; tests/stations_ref.py):
+ *   c[n]      = (b[2n] - 127) + j (b[2n+1] - 127)                 raw read_sync bytes, NO rotate_90 (the mixer tunes)
+ *   TAB[i]    = round(16384 cos(2 pi i / 1024)); cosq(p) = TAB[p >> 22], sinq(p) = TAB[((p >> 22) - 256) & 1023]
+ *   W[k][t]   = rnd(h[t] cosq(t inc_k)) + j rnd(-h[t] sinq(t inc_k)),  rnd(v) = (v + 8192) >> 14   (one real prototype h)
+ *   z[k][m]   = sum_{t < n_taps} W[k][t] c[decim m + t]               (output m comes with the call in which its last sample arrives)
+ *   y[k][m]   = (z * (cosq(psi) + j sinq(psi))) >> (14 + shift),  psi = m decim inc_k mod 2^32 (floor, per component, in i64)
+ * then fm_demod (f64 sample at the first output of every call, demod_pre carried) and low_pass_real per (stream, station), s16 out.
+ * With inc = 0 the taps are h, y = floor(z / 2^shift): fmd_firdemod on UNROTATED samples.  Feeding rot(B) -- the bytes rotate_90
+ * would make -- with h = 1...1, n_taps == decim, shift = 0 gives exactly fmd_demod(B).
+ * Domain: decim even, 2 ... 64; 1 <= n_taps <= 256; |h| <= 2047; 1 <= n_stations <= 32; any phase_inc; shift <= 24;
+ * ceil(256 * max_k sum_t (|Wr| + |Wi|) / 2^shift) <= 16384 (|y| <= 16384; <= 2048 selects the f32 discriminator, same results);
+ * rate_out >= rate_resample >= 1 (else FMD_ERR_BAD_RATES); nbytes % 8 == 0 (else FMD_ERR_BAD_LENGTH).  Everything else outside
+ * it is FMD_ERR_UNSUPPORTED, decided before a device is touched.  A call with fewer than 2 filter outputs returns
+ * FMD_ERR_TOO_SHORT and changes nothing.
+ * Layouts: iq [n_streams][nbytes], out [n_streams][n_stations][out_cap], phase_inc [n_streams][n_stations]; n_streams is
+ * dev->n_channels.  Stream lifetime and completion points: as fmd_firdemod_* (fmd_stations_check).  The f64 reports name the
+ * logical channel stream * n_stations + station. */
+typedef struct fmd_stations fmd_stations;
+/* floor((offset_hz * 2^32 + floor(capture_rate / 2)) / capture_rate) mod 2^32 in exact integers; needs 2 |offset_hz| <= capture_rate. */
+int fmd_stations_phase_inc(int32_t offset_hz, uint32_t capture_rate, uint32_t *inc);
+/* The NCO table TAB above, 1024 entries. */
+int fmd_stations_nco_table(int16_t *table);
+int fmd_stations_new(const int16_t *taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t *phase_inc,
+                     uint32_t n_stations, uint32_t rate_out, uint32_t rate_resample, const fmd_device_config *dev,
+                     fmd_stations **out);
+void fmd_stations_free(fmd_stations *b);
+int fmd_stations_reset(fmd_stations *b);
+/* Audio samples one call of nbytes can produce per (stream, station) (upper bound); 0 for decim or rate_out 0. */
+size_t fmd_stations_out_cap(uint32_t decim, uint32_t rate_out, uint32_t rate_resample, size_t nbytes);
+/* HOST buffers; out_len [n_streams * n_stations]. */
+int fmd_stations_demodulate_batch(fmd_stations *b, const uint8_t *iq, size_t nbytes, int16_t *out, size_t out_cap,
+                                  size_t *out_len);
+/* DEVICE buffers, enqueued on `stream` without synchronising; *out_len_each = audio samples per (stream, station). */
+int fmd_stations_demodulate_device(fmd_stations *b, const void *d_iq, size_t nbytes, void *d_out, size_t out_cap,
+                                   size_t *out_len_each, void *stream);
+int fmd_stations_check(fmd_stations *b);
+/* demod_pre, now_lpr, prev_lpr_index of one (stream, station); prev_index / lp_now are 0. */
+int fmd_stations_get_state(fmd_stations *b, uint32_t stream, uint32_t station, fmd_demod_state *state);
+int fmd_stations_f64_stats(const fmd_stations *b, uint64_t *guarded, uint64_t *patched);
+/* Name of the kernel this bank launches, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_stations_kernel_name(const fmd_stations *b, char *name, size_t cap);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

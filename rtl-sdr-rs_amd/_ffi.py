@@ -113,6 +113,19 @@ PROTOTYPES = {
     "fmd_firdemod_tiling": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fmd_firdemod_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_fir_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_stations_phase_inc": (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fmd_stations_nco_table": (C.c_int, [_i16p]),
+    "fmd_stations_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32,
+                                   C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_stations_free": (None, [_vp]),
+    "fmd_stations_reset": (C.c_int, [_vp]),
+    "fmd_stations_out_cap": (_sz, [C.c_uint32, C.c_uint32, C.c_uint32, _sz]),
+    "fmd_stations_demodulate_batch": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "fmd_stations_demodulate_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_stations_check": (C.c_int, [_vp]),
+    "fmd_stations_get_state": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(DemodState)]),
+    "fmd_stations_f64_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fmd_stations_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

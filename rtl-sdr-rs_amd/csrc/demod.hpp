@@ -10,6 +10,7 @@
 // fm::Error carrying the fmd_status.  Header-only; link with libfmd_hip.so.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -183,6 +184,49 @@ public:
 private:
     fmd_rtltcp* h_ = nullptr;
     uint32_t tuner_type_ = 0, gain_count_ = 0;
+};
+
+// Station bank (fmd_stations_*): `phase_incs` is [n_streams][n_stations]; demodulate() takes [n_streams][nbytes] and
+// returns audio [n_streams * n_stations] (row stream * n_stations + station).
+inline uint32_t phase_inc(int32_t offset_hz, uint32_t capture_rate)
+{
+    uint32_t inc = 0;
+    check(fmd_stations_phase_inc(offset_hz, capture_rate, &inc));
+    return inc;
+}
+
+class StationBank {
+public:
+    StationBank(const std::vector<int16_t>& taps, uint32_t decim, uint32_t shift, const std::vector<uint32_t>& phase_incs,
+                uint32_t n_streams, uint32_t rate_out, uint32_t rate_resample, int32_t device_id = -1)
+        : decim_(decim), rate_out_(rate_out), rate_resample_(rate_resample), n_streams_(n_streams),
+          n_stations_(n_streams ? (uint32_t)(phase_incs.size() / n_streams) : 0u)
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_stations_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, rate_out,
+                               rate_resample, &dev, &h_));
+    }
+    ~StationBank() { fmd_stations_free(h_); }
+    StationBank(const StationBank&) = delete;
+    StationBank& operator=(const StationBank&) = delete;
+
+    std::vector<std::vector<int16_t>> demodulate(const uint8_t* iq, size_t nbytes)
+    {
+        const size_t cap = std::max<size_t>(1, fmd_stations_out_cap(decim_, rate_out_, rate_resample_, nbytes));
+        const size_t rows = (size_t)n_streams_ * n_stations_;
+        std::vector<int16_t> out(cap * rows);
+        std::vector<size_t> lens(rows);
+        check(fmd_stations_demodulate_batch(h_, iq, nbytes, out.data(), cap, lens.data()));
+        std::vector<std::vector<int16_t>> res(rows);
+        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + r * cap, out.begin() + r * cap + lens[r]);
+        return res;
+    }
+    void reset() { check(fmd_stations_reset(h_)); }
+    uint32_t n_stations() const { return n_stations_; }
+
+private:
+    uint32_t decim_, rate_out_, rate_resample_, n_streams_, n_stations_;
+    fmd_stations* h_ = nullptr;
 };
 
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.

@@ -16,6 +16,10 @@
 // as rtl_tcp commands, DEFAULT_BUF_LENGTH blocks come back through fm::RtlTcpSource::read_sync, a short read ends the run
 // with the example's "samples lost" message (:122-125).
 //
+// Station bank, -S off1,off2,...: K stations at these offsets (Hz from the capture's centre) out of ONE capture file recorded at
+// the capture rate optimal_settings derives from -s (downsample x rate); the reference's own boxcar (h = 1...1, n_taps =
+// downsample) is the prototype filter, mixed to each station by fmd_stations_*; audio of station k goes to <prefix>.<k>.s16.
+//
 // EOF policy (the reference ignores the read count and never terminates at EOF): only COMPLETE
 // blocks are demodulated; a trailing partial block is dropped with a note on stderr.  Logging goes to stderr
 // because stdout carries audio (:37-38).
@@ -168,6 +172,54 @@ static int run_rtl_tcp(const char* hostport, uint32_t freq, uint32_t rate, uint3
     return 0;
 }
 
+// -S: one capture, K stations (fmd_stations_*)
+static int run_stations(const char* path, const char* list, const char* prefix, uint32_t freq, uint32_t rate, uint32_t resample)
+{
+    FILE* in = strcmp(path, "-") ? fopen(path, "rb") : stdin;
+    if (!in) { perror(path); return 2; }
+    std::vector<FILE*> out;
+    int rc = 0;
+    try {
+        const auto settings = fm::optimal_settings(freq, rate, resample);
+        const fm::DemodConfig& dc = settings.second;
+        const uint32_t capture = settings.first.capture_rate, D = dc.downsample;
+        std::vector<uint32_t> incs;
+        for (const char* p = list; *p;) {
+            char* end = nullptr;
+            const long off = strtol(p, &end, 10);
+            if (end == p) { fprintf(stderr, "bad -S list: %s\n", list); return 2; }
+            incs.push_back(fm::phase_inc((int32_t)off, capture));
+            p = *end == ',' ? end + 1 : end;
+        }
+        uint32_t shift = 0;                                  // |W| <= 1 for a boxcar: sum(|Wr| + |Wi|) <= 2 n_taps
+        while ((512ull * D + (1ull << shift) - 1) >> shift > 16384ull) ++shift;
+        fm::StationBank bank(std::vector<int16_t>(D, 1), D, shift, incs, 1, dc.rate_out, dc.rate_resample);
+        fprintf(stderr, "capture_rate: %u, %zu stations, decimate %u\n", capture, incs.size(), D);
+        for (size_t k = 0; k < incs.size(); ++k) {
+            const std::string name = std::string(prefix) + "." + std::to_string(k) + ".s16";
+            out.push_back(fopen(name.c_str(), "wb"));
+            if (!out.back()) { perror(name.c_str()); rc = 2; break; }
+        }
+        std::vector<uint8_t> buf(fm::DEFAULT_BUF_LENGTH);
+        while (!rc) {
+            size_t fill = 0, n;
+            while (fill < buf.size() && (n = fread(buf.data() + fill, 1, buf.size() - fill, in)) > 0) fill += n;
+            if (fill < buf.size()) {
+                if (fill) fprintf(stderr, "dropped %zu trailing bytes (not a complete %zu-byte block)\n", fill, buf.size());
+                break;
+            }
+            const auto audio = bank.demodulate(buf.data(), buf.size());
+            for (size_t k = 0; k < out.size(); ++k) fm::output(audio[k], out[k]);
+        }
+    } catch (const fm::Error& e) {
+        fprintf(stderr, "error: %s\n", e.what());
+        rc = 1;
+    }
+    for (FILE* f : out) if (f) fclose(f);
+    if (in != stdin) fclose(in);
+    return rc;
+}
+
 int main(int argc, char** argv)
 {
     uint32_t rate = 170000, resample = 32000, freq = 94900000;
@@ -176,6 +228,7 @@ int main(int argc, char** argv)
     const char* path = nullptr;
     const char* prefix = "audio";
     const char* rtl_tcp = nullptr;                           // -t host:port: live mode over rtl_tcp
+    const char* stations = nullptr;                          // -S off1,off2,...: station bank over one capture
     size_t max_blocks = 0;                                   // -n: stop after this many blocks (live mode; 0 = until the stream ends)
     std::vector<const char*> paths;
     for (int i = 1; i < argc; ++i) {
@@ -185,17 +238,21 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) prefix = argv[++i];
         else if (!strcmp(argv[i], "-g") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-t") && i + 1 < argc) rtl_tcp = argv[++i];
+        else if (!strcmp(argv[i], "-S") && i + 1 < argc) stations = argv[++i];
         else if (!strcmp(argv[i], "-n") && i + 1 < argc) max_blocks = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-b") && i + 1 < argc) { per_launch = strtoul(argv[++i], nullptr, 10); if (!per_launch) per_launch = 1; }
         else if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) {
             fprintf(stderr, "usage: %s [-f freq_hz] [-s sample_rate_hz] [-r resample_hz] [-b blocks_per_launch] <capture.bin | ->\n"
                             "       %s [-s ...] [-r ...] [-o prefix] [-g n_gpus] <a.bin> <b.bin> ...   (one channel per file)\n"
-                            "       %s [-f freq_hz] [-s ...] [-r ...] [-n blocks] -t host:port            (live: IQ from an rtl_tcp server)\n", argv[0], argv[0], argv[0]);
+                            "       %s [-f freq_hz] [-s ...] [-r ...] [-n blocks] -t host:port            (live: IQ from an rtl_tcp server)\n"
+                            "       %s [-s ...] [-r ...] [-o prefix] -S off1,off2,... <capture.bin | ->   (stations at these offsets in Hz)\n",
+                    argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else paths.push_back(argv[i]);
     }
     if (rtl_tcp) return run_rtl_tcp(rtl_tcp, freq, rate, resample, max_blocks);
     if (paths.empty()) { fprintf(stderr, "missing input file (use - for stdin)\n"); return 2; }
+    if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample);
     if (paths.size() > 1 && gpus > 0) return run_sink(paths, prefix, freq, rate, resample, gpus);
     if (paths.size() > 1) return run_bank(paths, prefix, freq, rate, resample);
     path = paths[0];

@@ -76,6 +76,11 @@ pub struct fmd_firdemod {
 }
 
 #[repr(C)]
+pub struct fmd_stations {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
 }
@@ -139,6 +144,18 @@ extern "C" {
     pub fn fmd_firdemod_tiling(f: *const fmd_firdemod, audio_per_tile: *mut u32, lds_bytes: *mut u32) -> c_int;
     pub fn fmd_firdemod_kernel_name(f: *const fmd_firdemod, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_fir_kernel_name(f: *const fmd_fir, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_stations_phase_inc(offset_hz: i32, capture_rate: u32, inc: *mut u32) -> c_int;
+    pub fn fmd_stations_nco_table(table: *mut i16) -> c_int;
+    pub fn fmd_stations_new(taps: *const i16, n_taps: u32, decim: u32, shift: u32, phase_inc: *const u32, n_stations: u32, rate_out: u32, rate_resample: u32, dev: *const DeviceConfig, out: *mut *mut fmd_stations) -> c_int;
+    pub fn fmd_stations_free(b: *mut fmd_stations);
+    pub fn fmd_stations_reset(b: *mut fmd_stations) -> c_int;
+    pub fn fmd_stations_out_cap(decim: u32, rate_out: u32, rate_resample: u32, nbytes: usize) -> usize;
+    pub fn fmd_stations_demodulate_batch(b: *mut fmd_stations, iq: *const u8, nbytes: usize, out: *mut i16, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn fmd_stations_demodulate_device(b: *mut fmd_stations, d_iq: *const c_void, nbytes: usize, d_out: *mut c_void, out_cap: usize, out_len_each: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_stations_check(b: *mut fmd_stations) -> c_int;
+    pub fn fmd_stations_get_state(b: *mut fmd_stations, stream: u32, station: u32, state: *mut DemodState) -> c_int;
+    pub fn fmd_stations_f64_stats(b: *const fmd_stations, guarded: *mut u64, patched: *mut u64) -> c_int;
+    pub fn fmd_stations_kernel_name(b: *const fmd_stations, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
@@ -293,6 +310,69 @@ impl DemodBank {
 impl Drop for DemodBank {
     fn drop(&mut self) {
         unsafe { fmd_demod_free(self.handle) }
+    }
+}
+
+/// Station bank (`fmd_stations_*`): `phase_incs.len() / n_streams` FM stations demodulated out of each of `n_streams` wideband
+/// streams -- mix by the station's offset, filter with `taps`, decimate by `decim`, then the reference's `fm_demod` and
+/// `low_pass_real` per station (include/fmd.h).
+pub struct StationBank {
+    handle: *mut fmd_stations,
+    pub decim: u32,
+    pub rate_out: u32,
+    pub rate_resample: u32,
+    pub n_streams: usize,
+    pub n_stations: usize,
+}
+
+unsafe impl Send for StationBank {}
+
+/// Phase increment (Q32 cycles per input sample) of a station `offset_hz` away from the capture's centre.
+pub fn phase_inc(offset_hz: i32, capture_rate: u32) -> Result<u32> {
+    let mut inc = 0u32;
+    check(unsafe { fmd_stations_phase_inc(offset_hz, capture_rate, &mut inc) })?;
+    Ok(inc)
+}
+
+impl StationBank {
+    /// `phase_incs` is `[n_streams][n_stations]`.
+    pub fn new(taps: &[i16], decim: u32, shift: u32, phase_incs: &[u32], n_streams: usize, rate_out: u32, rate_resample: u32,
+               device_id: i32) -> Result<Self> {
+        if n_streams == 0 || phase_incs.len() % n_streams != 0 {
+            return Err(FmdError { status: -1, message: "phase_incs must hold n_streams equal rows".into() });
+        }
+        let n_stations = phase_incs.len() / n_streams;
+        let dev = DeviceConfig { n_channels: n_streams as u32, device_id, flags: 0 };
+        let mut handle: *mut fmd_stations = std::ptr::null_mut();
+        check(unsafe {
+            fmd_stations_new(taps.as_ptr(), taps.len() as u32, decim, shift, phase_incs.as_ptr(), n_stations as u32, rate_out,
+                             rate_resample, &dev, &mut handle)
+        })?;
+        Ok(StationBank { handle, decim, rate_out, rate_resample, n_streams, n_stations })
+    }
+
+    /// `iq` is `[n_streams][nbytes]`; returns audio `[n_streams][n_stations]`.
+    pub fn demodulate(&mut self, iq: &[u8]) -> Result<Vec<Vec<Vec<i16>>>> {
+        assert!(iq.len() % self.n_streams == 0, "iq must hold n_streams equal-sized buffers");
+        let nbytes = iq.len() / self.n_streams;
+        let cap = unsafe { fmd_stations_out_cap(self.decim, self.rate_out, self.rate_resample, nbytes) }.max(1);
+        let rows = self.n_streams * self.n_stations;
+        let mut out = vec![0i16; cap * rows];
+        let mut lens = vec![0usize; rows];
+        check(unsafe { fmd_stations_demodulate_batch(self.handle, iq.as_ptr(), nbytes, out.as_mut_ptr(), cap, lens.as_mut_ptr()) })?;
+        Ok((0..self.n_streams)
+            .map(|s| (0..self.n_stations).map(|k| { let r = s * self.n_stations + k; out[r * cap..r * cap + lens[r]].to_vec() }).collect())
+            .collect())
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { fmd_stations_reset(self.handle) })
+    }
+}
+
+impl Drop for StationBank {
+    fn drop(&mut self) {
+        unsafe { fmd_stations_free(self.handle) }
     }
 }
 
