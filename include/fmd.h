@@ -355,6 +355,48 @@ int fmd_stations_f64_stats(const fmd_stations *b, uint64_t *guarded, uint64_t *p
 /* Name of the kernel this bank launches, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_stations_kernel_name(const fmd_stations *b, char *name, size_t cap);
 
+/* ---- power spectrum: where the stations are ------------------------------------------------------------------ */
+/* NEW SURFACE (rtl_power's job in the rtl-sdr ecosystem; the reference has none).  The integrated power of N DFT bins of every
+ * stream, to find the offsets a station bank is then tuned to.  A bin is a station-bank filter (the taps and the NCO table above)
+ * whose decimation is the frame hop.  Definition (integers only; tests/spectrum_ref.py):
+ *   c[n]      = (b[2n] - 127) + j (b[2n+1] - 127)                 raw read_sync bytes, NO rotate_90
+ *   N         = n_bins in {16, 32, 64, 128, 256};  hop a multiple of 8, 8 <= hop <= N (frame f starts at byte 2 hop f)
+ *   w[0..N)   = int16 window, |w| <= 2047;  inc_k = k 2^32 / N
+ *   W[k][t]   = rnd(w[t] cosq(t inc_k)) + j rnd(-w[t] sinq(t inc_k))     (the station bank's taps: |W| <= 2047; one i8 digit
+ *               when every |W| <= 127, two otherwise -- fmd_spectrum_tap_digits)
+ *   F         = floor((nbytes / 2 - N) / hop) + 1 frames per call, from sample 0 of the call; trailing samples that do not fill
+ *               a frame are ignored; NO state is carried between calls
+ *   z[k][f]   = sum_{t < N} W[k][t] c[f hop + t]                    (exact: |z| < 2^31)
+ *   p[k][f]   = (zr^2 + zi^2) >> shift                              (in 64 bits: zr^2 + zi^2 < 2^63; 0 <= shift <= 63)
+ *   P[s][k]   = sum_f p[k][f]  as a u64 modulo 2^64, natural DFT order: bin k lies (k < N/2 ? k : k - N) capture_rate / N Hz
+ *               from the centre (a tone at +f0 lands in bin f0 N / capture_rate: the sign convention of fmd_stations_phase_inc).
+ * Domain errors are refused before a device is touched: nbytes % 8 != 0 -> FMD_ERR_BAD_LENGTH; fewer than one frame ->
+ * FMD_ERR_TOO_SHORT and nothing is written; a bad n_bins, hop, window magnitude or shift > 63 -> FMD_ERR_UNSUPPORTED; NULL
+ * pointers or zero streams -> FMD_ERR_INVALID_ARG.
+ * Layouts: iq [n_streams][nbytes], power [n_streams][n_bins] u64; n_streams is dev->n_channels.  Stream lifetime and completion
+ * points: as fmd_stations_* (fmd_spectrum_check). */
+typedef struct fmd_spectrum fmd_spectrum;
+/* Exact integer Hann window: w[n] = (amplitude (16384 - TAB[(n 1024 / N) & 1023]) + 16384) >> 15, 1 <= amplitude <= 2047
+ * (amplitude <= 127 gives the one-digit form).  `window` holds n_bins entries. */
+int fmd_spectrum_hann(uint32_t n_bins, uint32_t amplitude, int16_t *window);
+/* inc_k = bin 2^32 / n_bins: the fmd_stations_new phase_inc that tunes a station bank to the centre of `bin`. */
+int fmd_spectrum_bin_inc(uint32_t bin, uint32_t n_bins, uint32_t *inc);
+/* F above; 0 for fewer than one frame or a bad n_bins / hop. */
+size_t fmd_spectrum_frames(uint32_t n_bins, uint32_t hop, size_t nbytes);
+int fmd_spectrum_new(const int16_t *window, uint32_t n_bins, uint32_t hop, uint32_t shift, const fmd_device_config *dev,
+                     fmd_spectrum **out);
+void fmd_spectrum_free(fmd_spectrum *s);
+/* HOST buffers; power [n_streams][n_bins] is overwritten. */
+int fmd_spectrum_power_batch(fmd_spectrum *s, const uint8_t *iq, size_t nbytes, uint64_t *power);
+/* DEVICE buffers (d_iq 4-byte aligned, d_power 8-byte aligned), enqueued on `stream` without synchronising.  accumulate = 0
+ * zeroes d_power on `stream` first; accumulate = 1 adds this call's power to it (integrating a long capture). */
+int fmd_spectrum_power_device(fmd_spectrum *s, const void *d_iq, size_t nbytes, void *d_power, int accumulate, void *stream);
+int fmd_spectrum_check(fmd_spectrum *s);
+/* 1 or 2: the i8 digits per tap on the matrix cores. */
+int fmd_spectrum_tap_digits(const fmd_spectrum *s);
+/* Name of the kernel this handle launches, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_spectrum_kernel_name(const fmd_spectrum *s, char *name, size_t cap);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

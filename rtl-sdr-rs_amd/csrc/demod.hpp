@@ -229,6 +229,50 @@ private:
     fmd_stations* h_ = nullptr;
 };
 
+// Power spectrum (fmd_spectrum_*): power() takes [n_streams][nbytes] and returns u64 [n_streams][n_bins] in natural DFT order.
+inline std::vector<int16_t> hann_window(uint32_t n_bins, uint32_t amplitude = 2047)
+{
+    std::vector<int16_t> w(n_bins);
+    check(fmd_spectrum_hann(n_bins, amplitude, w.data()));
+    return w;
+}
+
+class Spectrum {
+public:
+    Spectrum(const std::vector<int16_t>& window, uint32_t hop, uint32_t shift, uint32_t n_streams = 1, int32_t device_id = -1)
+        : n_bins_((uint32_t)window.size()), n_streams_(n_streams)
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_spectrum_new(window.data(), n_bins_, hop, shift, &dev, &h_));
+    }
+    ~Spectrum() { fmd_spectrum_free(h_); }
+    Spectrum(const Spectrum&) = delete;
+    Spectrum& operator=(const Spectrum&) = delete;
+
+    std::vector<uint64_t> power(const uint8_t* iq, size_t nbytes)
+    {
+        std::vector<uint64_t> p((size_t)n_streams_ * n_bins_);
+        check(fmd_spectrum_power_batch(h_, iq, nbytes, p.data()));
+        return p;
+    }
+    uint32_t bin_inc(uint32_t bin) const
+    {
+        uint32_t inc = 0;
+        check(fmd_spectrum_bin_inc(bin, n_bins_, &inc));
+        return inc;
+    }
+    // offset of bin k from the capture's centre, in Hz
+    double bin_offset_hz(uint32_t k, double capture_rate) const
+    {
+        return (k < n_bins_ / 2 ? (double)k : (double)k - n_bins_) * capture_rate / n_bins_;
+    }
+    uint32_t n_bins() const { return n_bins_; }
+
+private:
+    uint32_t n_bins_, n_streams_;
+    fmd_spectrum* h_ = nullptr;
+};
+
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.
 inline void output(const std::vector<int16_t>& buf, FILE* f = stdout)
 {

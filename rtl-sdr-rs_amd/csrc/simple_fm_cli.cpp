@@ -20,6 +20,10 @@
 // the capture rate optimal_settings derives from -s (downsample x rate); the reference's own boxcar (h = 1...1, n_taps =
 // downsample) is the prototype filter, mixed to each station by fmd_stations_*; audio of station k goes to <prefix>.<k>.s16.
 //
+// Power spectrum, -P N [-H hop]: the N-bin power spectrum (fmd_spectrum_*, integer Hann window of amplitude 2047, shift 16) of
+// ONE capture file whose sample rate is -s, integrated over the file's complete blocks; one line per bin in frequency order,
+// "offset_hz power" with the exact u64 power -- the offsets are where the stations are (-S).
+//
 // EOF policy (the reference ignores the read count and never terminates at EOF): only COMPLETE
 // blocks are demodulated; a trailing partial block is dropped with a note on stderr.  Logging goes to stderr
 // because stdout carries audio (:37-38).
@@ -220,6 +224,41 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
     return rc;
 }
 
+// -P: one capture, its power spectrum (fmd_spectrum_*)
+static int run_power(const char* path, uint32_t n_bins, uint32_t hop, uint32_t rate)
+{
+    FILE* in = strcmp(path, "-") ? fopen(path, "rb") : stdin;
+    if (!in) { perror(path); return 2; }
+    int rc = 0;
+    try {
+        fm::Spectrum sp(fm::hann_window(n_bins), hop ? hop : n_bins, 16);
+        std::vector<uint64_t> total(n_bins, 0);
+        std::vector<uint8_t> buf(fm::DEFAULT_BUF_LENGTH);
+        size_t blocks = 0;
+        for (;;) {
+            size_t fill = 0, n;
+            while (fill < buf.size() && (n = fread(buf.data() + fill, 1, buf.size() - fill, in)) > 0) fill += n;
+            if (fill < buf.size()) {
+                if (fill) fprintf(stderr, "dropped %zu trailing bytes (not a complete %zu-byte block)\n", fill, buf.size());
+                break;
+            }
+            const std::vector<uint64_t> p = sp.power(buf.data(), buf.size());
+            for (uint32_t k = 0; k < n_bins; ++k) total[k] += p[k];          // modulo 2^64, as the device path accumulates
+            ++blocks;
+        }
+        fprintf(stderr, "%zu blocks, %u bins of %.1f Hz\n", blocks, n_bins, (double)rate / n_bins);
+        for (uint32_t i = 0; i < n_bins; ++i) {
+            const uint32_t k = (i + n_bins / 2) % n_bins;                    // frequency order: -N/2 ... N/2 - 1
+            printf("%.3f %llu\n", sp.bin_offset_hz(k, rate), (unsigned long long)total[k]);
+        }
+    } catch (const fm::Error& e) {
+        fprintf(stderr, "error: %s\n", e.what());
+        rc = 1;
+    }
+    if (in != stdin) fclose(in);
+    return rc;
+}
+
 int main(int argc, char** argv)
 {
     uint32_t rate = 170000, resample = 32000, freq = 94900000;
@@ -229,6 +268,7 @@ int main(int argc, char** argv)
     const char* prefix = "audio";
     const char* rtl_tcp = nullptr;                           // -t host:port: live mode over rtl_tcp
     const char* stations = nullptr;                          // -S off1,off2,...: station bank over one capture
+    uint32_t power_bins = 0, power_hop = 0;                  // -P N [-H hop]: power spectrum of one capture
     size_t max_blocks = 0;                                   // -n: stop after this many blocks (live mode; 0 = until the stream ends)
     std::vector<const char*> paths;
     for (int i = 1; i < argc; ++i) {
@@ -239,19 +279,23 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-g") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-t") && i + 1 < argc) rtl_tcp = argv[++i];
         else if (!strcmp(argv[i], "-S") && i + 1 < argc) stations = argv[++i];
+        else if (!strcmp(argv[i], "-P") && i + 1 < argc) power_bins = strtoul(argv[++i], nullptr, 10);
+        else if (!strcmp(argv[i], "-H") && i + 1 < argc) power_hop = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-n") && i + 1 < argc) max_blocks = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-b") && i + 1 < argc) { per_launch = strtoul(argv[++i], nullptr, 10); if (!per_launch) per_launch = 1; }
         else if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) {
             fprintf(stderr, "usage: %s [-f freq_hz] [-s sample_rate_hz] [-r resample_hz] [-b blocks_per_launch] <capture.bin | ->\n"
                             "       %s [-s ...] [-r ...] [-o prefix] [-g n_gpus] <a.bin> <b.bin> ...   (one channel per file)\n"
                             "       %s [-f freq_hz] [-s ...] [-r ...] [-n blocks] -t host:port            (live: IQ from an rtl_tcp server)\n"
-                            "       %s [-s ...] [-r ...] [-o prefix] -S off1,off2,... <capture.bin | ->   (stations at these offsets in Hz)\n",
-                    argv[0], argv[0], argv[0], argv[0]);
+                            "       %s [-s ...] [-r ...] [-o prefix] -S off1,off2,... <capture.bin | ->   (stations at these offsets in Hz)\n"
+                            "       %s -s capture_rate_hz -P n_bins [-H hop] <capture.bin | ->       (power spectrum: offset_hz power per bin)\n",
+                    argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else paths.push_back(argv[i]);
     }
     if (rtl_tcp) return run_rtl_tcp(rtl_tcp, freq, rate, resample, max_blocks);
     if (paths.empty()) { fprintf(stderr, "missing input file (use - for stdin)\n"); return 2; }
+    if (power_bins) return run_power(paths[0], power_bins, power_hop, rate);
     if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample);
     if (paths.size() > 1 && gpus > 0) return run_sink(paths, prefix, freq, rate, resample, gpus);
     if (paths.size() > 1) return run_bank(paths, prefix, freq, rate, resample);

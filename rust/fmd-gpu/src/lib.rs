@@ -81,6 +81,11 @@ pub struct fmd_stations {
 }
 
 #[repr(C)]
+pub struct fmd_spectrum {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
 }
@@ -156,6 +161,16 @@ extern "C" {
     pub fn fmd_stations_get_state(b: *mut fmd_stations, stream: u32, station: u32, state: *mut DemodState) -> c_int;
     pub fn fmd_stations_f64_stats(b: *const fmd_stations, guarded: *mut u64, patched: *mut u64) -> c_int;
     pub fn fmd_stations_kernel_name(b: *const fmd_stations, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_spectrum_hann(n_bins: u32, amplitude: u32, window: *mut i16) -> c_int;
+    pub fn fmd_spectrum_bin_inc(bin: u32, n_bins: u32, inc: *mut u32) -> c_int;
+    pub fn fmd_spectrum_frames(n_bins: u32, hop: u32, nbytes: usize) -> usize;
+    pub fn fmd_spectrum_new(window: *const i16, n_bins: u32, hop: u32, shift: u32, dev: *const DeviceConfig, out: *mut *mut fmd_spectrum) -> c_int;
+    pub fn fmd_spectrum_free(s: *mut fmd_spectrum);
+    pub fn fmd_spectrum_power_batch(s: *mut fmd_spectrum, iq: *const u8, nbytes: usize, power: *mut u64) -> c_int;
+    pub fn fmd_spectrum_power_device(s: *mut fmd_spectrum, d_iq: *const c_void, nbytes: usize, d_power: *mut c_void, accumulate: c_int, stream: *mut c_void) -> c_int;
+    pub fn fmd_spectrum_check(s: *mut fmd_spectrum) -> c_int;
+    pub fn fmd_spectrum_tap_digits(s: *const fmd_spectrum) -> c_int;
+    pub fn fmd_spectrum_kernel_name(s: *const fmd_spectrum, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
@@ -373,6 +388,53 @@ impl StationBank {
 impl Drop for StationBank {
     fn drop(&mut self) {
         unsafe { fmd_stations_free(self.handle) }
+    }
+}
+
+/// Power spectrum (`fmd_spectrum_*`): the integrated power of `n_bins` DFT bins of each of `n_streams` streams, u64 in natural
+/// DFT order (include/fmd.h).
+pub struct Spectrum {
+    handle: *mut fmd_spectrum,
+    pub n_bins: u32,
+    pub n_streams: usize,
+}
+
+unsafe impl Send for Spectrum {}
+
+/// The library's exact integer Hann window (`amplitude` <= 127: one i8 digit per tap).
+pub fn hann_window(n_bins: u32, amplitude: u32) -> Result<Vec<i16>> {
+    let mut w = vec![0i16; n_bins as usize];
+    check(unsafe { fmd_spectrum_hann(n_bins, amplitude, w.as_mut_ptr()) })?;
+    Ok(w)
+}
+
+impl Spectrum {
+    pub fn new(window: &[i16], hop: u32, shift: u32, n_streams: usize, device_id: i32) -> Result<Self> {
+        let dev = DeviceConfig { n_channels: n_streams as u32, device_id, flags: 0 };
+        let mut handle: *mut fmd_spectrum = std::ptr::null_mut();
+        check(unsafe { fmd_spectrum_new(window.as_ptr(), window.len() as u32, hop, shift, &dev, &mut handle) })?;
+        Ok(Spectrum { handle, n_bins: window.len() as u32, n_streams })
+    }
+
+    /// `iq` is `[n_streams][nbytes]`; returns `[n_streams][n_bins]`.
+    pub fn power(&mut self, iq: &[u8]) -> Result<Vec<Vec<u64>>> {
+        assert!(iq.len() % self.n_streams == 0, "iq must hold n_streams equal-sized buffers");
+        let mut p = vec![0u64; self.n_streams * self.n_bins as usize];
+        check(unsafe { fmd_spectrum_power_batch(self.handle, iq.as_ptr(), iq.len() / self.n_streams, p.as_mut_ptr()) })?;
+        Ok(p.chunks(self.n_bins as usize).map(|c| c.to_vec()).collect())
+    }
+
+    /// The `StationBank` phase increment that tunes to the centre of `bin`.
+    pub fn bin_inc(&self, bin: u32) -> Result<u32> {
+        let mut inc = 0u32;
+        check(unsafe { fmd_spectrum_bin_inc(bin, self.n_bins, &mut inc) })?;
+        Ok(inc)
+    }
+}
+
+impl Drop for Spectrum {
+    fn drop(&mut self) {
+        unsafe { fmd_spectrum_free(self.handle) }
     }
 }
 
