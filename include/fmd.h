@@ -324,7 +324,11 @@ int fmd_firdemod_kernel_name(const fmd_firdemod *f, char *name, size_t cap);
  * would make -- with h = 1...1, n_taps == decim, shift = 0 gives exactly fmd_demod(B).
  * Domain: decim even, 2 ... 64; 1 <= n_taps <= 256; |h| <= 2047; 1 <= n_stations <= 32; any phase_inc; shift <= 24;
  * ceil(256 * max_k sum_t (|Wr| + |Wi|) / 2^shift) <= 16384 (|y| <= 16384; <= 2048 selects the f32 discriminator, same results);
- * rate_out >= rate_resample >= 1 (else FMD_ERR_BAD_RATES); nbytes % 8 == 0 (else FMD_ERR_BAD_LENGTH).  Everything else outside
+ * rate_out >= rate_resample >= 1 (else FMD_ERR_BAD_RATES); nbytes % 8 == 0 (else FMD_ERR_BAD_LENGTH).  Rates, with g = gcd(rate_out,
+ * rate_resample) and c = ceil(rate_out / rate_resample): rate_out / g <= 2^24, 3 rate_resample / g < 2^24, and one audio sample must
+ * fit a tile -- 2c + 3 <= 256 filter outputs (c <= 126) in raw + 2048 + 4 n_stations (2c + 3) + 24 <= 65536 bytes of LDS, where
+ * raw = roundup16(max(12 + 6 decim + 8 decim (16 ceil((2c + 3) / 64) - 1) + 64 ceil((12 + 2 n_taps) / 64), 12 + 2 decim (2c + 2) +
+ * 2 n_taps + 15)).  So c <= 116 fits every shape, c > 126 none (decim 2 from 2.4 Msps to 8 kHz: c = 150).  Everything else outside
  * it is FMD_ERR_UNSUPPORTED, decided before a device is touched.  A call with fewer than 2 filter outputs returns
  * FMD_ERR_TOO_SHORT and changes nothing.
  * Layouts: iq [n_streams][nbytes], out [n_streams][n_stations][out_cap], phase_inc [n_streams][n_stations]; n_streams is

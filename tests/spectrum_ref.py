@@ -52,3 +52,26 @@ def power(window, hop, shift, iq):
         p = ((zr * zr + zi * zi).astype(np.uint64)) >> np.uint64(shift)
         out[s] = p.sum(axis=0, dtype=np.uint64)                    # wraps modulo 2^64
     return out
+
+
+def power_chunked(window, hop, shift, iq, chunk=1 << 14):
+    """power() for long calls: frames in chunks of `chunk`, z from float64 products.  Every product c W and every partial sum is
+    an integer below 2^27 in magnitude (|c| <= 128, |W| <= 2047, N <= 256), so float64 holds each exactly whatever order the
+    matrix product sums in; the squares and the mod-2^64 sum are done in 64-bit integers as in power()."""
+    iq = np.atleast_2d(np.asarray(iq, dtype=np.uint8))
+    N = len(window)
+    F = frames(N, hop, iq.shape[1])
+    assert F >= 1
+    wr, wi = (a.astype(np.float64) for a in taps(window))
+    out = np.zeros((iq.shape[0], N), dtype=np.uint64)
+    for s in range(iq.shape[0]):
+        cr = iq[s, 0::2].astype(np.float64) - 127
+        ci = iq[s, 1::2].astype(np.float64) - 127
+        for f0 in range(0, F, chunk):
+            idx = np.arange(f0, min(F, f0 + chunk))[:, None] * hop + np.arange(N)[None, :]
+            xr, xi = cr[idx], ci[idx]
+            zr = (xr @ wr.T - xi @ wi.T).astype(np.int64)
+            zi = (xr @ wi.T + xi @ wr.T).astype(np.int64)
+            p = ((zr * zr + zi * zi).astype(np.uint64)) >> np.uint64(shift)
+            out[s] += p.sum(axis=0, dtype=np.uint64)
+    return out

@@ -53,10 +53,38 @@ def rot90(b):
     return out.ravel()
 
 
-class StationsRef:
-    """One input stream, K stations; feed() mirrors one fmd_stations call of that stream."""
+def z_direct(cr, ci, wr, wi, D, first, M):
+    """z[i][k] = sum_t W[k][t] c[first + D i + t] for i < M: [M, T] gather matrices times the tap matrix, int64.  Memory grows as
+    M T: the small shapes only."""
+    idx = (first + D * np.arange(M, dtype=np.int64))[:, None] + np.arange(wr.shape[1])[None, :]
+    xr, xi = cr[idx], ci[idx]                                # [M, T]
+    return xr @ wr.T - xi @ wi.T, xr @ wi.T + xi @ wr.T       # [M, K], exact in int64
 
-    def __init__(self, oracle, taps, decim, incs, rate_out, rate_resample, shift):
+
+def z_corr(cr, ci, wr, wi, D, first, M):
+    """z_direct by exact integer correlation, one polyphase branch at a time: taps t = D a + p meet samples D (i + a) + p, so
+    branch p is np.correlate of the samples c[first + p :: D] with the taps W[p :: D] -- only the M outputs are formed, memory
+    grows as the input."""
+    T = wr.shape[1]
+    cr = np.asarray(cr[first:first + D * (M - 1) + T], dtype=np.int64)
+    ci = np.asarray(ci[first:first + D * (M - 1) + T], dtype=np.int64)
+    zr = np.zeros((M, wr.shape[0]), dtype=np.int64)
+    zi = np.zeros((M, wr.shape[0]), dtype=np.int64)
+    for p in range(min(D, T)):
+        xr, xi = cr[p::D], ci[p::D]
+        for k in range(wr.shape[0]):
+            a, b = wr[k, p::D], wi[k, p::D]
+            n = M + a.size - 1
+            zr[:, k] += np.correlate(xr[:n], a, "valid") - np.correlate(xi[:n], b, "valid")
+            zi[:, k] += np.correlate(xr[:n], b, "valid") + np.correlate(xi[:n], a, "valid")
+    return zr, zi
+
+
+class StationsRef:
+    """One input stream, K stations; feed() mirrors one fmd_stations call of that stream.  `z` selects how the filter outputs
+    are formed: z_direct (gather matrices) or z_corr (correlation, for production-size calls); both are exact."""
+
+    def __init__(self, oracle, taps, decim, incs, rate_out, rate_resample, shift, z=None):
         self.o = oracle
         self.h = np.asarray(taps, dtype=np.int64)
         self.T, self.D, self.shift = self.h.size, int(decim), int(shift)
@@ -71,6 +99,7 @@ class StationsRef:
         self.base = 0                                        # global index of cr[0]
         self.pos = 0                                         # samples fed so far
         self.m_next = 0
+        self.z = z or z_direct
 
     def feed(self, buf):
         b = np.asarray(buf, dtype=np.uint8)
@@ -82,10 +111,7 @@ class StationsRef:
         ms = np.arange(self.m_next, max(m1, self.m_next), dtype=np.int64)
         if ms.size < 2:
             raise TooShort()
-        idx = (self.D * ms - self.base)[:, None] + np.arange(self.T)[None, :]
-        xr, xi = cr[idx], ci[idx]                            # [M, T]
-        zr = xr @ self.wr.T - xi @ self.wi.T                 # [M, K], exact in int64
-        zi = xr @ self.wi.T + xi @ self.wr.T
+        zr, zi = self.z(cr, ci, self.wr, self.wi, self.D, self.D * int(ms[0]) - self.base, ms.size)
         outs = []
         for k, inc in enumerate(self.incs):
             psi = (ms.astype(np.uint64) * np.uint64((self.D * inc) & 0xFFFFFFFF)) & 0xFFFFFFFF
@@ -104,7 +130,8 @@ class StationsRef:
             assert n >= 0
             outs.append(res[:n].copy())
         self.m_next = int(ms[-1]) + 1
-        keep = self.D * self.m_next - self.base               # samples before the next window are never read again
+        keep = min(self.D * self.m_next - self.base, cr.size)  # samples before the next window are never read again (with
+                                                               # n_taps < decim that window can start past the call's end)
         self.cr, self.ci = cr[keep:], ci[keep:]
         self.base += keep
         self.pos = end

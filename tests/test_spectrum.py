@@ -171,3 +171,21 @@ def test_code_object_has_the_spectrum_kernel_on_the_matrix_cores(code_objects): 
         assert m.get("vgpr_spill_count", 0) == 0 and m.get("sgpr_spill_count", 0) == 0, (n, m)
         assert not any(i.startswith("scratch_") for i in k["text"]), n
         assert not any(bad in n for bad in ("fmd_stations", "fmd_demod_tile_kernel", "fmd_demod_stream_kernel", "fmd_fir")), n
+
+
+@pytest.mark.parametrize("N,hop", [(16, 8), (32, 24), (64, 40), (128, 120), (256, 248), (256, 8)])
+def test_chunked_power_equals_the_direct_form(N, hop):
+    """spr.power_chunked (long calls) against spr.power, bit for bit: random and full-scale windows and bytes, chunks that split
+    the frames unevenly, and a sum that wraps modulo 2^64 at shift 0."""
+    rng = np.random.default_rng(300 + N + hop)
+    nbytes = 2 * (N + hop * 700 + int(rng.integers(0, hop)))
+    nbytes += (-nbytes) % 8
+    wins = [rng.integers(-2047, 2048, N).astype(np.int16), np.where(rng.random(N) < 0.5, -2047, 2047).astype(np.int16),
+            spr.hann(N, 127)]
+    data = [rng.integers(0, 256, (2, nbytes), dtype=np.uint8), np.where(rng.random((2, nbytes)) < 0.5, 0, 255).astype(np.uint8)]
+    for w in wins:
+        for b in data:
+            for shift in (0, 7):
+                want = spr.power(w, hop, shift, b)
+                for chunk in (97, 1 << 14):
+                    assert np.array_equal(spr.power_chunked(w, hop, shift, b, chunk=chunk), want), (chunk, shift)

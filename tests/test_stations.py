@@ -138,3 +138,89 @@ def test_code_object_has_the_station_kernel_on_the_matrix_cores(code_objects):  
         assert not any(i.startswith("scratch_") for i in k["text"]), n
         assert not any(bad in n for bad in ("fmd_demod_tile_kernel<", "fmd_demod_stream_kernel<", "fmd_fir_", "fmd_firdemod")), n
         assert any(i.startswith("global_load_lds_dwordx4") for i in k["text"]), n
+
+
+@pytest.mark.parametrize("D,T,K", [(2, 1, 1), (2, 3, 2), (4, 27, 3), (6, 5, 1), (10, 64, 8), (30, 59, 4), (64, 256, 2), (64, 26, 5)])
+def test_correlation_path_equals_the_gather_form(oracle, D, T, K):
+    """sr.z_corr (production-size calls) against sr.z_direct, bit for bit, over random and full-scale bytes and taps, and the
+    whole StationsRef chain fed the same calls through either."""
+    rng = np.random.default_rng(7000 + 100 * D + T)
+    for h in (rng.integers(-2047, 2048, T), np.where(rng.random(T) < 0.5, -2047, 2047)):
+        incs = [int(x) for x in rng.integers(0, 1 << 32, K)]
+        w = [sr.complex_taps(h, i) for i in incs]
+        wr, wi = np.stack([a for a, _ in w]), np.stack([b for _, b in w])
+        for b in (rng.integers(0, 256, 2 * (40 * D + T + 9)), np.where(rng.random(2 * (40 * D + T + 9)) < 0.5, 0, 255)):
+            cr, ci = b[0::2].astype(np.int64) - 127, b[1::2].astype(np.int64) - 127
+            for first, M in ((0, 1), (3, 17), (7, 40)):
+                zd, zc = sr.z_direct(cr, ci, wr, wi, D, first, M), sr.z_corr(cr, ci, wr, wi, D, first, M)
+                assert all(np.array_equal(a, c) and a.dtype == c.dtype for a, c in zip(zd, zc)), (first, M)
+    h = rng.integers(-2047, 2048, T).astype(np.int16)
+    incs = [int(x) for x in rng.integers(0, 1 << 32, K)]
+    shift = 0
+    while -(-256 * sr.max_gain(h, incs) >> shift) > 16384:
+        shift += 1
+    a = sr.StationsRef(oracle, h, D, incs, 240000, 32000, shift)
+    c = sr.StationsRef(oracle, h, D, incs, 240000, 32000, shift, z=sr.z_corr)
+    for n in (8 * (T + 2 * D), 8 * 5, 8 * 700, 8 * (T // 4 + 1)):
+        b = np.where(rng.random(n) < 0.3, 0, 255).astype(np.uint8) if n == 8 * 700 else rng.integers(0, 256, n, dtype=np.uint8)
+        try:
+            ea = a.feed(b)
+        except sr.TooShort:
+            with pytest.raises(sr.TooShort):
+                c.feed(b)
+            continue
+        ec = c.feed(b)
+        assert all(np.array_equal(x, y) for x, y in zip(ea, ec))
+        assert [a.state(k) for k in range(K)] == [c.state(k) for k in range(K)]
+
+
+def accepted_rates(D, T, K, rate_out, rate_resample):
+    """The rate rule of include/fmd.h (station bank, "Rates"), restated: the reduced terms, then one audio sample per tile."""
+    import math
+    g = math.gcd(rate_out, rate_resample)
+    fr, srr = rate_out // g, rate_resample // g
+    if fr > 1 << 24 or 3 * srr >= 1 << 24:
+        return False
+    c = -(-rate_out // rate_resample)
+    cap = 2 * c + 3
+    if cap > 256:
+        return False
+    groups = -(-cap // 64)                                   # 16-column groups of a wave
+    nkc = -(-(12 + 2 * T) // 64)
+    raw = max(12 + 6 * D + 8 * D * (16 * groups - 1) + 64 * nkc, 12 + 2 * D * (cap - 1) + 2 * T + 15)
+    raw = -(-raw // 16) * 16
+    return raw + 2048 + 4 * K * cap + 24 <= 65536
+
+
+def test_rate_ratio_rule_is_what_the_library_refuses():
+    """The bank refuses exactly the rate ratios the documented rule refuses: accepted shows up as FMD_ERR_NO_DEVICE without a GPU
+    (the sizing is decided before a device is queried), and as a handle with one."""
+    _, lib = _lib()
+    U, NODEV = -6, -8
+    rng = np.random.default_rng(17)
+    cases = [(2, 8, 1, 1260000, 10000), (2, 8, 1, 1260001, 10000), (64, 256, 32, 1160000, 10000), (64, 256, 32, 1161000, 10000),
+             (2, 64, 8, 1200000, 8000), (10, 64, 8, 240000, 32000), (2, 1, 1, 48000, 48000), (64, 256, 32, 48000, 48000),
+             (2, 8, 1, 1 << 24, 1), (2, 8, 1, (1 << 24) + 1, 1), (2, 8, 1, (1 << 24) - 1, 5592405), (2, 8, 1, (1 << 24) - 1, 5592406),
+             (2, 8, 1, 16777213, 16777212), (2, 8, 1, 4000037, 3999971)]
+    for c in (110, 116, 117, 120, 125, 126, 127):
+        for D, T, K in ((64, 256, 32), (64, 256, 1), (2, 256, 32), (64, 1, 32), (30, 128, 17), (62, 200, 24)):
+            cases.append((D, T, K, c * 10000, 10000))
+            cases.append((D, T, K, (c - 1) * 10007 + 1, 10007))
+    for _ in range(120):
+        D = 2 * int(rng.integers(1, 33))
+        T, K = int(rng.integers(1, 257)), int(rng.integers(1, 33))
+        slow = int(rng.integers(1, 200000))
+        fast = int(slow * rng.uniform(1.0, 140.0))
+        cases.append((D, T, K, fast, slow))
+    seen = set()
+    for D, T, K, fast, slow in cases:
+        want = accepted_rates(D, T, K, fast, slow)
+        seen.add(want)
+        rc = _new(lib, np.ones(T, np.int16), D, 24, np.zeros(K, np.uint32), K, fast, slow)
+        assert rc in ((0, NODEV) if want else (U,)), (D, T, K, fast, slow, rc)
+    assert seen == {True, False}
+    # the limits the header quotes
+    assert all(accepted_rates(64, 256, 32, 116 * r, r) for r in (1, 7, 10000))
+    assert not accepted_rates(64, 256, 32, 117 * 10000, 10000)
+    assert all(accepted_rates(D, T, K, 126 * 10000, 10000) for D, T, K in ((2, 8, 1), (10, 64, 8), (64, 1, 1)))
+    assert not accepted_rates(2, 1, 1, 126 * 10000 + 1, 10000)
