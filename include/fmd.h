@@ -359,6 +359,39 @@ int fmd_stations_f64_stats(const fmd_stations *b, uint64_t *guarded, uint64_t *p
 /* Name of the kernel this bank launches, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_stations_kernel_name(const fmd_stations *b, char *name, size_t cap);
 
+/* ---- channelizer: each station's narrowband IQ out of one wideband stream ---------------------------------- */
+/* NEW SURFACE (rtl_fm -M raw in the rtl-sdr ecosystem; the reference has none).  K digital down-converters per input stream, each
+ * returning the station's decimated complex baseband -- the station bank's y, before any demodulator.  Definition (integers only;
+ * tests/channelizer_ref.py): the station bank's c, TAB, cosq / sinq, W[k][t], z[k][m] and
+ *   y[k][m]   = (z * (cosq(psi) + j sinq(psi))) >> (14 + shift),  psi = m decim inc_k mod 2^32 (floor, per component, in i64)
+ * exactly as above (output m comes with the call in which its last sample arrives; the filter history and m carry across calls),
+ * stored as the int16 pair (yr, yi).  No fm_demod, no resampler: the station bank is this followed by fm_demod + low_pass_real.
+ * With inc = 0, h = 1...1, n_taps == decim and shift = 0, fed rot(B), it is low_pass_complex (simple_fm.rs:337-352) of B.
+ * Domain: the station bank's filter domain -- decim even, 2 ... 64; 1 <= n_taps <= 256; |h| <= 2047; 1 <= n_stations <= 32; any
+ * phase_inc; shift <= 24; ceil(256 * max_k sum_t (|Wr| + |Wi|) / 2^shift) <= 16384, so |y| <= 16384 and the int16 output is exact.
+ * nbytes % 8 != 0 -> FMD_ERR_BAD_LENGTH; a call that completes no output -> FMD_ERR_TOO_SHORT and nothing changes; everything else
+ * outside the domain -> FMD_ERR_UNSUPPORTED, decided before a device is touched.
+ * Layouts: iq [n_streams][nbytes], out [n_streams][n_stations][out_cap][2] int16 (yr, yi), phase_inc [n_streams][n_stations];
+ * n_streams is dev->n_channels.  Stream lifetime and completion points: as fmd_stations_* (fmd_channelizer_check). */
+typedef struct fmd_channelizer fmd_channelizer;
+int fmd_channelizer_new(const int16_t *taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t *phase_inc,
+                        uint32_t n_stations, const fmd_device_config *dev, fmd_channelizer **out);
+void fmd_channelizer_free(fmd_channelizer *c);
+int fmd_channelizer_reset(fmd_channelizer *c);
+/* ceil(nbytes / (2 decim)): outputs one call of nbytes can produce per (stream, station), whatever the history; 0 for decim 0. */
+size_t fmd_channelizer_out_cap(uint32_t decim, size_t nbytes);
+/* HOST buffers; *out_len = outputs per (stream, station) (the same for all). */
+int fmd_channelizer_run_batch(fmd_channelizer *c, const uint8_t *iq, size_t nbytes, int16_t *out, size_t out_cap,
+                              size_t *out_len);
+/* DEVICE buffers (d_iq and d_out 4-byte aligned), enqueued on `stream` without synchronising; *out_len as above. */
+int fmd_channelizer_run_device(fmd_channelizer *c, const void *d_iq, size_t nbytes, void *d_out, size_t out_cap,
+                               size_t *out_len, void *stream);
+int fmd_channelizer_check(fmd_channelizer *c);
+/* Outputs per (stream, station) produced since creation or the last reset: the next output's index m (to timestamp samples). */
+int fmd_channelizer_outputs(const fmd_channelizer *c, uint64_t *outputs);
+/* Name of the kernel this handle launches, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_channelizer_kernel_name(const fmd_channelizer *c, char *name, size_t cap);
+
 /* ---- power spectrum: where the stations are ------------------------------------------------------------------ */
 /* NEW SURFACE (rtl_power's job in the rtl-sdr ecosystem; the reference has none).  The integrated power of N DFT bins of every
  * stream, to find the offsets a station bank is then tuned to.  A bin is a station-bank filter (the taps and the NCO table above)

@@ -126,6 +126,16 @@ PROTOTYPES = {
     "fmd_stations_get_state": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(DemodState)]),
     "fmd_stations_f64_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fmd_stations_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_channelizer_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                                      C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_channelizer_free": (None, [_vp]),
+    "fmd_channelizer_reset": (C.c_int, [_vp]),
+    "fmd_channelizer_out_cap": (_sz, [C.c_uint32, _sz]),
+    "fmd_channelizer_run_batch": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "fmd_channelizer_run_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_channelizer_check": (C.c_int, [_vp]),
+    "fmd_channelizer_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "fmd_channelizer_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_spectrum_hann": (C.c_int, [C.c_uint32, C.c_uint32, _i16p]),
     "fmd_spectrum_bin_inc": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "fmd_spectrum_frames": (_sz, [C.c_uint32, C.c_uint32, _sz]),

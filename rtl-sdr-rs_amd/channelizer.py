@@ -1,0 +1,89 @@
+"""Host-side wrapper of the channelizer (include/fmd.h, fmd_channelizer_*): K digital down-converters per wideband IQ stream -- mix
+by the station's offset, filter with one real prototype, decimate -- each returning the station's complex baseband as int16
+(yr, yi) pairs.  The station bank (stations.py) is this followed by fm_demod and low_pass_real."""
+import ctypes as C
+
+import numpy as np
+
+from ._ffi import DeviceConfig, check, lib
+from .stations import stations_auto_shift
+
+
+def as_complex(x):
+    """int16 [..., 2] (yr, yi) pairs -> complex64 [...]."""
+    x = np.asarray(x)
+    if x.shape[-1:] != (2,):
+        raise ValueError("expected a trailing axis of 2 (yr, yi)")
+    return (x[..., 0].astype(np.float32) + 1j * x[..., 1].astype(np.float32)).astype(np.complex64)
+
+
+class Channelizer:
+    """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream).  `shift=None` takes the
+    smallest normalisation shift with |y| <= 16384."""
+
+    def __init__(self, taps, decim, phase_incs, n_streams=1, shift=None, device_id=-1):
+        self.taps = np.ascontiguousarray(taps, dtype=np.int16)
+        self.decim, self.n_streams = int(decim), int(n_streams)
+        incs = np.asarray(phase_incs, dtype=np.uint32)
+        if incs.ndim == 1:
+            incs = np.tile(incs, (self.n_streams, 1))
+        if incs.ndim != 2 or incs.shape[0] != self.n_streams:
+            raise ValueError("phase_incs must be [n_streams, n_stations]")
+        self.phase_incs = np.ascontiguousarray(incs)
+        self.n_stations = incs.shape[1]
+        self.shift = stations_auto_shift(self.taps, self.phase_incs, limit=16384) if shift is None else int(shift)
+        self._h = C.c_void_p()
+        dev = DeviceConfig(self.n_streams, device_id, 0)
+        check(lib().fmd_channelizer_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim, self.shift,
+                                        self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations, C.byref(dev),
+                                        C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().fmd_channelizer_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:                                                 # (at interpreter shutdown the module globals may be gone already)
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(lib().fmd_channelizer_reset(self._h))
+
+    def out_cap(self, nbytes):
+        return int(lib().fmd_channelizer_out_cap(self.decim, nbytes))
+
+    def outputs(self):
+        """Outputs per (stream, station) produced since creation or reset: the index m of the next one."""
+        n = C.c_uint64(0)
+        check(lib().fmd_channelizer_outputs(self._h, C.byref(n)))
+        return n.value
+
+    def run_batch(self, iq):
+        """iq uint8 [n_streams, nbytes] -> int16 array [n_streams, n_stations, n_out, 2] of (yr, yi)."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        if iq.ndim != 2 or iq.shape[0] != self.n_streams:
+            raise ValueError("iq must be [n_streams, nbytes]")
+        cap = max(1, self.out_cap(iq.shape[1]))
+        out = np.empty((self.n_streams, self.n_stations, cap, 2), dtype=np.int16)
+        n = C.c_size_t(0)
+        check(lib().fmd_channelizer_run_batch(self._h, iq.ctypes.data, iq.shape[1], out.ctypes.data, cap, C.byref(n)))
+        return out[:, :, :n.value].copy()
+
+    def run_device(self, d_iq, nbytes, d_out, out_cap, stream=None):
+        """Enqueue on device pointers (d_out [n_streams][n_stations][out_cap][2] int16); returns the outputs per (stream, station).
+        `stream` must stay alive until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
+        n = C.c_size_t(0)
+        check(lib().fmd_channelizer_run_device(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
+        return n.value
+
+    def check(self):
+        check(lib().fmd_channelizer_check(self._h))
+
+    def kernel_name(self):
+        """The kernel this channelizer launches, as rocprofv3 --kernel-trace prints it."""
+        buf = C.create_string_buffer(128)
+        check(lib().fmd_channelizer_kernel_name(self._h, buf, len(buf)))
+        return buf.value.decode()

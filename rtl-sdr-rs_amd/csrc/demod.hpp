@@ -229,6 +229,46 @@ private:
     fmd_stations* h_ = nullptr;
 };
 
+// Channelizer (fmd_channelizer_*): `phase_incs` is [n_streams][n_stations]; run() takes [n_streams][nbytes] and returns
+// interleaved (yr, yi) baseband [n_streams * n_stations] (row stream * n_stations + station).
+class Channelizer {
+public:
+    Channelizer(const std::vector<int16_t>& taps, uint32_t decim, uint32_t shift, const std::vector<uint32_t>& phase_incs,
+                uint32_t n_streams, int32_t device_id = -1)
+        : decim_(decim), n_streams_(n_streams), n_stations_(n_streams ? (uint32_t)(phase_incs.size() / n_streams) : 0u)
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_channelizer_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, &dev, &h_));
+    }
+    ~Channelizer() { fmd_channelizer_free(h_); }
+    Channelizer(const Channelizer&) = delete;
+    Channelizer& operator=(const Channelizer&) = delete;
+
+    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    {
+        const size_t cap = std::max<size_t>(1, fmd_channelizer_out_cap(decim_, nbytes));
+        const size_t rows = (size_t)n_streams_ * n_stations_;
+        std::vector<int16_t> out(2 * cap * rows);
+        size_t n = 0;
+        check(fmd_channelizer_run_batch(h_, iq, nbytes, out.data(), cap, &n));
+        std::vector<std::vector<int16_t>> res(rows);
+        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + 2 * r * cap, out.begin() + 2 * (r * cap + n));
+        return res;
+    }
+    uint64_t outputs() const
+    {
+        uint64_t n = 0;
+        check(fmd_channelizer_outputs(h_, &n));
+        return n;
+    }
+    void reset() { check(fmd_channelizer_reset(h_)); }
+    uint32_t n_stations() const { return n_stations_; }
+
+private:
+    uint32_t decim_, n_streams_, n_stations_;
+    fmd_channelizer* h_ = nullptr;
+};
+
 // Power spectrum (fmd_spectrum_*): power() takes [n_streams][nbytes] and returns u64 [n_streams][n_bins] in natural DFT order.
 inline std::vector<int16_t> hann_window(uint32_t n_bins, uint32_t amplitude = 2047)
 {

@@ -19,6 +19,8 @@
 // Station bank, -S off1,off2,...: K stations at these offsets (Hz from the capture's centre) out of ONE capture file recorded at
 // the capture rate optimal_settings derives from -s (downsample x rate); the reference's own boxcar (h = 1...1, n_taps =
 // downsample) is the prototype filter, mixed to each station by fmd_stations_*; audio of station k goes to <prefix>.<k>.s16.
+// With -I the same filter runs through the channelizer (fmd_channelizer_*) instead: station k's complex baseband at
+// capture_rate / downsample goes to <prefix>.<k>.cs16 as interleaved s16 (I, Q) pairs, no demodulation.
 //
 // Power spectrum, -P N [-H hop]: the N-bin power spectrum (fmd_spectrum_*, integer Hann window of amplitude 2047, shift 16) of
 // ONE capture file whose sample rate is -s, integrated over the file's complete blocks; one line per bin in frequency order,
@@ -32,6 +34,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -176,8 +179,9 @@ static int run_rtl_tcp(const char* hostport, uint32_t freq, uint32_t rate, uint3
     return 0;
 }
 
-// -S: one capture, K stations (fmd_stations_*)
-static int run_stations(const char* path, const char* list, const char* prefix, uint32_t freq, uint32_t rate, uint32_t resample)
+// -S: one capture, K stations (fmd_stations_*; with -I their baseband, fmd_channelizer_*)
+static int run_stations(const char* path, const char* list, const char* prefix, uint32_t freq, uint32_t rate, uint32_t resample,
+                        bool iq_out)
 {
     FILE* in = strcmp(path, "-") ? fopen(path, "rb") : stdin;
     if (!in) { perror(path); return 2; }
@@ -197,10 +201,13 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
         }
         uint32_t shift = 0;                                  // |W| <= 1 for a boxcar: sum(|Wr| + |Wi|) <= 2 n_taps
         while ((512ull * D + (1ull << shift) - 1) >> shift > 16384ull) ++shift;
-        fm::StationBank bank(std::vector<int16_t>(D, 1), D, shift, incs, 1, dc.rate_out, dc.rate_resample);
+        std::unique_ptr<fm::StationBank> bank;
+        std::unique_ptr<fm::Channelizer> chan;
+        if (iq_out) chan.reset(new fm::Channelizer(std::vector<int16_t>(D, 1), D, shift, incs, 1));
+        else bank.reset(new fm::StationBank(std::vector<int16_t>(D, 1), D, shift, incs, 1, dc.rate_out, dc.rate_resample));
         fprintf(stderr, "capture_rate: %u, %zu stations, decimate %u\n", capture, incs.size(), D);
         for (size_t k = 0; k < incs.size(); ++k) {
-            const std::string name = std::string(prefix) + "." + std::to_string(k) + ".s16";
+            const std::string name = std::string(prefix) + "." + std::to_string(k) + (iq_out ? ".cs16" : ".s16");
             out.push_back(fopen(name.c_str(), "wb"));
             if (!out.back()) { perror(name.c_str()); rc = 2; break; }
         }
@@ -212,8 +219,8 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
                 if (fill) fprintf(stderr, "dropped %zu trailing bytes (not a complete %zu-byte block)\n", fill, buf.size());
                 break;
             }
-            const auto audio = bank.demodulate(buf.data(), buf.size());
-            for (size_t k = 0; k < out.size(); ++k) fm::output(audio[k], out[k]);
+            const auto rows = iq_out ? chan->run(buf.data(), buf.size()) : bank->demodulate(buf.data(), buf.size());
+            for (size_t k = 0; k < out.size(); ++k) fm::output(rows[k], out[k]);
         }
     } catch (const fm::Error& e) {
         fprintf(stderr, "error: %s\n", e.what());
@@ -268,6 +275,7 @@ int main(int argc, char** argv)
     const char* prefix = "audio";
     const char* rtl_tcp = nullptr;                           // -t host:port: live mode over rtl_tcp
     const char* stations = nullptr;                          // -S off1,off2,...: station bank over one capture
+    bool iq_out = false;                                     // -I: with -S, each station's baseband IQ instead of audio
     uint32_t power_bins = 0, power_hop = 0;                  // -P N [-H hop]: power spectrum of one capture
     size_t max_blocks = 0;                                   // -n: stop after this many blocks (live mode; 0 = until the stream ends)
     std::vector<const char*> paths;
@@ -279,6 +287,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-g") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-t") && i + 1 < argc) rtl_tcp = argv[++i];
         else if (!strcmp(argv[i], "-S") && i + 1 < argc) stations = argv[++i];
+        else if (!strcmp(argv[i], "-I")) iq_out = true;
         else if (!strcmp(argv[i], "-P") && i + 1 < argc) power_bins = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-H") && i + 1 < argc) power_hop = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-n") && i + 1 < argc) max_blocks = strtoul(argv[++i], nullptr, 10);
@@ -288,15 +297,16 @@ int main(int argc, char** argv)
                             "       %s [-s ...] [-r ...] [-o prefix] [-g n_gpus] <a.bin> <b.bin> ...   (one channel per file)\n"
                             "       %s [-f freq_hz] [-s ...] [-r ...] [-n blocks] -t host:port            (live: IQ from an rtl_tcp server)\n"
                             "       %s [-s ...] [-r ...] [-o prefix] -S off1,off2,... <capture.bin | ->   (stations at these offsets in Hz)\n"
+                            "       %s [-s ...] [-o prefix] -S off1,off2,... -I <capture.bin | ->        (their baseband: s16 I/Q at capture_rate / downsample)\n"
                             "       %s -s capture_rate_hz -P n_bins [-H hop] <capture.bin | ->       (power spectrum: offset_hz power per bin)\n",
-                    argv[0], argv[0], argv[0], argv[0], argv[0]);
+                    argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else paths.push_back(argv[i]);
     }
     if (rtl_tcp) return run_rtl_tcp(rtl_tcp, freq, rate, resample, max_blocks);
     if (paths.empty()) { fprintf(stderr, "missing input file (use - for stdin)\n"); return 2; }
     if (power_bins) return run_power(paths[0], power_bins, power_hop, rate);
-    if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample);
+    if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample, iq_out);
     if (paths.size() > 1 && gpus > 0) return run_sink(paths, prefix, freq, rate, resample, gpus);
     if (paths.size() > 1) return run_bank(paths, prefix, freq, rate, resample);
     path = paths[0];

@@ -81,6 +81,11 @@ pub struct fmd_stations {
 }
 
 #[repr(C)]
+pub struct fmd_channelizer {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
 pub struct fmd_spectrum {
     _private: [u8; 0],
 }
@@ -161,6 +166,15 @@ extern "C" {
     pub fn fmd_stations_get_state(b: *mut fmd_stations, stream: u32, station: u32, state: *mut DemodState) -> c_int;
     pub fn fmd_stations_f64_stats(b: *const fmd_stations, guarded: *mut u64, patched: *mut u64) -> c_int;
     pub fn fmd_stations_kernel_name(b: *const fmd_stations, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_channelizer_new(taps: *const i16, n_taps: u32, decim: u32, shift: u32, phase_inc: *const u32, n_stations: u32, dev: *const DeviceConfig, out: *mut *mut fmd_channelizer) -> c_int;
+    pub fn fmd_channelizer_free(c: *mut fmd_channelizer);
+    pub fn fmd_channelizer_reset(c: *mut fmd_channelizer) -> c_int;
+    pub fn fmd_channelizer_out_cap(decim: u32, nbytes: usize) -> usize;
+    pub fn fmd_channelizer_run_batch(c: *mut fmd_channelizer, iq: *const u8, nbytes: usize, out: *mut i16, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn fmd_channelizer_run_device(c: *mut fmd_channelizer, d_iq: *const c_void, nbytes: usize, d_out: *mut c_void, out_cap: usize, out_len: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_channelizer_check(c: *mut fmd_channelizer) -> c_int;
+    pub fn fmd_channelizer_outputs(c: *const fmd_channelizer, outputs: *mut u64) -> c_int;
+    pub fn fmd_channelizer_kernel_name(c: *const fmd_channelizer, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_spectrum_hann(n_bins: u32, amplitude: u32, window: *mut i16) -> c_int;
     pub fn fmd_spectrum_bin_inc(bin: u32, n_bins: u32, inc: *mut u32) -> c_int;
     pub fn fmd_spectrum_frames(n_bins: u32, hop: u32, nbytes: usize) -> usize;
@@ -388,6 +402,65 @@ impl StationBank {
 impl Drop for StationBank {
     fn drop(&mut self) {
         unsafe { fmd_stations_free(self.handle) }
+    }
+}
+
+/// Channelizer (`fmd_channelizer_*`): `phase_incs.len() / n_streams` digital down-converters per wideband stream -- mix by the
+/// station's offset, filter with `taps`, decimate by `decim` -- each returning the station's complex baseband as `(yr, yi)` i16
+/// pairs (include/fmd.h).
+pub struct Channelizer {
+    handle: *mut fmd_channelizer,
+    pub decim: u32,
+    pub n_streams: usize,
+    pub n_stations: usize,
+}
+
+unsafe impl Send for Channelizer {}
+
+impl Channelizer {
+    /// `phase_incs` is `[n_streams][n_stations]`.
+    pub fn new(taps: &[i16], decim: u32, shift: u32, phase_incs: &[u32], n_streams: usize, device_id: i32) -> Result<Self> {
+        if n_streams == 0 || phase_incs.len() % n_streams != 0 {
+            return Err(FmdError { status: -1, message: "phase_incs must hold n_streams equal rows".into() });
+        }
+        let n_stations = phase_incs.len() / n_streams;
+        let dev = DeviceConfig { n_channels: n_streams as u32, device_id, flags: 0 };
+        let mut handle: *mut fmd_channelizer = std::ptr::null_mut();
+        check(unsafe {
+            fmd_channelizer_new(taps.as_ptr(), taps.len() as u32, decim, shift, phase_incs.as_ptr(), n_stations as u32, &dev, &mut handle)
+        })?;
+        Ok(Channelizer { handle, decim, n_streams, n_stations })
+    }
+
+    /// `iq` is `[n_streams][nbytes]`; returns interleaved `(yr, yi)` samples `[n_streams][n_stations]`.
+    pub fn run(&mut self, iq: &[u8]) -> Result<Vec<Vec<Vec<i16>>>> {
+        assert!(iq.len() % self.n_streams == 0, "iq must hold n_streams equal-sized buffers");
+        let nbytes = iq.len() / self.n_streams;
+        let cap = unsafe { fmd_channelizer_out_cap(self.decim, nbytes) }.max(1);
+        let rows = self.n_streams * self.n_stations;
+        let mut out = vec![0i16; 2 * cap * rows];
+        let mut n = 0usize;
+        check(unsafe { fmd_channelizer_run_batch(self.handle, iq.as_ptr(), nbytes, out.as_mut_ptr(), cap, &mut n) })?;
+        Ok((0..self.n_streams)
+            .map(|s| (0..self.n_stations).map(|k| { let r = s * self.n_stations + k; out[2 * r * cap..2 * (r * cap + n)].to_vec() }).collect())
+            .collect())
+    }
+
+    /// Outputs per (stream, station) produced since creation or the last reset.
+    pub fn outputs(&self) -> Result<u64> {
+        let mut n = 0u64;
+        check(unsafe { fmd_channelizer_outputs(self.handle, &mut n) })?;
+        Ok(n)
+    }
+
+    pub fn reset(&mut self) -> Result<()> {
+        check(unsafe { fmd_channelizer_reset(self.handle) })
+    }
+}
+
+impl Drop for Channelizer {
+    fn drop(&mut self) {
+        unsafe { fmd_channelizer_free(self.handle) }
     }
 }
 
