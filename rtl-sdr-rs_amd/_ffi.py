@@ -3,6 +3,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 SO_PATH = os.environ.get("FMD_LIB") or os.path.join(PKG_DIR, "libfmd_hip.so")   # FMD_LIB: tuning builds only
@@ -218,3 +220,45 @@ class FmdError(RuntimeError):
 def check(status):
     if status != FMD_OK:
         raise FmdError(status)
+
+
+class Handle:
+    """A library handle `self._h` whose entry points are fmd_<_prefix>_*: free and kernel_name."""
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(lib(), "fmd_%s_%s" % (self._prefix, name))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._fn("free")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:                                                 # (at interpreter shutdown the module globals may be gone already)
+            self.close()
+        except Exception:
+            pass
+
+    def kernel_name(self):
+        """The kernel this handle launches, as rocprofv3 --kernel-trace prints it."""
+        buf = C.create_string_buffer(128)
+        check(self._fn("kernel_name")(self._h, buf, len(buf)))
+        return buf.value.decode()
+
+
+class CheckedHandle(Handle):
+    """A Handle with a completion point, fmd_<_prefix>_check."""
+
+    def check(self):
+        check(self._fn("check")(self._h))
+
+
+def stream_phase_incs(phase_incs, n_streams):
+    """`phase_incs` as a contiguous uint32 [n_streams, n_stations] (a flat list of n_stations is taken for every stream)."""
+    incs = np.asarray(phase_incs, dtype=np.uint32)
+    if incs.ndim == 1:
+        incs = np.tile(incs, (n_streams, 1))
+    if incs.ndim != 2 or incs.shape[0] != n_streams:
+        raise ValueError("phase_incs must be [n_streams, n_stations]")
+    return np.ascontiguousarray(incs)

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DeviceConfig, check, lib
+from ._ffi import DeviceConfig, CheckedHandle, check, lib, stream_phase_incs
 from .stations import stations_auto_shift
 
 
@@ -17,37 +17,22 @@ def as_complex(x):
     return (x[..., 0].astype(np.float32) + 1j * x[..., 1].astype(np.float32)).astype(np.complex64)
 
 
-class Channelizer:
+class Channelizer(CheckedHandle):
     """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream).  `shift=None` takes the
     smallest normalisation shift with |y| <= 16384."""
+    _prefix = "channelizer"
 
     def __init__(self, taps, decim, phase_incs, n_streams=1, shift=None, device_id=-1):
         self.taps = np.ascontiguousarray(taps, dtype=np.int16)
         self.decim, self.n_streams = int(decim), int(n_streams)
-        incs = np.asarray(phase_incs, dtype=np.uint32)
-        if incs.ndim == 1:
-            incs = np.tile(incs, (self.n_streams, 1))
-        if incs.ndim != 2 or incs.shape[0] != self.n_streams:
-            raise ValueError("phase_incs must be [n_streams, n_stations]")
-        self.phase_incs = np.ascontiguousarray(incs)
-        self.n_stations = incs.shape[1]
+        self.phase_incs = stream_phase_incs(phase_incs, self.n_streams)
+        self.n_stations = self.phase_incs.shape[1]
         self.shift = stations_auto_shift(self.taps, self.phase_incs, limit=16384) if shift is None else int(shift)
         self._h = C.c_void_p()
         dev = DeviceConfig(self.n_streams, device_id, 0)
         check(lib().fmd_channelizer_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim, self.shift,
                                         self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations, C.byref(dev),
                                         C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib().fmd_channelizer_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:                                                 # (at interpreter shutdown the module globals may be gone already)
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         check(lib().fmd_channelizer_reset(self._h))
@@ -78,12 +63,3 @@ class Channelizer:
         n = C.c_size_t(0)
         check(lib().fmd_channelizer_run_device(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
         return n.value
-
-    def check(self):
-        check(lib().fmd_channelizer_check(self._h))
-
-    def kernel_name(self):
-        """The kernel this channelizer launches, as rocprofv3 --kernel-trace prints it."""
-        buf = C.create_string_buffer(128)
-        check(lib().fmd_channelizer_kernel_name(self._h, buf, len(buf)))
-        return buf.value.decode()

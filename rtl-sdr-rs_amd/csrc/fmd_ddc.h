@@ -1,0 +1,399 @@
+// fmd_ddc.h -- what the three matrix-core handles share: the station bank (fmd_stations.hip), the channelizer
+// (fmd_channelizer.hip) and the power-spectrum scanner (fmd_spectrum.hip).
+//   plan (host):        the NCO table, the complex taps of every row, the matrix-core A fragments and their centring constants;
+//   front end (device): the bank's and the channelizer's digital down-converter -- staging of the filter windows and the NCO
+//                       table in LDS, the history write, the contraction on the matrix cores, the rotation back to baseband;
+//   handle core (host): device, stream, uploaded plan, double-buffered history, batch staging buffers.
+// Definitions: include/fmd.h, "station bank", "channelizer", "power spectrum".
+#pragma once
+
+#include "../../include/fmd.h"
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "fmd_host.h"
+
+// ---- plan ---------------------------------------------------------------------------------------------------------------------
+
+// TAB[i] = round(16384 cos(2 pi i / 1024)); no entry lies near a rounding tie, so any libm gives the same table.
+inline void fmd_st_nco_table(int16_t* tab)
+{
+    const double two_pi = 6.28318530717958647692528676655900577;
+    for (int i = 0; i < 1024; ++i) tab[i] = (int16_t)std::lround(16384.0 * std::cos(two_pi * i / 1024.0));
+}
+inline int fmd_st_cosq(const int16_t* tab, uint32_t phi) { return tab[phi >> 22]; }
+inline int fmd_st_sinq(const int16_t* tab, uint32_t phi) { return tab[((phi >> 22) - 256u) & 1023u]; }
+
+// W[t] = rnd(h[t] cosq(t inc)) + j rnd(-h[t] sinq(t inc)), rnd(v) = (v + 8192) >> 14 (arithmetic shift): |W| <= 2047.
+inline void fmd_st_complex_taps(const int16_t* h, uint32_t n_taps, uint32_t inc, const int16_t* tab, int32_t* wr, int32_t* wi)
+{
+    for (uint32_t t = 0; t < n_taps; ++t) {
+        const uint32_t phi = t * inc;                                    // mod 2^32
+        wr[t] = (h[t] * fmd_st_cosq(tab, phi) + 8192) >> 14;
+        wi[t] = (-h[t] * fmd_st_sinq(tab, phi) + 8192) >> 14;
+    }
+}
+
+// The tap matrix on the matrix cores (v_mfma_i32_16x16x64_i8, A = 16 rows x 64 bytes per K chunk).  Rows:
+//   two digits (any |W| <= 2047): row 4 i + (zr_lo, zr_hi, zi_lo, zi_hi) of tap row 4 rt + i, W = 128 hi + lo (|lo| <= 64, |hi| <= 16);
+//   one digit (every |W| <= 127): row 2 i + (zr, zi) of tap row 8 rt + i.
+// K index = byte offset from a 16-byte aligned address; the window of the column's output starts `delta` bytes further, byte 2 t
+// is I and 2 t + 1 is Q of sample t.  With B = b - 128 (the bytes xor 0x80, as s8) the sample is c = (B_I + 1) + j (B_Q + 1), so
+//   zr = sum Wr cI - Wi cQ  -> I weight Wr, Q weight -Wi, constant sum (Wr - Wi)
+//   zi = sum Wi cI + Wr cQ  -> I weight Wi, Q weight  Wr, constant sum (Wr + Wi).
+// A tap row is a (stream, station) of the bank and the channelizer, a DFT bin of the scanner.
+struct FmdDdcPlan {
+    uint32_t K = 0, T = 0, S = 0;     // tap rows per stream, taps, streams
+    uint32_t digits = 2;              // i8 digits per tap
+    uint32_t spt = 4;                 // tap rows per row tile (4: two digits, 8: one)
+    uint32_t nrt = 0, nkc = 0;        // row tiles, 64-byte K chunks
+    std::vector<uint32_t> amat;       // [S][deltas][nrt][nkc][64 lanes][4 dwords]
+    std::vector<int32_t> kconst;      // [S][K][2]: the additive constants of zr, zi
+    std::vector<uint32_t> dinc;       // [S][K]: decim * inc mod 2^32 (output rotation step; down-converters only)
+    uint64_t max_gain = 0;            // max over tap rows of sum_t |Wr| + |Wi|
+};
+
+inline int fmd_st_a_entry(const int32_t* wr, const int32_t* wi, uint32_t T, uint32_t comp, uint32_t kb, uint32_t delta)
+{
+    if (kb < delta || kb - delta >= 2u * T) return 0;
+    const uint32_t u = kb - delta, t = u >> 1, q = u & 1u;
+    return comp == 0u ? (q ? -wi[t] : wr[t]) : (q ? wr[t] : wi[t]);
+}
+
+// The A fragments of the K tap rows of one stream, for the window offsets delta = 4 dl, dl < ndelta:
+// ab = [ndelta][nrt][nkc][64 lanes][16 bytes] (lane l: row l & 15, K bytes 16 (l >> 4) ... + 15 of the chunk).
+inline void fmd_ddc_pack_a(const int32_t* wr, const int32_t* wi, uint32_t T, uint32_t K, uint32_t nrt, uint32_t nkc,
+                           uint32_t ndelta, bool small, uint8_t* ab)
+{
+    for (uint32_t dl = 0; dl < ndelta; ++dl)
+        for (uint32_t rt = 0; rt < nrt; ++rt)
+            for (uint32_t kc = 0; kc < nkc; ++kc)
+                for (uint32_t lane = 0; lane < 64; ++lane) {
+                    const uint32_t row = lane & 15u, q = lane >> 4;
+                    uint32_t k, comp, dsel;
+                    if (small) { k = 8u * rt + (row >> 1); comp = row & 1u; dsel = 0u; }
+                    else { k = 4u * rt + (row >> 2); comp = (row >> 1) & 1u; dsel = 1u + (row & 1u); }
+                    if (k >= K) continue;
+                    const size_t base = ((((size_t)dl * nrt + rt) * nkc + kc) * 64 + lane) * 16;
+                    for (uint32_t b = 0; b < 16; ++b) {
+                        const int v = fmd_st_a_entry(&wr[(size_t)k * T], &wi[(size_t)k * T], T, comp, 64u * kc + 16u * q + b, 4u * dl);
+                        const int lo = ((v + 64) & 127) - 64, hi = (v - lo) / 128;
+                        ab[base + b] = (uint8_t)(int8_t)(dsel == 0u ? v : (dsel == 1u ? lo : hi));
+                    }
+                }
+}
+
+// The plan of S streams x K tap rows, row sk mixed by inc[sk]: taps, constants, digits, and A fragments for `ndelta` offsets.
+inline void fmd_ddc_build_plan(const int16_t* h, uint32_t T, const uint32_t* inc, uint32_t S, uint32_t K, uint32_t ndelta,
+                               uint32_t nkc, FmdDdcPlan& P)
+{
+    int16_t tab[1024];
+    fmd_st_nco_table(tab);
+    P.K = K; P.T = T; P.S = S;
+    std::vector<int32_t> wr((size_t)S * K * T), wi((size_t)S * K * T);
+    bool small = true;
+    P.max_gain = 0;
+    P.kconst.assign((size_t)S * K * 2, 0);
+    for (size_t sk = 0; sk < (size_t)S * K; ++sk) {
+        int32_t* r = &wr[sk * T];
+        int32_t* i = &wi[sk * T];
+        fmd_st_complex_taps(h, T, inc[sk], tab, r, i);
+        uint64_t g = 0;
+        int64_t cre = 0, cim = 0;
+        for (uint32_t t = 0; t < T; ++t) {
+            g += (uint64_t)(r[t] < 0 ? -r[t] : r[t]) + (uint64_t)(i[t] < 0 ? -i[t] : i[t]);
+            if (r[t] > 127 || r[t] < -127 || i[t] > 127 || i[t] < -127) small = false;
+            cre += r[t] - i[t];
+            cim += r[t] + i[t];
+        }
+        if (g > P.max_gain) P.max_gain = g;
+        P.kconst[2 * sk] = (int32_t)cre;
+        P.kconst[2 * sk + 1] = (int32_t)cim;
+    }
+    P.digits = small ? 1u : 2u;
+    P.spt = small ? 8u : 4u;
+    P.nrt = (K + P.spt - 1u) / P.spt;
+    P.nkc = nkc;
+    const size_t per_stream = (size_t)ndelta * P.nrt * P.nkc * 64 * 4;
+    P.amat.assign(S * per_stream, 0u);
+    for (uint32_t s = 0; s < S; ++s)
+        fmd_ddc_pack_a(&wr[(size_t)s * K * T], &wi[(size_t)s * K * T], T, K, P.nrt, P.nkc, ndelta, small,
+                       reinterpret_cast<uint8_t*>(P.amat.data() + s * per_stream));
+}
+
+// The down-converters' plan (bank, channelizer): a window starts 0, 4, 8 or 12 bytes past a 16-byte boundary.
+inline void fmd_st_build_plan(const int16_t* h, uint32_t T, uint32_t decim, const uint32_t* inc, uint32_t S, uint32_t K,
+                              FmdDdcPlan& P)
+{
+    fmd_ddc_build_plan(h, T, inc, S, K, 4u, (12u + 2u * T + 63u) / 64u, P);
+    P.dinc.assign((size_t)S * K, 0u);
+    for (size_t sk = 0; sk < (size_t)S * K; ++sk) P.dinc[sk] = decim * inc[sk];
+}
+
+// ---- device front end of the down-converters ----------------------------------------------------------------------------------
+// One workgroup stages the raw bytes of a tile's filter windows of ONE stream and forms the tile's outputs for every station:
+// wave w takes the outputs w + 4 i, whose windows sit 8 D i bytes apart -- 16-byte aligned for even D -- at a common offset delta
+// from an aligned address; the host built the A fragments for each delta, and the wave loads the set that fits its offset.
+// `Launch` is the kernel's launch struct; the fields read here have the same names in both.
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FMD_DDC_GLOBAL __attribute__((address_space(1)))
+#else
+#define FMD_DDC_GLOBAL
+#endif
+
+namespace fmd_ddc {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kGroups = 4;                           // 16-column MFMA groups per wave: at most 4 waves x 4 x 16 = 256 outputs per tile
+constexpr uint32_t kTableBytes = 2048;                    // 1024 x i16
+typedef int i4 __attribute__((ext_vector_type(4)));
+
+template <class Launch>
+__device__ __forceinline__ uint32_t virt_dword(const Launch& L, uint32_t s, uint32_t v)   // v: virtual byte, multiple of 4
+{
+    typedef const FMD_DDC_GLOBAL uint32_t* gw;
+    if (v < L.HB) return ((gw)(uintptr_t)(L.hist_in + (uint64_t)s * L.HB + v))[0];
+    const uint64_t b = (uint64_t)(v - L.HB);
+    if (b >= L.nbytes) return 0u;                          // beyond the call: only outputs that are discarded read it
+    return ((gw)(uintptr_t)(L.iq + (uint64_t)s * L.nbytes + b))[0];
+}
+
+__device__ __forceinline__ void dma16(const unsigned char* g, unsigned char* lds_wave_base)
+{
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 2 /* nt */);
+}
+
+// rotation back to baseband and the normalising shift (include/fmd.h step 5), packed re | im << 16
+__device__ __forceinline__ uint32_t rotate(const int16_t* tab, int zr, int zi, uint32_t psi, uint32_t sh)
+{
+    const uint32_t ix = psi >> 22;
+    const int64_t C = tab[ix], S = tab[(ix - 256u) & 1023u];
+    const int yr = (int)(((int64_t)zr * C + (int64_t)zi * S) >> sh);
+    const int yi = (int)(((int64_t)zi * C - (int64_t)zr * S) >> sh);
+    return ((uint32_t)yr & 0xFFFFu) | ((uint32_t)yi << 16);
+}
+
+// The nq 16-byte chunks from virtual byte `base` (history ++ call) into LDS at 0 -- global_load_lds_dwordx4 when the range is
+// whole, aligned and inside the call, through registers otherwise -- and the NCO table into `tab`.  The caller waits (vmcnt(0))
+// and synchronises.
+template <class Launch>
+__device__ __forceinline__ void stage(const Launch& L, uint32_t s, uint32_t base, uint32_t nq, uint32_t* lds, int16_t* tab,
+                                      uint32_t tid, uint32_t wave)
+{
+    const uint8_t* const row = L.iq + (uint64_t)s * L.nbytes;
+    const bool whole = base >= L.HB && (uint64_t)(base - L.HB) + 16ull * nq <= L.nbytes && (((uintptr_t)row + (base - L.HB)) & 15u) == 0u;
+    if (whole) {
+        const unsigned char* src = row + (base - L.HB) + 16u * tid;
+        unsigned char* dst = reinterpret_cast<unsigned char*>(lds) + 1024u * wave;
+        const uint32_t nfull = nq / kThreads, ntail = nq - nfull * kThreads;
+        for (uint32_t l = 0; l < nfull; ++l) dma16(src + (16u * kThreads) * l, dst + (16u * kThreads) * l);
+        if (tid < ntail) dma16(src + (16u * kThreads) * nfull, dst + (16u * kThreads) * nfull);
+    } else {
+        i4* lq = reinterpret_cast<i4*>(lds);
+        for (uint32_t i = tid; i < nq; i += kThreads) {
+            const uint32_t v = base + 16u * i;
+            lq[i] = i4{(int)virt_dword(L, s, v), (int)virt_dword(L, s, v + 4u), (int)virt_dword(L, s, v + 8u), (int)virt_dword(L, s, v + 12u)};
+        }
+    }
+    typedef const FMD_DDC_GLOBAL uint32_t* gw;
+    uint32_t* const tw = reinterpret_cast<uint32_t*>(tab);
+    for (uint32_t i = tid; i < kTableBytes / 4u; i += kThreads) tw[i] = ((gw)(uintptr_t)L.tab)[i];
+}
+
+// the next call's history of stream s (virtual bytes nbytes ... nbytes + HB); one tile per stream writes it
+template <class Launch>
+__device__ __forceinline__ void write_history(const Launch& L, uint32_t s, uint32_t tid)
+{
+    typedef FMD_DDC_GLOBAL uint32_t* gwo;
+    for (uint32_t i = tid; i < L.HB / 4u; i += kThreads)
+        ((gwo)(uintptr_t)(L.hist_out + (uint64_t)s * L.HB))[i] = virt_dword(L, s, (uint32_t)L.nbytes + 4u * i);
+}
+
+// The contraction on the matrix cores (A = the stream's tap fragments, B = the staged window bytes xor 0x80 -> s8, one column per
+// output), then per (station k, output o < no of the tile): the centring constants, the rotation by the NCO, the normalising
+// shift, packed into ypk[k stride + col + o].  d0: offset of output 0's window from the staged base; m0: global index (mod 2^32)
+// of output 0.
+template <class Launch>
+__device__ __forceinline__ void contract(const Launch& L, uint32_t s, uint32_t wave, uint32_t lane, uint32_t d0, uint32_t no,
+                                         uint32_t m0, const uint32_t* lds, const int16_t* tab, uint32_t* ypk, uint32_t stride,
+                                         uint32_t col)
+{
+    const uint8_t* lb = reinterpret_cast<const uint8_t*>(lds);
+    const uint32_t j = lane & 15u, q = lane >> 4;
+    const uint32_t pw = d0 + 2u * L.D * wave;               // window of the wave's first output
+    const uint32_t aw = pw & ~15u, dl = (pw & 15u) >> 2;
+    const uint32_t nout_w = no > wave ? (no - wave + 3u) >> 2 : 0u;
+    const uint32_t groups = (nout_w + 15u) >> 4;            // wave-uniform, <= kGroups
+    typedef const FMD_DDC_GLOBAL i4* gq;
+    const gq amat = (gq)(uintptr_t)L.amat + (((uint64_t)s * 4u + dl) * L.nrt) * L.nkc * 64u + lane;
+    const uint32_t bcol = aw + 8u * L.D * j + 16u * q;      // this lane's B bytes of group 0, chunk 0
+    const uint32_t sh = 14u + L.shift;
+    for (uint32_t rt = 0; rt < L.nrt; ++rt) {
+        i4 acc[kGroups];
+#pragma unroll
+        for (uint32_t g = 0; g < kGroups; ++g) acc[g] = i4{0, 0, 0, 0};
+        for (uint32_t kc = 0; kc < L.nkc; ++kc) {
+            const i4 A = amat[(rt * L.nkc + kc) * 64u];
+#pragma unroll
+            for (uint32_t g = 0; g < kGroups; ++g) {
+                if (g < groups) {
+                    i4 B = *reinterpret_cast<const i4*>(lb + bcol + 128u * L.D * g + 64u * kc);
+                    B = B ^ (int)0x80808080;                                                   // u8 -> s8
+                    acc[g] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, acc[g], 0, 0, 0);
+                }
+            }
+        }
+        // lane (j, q) holds rows 4 q ... 4 q + 3 of column j: two digits -> (zr_lo, zr_hi, zi_lo, zi_hi) of station 4 rt + q;
+        // one digit -> (zr, zi) of stations 8 rt + 2 q and 8 rt + 2 q + 1
+        const uint32_t ka = L.digits == 2u ? 4u * rt + q : 8u * rt + 2u * q;
+        const uint32_t sk = s * L.K + ka;
+        const bool has0 = ka < L.K, has1 = L.digits == 1u && ka + 1u < L.K;
+        int c0r = 0, c0i = 0, c1r = 0, c1i = 0;               // centring constants and phase steps, once per row tile
+        uint32_t i0 = 0u, i1 = 0u;
+        if (has0) { c0r = L.kconst[2u * sk]; c0i = L.kconst[2u * sk + 1u]; i0 = L.dinc[sk]; }
+        if (has1) { c1r = L.kconst[2u * sk + 2u]; c1i = L.kconst[2u * sk + 3u]; i1 = L.dinc[sk + 1u]; }
+#pragma unroll
+        for (uint32_t g = 0; g < kGroups; ++g) {
+            const uint32_t o = wave + 4u * (16u * g + j);      // output o of the tile
+            if (g < groups && o < no) {
+                const uint32_t m = m0 + o;
+                if (has0) {
+                    if (L.digits == 2u) {
+                        const int zr = (int)((uint32_t)acc[g].x + ((uint32_t)acc[g].y << 7)) + c0r;
+                        const int zi = (int)((uint32_t)acc[g].z + ((uint32_t)acc[g].w << 7)) + c0i;
+                        ypk[ka * stride + col + o] = rotate(tab, zr, zi, m * i0, sh);
+                    } else {
+                        ypk[ka * stride + col + o] = rotate(tab, acc[g].x + c0r, acc[g].y + c0i, m * i0, sh);
+                    }
+                }
+                if (has1) ypk[(ka + 1u) * stride + col + o] = rotate(tab, acc[g].z + c1r, acc[g].w + c1i, m * i1, sh);
+            }
+        }
+    }
+}
+
+}  // namespace fmd_ddc
+
+// ---- handle core (host) -------------------------------------------------------------------------------------------------------
+
+// A failed HIP call: the message, FMD_ERR_NOMEM / FMD_ERR_HIP.
+#define FMD_DDC_TRY(expr)                                                                   \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess) {                                                             \
+            char m_[256];                                                                   \
+            snprintf(m_, sizeof m_, "%s failed: %s", #expr, hipGetErrorString(e_));         \
+            fmd_internal_set_err(m_);                                                       \
+            return e_ == hipErrorOutOfMemory ? FMD_ERR_NOMEM : FMD_ERR_HIP;                 \
+        }                                                                                   \
+    } while (0)
+
+#define FMD_DDC_ON_DEVICE(dev)                                                              \
+    FmdDeviceGuard dev_guard_(dev);                                                         \
+    if (dev_guard_.error() != hipSuccess) { fmd_internal_set_err("hipSetDevice failed"); return FMD_ERR_HIP; }
+
+// What each of fmd_stations, fmd_channelizer and fmd_spectrum holds on the device.
+struct FmdDdcCore {
+    int device = 0;
+    hipStream_t stream = nullptr;                         // the host entry points' own stream
+    FmdStreamOrder order;
+    uint32_t* d_amat = nullptr;
+    int32_t* d_kconst = nullptr;
+    uint32_t* d_dinc = nullptr;                           // down-converters only: phase steps and the NCO table
+    uint32_t* d_tab = nullptr;
+    uint8_t* d_hist[2] = {nullptr, nullptr};              // down-converters only: raw-byte history, read [cur], written [cur ^ 1]
+    size_t hist_bytes = 0;
+    int cur = 0;
+    uint64_t pos = 0;                                     // samples consumed per stream
+    void* d_iq = nullptr; size_t d_iq_cap = 0;            // batch staging (bytes)
+    void* d_out = nullptr; size_t d_out_cap = 0;
+};
+
+// The device of `dev` (device_id < 0: the current one) if it is a gfx950; FMD_ERR_NO_DEVICE otherwise.  Touches no allocation.
+inline int fmd_ddc_open(FmdDdcCore& c, const fmd_device_config* dev)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { fmd_internal_set_err("no HIP device (this library has no CPU path)"); return FMD_ERR_NO_DEVICE; }
+    int device = dev->device_id;
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    hipDeviceProp_t prop;
+    if (device >= ndev || hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        fmd_internal_set_err("device is not a gfx950"); return FMD_ERR_NO_DEVICE;
+    }
+    c.device = device;
+    return FMD_OK;
+}
+
+// On c.device: the plan's buffers (the NCO table with the phase steps), a zeroed history of `hist_bytes` twice when non-zero,
+// the stream.  nullptr, or what failed.
+inline const char* fmd_ddc_upload(FmdDdcCore& c, const FmdDdcPlan& P, size_t hist_bytes)
+{
+    if (hipMalloc(&c.d_amat, P.amat.size() * 4) != hipSuccess || hipMemcpy(c.d_amat, P.amat.data(), P.amat.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return "hipMalloc(tap matrix)";
+    if (hipMalloc(&c.d_kconst, P.kconst.size() * 4) != hipSuccess || hipMemcpy(c.d_kconst, P.kconst.data(), P.kconst.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return "hipMalloc(constants)";
+    if (!P.dinc.empty()) {
+        if (hipMalloc(&c.d_dinc, P.dinc.size() * 4) != hipSuccess || hipMemcpy(c.d_dinc, P.dinc.data(), P.dinc.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return "hipMalloc(phase steps)";
+        int16_t tab[1024];
+        fmd_st_nco_table(tab);
+        if (hipMalloc(&c.d_tab, sizeof tab) != hipSuccess || hipMemcpy(c.d_tab, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess)
+            return "hipMalloc(NCO table)";
+    }
+    c.hist_bytes = hist_bytes;
+    for (int i = 0; i < 2 && hist_bytes; ++i)
+        if (hipMalloc(&c.d_hist[i], hist_bytes) != hipSuccess || hipMemset(c.d_hist[i], 0, hist_bytes) != hipSuccess) return "hipMalloc(history)";
+    if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate";
+    return nullptr;
+}
+
+// Back to position 0 with an all-zero history (the caller has synchronised the device).  The position, the buffer index and the
+// stream order change only once the device has finished the memsets, so a failure leaves them as they were.
+inline hipError_t fmd_ddc_zero_history(FmdDdcCore& c)
+{
+    for (int i = 0; i < 2; ++i) {
+        const hipError_t e = hipMemset(c.d_hist[i], 0, c.hist_bytes);
+        if (e != hipSuccess) return e;
+    }
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return e;
+    c.pos = 0; c.cur = 0;
+    c.order.reset();
+    return hipSuccess;
+}
+
+// Everything the core holds (on c.device: the caller holds the device guard).
+inline void fmd_ddc_release(FmdDdcCore& c)
+{
+    (void)hipDeviceSynchronize();
+    c.order.destroy();
+    for (void* p : {(void*)c.d_amat, (void*)c.d_kconst, (void*)c.d_dinc, (void*)c.d_tab, (void*)c.d_hist[0], (void*)c.d_hist[1], c.d_iq, c.d_out})
+        if (p) (void)hipFree(p);
+    if (c.stream) (void)hipStreamDestroy(c.stream);
+}
+
+// A batch staging buffer of at least `bytes` (at least 1) bytes, reallocated only when it grows.
+inline hipError_t fmd_ddc_grow(void*& p, size_t& cap, size_t bytes)
+{
+    if (bytes <= cap) return hipSuccess;
+    if (p) {
+        const hipError_t e = hipFree(p);
+        p = nullptr; cap = 0;
+        if (e != hipSuccess) return e;
+    }
+    const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+}
+
+// snprintf's result in a `_kernel_name` entry point -> FMD_OK / FMD_ERR_CAPACITY
+inline int fmd_ddc_name_rc(int n, size_t cap) { return n < 0 || (size_t)n >= cap ? FMD_ERR_CAPACITY : FMD_OK; }

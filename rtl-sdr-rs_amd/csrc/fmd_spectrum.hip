@@ -4,7 +4,7 @@
 //     z[k][f] = sum_{t < N} W[k][t] c[f hop + t]      (W = window x NCO twiddles at inc_k = k 2^32 / N, c = raw bytes - 127)
 //     P[k]    = sum_f (zr^2 + zi^2) >> shift          (u64, natural DFT order)
 // A DFT bin is a station-bank filter whose decimation is the hop and which needs no back-rotation, so the tap matrix and its
-// centring constants are the station bank's (fmd_stations_common.h: fmd_st_complex_taps, the i8 digits, W = 128 hi + lo).
+// centring constants are the station bank's (fmd_ddc.h: fmd_st_complex_taps, the i8 digits, W = 128 hi + lo).
 // Unlike the bank the tap matrix is the same for every stream and every frame starts 16-byte aligned, so this is a GEMM proper:
 //   rows    = bin x {zr, zi} x i8 digit (a 16-row tile holds (zr_lo, zr_hi, zi_lo, zi_hi) of 4 bins, or (zr, zi) of 8),
 //   K       = the frame's 2 N bytes, padded with zero A entries to whole 64-byte chunks,
@@ -21,19 +21,10 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstring>
 #include <new>
 #include <vector>
 
-#include "fmd_host.h"
-#include "fmd_stations_common.h"
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FMD_SP_GLOBAL __attribute__((address_space(1)))
-#else
-#define FMD_SP_GLOBAL
-#endif
+#include "fmd_ddc.h"
 
 namespace fmd_sp {
 
@@ -89,8 +80,8 @@ __global__ void __launch_bounds__(kThreads) fmd_spectrum_power_kernel(const SpLa
     const uint32_t j = lane & 15u, q = lane >> 4;
     const uint8_t* const row = L.iq + (uint64_t)s * L.nbytes;
     const uint32_t kbytes = 2u * L.n_bins;
-    typedef const FMD_SP_GLOBAL sp_i4* gq;
-    typedef const FMD_SP_GLOBAL uint32_t* gw;
+    typedef const FMD_DDC_GLOBAL sp_i4* gq;
+    typedef const FMD_DDC_GLOBAL uint32_t* gw;
     for (uint32_t fb = f_begin + 16u * G * wave; fb < f_end; fb += 16u * G * kWaves) {
         // ---- the batch's frame bytes, straight into registers ------------------------------------------------------------
         sp_i4 B[G][NKC];
@@ -168,80 +159,24 @@ __global__ void __launch_bounds__(kThreads) fmd_spectrum_power_kernel(const SpLa
         if (part[i]) atomicAdd(L.power + (uint64_t)s * L.n_bins + i, part[i]);
 }
 
-#define SP_TRY(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof m_, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-            fmd_internal_set_err(m_);                                                       \
-            return e_ == hipErrorOutOfMemory ? FMD_ERR_NOMEM : FMD_ERR_HIP;                 \
-        }                                                                                   \
-    } while (0)
-
-#define SP_ON_DEVICE(dev)                                                                   \
-    FmdDeviceGuard dev_guard_(dev);                                                         \
-    if (dev_guard_.error() != hipSuccess) { fmd_internal_set_err("hipSetDevice failed"); return FMD_ERR_HIP; }
-
 }  // namespace fmd_sp
 
 struct fmd_spectrum {
     uint32_t N = 0, hop = 0, shift = 0, S = 0;
     uint32_t digits = 2, nrt = 0, nkc = 0;
-    int device = 0;
-    uint32_t* d_amat = nullptr;
-    int32_t* d_kconst = nullptr;
-    FmdStreamOrder order;
-    hipStream_t stream = nullptr;
-    uint8_t* d_iq = nullptr; size_t d_iq_cap = 0;
-    unsigned long long* d_power = nullptr;
+    FmdDdcCore core;                                      // core.d_out: the host entry point's power sums
 };
 
 namespace {
 
 bool sp_valid_bins(uint32_t n) { return n == 16 || n == 32 || n == 64 || n == 128 || n == 256; }
 
-// The A fragments of v_mfma_i32_16x16x64_i8 (lane l: row l & 15, K bytes 16 (l >> 4) ... + 15 of the chunk) and the centring
-// constants.  K byte 2 t is I, 2 t + 1 is Q of sample t; with c = B + 1
-//   zr = sum Wr cI - Wi cQ  -> I weight Wr, Q weight -Wi, constant sum (Wr - Wi)
-//   zi = sum Wi cI + Wr cQ  -> I weight Wi, Q weight  Wr, constant sum (Wr + Wi).
-void sp_build_plan(const int16_t* w, uint32_t N, fmd_spectrum* h, std::vector<uint32_t>& amat, std::vector<int32_t>& kconst)
+// One tap row per bin, mixed by inc_k = k 2^32 / N; every frame starts 16-byte aligned (one delta, no slack in K).
+void sp_build_plan(const int16_t* w, uint32_t N, FmdDdcPlan& P)
 {
-    int16_t tab[1024];
-    fmd_st_nco_table(tab);
-    std::vector<int32_t> wr((size_t)N * N), wi((size_t)N * N);
-    bool small = true;
-    kconst.assign(2u * N, 0);
-    for (uint32_t k = 0; k < N; ++k) {
-        int32_t* r = &wr[(size_t)k * N];
-        int32_t* i = &wi[(size_t)k * N];
-        fmd_st_complex_taps(w, N, k * (uint32_t)((1ull << 32) / N), tab, r, i);
-        for (uint32_t t = 0; t < N; ++t) {
-            if (r[t] > 127 || r[t] < -127 || i[t] > 127 || i[t] < -127) small = false;
-            kconst[2u * k] += r[t] - i[t];
-            kconst[2u * k + 1u] += r[t] + i[t];
-        }
-    }
-    h->digits = small ? 1u : 2u;
-    h->nrt = small ? N / 8u : N / 4u;
-    h->nkc = (2u * N + 63u) / 64u;
-    amat.assign((size_t)h->nrt * h->nkc * 64 * 4, 0u);
-    uint8_t* ab = reinterpret_cast<uint8_t*>(amat.data());
-    for (uint32_t rt = 0; rt < h->nrt; ++rt)
-        for (uint32_t c = 0; c < h->nkc; ++c)
-            for (uint32_t lane = 0; lane < 64; ++lane) {
-                const uint32_t rw = lane & 15u, q = lane >> 4;
-                uint32_t k, comp, dsel;
-                if (small) { k = 8u * rt + (rw >> 1); comp = rw & 1u; dsel = 0u; }
-                else { k = 4u * rt + (rw >> 2); comp = (rw >> 1) & 1u; dsel = 1u + (rw & 1u); }
-                const size_t base = (((size_t)rt * h->nkc + c) * 64 + lane) * 16;
-                for (uint32_t b = 0; b < 16; ++b) {
-                    const uint32_t kb = 64u * c + 16u * q + b;
-                    const int v = fmd_st_a_entry(&wr[(size_t)k * N], &wi[(size_t)k * N], N, comp, kb, 0u);
-                    const int lo = ((v + 64) & 127) - 64, hi = (v - lo) / 128;
-                    ab[base + b] = (uint8_t)(int8_t)(dsel == 0u ? v : (dsel == 1u ? lo : hi));
-                }
-            }
+    std::vector<uint32_t> inc(N);
+    for (uint32_t k = 0; k < N; ++k) inc[k] = k * (uint32_t)((1ull << 32) / N);
+    fmd_ddc_build_plan(w, N, inc.data(), 1u, N, 1u, (2u * N + 63u) / 64u, P);
 }
 
 uint64_t sp_frames(uint32_t N, uint32_t hop, uint64_t nbytes)
@@ -269,8 +204,8 @@ int sp_enqueue(fmd_spectrum* h, const void* d_iq, size_t nbytes, uint64_t F, voi
     L.hop = h->hop; L.F = (uint32_t)F;
     L.n_bins = h->N; L.nrt = h->nrt; L.digits = h->digits; L.shift = h->shift;
     L.aligned = ((uintptr_t)d_iq & 15u) == 0 && nbytes % 16 == 0 ? 1u : 0u;
-    L.amat = reinterpret_cast<const sp_i4*>(h->d_amat);
-    L.kconst = h->d_kconst;
+    L.amat = reinterpret_cast<const sp_i4*>(h->core.d_amat);
+    L.kconst = h->core.d_kconst;
     L.power = static_cast<unsigned long long*>(d_power);
     // blocks: about 2048 over the whole grid, each at least one batch of every wave
     const uint32_t batch = 16u * (h->nkc >= 8 ? 4u : 8u);
@@ -283,8 +218,8 @@ int sp_enqueue(fmd_spectrum* h, const void* d_iq, size_t nbytes, uint64_t F, voi
     fpb = (fpb + batch - 1) / batch * batch;
     bps = (F + fpb - 1) / fpb;
     L.fpb = (uint32_t)fpb;
-    SP_TRY(h->order.before(stream));
-    if (!accumulate) SP_TRY(hipMemsetAsync(d_power, 0, (size_t)h->S * h->N * sizeof(uint64_t), stream));
+    FMD_DDC_TRY(h->core.order.before(stream));
+    if (!accumulate) FMD_DDC_TRY(hipMemsetAsync(d_power, 0, (size_t)h->S * h->N * sizeof(uint64_t), stream));
     const size_t lds = (size_t)h->N * 16u;
     const dim3 grid((uint32_t)bps, h->S), block(kThreads);
     switch (h->nkc) {
@@ -293,8 +228,8 @@ int sp_enqueue(fmd_spectrum* h, const void* d_iq, size_t nbytes, uint64_t F, voi
     case 4: hipLaunchKernelGGL(fmd_spectrum_power_kernel<4>, grid, block, lds, stream, L); break;
     default: hipLaunchKernelGGL(fmd_spectrum_power_kernel<8>, grid, block, lds, stream, L); break;
     }
-    SP_TRY(hipGetLastError());
-    (void)h->order.after(stream);
+    FMD_DDC_TRY(hipGetLastError());
+    (void)h->core.order.after(stream);
     return FMD_OK;
 }
 
@@ -344,28 +279,16 @@ int fmd_spectrum_new(const int16_t* window, uint32_t n_bins, uint32_t hop, uint3
     fmd_spectrum* h = new (std::nothrow) fmd_spectrum();
     if (!h) return FMD_ERR_NOMEM;
     h->N = n_bins; h->hop = hop; h->shift = shift; h->S = dev->n_channels;
-    std::vector<uint32_t> amat;
-    std::vector<int32_t> kconst;
-    sp_build_plan(window, n_bins, h, amat, kconst);
+    FmdDdcPlan P;
+    sp_build_plan(window, n_bins, P);
+    h->digits = P.digits; h->nrt = P.nrt; h->nkc = P.nkc;
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { delete h; fmd_internal_set_err("no HIP device (this library has no CPU path)"); return FMD_ERR_NO_DEVICE; }
-    int device = dev->device_id;
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    hipDeviceProp_t prop;
-    if (device >= ndev || hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        delete h; fmd_internal_set_err("device is not a gfx950"); return FMD_ERR_NO_DEVICE;
-    }
-    h->device = device;
+    if (const int rc = fmd_ddc_open(h->core, dev)) { delete h; return rc; }
     auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_spectrum_free(h); return FMD_ERR_HIP; };
-    FmdDeviceGuard guard(device);
+    FmdDeviceGuard guard(h->core.device);
     if (guard.error() != hipSuccess) return fail("hipSetDevice");
-    if (hipMalloc(&h->d_amat, amat.size() * 4) != hipSuccess || hipMemcpy(h->d_amat, amat.data(), amat.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return fail("hipMalloc(tap matrix)");
-    if (hipMalloc(&h->d_kconst, kconst.size() * 4) != hipSuccess || hipMemcpy(h->d_kconst, kconst.data(), kconst.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return fail("hipMalloc(constants)");
-    if (hipMalloc(&h->d_power, (size_t)h->S * n_bins * sizeof(uint64_t)) != hipSuccess) return fail("hipMalloc(power)");
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate");
+    if (const char* what = fmd_ddc_upload(h->core, P, 0)) return fail(what);
+    if (fmd_ddc_grow(h->core.d_out, h->core.d_out_cap, (size_t)h->S * n_bins * sizeof(uint64_t)) != hipSuccess) return fail("hipMalloc(power)");
     if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
     *out = h;
     return FMD_OK;
@@ -374,14 +297,8 @@ int fmd_spectrum_new(const int16_t* window, uint32_t n_bins, uint32_t hop, uint3
 void fmd_spectrum_free(fmd_spectrum* h)
 {
     if (!h) return;
-    FmdDeviceGuard guard(h->device);
-    (void)hipDeviceSynchronize();
-    h->order.destroy();
-    if (h->d_amat) (void)hipFree(h->d_amat);
-    if (h->d_kconst) (void)hipFree(h->d_kconst);
-    if (h->d_iq) (void)hipFree(h->d_iq);
-    if (h->d_power) (void)hipFree(h->d_power);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    FmdDeviceGuard guard(h->core.device);
+    fmd_ddc_release(h->core);
     delete h;
 }
 
@@ -391,18 +308,15 @@ int fmd_spectrum_power_batch(fmd_spectrum* h, const uint8_t* iq, size_t nbytes, 
     uint64_t F = 0;
     int rc = sp_check_len(h, nbytes, &F);
     if (rc) return rc;
-    SP_ON_DEVICE(h->device);
+    FMD_DDC_ON_DEVICE(h->core.device);
+    FmdDdcCore& c = h->core;
     const size_t in_bytes = nbytes * (size_t)h->S;
-    if (in_bytes > h->d_iq_cap) {
-        if (h->d_iq) { SP_TRY(hipFree(h->d_iq)); h->d_iq = nullptr; h->d_iq_cap = 0; }
-        SP_TRY(hipMalloc(&h->d_iq, in_bytes));
-        h->d_iq_cap = in_bytes;
-    }
-    SP_TRY(hipMemcpyAsync(h->d_iq, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = sp_enqueue(h, h->d_iq, nbytes, F, h->d_power, false, h->stream);
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
+    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
+    rc = sp_enqueue(h, c.d_iq, nbytes, F, c.d_out, false, c.stream);
     if (rc) return rc;
-    SP_TRY(hipMemcpyAsync(power, h->d_power, (size_t)h->S * h->N * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    SP_TRY(hipStreamSynchronize(h->stream));
+    FMD_DDC_TRY(hipMemcpyAsync(power, c.d_out, (size_t)h->S * h->N * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
+    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
     return FMD_OK;
 }
 
@@ -413,16 +327,16 @@ int fmd_spectrum_power_device(fmd_spectrum* h, const void* d_iq, size_t nbytes, 
     int rc = sp_check_len(h, nbytes, &F);
     if (rc) return rc;
     if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_power & 7u) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
-    SP_ON_DEVICE(h->device);
+    FMD_DDC_ON_DEVICE(h->core.device);
     return sp_enqueue(h, d_iq, nbytes, F, d_power, accumulate != 0, static_cast<hipStream_t>(stream));
 }
 
 int fmd_spectrum_check(fmd_spectrum* h)
 {
     if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    SP_ON_DEVICE(h->device);
-    SP_TRY(h->order.wait_last());
-    SP_TRY(hipGetLastError());
+    FMD_DDC_ON_DEVICE(h->core.device);
+    FMD_DDC_TRY(h->core.order.wait_last());
+    FMD_DDC_TRY(hipGetLastError());
     return FMD_OK;
 }
 
@@ -435,8 +349,7 @@ int fmd_spectrum_tap_digits(const fmd_spectrum* h)
 int fmd_spectrum_kernel_name(const fmd_spectrum* h, char* name, size_t cap)
 {
     if (!h || !name || cap == 0) return FMD_ERR_INVALID_ARG;
-    const int n = snprintf(name, cap, "fmd_sp::fmd_spectrum_power_kernel<%u>", h->nkc);
-    return n < 0 || (size_t)n >= cap ? FMD_ERR_CAPACITY : FMD_OK;
+    return fmd_ddc_name_rc(snprintf(name, cap, "fmd_sp::fmd_spectrum_power_kernel<%u>", h->nkc), cap);
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@
 //   1. stage the raw bytes of the tile's filter windows in LDS (global_load_lds_dwordx4; through registers where the range touches
 //      the stream's history or is not 16-byte aligned), and the NCO table;
 //   2. the contraction on the matrix cores, v_mfma_i32_16x16x64_i8: A = the stream's station tap matrix (rows: station x
-//      {zr, zi} x i8 digit, fmd_stations_common.h), B = window bytes (xor 0x80 -> s8), one column per filter output.  A window
+//      {zr, zi} x i8 digit, fmd_ddc.h), B = window bytes (xor 0x80 -> s8), one column per filter output.  A window
 //      starts at 2 D m bytes, only 4-byte aligned: wave w takes the outputs o = w + 4 i of the tile, whose windows sit 8 D i
 //      bytes apart -- 16-byte aligned for even D -- at a common offset delta in {0, 4, 8, 12} from an aligned address; the host
 //      built the A fragments for each delta, and the wave loads the set that fits its offset;
@@ -25,33 +25,21 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <new>
-#include <vector>
 
+#include "fmd_ddc.h"
 #include "fmd_device.h"
-#include "fmd_host.h"
 #include "fmd_internal.h"
 #include "fmd_kernels.h"
-#include "fmd_stations_common.h"
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FMD_ST_GLOBAL __attribute__((address_space(1)))
-#else
-#define FMD_ST_GLOBAL
-#endif
 
 namespace fmd_st {
 
 using namespace fmd_dev;
+using fmd_ddc::kThreads;
+using fmd_ddc::kTableBytes;
 
-constexpr int kThreads = 256;
-constexpr uint32_t kGroupsPerWave = 4;                    // 16-column MFMA groups per wave: 4 waves x 4 x 16 = 256 outputs per tile
-constexpr uint32_t kMaxOutputs = 4u * 16u * kGroupsPerWave;
-constexpr uint32_t kTableBytes = 2048;                    // 1024 x i16
-typedef int st_i4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t kMaxOutputs = 4u * 16u * fmd_ddc::kGroups;   // 4 waves x 4 groups x 16 columns = 256 outputs per tile
 
 struct StLaunch {
     const uint8_t* iq;         // [S][nbytes]
@@ -84,21 +72,6 @@ struct StLaunch {
     int32_t f64_skew;          // -DFMD_EXPERIMENT builds only
 };
 
-__device__ __forceinline__ uint32_t virt_dword(const StLaunch& L, uint32_t s, uint32_t v)   // v: virtual byte, multiple of 4
-{
-    typedef const FMD_ST_GLOBAL uint32_t* gw;
-    if (v < L.HB) return ((gw)(uintptr_t)(L.hist_in + (uint64_t)s * L.HB + v))[0];
-    const uint64_t b = (uint64_t)(v - L.HB);
-    if (b >= L.nbytes) return 0u;                          // beyond the call: only outputs that are discarded read it
-    return ((gw)(uintptr_t)(L.iq + (uint64_t)s * L.nbytes + b))[0];
-}
-
-__device__ __forceinline__ void dma16(const unsigned char* g, unsigned char* lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 2 /* nt */);
-}
-
 static __device__ __noinline__ void exc_emit_st(FmdExcBuf* exc, uint32_t c, uint32_t seq, int k, int sum, int d_gpu, int cr, int ci,
                                                 int16_t* out_elem)
 {
@@ -108,16 +81,6 @@ static __device__ __noinline__ void exc_emit_st(FmdExcBuf* exc, uint32_t c, uint
     atomicAdd(&exc->guarded_total, 1u);
     const uint32_t slot = atomicAdd(&exc->count, 1u);
     if (slot < FMD_EXC_CAP) exc->rec[slot] = e; else atomicOr(&exc->err, FMD_DEVERR_EXC_CAP);
-}
-
-// rotation back to baseband and the normalising shift (include/fmd.h step 5), packed re | im << 16
-__device__ __forceinline__ uint32_t st_rotate(const int16_t* tab, int zr, int zi, uint32_t psi, uint32_t sh)
-{
-    const uint32_t ix = psi >> 22;
-    const int64_t C = tab[ix], S = tab[(ix - 256u) & 1023u];
-    const int yr = (int)(((int64_t)zr * C + (int64_t)zi * S) >> sh);
-    const int yi = (int)(((int64_t)zi * C - (int64_t)zr * S) >> sh);
-    return pack_lp(yr, yi);
 }
 
 __global__ void __launch_bounds__(kThreads) fmd_stations_kernel(const StLaunch L)
@@ -145,89 +108,12 @@ __global__ void __launch_bounds__(kThreads) fmd_stations_kernel(const StLaunch L
     int* const gse = reinterpret_cast<int*>(ypk + L.K * L.lp_cap);           // (first, last) discriminator sample of each group
 
     // ---- 1. staging ---------------------------------------------------------------------------------------------------------
-    const uint8_t* const row = L.iq + (uint64_t)s * L.nbytes;
-    const bool whole = base >= L.HB && (uint64_t)(base - L.HB) + 16ull * nq <= L.nbytes && (((uintptr_t)row + (base - L.HB)) & 15u) == 0u;
-    if (whole) {
-        const unsigned char* src = row + (base - L.HB) + 16u * tid;
-        unsigned char* dst = reinterpret_cast<unsigned char*>(lds) + 1024u * wave;
-        const uint32_t nfull = nq / kThreads, ntail = nq - nfull * kThreads;
-        for (uint32_t l = 0; l < nfull; ++l) dma16(src + (16u * kThreads) * l, dst + (16u * kThreads) * l);
-        if (tid < ntail) dma16(src + (16u * kThreads) * nfull, dst + (16u * kThreads) * nfull);
-    } else {
-        st_i4* lq = reinterpret_cast<st_i4*>(lds);
-        for (uint32_t i = tid; i < nq; i += kThreads) {
-            const uint32_t v = base + 16u * i;
-            lq[i] = st_i4{(int)virt_dword(L, s, v), (int)virt_dword(L, s, v + 4u), (int)virt_dword(L, s, v + 8u), (int)virt_dword(L, s, v + 12u)};
-        }
-    }
-    {
-        typedef const FMD_ST_GLOBAL uint32_t* gw;
-        uint32_t* const tw = reinterpret_cast<uint32_t*>(tab);
-        for (uint32_t i = tid; i < kTableBytes / 4u; i += kThreads) tw[i] = ((gw)(uintptr_t)L.tab)[i];
-    }
+    fmd_ddc::stage(L, s, base, nq, lds, tab, tid, wave);
     __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0): the LDS-DMAs have landed
     __syncthreads();
 
     // ---- 2./3. contraction on the matrix cores, rotation, packing -----------------------------------------------------------
-    {
-        const uint8_t* lb = reinterpret_cast<const uint8_t*>(lds);
-        const uint32_t j = lane & 15u, q = lane >> 4;
-        const uint32_t pw = d0 + 2u * L.D * wave;           // window of the wave's first output o0 + wave
-        const uint32_t aw = pw & ~15u, dl = (pw & 15u) >> 2;
-        const uint32_t nout_w = no > wave ? (no - wave + 3u) >> 2 : 0u;
-        const uint32_t groups = (nout_w + 15u) >> 4;        // wave-uniform, <= kGroupsPerWave
-        typedef const FMD_ST_GLOBAL st_i4* gq;
-        const gq amat = (gq)(uintptr_t)L.amat + (((uint64_t)s * 4u + dl) * L.nrt) * L.nkc * 64u + lane;
-        const uint32_t col = aw + 8u * L.D * j + 16u * q;   // this lane's B bytes of group 0, chunk 0
-        const uint32_t sh = 14u + L.shift;
-        for (uint32_t rt = 0; rt < L.nrt; ++rt) {
-            st_i4 acc[kGroupsPerWave];
-#pragma unroll
-            for (uint32_t g = 0; g < kGroupsPerWave; ++g) acc[g] = st_i4{0, 0, 0, 0};
-            for (uint32_t kc = 0; kc < L.nkc; ++kc) {
-                const st_i4 A = amat[(rt * L.nkc + kc) * 64u];
-#pragma unroll
-                for (uint32_t g = 0; g < kGroupsPerWave; ++g) {
-                    if (g < groups) {
-                        st_i4 B = *reinterpret_cast<const st_i4*>(lb + col + 128u * L.D * g + 64u * kc);
-                        B = B ^ (int)0x80808080;                                               // u8 -> s8
-                        acc[g] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, acc[g], 0, 0, 0);
-                    }
-                }
-            }
-            // lane (j, q) holds rows 4 q ... 4 q + 3 of column j: two digits -> (zr_lo, zr_hi, zi_lo, zi_hi) of station 4 rt + q;
-            // one digit -> (zr, zi) of stations 8 rt + 2 q and 8 rt + 2 q + 1
-#pragma unroll
-            for (uint32_t g = 0; g < kGroupsPerWave; ++g) {
-                const uint32_t o = wave + 4u * (16u * g + j);  // output o0 + o of the call
-                if (g < groups && o < no) {
-                    const uint32_t m = L.m0_lo + o0 + o;
-                    const uint32_t yi = o0 + o - (uint32_t)jfirst;
-                    if (L.digits == 2u) {
-                        const uint32_t k = 4u * rt + q;
-                        if (k < L.K) {
-                            const uint32_t sk = s * L.K + k;
-                            const int zr = (int)((uint32_t)acc[g].x + ((uint32_t)acc[g].y << 7)) + L.kconst[2u * sk];
-                            const int zi = (int)((uint32_t)acc[g].z + ((uint32_t)acc[g].w << 7)) + L.kconst[2u * sk + 1u];
-                            ypk[k * L.lp_cap + yi] = st_rotate(tab, zr, zi, m * L.dinc[sk], sh);
-                        }
-                    } else {
-                        const uint32_t k = 8u * rt + 2u * q;
-                        if (k < L.K) {
-                            const uint32_t sk = s * L.K + k;
-                            ypk[k * L.lp_cap + yi] = st_rotate(tab, acc[g].x + L.kconst[2u * sk], acc[g].y + L.kconst[2u * sk + 1u],
-                                                               m * L.dinc[sk], sh);
-                        }
-                        if (k + 1u < L.K) {
-                            const uint32_t sk = s * L.K + k + 1u;
-                            ypk[(k + 1u) * L.lp_cap + yi] = st_rotate(tab, acc[g].z + L.kconst[2u * sk], acc[g].w + L.kconst[2u * sk + 1u],
-                                                                      m * L.dinc[sk], sh);
-                        }
-                    }
-                }
-            }
-        }
-    }
+    fmd_ddc::contract(L, s, wave, lane, d0, no, L.m0_lo + o0, lds, tab, ypk, L.lp_cap, o0 - (uint32_t)jfirst);
     if (jfirst < 0)                                          // y[-1] = demod_pre of every station
         for (uint32_t k = tid; k < L.K; k += kThreads) {
             const FmdChanState& st = L.st_in[s * L.K + k];
@@ -246,11 +132,7 @@ __global__ void __launch_bounds__(kThreads) fmd_stations_kernel(const StLaunch L
         gse[2u * k] = s0; gse[2u * k + 1u] = e;
     }
     // the stream's last tile also writes the next call's history (virtual bytes nbytes ... nbytes + HB)
-    if (T.last) {
-        typedef FMD_ST_GLOBAL uint32_t* gwo;
-        for (uint32_t i = tid; i < L.HB / 4u; i += kThreads)
-            ((gwo)(uintptr_t)(L.hist_out + (uint64_t)s * L.HB))[i] = virt_dword(L, s, (uint32_t)L.nbytes + 4u * i);
-    }
+    if (T.last) fmd_ddc::write_history(L, s, tid);
     __syncthreads();
 
     // ---- 4. fm_demod (:355-367) + low_pass_real (:408-426), one lane per (station, audio group) ---------------------------------
@@ -300,36 +182,14 @@ __global__ void __launch_bounds__(kThreads) fmd_stations_kernel(const StLaunch L
     }
 }
 
-#define ST_TRY(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof m_, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-            fmd_internal_set_err(m_);                                                       \
-            return e_ == hipErrorOutOfMemory ? FMD_ERR_NOMEM : FMD_ERR_HIP;                 \
-        }                                                                                   \
-    } while (0)
-
-#define ST_ON_DEVICE(dev)                                                                   \
-    FmdDeviceGuard dev_guard_(dev);                                                         \
-    if (dev_guard_.error() != hipSuccess) { fmd_internal_set_err("hipSetDevice failed"); return FMD_ERR_HIP; }
-
 }  // namespace fmd_st
 
 struct fmd_stations {
     uint32_t T = 0, D = 0, K = 0, S = 0, shift = 0, HB = 0;
     uint32_t lp_bound = 0;                                // ceil(256 max_gain / 2^shift): the largest |y| component
-    int device = 0;
-    uint64_t pos = 0;                                     // samples consumed per stream
-    FmdStationsPlan plan;
-    uint32_t* d_amat = nullptr;
-    int32_t* d_kconst = nullptr;
-    uint32_t* d_dinc = nullptr;
-    uint32_t* d_tab = nullptr;
-    uint8_t* d_hist[2] = {nullptr, nullptr};
-    FmdChanState* d_state[2] = {nullptr, nullptr};
-    int cur = 0;
+    FmdDdcPlan plan;
+    FmdDdcCore core;
+    FmdChanState* d_state[2] = {nullptr, nullptr};        // read [core.cur], written [core.cur ^ 1]
     FmdRates r{};
     uint32_t i0r = 0;                                     // resampler phase (identical for every station)
     uint32_t lp_cap = 0, raw_bytes = 0;
@@ -340,16 +200,12 @@ struct fmd_stations {
     int32_t f64_skew = 0;
     uint32_t seq = 0;
     uint64_t f64_guarded = 0, f64_patched = 0;
-    FmdStreamOrder order;
-    hipStream_t stream = nullptr;
-    uint8_t* d_iq = nullptr; size_t d_iq_cap = 0;
-    int16_t* d_out = nullptr; size_t d_out_cap = 0;
 };
 
 namespace {
 
 using fmd_st::kMaxOutputs;
-using fmd_st::kTableBytes;
+using fmd_ddc::kTableBytes;
 
 constexpr size_t kLdsBudget = 40960;                      // 4 tiles per CU
 
@@ -372,7 +228,7 @@ bool st_sizes(const fmd_stations* b, uint32_t kt, uint32_t* lp_cap, uint32_t* ra
 
 void st_counts(const fmd_stations* b, uint64_t ns, uint64_t* m0, uint64_t* m1)
 {
-    const uint64_t S = b->pos, T = b->T, M = b->D;
+    const uint64_t S = b->core.pos, T = b->T, M = b->D;
     *m0 = S >= T ? (S - T) / M + 1 : 0;
     *m1 = S + ns >= T ? (S + ns - T) / M + 1 : 0;
 }
@@ -398,13 +254,14 @@ int st_enqueue(fmd_stations* b, const void* d_iq, size_t nbytes, void* d_out, si
     if (L.P.nt > (1u << 30) || b->S > 65535u) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
     L.iq = static_cast<const uint8_t*>(d_iq);
     L.nbytes = nbytes;
-    L.hist_in = b->d_hist[b->cur]; L.hist_out = b->d_hist[b->cur ^ 1];
+    FmdDdcCore& c = b->core;
+    L.hist_in = c.d_hist[c.cur]; L.hist_out = c.d_hist[c.cur ^ 1];
     L.HB = b->HB;
-    L.vb_first = (uint32_t)(2ull * (b->D * m0 + b->HB / 2 - b->pos));   // >= 0: the window of output m0 starts at most n_taps - 1 samples back
+    L.vb_first = (uint32_t)(2ull * (b->D * m0 + b->HB / 2 - c.pos));   // >= 0: the window of output m0 starts at most n_taps - 1 samples back
     L.m0_lo = (uint32_t)m0;
     L.D = b->D; L.T = b->T; L.K = b->K; L.S = b->S; L.shift = b->shift;
     L.nrt = b->plan.nrt; L.nkc = b->plan.nkc; L.digits = b->plan.digits;
-    L.amat = b->d_amat; L.kconst = b->d_kconst; L.dinc = b->d_dinc; L.tab = b->d_tab;
+    L.amat = c.d_amat; L.kconst = c.d_kconst; L.dinc = c.d_dinc; L.tab = c.d_tab;
     L.r = r; L.tl = fmd_make_tiling(r);
     L.fa = r.fr / r.sr; L.fb = r.fr % r.sr;
     L.sr_shift = 32u;
@@ -412,24 +269,24 @@ int st_enqueue(fmd_stations* b, const void* d_iq, size_t nbytes, void* d_out, si
     L.inv_sr = 1.0f / (float)r.sr; L.inv_R = 1.0f / (float)r.R;
     L.lp_cap = b->lp_cap; L.raw_bytes = b->raw_bytes;
     L.f32_disc = b->lp_bound <= 2048u ? 1u : 0u;
-    L.st_in = b->d_state[b->cur]; L.st_out = b->d_state[b->cur ^ 1];
+    L.st_in = b->d_state[c.cur]; L.st_out = b->d_state[c.cur ^ 1];
     L.out = static_cast<int16_t*>(d_out); L.out_stride = out_cap;
     L.exc = b->d_exc; L.f64_guard = b->f64_guard; L.seq = b->seq + 1; L.f64_skew = b->f64_skew;
-    ST_TRY(b->order.before(stream));
+    FMD_DDC_TRY(c.order.before(stream));
     hipLaunchKernelGGL(fmd_st::fmd_stations_kernel, dim3(L.P.nt, b->S), dim3(fmd_st::kThreads), b->lds, stream, L);
-    ST_TRY(hipGetLastError());
-    (void)b->order.after(stream);
+    FMD_DDC_TRY(hipGetLastError());
+    (void)c.order.after(stream);
     b->seq += 1;
-    b->cur ^= 1;
+    c.cur ^= 1;
     b->i0r = fmd_next_lpr_index_r(r, b->i0r, L.P.M, L.P.K);
-    b->pos += ns;
+    c.pos += ns;
     if (n_each) *n_each = L.P.K;
     return FMD_OK;
 }
 
 int st_settle(fmd_stations* b, int16_t* host_out, size_t host_cap)
 {
-    return fmd_internal_resolve_exc(b->d_exc, b->r.R, b->seq, b->seq, b->d_state[b->cur], host_out, host_cap, &b->f64_guarded,
+    return fmd_internal_resolve_exc(b->d_exc, b->r.R, b->seq, b->seq, b->d_state[b->core.cur], host_out, host_cap, &b->f64_guarded,
                                     &b->f64_patched);
 }
 
@@ -517,37 +374,16 @@ int fmd_stations_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint3
     if (const char* g = fmd_knob("FMD_F64_GUARD_LOG2")) b->f64_guard = ldexp(1.0, atoi(g));   // experiment build only
     b->f64_skew = fmd_knob_i32("FMD_F64_SKEW", 0);
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { delete b; fmd_internal_set_err("no HIP device (this library has no CPU path)"); return FMD_ERR_NO_DEVICE; }
-    int device = dev->device_id;
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    hipDeviceProp_t prop;
-    if (device >= ndev || hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        delete b; fmd_internal_set_err("device is not a gfx950"); return FMD_ERR_NO_DEVICE;
-    }
-    b->device = device;
+    if (const int rc = fmd_ddc_open(b->core, dev)) { delete b; return rc; }
     auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_stations_free(b); return FMD_ERR_HIP; };
-    FmdDeviceGuard guard(device);
+    FmdDeviceGuard guard(b->core.device);
     if (guard.error() != hipSuccess) return fail("hipSetDevice");
-    const FmdStationsPlan& P = b->plan;
-    if (hipMalloc(&b->d_amat, P.amat.size() * 4) != hipSuccess || hipMemcpy(b->d_amat, P.amat.data(), P.amat.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return fail("hipMalloc(tap matrix)");
-    if (hipMalloc(&b->d_kconst, P.kconst.size() * 4) != hipSuccess || hipMemcpy(b->d_kconst, P.kconst.data(), P.kconst.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return fail("hipMalloc(constants)");
-    if (hipMalloc(&b->d_dinc, P.dinc.size() * 4) != hipSuccess || hipMemcpy(b->d_dinc, P.dinc.data(), P.dinc.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return fail("hipMalloc(phase steps)");
-    int16_t tab[1024];
-    fmd_st_nco_table(tab);
-    if (hipMalloc(&b->d_tab, sizeof tab) != hipSuccess || hipMemcpy(b->d_tab, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess)
-        return fail("hipMalloc(NCO table)");
-    const size_t hb = (size_t)b->S * (b->HB ? b->HB : 16), sb = (size_t)b->S * b->K * sizeof(FmdChanState);
-    for (int i = 0; i < 2; ++i) {
-        if (hipMalloc(&b->d_hist[i], hb) != hipSuccess || hipMemset(b->d_hist[i], 0, hb) != hipSuccess) return fail("hipMalloc(history)");
+    if (const char* what = fmd_ddc_upload(b->core, b->plan, (size_t)b->S * (b->HB ? b->HB : 16))) return fail(what);
+    const size_t sb = (size_t)b->S * b->K * sizeof(FmdChanState);
+    for (int i = 0; i < 2; ++i)
         if (hipMalloc(&b->d_state[i], sb) != hipSuccess || hipMemset(b->d_state[i], 0, sb) != hipSuccess) return fail("hipMalloc(state)");
-    }
     if (hipMalloc(&b->d_exc, sizeof(FmdExcBuf)) != hipSuccess || hipMemset(b->d_exc, 0, sizeof(FmdExcBuf)) != hipSuccess) return fail("hipMalloc(reports)");
     if (hipHostMalloc(reinterpret_cast<void**>(&b->h_head), 16, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc(report head)");
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate");
     if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
     *out = b;
     return FMD_OK;
@@ -556,33 +392,24 @@ int fmd_stations_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint3
 void fmd_stations_free(fmd_stations* b)
 {
     if (!b) return;
-    FmdDeviceGuard guard(b->device);
-    (void)hipDeviceSynchronize();
-    b->order.destroy();
-    if (b->d_amat) (void)hipFree(b->d_amat);
-    if (b->d_kconst) (void)hipFree(b->d_kconst);
-    if (b->d_dinc) (void)hipFree(b->d_dinc);
-    if (b->d_tab) (void)hipFree(b->d_tab);
-    for (int i = 0; i < 2; ++i) { if (b->d_hist[i]) (void)hipFree(b->d_hist[i]); if (b->d_state[i]) (void)hipFree(b->d_state[i]); }
+    FmdDeviceGuard guard(b->core.device);
+    fmd_ddc_release(b->core);
+    for (int i = 0; i < 2; ++i) if (b->d_state[i]) (void)hipFree(b->d_state[i]);
     if (b->d_exc) (void)hipFree(b->d_exc);
     if (b->h_head) (void)hipHostFree(b->h_head);
-    if (b->d_iq) (void)hipFree(b->d_iq);
-    if (b->d_out) (void)hipFree(b->d_out);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
 
 int fmd_stations_reset(fmd_stations* b)
 {
     if (!b) return FMD_ERR_INVALID_ARG;
-    ST_ON_DEVICE(b->device);
-    ST_TRY(hipDeviceSynchronize());
-    const size_t hb = (size_t)b->S * (b->HB ? b->HB : 16), sb = (size_t)b->S * b->K * sizeof(FmdChanState);
-    for (int i = 0; i < 2; ++i) { ST_TRY(hipMemset(b->d_hist[i], 0, hb)); ST_TRY(hipMemset(b->d_state[i], 0, sb)); }
-    ST_TRY(hipMemset(b->d_exc, 0, 16));
-    ST_TRY(hipDeviceSynchronize());
-    b->pos = 0; b->cur = 0; b->i0r = 0;
-    b->order.reset();
+    FMD_DDC_ON_DEVICE(b->core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    const size_t sb = (size_t)b->S * b->K * sizeof(FmdChanState);
+    for (int i = 0; i < 2; ++i) FMD_DDC_TRY(hipMemset(b->d_state[i], 0, sb));
+    FMD_DDC_TRY(hipMemset(b->d_exc, 0, 16));
+    FMD_DDC_TRY(fmd_ddc_zero_history(b->core));          // (ends with the device synchronised)
+    b->i0r = 0;
     return FMD_OK;
 }
 
@@ -590,61 +417,55 @@ int fmd_stations_demodulate_device(fmd_stations* b, const void* d_iq, size_t nby
                                    size_t* out_len_each, void* stream)
 {
     if (!b || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    ST_ON_DEVICE(b->device);
+    FMD_DDC_ON_DEVICE(b->core.device);
     return st_enqueue(b, d_iq, nbytes, d_out, out_cap, out_len_each, static_cast<hipStream_t>(stream));
 }
 
 int fmd_stations_check(fmd_stations* b)
 {
     if (!b) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    ST_ON_DEVICE(b->device);
-    if (b->order.have_last && b->h_head) {                   // one stream synchronisation in the common case (see fmd_demod_check)
+    FMD_DDC_ON_DEVICE(b->core.device);
+    const FmdStreamOrder& order = b->core.order;
+    if (order.have_last && b->h_head) {                      // one stream synchronisation in the common case (see fmd_demod_check)
         b->h_head[0] = b->h_head[1] = ~0u;
-        hipError_t e = hipMemcpyAsync(b->h_head, b->d_exc, 16, hipMemcpyDeviceToHost, b->order.last);
-        if (e == hipSuccess) e = hipStreamSynchronize(b->order.last);
+        hipError_t e = hipMemcpyAsync(b->h_head, b->d_exc, 16, hipMemcpyDeviceToHost, order.last);
+        if (e == hipSuccess) e = hipStreamSynchronize(order.last);
         if (e == hipSuccess && b->h_head[0] == 0u && b->h_head[1] == 0u) return FMD_OK;
         if (e != hipSuccess) (void)hipGetLastError();
     }
-    ST_TRY(hipDeviceSynchronize());
+    FMD_DDC_TRY(hipDeviceSynchronize());
     return st_settle(b, nullptr, 0);
 }
 
 int fmd_stations_demodulate_batch(fmd_stations* b, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap, size_t* out_len)
 {
     if (!b || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    ST_ON_DEVICE(b->device);
+    FMD_DDC_ON_DEVICE(b->core.device);
     if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
+    FmdDdcCore& c = b->core;
     const size_t rows = (size_t)b->S * b->K;
-    const size_t in_bytes = nbytes * (size_t)b->S, out_elems = out_cap * rows;
-    if (in_bytes > b->d_iq_cap) {
-        if (b->d_iq) { ST_TRY(hipFree(b->d_iq)); b->d_iq = nullptr; b->d_iq_cap = 0; }
-        ST_TRY(hipMalloc(&b->d_iq, in_bytes ? in_bytes : 1));
-        b->d_iq_cap = in_bytes;
-    }
-    if (out_elems > b->d_out_cap) {
-        if (b->d_out) { ST_TRY(hipFree(b->d_out)); b->d_out = nullptr; b->d_out_cap = 0; }
-        ST_TRY(hipMalloc(&b->d_out, (out_elems ? out_elems : 1) * sizeof(int16_t)));
-        b->d_out_cap = out_elems;
-    }
-    ST_TRY(hipMemcpyAsync(b->d_iq, iq, in_bytes, hipMemcpyHostToDevice, b->stream));
+    const size_t in_bytes = nbytes * (size_t)b->S, out_bytes = out_cap * rows * sizeof(int16_t);
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
+    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
     size_t n = 0;
-    int rc = st_enqueue(b, b->d_iq, nbytes, b->d_out, out_cap, &n, b->stream);
+    int rc = st_enqueue(b, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream);
     if (rc) return rc;
-    if (n) ST_TRY(hipMemcpyAsync(out, b->d_out, out_elems * sizeof(int16_t), hipMemcpyDeviceToHost, b->stream));
-    ST_TRY(hipStreamSynchronize(b->stream));
-    for (size_t c = 0; c < rows; ++c) out_len[c] = n;
+    if (n) FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
+    for (size_t row = 0; row < rows; ++row) out_len[row] = n;
     return st_settle(b, out, out_cap);
 }
 
 int fmd_stations_get_state(fmd_stations* b, uint32_t stream, uint32_t station, fmd_demod_state* state)
 {
     if (!b || !state || stream >= b->S || station >= b->K) { fmd_internal_set_err("bad argument"); return FMD_ERR_INVALID_ARG; }
-    ST_ON_DEVICE(b->device);
-    ST_TRY(hipDeviceSynchronize());
+    FMD_DDC_ON_DEVICE(b->core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
     int rc = st_settle(b, nullptr, 0);
     if (rc) return rc;
     FmdChanState s;
-    ST_TRY(hipMemcpy(&s, b->d_state[b->cur] + ((size_t)stream * b->K + station), sizeof(s), hipMemcpyDeviceToHost));
+    FMD_DDC_TRY(hipMemcpy(&s, b->d_state[b->core.cur] + ((size_t)stream * b->K + station), sizeof(s), hipMemcpyDeviceToHost));
     memset(state, 0, sizeof(*state));
     state->now_lpr = s.now_lpr;
     state->prev_lpr_index = (int32_t)(s.lpr_index_r * b->r.g);
@@ -663,8 +484,7 @@ int fmd_stations_f64_stats(const fmd_stations* b, uint64_t* guarded, uint64_t* p
 int fmd_stations_kernel_name(const fmd_stations* b, char* name, size_t cap)
 {
     if (!b || !name || cap == 0) return FMD_ERR_INVALID_ARG;
-    const int n = snprintf(name, cap, "fmd_st::fmd_stations_kernel");
-    return n < 0 || (size_t)n >= cap ? FMD_ERR_CAPACITY : FMD_OK;
+    return fmd_ddc_name_rc(snprintf(name, cap, "fmd_st::fmd_stations_kernel"), cap);
 }
 
 }  // extern "C"

@@ -7,10 +7,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DemodState, DeviceConfig, check, lib
+from ._ffi import CheckedHandle, DemodState, DeviceConfig, Handle, check, lib
 
 
-class FirBank:
+class FirBank(Handle):
+    _prefix = "fir"
+
     def __init__(self, taps, decim, n_channels=1, device_id=-1):
         self.taps = np.ascontiguousarray(taps, dtype=np.int16)
         self.decim, self.n_channels = int(decim), int(n_channels)
@@ -18,17 +20,6 @@ class FirBank:
         dev = DeviceConfig(self.n_channels, device_id, 0)
         check(lib().fmd_fir_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim,
                                 C.byref(dev), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib().fmd_fir_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:                                                 # (at interpreter shutdown the module globals may be gone already)
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         check(lib().fmd_fir_reset(self._h))
@@ -51,12 +42,6 @@ class FirBank:
         check(lib().fmd_fir_filter_batch(self._h, iq.ctypes.data, iq.shape[1], out.ctypes.data, cap, lens))
         return out[:, :lens[0], :].copy()
 
-    def kernel_name(self):
-        """The kernel this bank launches, as rocprofv3 --kernel-trace prints it."""
-        buf = C.create_string_buffer(128)
-        check(lib().fmd_fir_kernel_name(self._h, buf, len(buf)))
-        return buf.value.decode()
-
     def filter_device(self, d_iq, nbytes, d_out, out_cap, stream=None):
         """Enqueue on device pointers.  `stream` must stay alive until the handle's next `filter_device` call has returned
         (stream lifetime rule of include/fmd.h)."""
@@ -77,9 +62,10 @@ def auto_shift(taps, limit=2048):
     return s
 
 
-class FirDemodBank:
+class FirDemodBank(CheckedHandle):
     """Tapped FIR -> discriminator -> resampler in one kernel (include/fmd.h, fmd_firdemod_*): Demod::demodulate
     (simple_fm.rs:256-269) with the boxcar replaced by `taps` (decimate by `decim`, normalise by >> shift)."""
+    _prefix = "firdemod"
 
     def __init__(self, taps, decim, rate_out, rate_resample, n_channels=1, shift=None, device_id=-1):
         self.taps = np.ascontiguousarray(taps, dtype=np.int16)
@@ -90,17 +76,6 @@ class FirDemodBank:
         dev = DeviceConfig(self.n_channels, device_id, 0)
         check(lib().fmd_firdemod_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim, self.shift,
                                      self.rate_out, self.rate_resample, C.byref(dev), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib().fmd_firdemod_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:                                                 # (at interpreter shutdown the module globals may be gone already)
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         check(lib().fmd_firdemod_reset(self._h))
@@ -125,9 +100,6 @@ class FirDemodBank:
         n = C.c_size_t(0)
         check(lib().fmd_firdemod_demodulate_device(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
         return n.value
-
-    def check(self):
-        check(lib().fmd_firdemod_check(self._h))
 
     def get_state(self, channel=0):
         s = DemodState()
@@ -155,9 +127,3 @@ class FirDemodBank:
         a, b = C.c_uint32(), C.c_uint32()
         check(lib().fmd_firdemod_tiling(self._h, C.byref(a), C.byref(b)))
         return {"audio_per_tile": a.value, "lds_bytes": b.value}
-
-    def kernel_name(self):
-        """The kernel this bank launches, as rocprofv3 --kernel-trace prints it."""
-        buf = C.create_string_buffer(128)
-        check(lib().fmd_firdemod_kernel_name(self._h, buf, len(buf)))
-        return buf.value.decode()

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DeviceConfig, check, lib
+from ._ffi import DeviceConfig, CheckedHandle, check, lib
 
 
 def hann_window(n_bins, amplitude=2047):
@@ -14,9 +14,10 @@ def hann_window(n_bins, amplitude=2047):
     return w
 
 
-class Spectrum:
+class Spectrum(CheckedHandle):
     """N-bin power spectrum of `n_streams` streams: frames of N samples every `hop` samples, |DFT|^2 >> shift summed over the
     frames of a call (u64, natural DFT order).  `window` defaults to hann_window(n_bins)."""
+    _prefix = "spectrum"
 
     def __init__(self, n_bins, hop=None, window=None, shift=0, n_streams=1, device_id=-1):
         self.n_bins, self.n_streams = int(n_bins), int(n_streams)
@@ -27,17 +28,6 @@ class Spectrum:
         dev = DeviceConfig(self.n_streams, device_id, 0)
         check(lib().fmd_spectrum_new(self.window.ctypes.data_as(C.POINTER(C.c_int16)), self.window.size, self.hop, self.shift,
                                      C.byref(dev), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib().fmd_spectrum_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:                                                 # (at interpreter shutdown the module globals may be gone already)
-            self.close()
-        except Exception:
-            pass
 
     def frames(self, nbytes):
         return int(lib().fmd_spectrum_frames(self.n_bins, self.hop, int(nbytes)))
@@ -56,9 +46,6 @@ class Spectrum:
         `power_device` call or `check` has returned (stream lifetime rule of include/fmd.h)."""
         check(lib().fmd_spectrum_power_device(self._h, d_iq, int(nbytes), d_power, 1 if accumulate else 0, stream))
 
-    def check(self):
-        check(lib().fmd_spectrum_check(self._h))
-
     def tap_digits(self):
         return int(lib().fmd_spectrum_tap_digits(self._h))
 
@@ -72,11 +59,6 @@ class Spectrum:
         inc = C.c_uint32(0)
         check(lib().fmd_spectrum_bin_inc(int(k) % self.n_bins, self.n_bins, C.byref(inc)))
         return inc.value
-
-    def kernel_name(self):
-        buf = C.create_string_buffer(128)
-        check(lib().fmd_spectrum_kernel_name(self._h, buf, len(buf)))
-        return buf.value.decode()
 
 
 def find_stations(power, rate, count, channel_hz=200e3, min_snr_db=10.0):

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DemodState, DeviceConfig, check, lib
+from ._ffi import DemodState, DeviceConfig, CheckedHandle, check, lib, stream_phase_incs
 
 
 def phase_inc(offset_hz, rate):
@@ -43,19 +43,15 @@ def stations_auto_shift(taps, phase_incs, limit=2048):
     return s
 
 
-class StationBank:
+class StationBank(CheckedHandle):
     """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream)."""
+    _prefix = "stations"
 
     def __init__(self, taps, decim, phase_incs, rate_out, rate_resample, n_streams=1, shift=None, device_id=-1):
         self.taps = np.ascontiguousarray(taps, dtype=np.int16)
         self.decim, self.n_streams = int(decim), int(n_streams)
-        incs = np.asarray(phase_incs, dtype=np.uint32)
-        if incs.ndim == 1:
-            incs = np.tile(incs, (self.n_streams, 1))
-        if incs.ndim != 2 or incs.shape[0] != self.n_streams:
-            raise ValueError("phase_incs must be [n_streams, n_stations]")
-        self.phase_incs = np.ascontiguousarray(incs)
-        self.n_stations = incs.shape[1]
+        self.phase_incs = stream_phase_incs(phase_incs, self.n_streams)
+        self.n_stations = self.phase_incs.shape[1]
         self.rate_out, self.rate_resample = int(rate_out), int(rate_resample)
         self.shift = stations_auto_shift(self.taps, self.phase_incs) if shift is None else int(shift)
         self._h = C.c_void_p()
@@ -63,17 +59,6 @@ class StationBank:
         check(lib().fmd_stations_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim, self.shift,
                                      self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations, self.rate_out,
                                      self.rate_resample, C.byref(dev), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib().fmd_stations_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:                                                 # (at interpreter shutdown the module globals may be gone already)
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         check(lib().fmd_stations_reset(self._h))
@@ -99,9 +84,6 @@ class StationBank:
         check(lib().fmd_stations_demodulate_device(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
         return n.value
 
-    def check(self):
-        check(lib().fmd_stations_check(self._h))
-
     def get_state(self, stream=0, station=0):
         s = DemodState()
         check(lib().fmd_stations_get_state(self._h, stream, station, C.byref(s)))
@@ -111,9 +93,3 @@ class StationBank:
         g, p = C.c_uint64(), C.c_uint64()
         check(lib().fmd_stations_f64_stats(self._h, C.byref(g), C.byref(p)))
         return g.value, p.value
-
-    def kernel_name(self):
-        """The kernel this bank launches, as rocprofv3 --kernel-trace prints it."""
-        buf = C.create_string_buffer(128)
-        check(lib().fmd_stations_kernel_name(self._h, buf, len(buf)))
-        return buf.value.decode()
