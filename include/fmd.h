@@ -392,6 +392,60 @@ int fmd_channelizer_outputs(const fmd_channelizer *c, uint64_t *outputs);
 /* Name of the kernel this handle launches, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_channelizer_kernel_name(const fmd_channelizer *c, char *name, size_t cap);
 
+/* ---- stereo station bank: pilot-locked L/R audio per FM station ---------------------------------------------- */
+/* NEW SURFACE (the reference demodulates mono only).  This is the project's own operator, not the reference's chain: the
+ * channelizer's y, the reference's integer discriminator at the multiplex (MPX) rate, a block-wise pilot estimate and a
+ * FIR on the sum and the difference signal.  Definition (integers only; tests/stereo_ref.py), per (stream, station k):
+ *   y[m]      the channelizer's output (above), m counted from creation or reset
+ *   x[m]      = (i16) polar_discriminant_fast(y[m], y[m-1])        (simple_fm.rs:377-405; y[-1] = 0, y[m-1] carries across calls)
+ *   inc_p     = floor((19000 decim 2^32 + floor(capture_rate / 2)) / capture_rate) mod 2^32,  theta_m = m inc_p mod 2^32
+ *   block j   = the samples m with floor(m / P) = j;  I_j = sum x[m] cosq(theta_m),  Q_j = sum x[m] sinq(theta_m)  (exact, i64)
+ *   present_j = pilot_min > 0 && I_j^2 + Q_j^2 >= (pilot_min P 8192)^2                                          (exact, 128-bit)
+ *   e = max(0, bitlen(max(|I_j|, |Q_j|)) - 23),  a = I_j >> e,  b = Q_j >> e,  E = a^2 + b^2
+ *   c2_j = tdiv((b^2 - a^2) << 14, E),  s2_j = tdiv((2 a b) << 14, E)          (cos 2 alpha, sin 2 alpha in Q14; tdiv truncates)
+ *   kc[m] = (sinq(2 theta_m) c2 + cosq(2 theta_m) s2) >> 13 with the estimate of block j - 1 = floor(m / P) - 1 when that block is
+ *           present, 0 otherwise (block -1 is absent): 2 sin(2 theta + 2 alpha) in Q14 for a pilot A sin(theta + alpha)
+ *   s[m]  = (x[m] kc[m]) >> 14
+ *   M[n]  = sum_t g[t] x[R n + t],  S[n] = sum_t g[t] s[R n + t]     (t < Ta; exact in i32)
+ *   L[n]  = sat16((M + S) >> (audio_shift + 1)),  Rch[n] = sat16((M - S) >> (audio_shift + 1))
+ * Shifts are arithmetic (floor).  Audio sample n comes with the call in which x[R n + Ta - 1] arrives; out is
+ * [n_streams][n_stations][out_cap][2] int16 (L, R): interleaved stereo s16 at capture_rate / (decim R).
+ * Domain (else FMD_ERR_UNSUPPORTED, decided before a device is queried): the channelizer's filter domain; capture_rate >=
+ * 106000 decim; P a power of two in [1024, 16384]; 1 <= R <= 32; 1 <= Ta <= 256; sum |g| <= 16383; audio_shift <= 16;
+ * pilot_min <= 16384 (0: every block is absent, the output is mono).  nbytes % 8 != 0 -> FMD_ERR_BAD_LENGTH; a call that completes
+ * no audio sample -> FMD_ERR_TOO_SHORT and changes nothing.  Stream lifetime and completion points: as fmd_channelizer_*. */
+typedef struct fmd_stereo fmd_stereo;
+typedef struct fmd_stereo_config {
+    uint32_t capture_rate;   /* Hz: sets the pilot step inc_p                                         */
+    uint32_t block;          /* P: pilot-estimate block length in MPX samples                         */
+    uint32_t audio_decim;    /* R                                                                     */
+    uint32_t audio_shift;
+    uint32_t pilot_min;      /* presence threshold in discriminator units (the pilot's amplitude in x) */
+} fmd_stereo_config;
+int fmd_stereo_new(const int16_t *taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t *phase_inc,
+                   uint32_t n_stations, const int16_t *audio_taps, uint32_t n_audio_taps, const fmd_stereo_config *cfg,
+                   const fmd_device_config *dev, fmd_stereo **out);
+void fmd_stereo_free(fmd_stereo *s);
+int fmd_stereo_reset(fmd_stereo *s);
+/* ceil(nbytes / (2 decim R)): audio samples one call of nbytes can complete per (stream, station), whatever the history;
+ * 0 for decim 0 or R 0. */
+size_t fmd_stereo_out_cap(uint32_t decim, uint32_t audio_decim, size_t nbytes);
+/* HOST buffers; *out_len = audio samples per (stream, station) (the same for all). */
+int fmd_stereo_run_batch(fmd_stereo *s, const uint8_t *iq, size_t nbytes, int16_t *out, size_t out_cap, size_t *out_len);
+/* DEVICE buffers (d_iq and d_out 4-byte aligned), enqueued on `stream` without synchronising; *out_len as above. */
+int fmd_stereo_run_device(fmd_stereo *s, const void *d_iq, size_t nbytes, void *d_out, size_t out_cap, size_t *out_len,
+                          void *stream);
+int fmd_stereo_check(fmd_stereo *s);
+/* Audio samples per (stream, station) produced since creation or the last reset. */
+int fmd_stereo_outputs(const fmd_stereo *s, uint64_t *outputs);
+/* The last completed block's pilot: *present = present_j, *level = isqrt(I_j^2 + Q_j^2) / (P 8192), the pilot amplitude in
+ * discriminator units (0 and 0 before the first block completes).  Synchronises first. */
+int fmd_stereo_pilot(fmd_stereo *s, uint32_t stream, uint32_t station, int *present, uint32_t *level);
+/* inc_p of the definition; FMD_ERR_INVALID_ARG for capture_rate 0 or decim 0. */
+int fmd_stereo_pilot_inc(uint32_t capture_rate, uint32_t decim, uint32_t *inc);
+/* Name of pass 0 (front end + discriminator + pilot sums) or 1 (carrier, FIRs, matrix), as `rocprofv3 --kernel-trace` prints it. */
+int fmd_stereo_kernel_name(const fmd_stereo *s, uint32_t pass, char *name, size_t cap);
+
 /* ---- power spectrum: where the stations are ------------------------------------------------------------------ */
 /* NEW SURFACE (rtl_power's job in the rtl-sdr ecosystem; the reference has none).  The integrated power of N DFT bins of every
  * stream, to find the offsets a station bank is then tuned to.  A bin is a station-bank filter (the taps and the NCO table above)

@@ -138,6 +138,18 @@ PROTOTYPES = {
     "fmd_channelizer_check": (C.c_int, [_vp]),
     "fmd_channelizer_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "fmd_channelizer_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_stereo_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, _i16p, C.c_uint32,
+                                 _vp, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_stereo_free": (None, [_vp]),
+    "fmd_stereo_reset": (C.c_int, [_vp]),
+    "fmd_stereo_out_cap": (_sz, [C.c_uint32, C.c_uint32, _sz]),
+    "fmd_stereo_run_batch": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "fmd_stereo_run_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_stereo_check": (C.c_int, [_vp]),
+    "fmd_stereo_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "fmd_stereo_pilot": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "fmd_stereo_pilot_inc": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fmd_stereo_kernel_name": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_size_t]),
     "fmd_spectrum_hann": (C.c_int, [C.c_uint32, C.c_uint32, _i16p]),
     "fmd_spectrum_bin_inc": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "fmd_spectrum_frames": (_sz, [C.c_uint32, C.c_uint32, _sz]),

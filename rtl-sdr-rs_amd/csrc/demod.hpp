@@ -11,6 +11,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -267,6 +268,87 @@ public:
 private:
     uint32_t decim_, n_streams_, n_stations_;
     fmd_channelizer* h_ = nullptr;
+};
+
+// Audio taps of a StereoBank, as the Python stereo_taps(): a Hamming-windowed sinc low-pass at cutoff_hz convolved with the
+// sampled first-order de-emphasis response (tau_us 0: none), scaled to sum |g| <= 16383.
+inline std::vector<int16_t> stereo_taps(double mpx_rate, uint32_t n_taps, double cutoff_hz = 15000, double tau_us = 75)
+{
+    if (n_taps < 1 || n_taps > 256) throw Error(FMD_ERR_INVALID_ARG);
+    const double pi = 3.14159265358979323846;
+    std::vector<double> d(1, 1.0);
+    if (tau_us > 0) {
+        const uint32_t nd = std::max<uint32_t>(1, n_taps / 2);
+        const double a = std::exp(-1.0 / (tau_us * 1e-6 * mpx_rate));
+        d.assign(nd, 0.0);
+        for (uint32_t i = 0; i < nd; ++i) d[i] = (1 - a) * std::pow(a, (double)i);
+    }
+    const uint32_t nl = n_taps - (uint32_t)d.size() + 1;
+    std::vector<double> lp(nl), g(n_taps, 0.0);
+    const double fc = 2 * cutoff_hz / mpx_rate;
+    for (uint32_t i = 0; i < nl; ++i) {
+        const double t = i - (nl - 1) / 2.0, x = pi * fc * t;
+        const double w = nl > 1 ? 0.54 - 0.46 * std::cos(2 * pi * i / (nl - 1)) : 1.0;
+        lp[i] = fc * (t == 0 ? 1.0 : std::sin(x) / x) * w;
+    }
+    for (uint32_t i = 0; i < nl; ++i)
+        for (size_t j = 0; j < d.size(); ++j) g[i + j] += lp[i] * d[j];
+    double sum = 0;
+    for (double v : g) sum += std::fabs(v);
+    std::vector<int16_t> out(n_taps);
+    for (uint32_t i = 0; i < n_taps; ++i) out[i] = (int16_t)std::floor(g[i] / sum * (16383.0 - n_taps) + 0.5);
+    return out;
+}
+
+// Stereo station bank (fmd_stereo_*): run() takes [n_streams][nbytes] and returns interleaved (L, R) audio
+// [n_streams * n_stations] (row stream * n_stations + station) at capture_rate / (decim audio_decim).
+class StereoBank {
+public:
+    StereoBank(const std::vector<int16_t>& taps, uint32_t decim, uint32_t shift, const std::vector<uint32_t>& phase_incs,
+               uint32_t n_streams, const std::vector<int16_t>& audio_taps, const fmd_stereo_config& cfg, int32_t device_id = -1)
+        : decim_(decim), audio_decim_(cfg.audio_decim), n_streams_(n_streams),
+          n_stations_(n_streams ? (uint32_t)(phase_incs.size() / n_streams) : 0u)
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_stereo_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, audio_taps.data(),
+                             (uint32_t)audio_taps.size(), &cfg, &dev, &h_));
+    }
+    ~StereoBank() { fmd_stereo_free(h_); }
+    StereoBank(const StereoBank&) = delete;
+    StereoBank& operator=(const StereoBank&) = delete;
+
+    // FMD_ERR_TOO_SHORT (a call that completes no audio sample) returns empty rows and changes nothing.
+    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    {
+        const size_t cap = std::max<size_t>(1, fmd_stereo_out_cap(decim_, audio_decim_, nbytes));
+        const size_t rows = (size_t)n_streams_ * n_stations_;
+        std::vector<int16_t> out(2 * cap * rows);
+        size_t n = 0;
+        const int rc = fmd_stereo_run_batch(h_, iq, nbytes, out.data(), cap, &n);
+        if (rc == FMD_ERR_TOO_SHORT) return std::vector<std::vector<int16_t>>(rows);
+        check(rc);
+        std::vector<std::vector<int16_t>> res(rows);
+        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + 2 * r * cap, out.begin() + 2 * (r * cap + n));
+        return res;
+    }
+    std::pair<bool, uint32_t> pilot(uint32_t stream, uint32_t station)
+    {
+        int present = 0;
+        uint32_t level = 0;
+        check(fmd_stereo_pilot(h_, stream, station, &present, &level));
+        return {present != 0, level};
+    }
+    uint64_t outputs() const
+    {
+        uint64_t n = 0;
+        check(fmd_stereo_outputs(h_, &n));
+        return n;
+    }
+    void reset() { check(fmd_stereo_reset(h_)); }
+
+private:
+    uint32_t decim_, audio_decim_, n_streams_, n_stations_;
+    fmd_stereo* h_ = nullptr;
 };
 
 // Power spectrum (fmd_spectrum_*): power() takes [n_streams][nbytes] and returns u64 [n_streams][n_bins] in natural DFT order.

@@ -1,0 +1,570 @@
+// fmd_stereo.hip -- stereo station bank: pilot-locked L/R audio per FM station, K stations per wideband IQ stream, in two
+// gfx950 kernels per call.
+//
+// Definition (include/fmd.h, "stereo station bank"; tests/stereo_ref.py): the channelizer's y, the reference's integer
+// discriminator at the multiplex rate x[m] = (i16) polar_discriminant_fast(y[m], y[m-1]), the pilot's correlations I_j, Q_j per
+// block of P samples, the subcarrier kc[m] = 2 sin(2 theta + 2 alpha) in Q14 from the estimate of block j - 1, s = x kc >> 14,
+// and one FIR g (stride R) over the sum x and the difference s; L / R = (M +- S) >> (audio_shift + 1), saturated.
+//
+// Pass 1 (fmd_stereo_mpx_kernel): one workgroup = one tile of up to 64 G - 1 consecutive MPX samples of ONE stream, all K stations:
+//   1. - 3. the channelizer's front end (fmd_ddc.h: staging, contraction on v_mfma_i32_16x16x64_i8, rotation into LDS rows), over
+//      the tile's outputs AND the output before them (recomputed; the call's first tile takes it from the carried last y);
+//   4. one wave per station row: the integer discriminator (fmd_device.h disc_nosel), the pilot products x cosq(theta),
+//      x sinq(theta) summed per block (a tile touches at most two: P >= 1024), reduced across the wave and added into the call's
+//      block sums with 64-bit integer atomics (exact in any order); x stored as i16.
+// Pass 2 (fmd_stereo_audio_kernel): one workgroup = one (stream, station) row and one tile of up to 256 audio samples:
+//   1. the estimate (present, c2, s2) of each block the tile's inputs need, one lane per block (i64 / 128-bit arithmetic);
+//   2. (x, s) of every MPX sample the tile's FIR reads into LDS: the carried Ta - 1 samples of the previous call from the history,
+//      the call's own with s = (x kc) >> 14, kc from the NCO table in LDS;
+//   3. one lane per audio sample: both FIRs with v_mad_i32_i24 (|g| <= 16383, |x| <= 32768, |s| <= 65540 fit 24-bit operands), the
+//      matrix step, saturation, one dword store of the (L, R) pair.
+// The last tile of a row writes the next call's (x, s) history; tile 0 the next call's block carry (the sums of the last
+// complete block, the partial sums of a block that straddles calls).
+#include "../../include/fmd.h"
+
+#include <hip/hip_runtime.h>
+
+#include <new>
+
+#include "fmd_ddc.h"
+#include "fmd_device.h"
+#include "fmd_internal.h"
+
+namespace fmd_sto {
+
+using fmd_ddc::kThreads;
+using fmd_ddc::kTableBytes;
+
+constexpr uint32_t kAudioTile = 256;                      // audio samples per pass-2 tile (at most)
+constexpr uint32_t kXCap = 2048;                          // (x, s) pairs a pass-2 tile stages: R tile + 2 Ta <= kXCap
+constexpr uint32_t kMaxBlocks = 4;                        // blocks one pass-2 tile touches (<= 3: kXCap / 1024 + 1)
+
+struct MpxLaunch {
+    const uint8_t* iq;         // [S][nbytes]
+    uint64_t nbytes;
+    const uint8_t* hist_in;    // [S][HB]
+    uint8_t* hist_out;
+    uint32_t HB;
+    uint32_t vb_first;         // virtual byte of the window of the call's first output
+    uint64_t m0;               // global index of the call's first output
+    uint32_t M;                // outputs of this call per (stream, station)
+    uint32_t D, T, K, S, shift;
+    uint32_t nrt, nkc, digits;
+    uint32_t tile, cols;       // outputs per tile (cols - 1), LDS row length
+    uint32_t ntiles, raw_bytes;
+    uint32_t pshift, inc_p;    // log2 P, pilot step
+    uint64_t jfirst;           // block of the call's first output
+    const uint32_t* amat;
+    const int32_t* kconst;
+    const uint32_t* dinc;
+    const uint32_t* tab;
+    const uint32_t* ylast_in;  // [S K]: y[m0 - 1], packed
+    uint32_t* ylast_out;
+    int16_t* x;                // [S K][M]
+    unsigned long long* sums;  // [nbc][S K][2]: I, Q of block jfirst + i, this call's samples only
+};
+
+__device__ __forceinline__ long long wave_sum(long long v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(kThreads) fmd_stereo_mpx_kernel(const MpxLaunch L)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t s = blockIdx.y, t = blockIdx.x;
+    if (s >= L.S || t >= L.ntiles) return;
+
+    const uint32_t o0 = t * L.tile;                          // first output (of this call) of the tile
+    const uint32_t no = L.M - o0 < L.tile ? L.M - o0 : L.tile;
+    const uint32_t c0 = t ? o0 - 1u : o0;                    // first output contracted: the one before the tile, except in tile 0
+    const uint32_t nc = t ? no + 1u : no;
+    const uint32_t vb = L.vb_first + 2u * L.D * c0;
+    const uint32_t base = vb & ~15u, d0 = vb - base;
+    const uint32_t nq = (d0 + 2u * L.D * (nc - 1u) + 2u * L.T + 15u) >> 4;   // <= raw_bytes / 16: host plan
+    int16_t* const tab = reinterpret_cast<int16_t*>(lds + (L.raw_bytes >> 2));
+    uint32_t* const ypk = lds + ((L.raw_bytes + kTableBytes) >> 2);          // [K][cols]: y of output o0 - 1 + i at i
+
+    // ---- 1. staging ---------------------------------------------------------------------------------------------------------
+    fmd_ddc::stage(L, s, base, nq, lds, tab, tid, wave);
+    if (t == L.ntiles - 1u) fmd_ddc::write_history(L, s, tid);
+    __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0): the LDS-DMAs have landed
+    __syncthreads();
+
+    // ---- 2./3. contraction, rotation, packing -------------------------------------------------------------------------------
+    fmd_ddc::contract(L, s, wave, lane, d0, nc, (uint32_t)L.m0 + c0, lds, tab, ypk, L.cols, t ? 0u : 1u);
+    if (t == 0u)
+        for (uint32_t k = tid; k < L.K; k += kThreads) ypk[k * L.cols] = L.ylast_in[s * L.K + k];
+    __syncthreads();
+    if (t == L.ntiles - 1u)
+        for (uint32_t k = tid; k < L.K; k += kThreads) L.ylast_out[s * L.K + k] = ypk[k * L.cols + no];
+
+    // ---- 4. discriminator, pilot sums, x --------------------------------------------------------------------------------------
+    const uint64_t mt = L.m0 + o0;                           // global index of the tile's first output
+    const uint64_t b0 = mt >> L.pshift;
+    const uint64_t SK = (uint64_t)L.S * L.K;
+    for (uint32_t k = wave; k < L.K; k += 4u) {
+        const uint32_t* y = ypk + k * L.cols;
+        const uint64_t row = (uint64_t)s * L.K + k;
+        int16_t* const xo = L.x + row * L.M + o0;
+        long long i0 = 0, q0 = 0, i1 = 0, q1 = 0;
+        for (uint32_t o = lane; o < no; o += 64u) {
+            const int xv = (int)(int16_t)fmd_dev::disc_nosel(y[o + 1u], y[o]);
+            const uint64_t m = mt + o;
+            const uint32_t ix = ((uint32_t)m * L.inc_p) >> 22;
+            const int pc = xv * (int)tab[ix], ps = xv * (int)tab[(ix - 256u) & 1023u];   // |x tab| <= 2^29
+            if ((m >> L.pshift) == b0) { i0 += pc; q0 += ps; } else { i1 += pc; q1 += ps; }
+            xo[o] = (int16_t)xv;
+        }
+        i0 = wave_sum(i0); q0 = wave_sum(q0); i1 = wave_sum(i1); q1 = wave_sum(q1);
+        if (lane == 0u) {
+            unsigned long long* const p0 = L.sums + ((b0 - L.jfirst) * SK + row) * 2u;
+            atomicAdd(p0, (unsigned long long)i0);
+            atomicAdd(p0 + 1, (unsigned long long)q0);
+            if (((mt + no - 1u) >> L.pshift) != b0) {        // the tile straddles a block edge
+                unsigned long long* const p1 = p0 + 2u * SK;
+                atomicAdd(p1, (unsigned long long)i1);
+                atomicAdd(p1 + 1, (unsigned long long)q1);
+            }
+        }
+    }
+}
+
+struct AudioLaunch {
+    const int16_t* x;          // [S K][M]
+    uint32_t M;
+    const int32_t* xh_in;      // [S K][HXS][2]: (x, s) of the HX samples before the call
+    int32_t* xh_out;
+    uint32_t HX, HXS;          // Ta - 1, row stride (>= 1)
+    const long long* sums;     // [nbc][S K][2]
+    const long long* carry_in; // [S K][4]: I, Q of block jfirst - 1; partial I, Q of block jfirst from earlier calls
+    long long* carry_out;
+    uint32_t SK;
+    uint64_t mS, mE, jfirst;   // MPX samples before / after the call, block of mS
+    uint64_t nS;               // audio samples before the call
+    uint32_t NA, na, ntiles;   // audio samples of the call, per tile, tiles per row
+    uint32_t R, Ta, audio_shift;
+    uint32_t pshift, inc_p;
+    uint64_t thr;              // pilot_min P 8192 (0: every block absent)
+    const int16_t* g;
+    const uint32_t* tab;
+    uint32_t* out;             // [S K][out_stride] (L, R) pairs
+    uint64_t out_stride;
+};
+
+// I, Q of block j (>= jfirst - 1, every sample of it already in the sums)
+__device__ __forceinline__ void block_iq(const AudioLaunch& L, uint32_t row, int64_t j, long long& I, long long& Q)
+{
+    const int64_t jf = (int64_t)L.jfirst;
+    if (j < 0) { I = 0; Q = 0; return; }
+    if (j == jf - 1) { I = L.carry_in[4u * row]; Q = L.carry_in[4u * row + 1u]; return; }
+    const long long* p = L.sums + ((uint64_t)(j - jf) * L.SK + row) * 2u;
+    I = p[0]; Q = p[1];
+    if (j == jf) { I += L.carry_in[4u * row + 2u]; Q += L.carry_in[4u * row + 3u]; }
+}
+
+// a^2 + b^2 >= thr^2 in 128 bits (|a|, |b| <= 2^43, thr <= 2^41)
+__device__ __forceinline__ bool pilot_present(long long I, long long Q, uint64_t thr)
+{
+    if (thr == 0u) return false;
+    const uint64_t ua = (uint64_t)(I < 0 ? -I : I), ub = (uint64_t)(Q < 0 ? -Q : Q);
+    const uint64_t alo = ua * ua, ahi = __umul64hi(ua, ua), blo = ub * ub, bhi = __umul64hi(ub, ub);
+    const uint64_t lo = alo + blo, hi = ahi + bhi + (lo < alo ? 1u : 0u);
+    const uint64_t tlo = thr * thr, thi = __umul64hi(thr, thr);
+    return hi > thi || (hi == thi && lo >= tlo);
+}
+
+__global__ void __launch_bounds__(kThreads) fmd_stereo_audio_kernel(const AudioLaunch L)
+{
+    __shared__ __attribute__((aligned(16))) int2 xs[kXCap];
+    __shared__ int32_t gl[256];
+    __shared__ int16_t tab[1024];
+    __shared__ int32_t est[kMaxBlocks][3];                   // present, c2, s2 of block jA - 1 + i
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row = blockIdx.x / L.ntiles, t = blockIdx.x - row * L.ntiles;
+    if (row >= L.SK) return;
+
+    const uint32_t na0 = t * L.na;                           // first audio sample (of this call) of the tile
+    const uint32_t cnt = L.NA - na0 < L.na ? L.NA - na0 : L.na;
+    const bool last = t == L.ntiles - 1u;
+    // virtual index v: MPX sample mS - HX + v (v < HX: the carried history)
+    const uint32_t vfir = (uint32_t)(L.R * (L.nS + na0) + L.HX - L.mS);      // the tile's first FIR window
+    const uint32_t vtot = L.HX + L.M;
+    uint32_t vlo = vfir, vhi = vfir + L.R * (cnt - 1u) + L.Ta;
+    if (last) { vlo = vlo < L.M ? vlo : L.M; vhi = vtot; }   // the last tile also forms the next call's history
+    const uint32_t span = vhi - vlo;                         // <= kXCap: host plan
+    const uint32_t va = vlo > L.HX ? vlo : L.HX;             // first virtual index of the call's own samples
+    const uint64_t jA = (L.mS + (va - L.HX)) >> L.pshift;
+
+    // ---- 1. block estimates, the NCO table, the taps ------------------------------------------------------------------------
+    if (va < vhi && tid < kMaxBlocks) {
+        const uint64_t jB = (L.mS + (vhi - 1u - L.HX)) >> L.pshift;
+        if (jA + tid <= jB) {
+            long long I, Q;
+            block_iq(L, row, (int64_t)(jA + tid) - 1, I, Q);
+            int present = pilot_present(I, Q, L.thr) ? 1 : 0, c2 = 0, s2 = 0;
+            if (present) {
+                const uint64_t mx = (uint64_t)(I < 0 ? -I : I) | (uint64_t)(Q < 0 ? -Q : Q);   // same bit length as the max
+                const int bl = 64 - __builtin_clzll(mx);
+                const int e = bl > 23 ? bl - 23 : 0;
+                const long long a = I >> e, b = Q >> e;
+                const long long E = a * a + b * b;
+                c2 = (int)((b * b - a * a) * 16384 / E);
+                s2 = (int)((2 * a * b) * 16384 / E);
+            }
+            est[tid][0] = present; est[tid][1] = c2; est[tid][2] = s2;
+        }
+    }
+    for (uint32_t i = tid; i < 512u; i += kThreads) reinterpret_cast<uint32_t*>(tab)[i] = L.tab[i];
+    for (uint32_t i = tid; i < L.Ta; i += kThreads) gl[i] = L.g[i];
+    __syncthreads();
+
+    // ---- 2. (x, s) of the tile's samples ------------------------------------------------------------------------------------
+    const int16_t* const xr = L.x + (uint64_t)row * L.M;
+    const int32_t* const hin = L.xh_in + (uint64_t)row * L.HXS * 2u;
+    for (uint32_t i = tid; i < span; i += kThreads) {
+        const uint32_t v = vlo + i;
+        int2 p;
+        if (v < L.HX) {
+            p = int2{hin[2u * v], hin[2u * v + 1u]};
+        } else {
+            const uint64_t m = L.mS + (v - L.HX);
+            const int xv = xr[v - L.HX];
+            const uint32_t jj = (uint32_t)((m >> L.pshift) - jA);
+            int sv = 0;
+            if (est[jj][0]) {
+                const uint32_t ix = (((uint32_t)m * L.inc_p) << 1) >> 22;                  // 2 theta
+                const int kc = (tab[(ix - 256u) & 1023u] * est[jj][1] + tab[ix] * est[jj][2]) >> 13;
+                sv = (xv * kc) >> 14;
+            }
+            p = int2{xv, sv};
+        }
+        xs[i] = p;
+    }
+    __syncthreads();
+    if (last) {                                              // the next call's history: virtual indices M ... M + HX - 1
+        int32_t* const hout = L.xh_out + (uint64_t)row * L.HXS * 2u;
+        for (uint32_t i = tid; i < L.HX; i += kThreads) {
+            const int2 p = xs[L.M + i - vlo];
+            hout[2u * i] = p.x; hout[2u * i + 1u] = p.y;
+        }
+    }
+    if (t == 0u && tid == 0u) {                              // the next call's block carry
+        const int64_t jn = (int64_t)(L.mE >> L.pshift);
+        long long I = 0, Q = 0, Ip = 0, Qp = 0;
+        if (jn >= 1) block_iq(L, row, jn - 1, I, Q);
+        if (L.mE & ((1ull << L.pshift) - 1u)) block_iq(L, row, jn, Ip, Qp);
+        long long* const c = L.carry_out + 4u * row;
+        c[0] = I; c[1] = Q; c[2] = Ip; c[3] = Qp;
+    }
+
+    // ---- 3. FIRs, matrix, saturation ------------------------------------------------------------------------------------------
+    uint32_t* const out = L.out + (uint64_t)row * L.out_stride + na0;
+    const uint32_t sh = L.audio_shift + 1u;
+    for (uint32_t i = tid; i < cnt; i += kThreads) {
+        const int2* w = xs + (vfir - vlo) + L.R * i;
+        int m = 0, sd = 0;
+        for (uint32_t k = 0; k < L.Ta; ++k) {
+            const int2 p = w[k];
+            const int gk = gl[k];
+            m = __mul24(gk, p.x) + m;
+            sd = __mul24(gk, p.y) + sd;
+        }
+        int l = (m + sd) >> sh, r = (m - sd) >> sh;
+        l = l > 32767 ? 32767 : (l < -32768 ? -32768 : l);
+        r = r > 32767 ? 32767 : (r < -32768 ? -32768 : r);
+        out[i] = ((uint32_t)l & 0xFFFFu) | ((uint32_t)r << 16);
+    }
+}
+
+}  // namespace fmd_sto
+
+struct fmd_stereo {
+    uint32_t T = 0, D = 0, K = 0, S = 0, shift = 0, HB = 0;
+    uint32_t groups = 0, tile = 0, cols = 0, raw_bytes = 0;
+    size_t lds = 0;
+    uint32_t Ta = 0, R = 0, P = 0, pshift = 0, audio_shift = 0, pilot_min = 0, inc_p = 0;
+    uint32_t HX = 0, HXS = 0, na = 0;
+    FmdDdcPlan plan;
+    FmdDdcCore core;
+    int16_t* d_g = nullptr;
+    uint32_t* d_ylast[2] = {nullptr, nullptr};            // [S K] packed y, read [core.cur], written [core.cur ^ 1]
+    int32_t* d_xh[2] = {nullptr, nullptr};                // [S K][HXS][2] (x, s) history
+    long long* d_carry[2] = {nullptr, nullptr};           // [S K][4] block carry
+    void* d_x = nullptr; size_t d_x_cap = 0;              // the call's MPX samples
+    void* d_sums = nullptr; size_t d_sums_cap = 0;        // the call's block sums
+};
+
+namespace {
+
+using fmd_ddc::kTableBytes;
+
+constexpr size_t kLdsBudget = 40960;
+
+size_t st_lds(uint32_t D, uint32_t nkc, uint32_t T, uint32_t K, uint32_t G, uint32_t* raw_bytes)
+{
+    const uint64_t cap = 64ull * G;                       // contracted outputs per tile (the tile's and the one before)
+    const uint64_t reads = 12 + 6ull * D + 8ull * D * (16 * G - 1) + 64ull * nkc;
+    const uint64_t staged = 12 + 2ull * D * (cap - 1) + 2ull * T + 15;
+    const uint64_t raw = ((reads > staged ? reads : staged) + 15) & ~15ull;
+    *raw_bytes = (uint32_t)raw;
+    return (size_t)(raw + kTableBytes + 4ull * K * cap);
+}
+
+uint64_t st_mpx(const fmd_stereo* h, uint64_t S) { return S >= h->T ? (S - h->T) / h->D + 1 : 0; }
+uint64_t st_audio(const fmd_stereo* h, uint64_t m) { return m >= h->Ta ? (m - h->Ta) / h->R + 1 : 0; }
+
+int st_enqueue(fmd_stereo* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
+{
+    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
+    if (nbytes > (1ull << 31) - (1ull << 20)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
+    if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & 3u) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
+    FmdDdcCore& c = h->core;
+    const uint64_t ns = nbytes / 2;
+    const uint64_t mS = st_mpx(h, c.pos), mE = st_mpx(h, c.pos + ns), M = mE - mS;
+    const uint64_t nS = st_audio(h, mS), NA = st_audio(h, mE) - nS;
+    if (NA < 1) { fmd_internal_set_err("the call completes no audio sample"); return FMD_ERR_TOO_SHORT; }
+    if (NA > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
+    const uint64_t SK = (uint64_t)h->S * h->K;
+    const uint64_t nt1 = (M + h->tile - 1) / h->tile, nt2 = (NA + h->na - 1) / h->na;
+    if (nt1 > (1u << 30) || h->S > 65535u || nt2 * SK > 0x7FFFFFFFull) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
+    const uint64_t jfirst = mS >> h->pshift, nbc = ((mE - 1) >> h->pshift) - jfirst + 1;
+    const size_t sums_bytes = (size_t)(nbc * SK * 16);
+    FMD_DDC_TRY(fmd_ddc_grow(h->d_x, h->d_x_cap, (size_t)(SK * M * 2)));
+    FMD_DDC_TRY(fmd_ddc_grow(h->d_sums, h->d_sums_cap, sums_bytes));
+    const int cur = c.cur;
+
+    fmd_sto::MpxLaunch A{};
+    A.iq = static_cast<const uint8_t*>(d_iq);
+    A.nbytes = nbytes;
+    A.hist_in = c.d_hist[cur]; A.hist_out = c.d_hist[cur ^ 1];
+    A.HB = h->HB;
+    A.vb_first = (uint32_t)(2ull * (h->D * mS + h->HB / 2 - c.pos));
+    A.m0 = mS; A.M = (uint32_t)M;
+    A.D = h->D; A.T = h->T; A.K = h->K; A.S = h->S; A.shift = h->shift;
+    A.nrt = h->plan.nrt; A.nkc = h->plan.nkc; A.digits = h->plan.digits;
+    A.tile = h->tile; A.cols = h->cols; A.ntiles = (uint32_t)nt1; A.raw_bytes = h->raw_bytes;
+    A.pshift = h->pshift; A.inc_p = h->inc_p; A.jfirst = jfirst;
+    A.amat = c.d_amat; A.kconst = c.d_kconst; A.dinc = c.d_dinc; A.tab = c.d_tab;
+    A.ylast_in = h->d_ylast[cur]; A.ylast_out = h->d_ylast[cur ^ 1];
+    A.x = static_cast<int16_t*>(h->d_x);
+    A.sums = static_cast<unsigned long long*>(h->d_sums);
+
+    fmd_sto::AudioLaunch B{};
+    B.x = A.x; B.M = (uint32_t)M;
+    B.xh_in = h->d_xh[cur]; B.xh_out = h->d_xh[cur ^ 1];
+    B.HX = h->HX; B.HXS = h->HXS;
+    B.sums = static_cast<const long long*>(h->d_sums);
+    B.carry_in = h->d_carry[cur]; B.carry_out = h->d_carry[cur ^ 1];
+    B.SK = (uint32_t)SK;
+    B.mS = mS; B.mE = mE; B.jfirst = jfirst; B.nS = nS;
+    B.NA = (uint32_t)NA; B.na = h->na; B.ntiles = (uint32_t)nt2;
+    B.R = h->R; B.Ta = h->Ta; B.audio_shift = h->audio_shift;
+    B.pshift = h->pshift; B.inc_p = h->inc_p;
+    B.thr = (uint64_t)h->pilot_min * h->P * 8192u;
+    B.g = h->d_g; B.tab = c.d_tab;
+    B.out = static_cast<uint32_t*>(d_out); B.out_stride = out_cap;
+
+    FMD_DDC_TRY(c.order.before(stream));
+    FMD_DDC_TRY(hipMemsetAsync(h->d_sums, 0, sums_bytes, stream));
+    hipLaunchKernelGGL(fmd_sto::fmd_stereo_mpx_kernel, dim3(A.ntiles, h->S), dim3(fmd_sto::kThreads), h->lds, stream, A);
+    FMD_DDC_TRY(hipGetLastError());
+    hipLaunchKernelGGL(fmd_sto::fmd_stereo_audio_kernel, dim3((uint32_t)(nt2 * SK)), dim3(fmd_sto::kThreads), 0, stream, B);
+    FMD_DDC_TRY(hipGetLastError());
+    (void)c.order.after(stream);
+    c.cur ^= 1;
+    c.pos += ns;
+    if (out_len) *out_len = (size_t)NA;
+    return FMD_OK;
+}
+
+uint64_t isqrt_u128(unsigned __int128 v)
+{
+    uint64_t r = (uint64_t)std::sqrt((double)v);
+    while ((unsigned __int128)r * r > v) --r;
+    while ((unsigned __int128)(r + 1) * (r + 1) <= v) ++r;
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fmd_stereo_out_cap(uint32_t decim, uint32_t audio_decim, size_t nbytes)
+{
+    if (!decim || !audio_decim) return 0;
+    const uint64_t d = 2ull * decim * audio_decim;
+    return (size_t)((nbytes + d - 1) / d);
+}
+
+int fmd_stereo_pilot_inc(uint32_t capture_rate, uint32_t decim, uint32_t* inc)
+{
+    if (!inc || !capture_rate || !decim) { fmd_internal_set_err("null argument or zero rate"); return FMD_ERR_INVALID_ARG; }
+    const unsigned __int128 num = ((unsigned __int128)19000u * decim << 32) + capture_rate / 2u;
+    *inc = (uint32_t)(uint64_t)(num / capture_rate);
+    return FMD_OK;
+}
+
+int fmd_stereo_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t* phase_inc,
+                   uint32_t n_stations, const int16_t* audio_taps, uint32_t n_audio_taps, const fmd_stereo_config* cfg,
+                   const fmd_device_config* dev, fmd_stereo** out)
+{
+    if (!taps || !phase_inc || !audio_taps || !cfg || !dev || !out || dev->n_channels == 0) {
+        fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    if (n_taps == 0 || n_taps > 256 || decim < 2 || decim % 2 != 0 || decim > 64 || shift > 24 || n_stations == 0 || n_stations > 32 ||
+        dev->n_channels > 65535u) {
+        fmd_internal_set_err("need 1 <= n_taps <= 256, an even 2 <= decim <= 64, shift <= 24, 1 <= n_stations <= 32, n_streams <= 65535");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    for (uint32_t t = 0; t < n_taps; ++t)
+        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
+    if ((uint64_t)cfg->capture_rate < 106000ull * decim) { fmd_internal_set_err("need capture_rate >= 106000 * decim"); return FMD_ERR_UNSUPPORTED; }
+    const uint32_t P = cfg->block;
+    if (P < 1024u || P > 16384u || (P & (P - 1u)) != 0) { fmd_internal_set_err("block must be a power of two in [1024, 16384]"); return FMD_ERR_UNSUPPORTED; }
+    if (cfg->audio_decim < 1u || cfg->audio_decim > 32u || n_audio_taps < 1u || n_audio_taps > 256u || cfg->audio_shift > 16u ||
+        cfg->pilot_min > 16384u) {
+        fmd_internal_set_err("need 1 <= audio_decim <= 32, 1 <= n_audio_taps <= 256, audio_shift <= 16, pilot_min <= 16384");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    uint64_t gsum = 0;
+    for (uint32_t t = 0; t < n_audio_taps; ++t) gsum += (uint64_t)(audio_taps[t] < 0 ? -(int)audio_taps[t] : audio_taps[t]);
+    if (gsum > 16383u) { fmd_internal_set_err("sum |audio_taps| > 16383"); return FMD_ERR_UNSUPPORTED; }
+    fmd_stereo* h = new (std::nothrow) fmd_stereo();
+    if (!h) return FMD_ERR_NOMEM;
+    h->T = n_taps; h->D = decim; h->K = n_stations; h->S = dev->n_channels; h->shift = shift;
+    fmd_st_build_plan(taps, n_taps, decim, phase_inc, h->S, h->K, h->plan);
+    const uint64_t bound = (256ull * h->plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
+    if (bound > 16384ull) {
+        delete h;
+        fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    for (uint32_t G = fmd_ddc::kGroups; G >= 1; --G) {
+        uint32_t rb;
+        const size_t l = st_lds(decim, h->plan.nkc, n_taps, n_stations, G, &rb);
+        if (l <= kLdsBudget || G == 1) { h->groups = G; h->cols = 64u * G; h->tile = 64u * G - 1u; h->raw_bytes = rb; h->lds = l; break; }
+    }
+    h->HB = 2u * ((n_taps - 1u + 7u) & ~7u);
+    h->Ta = n_audio_taps; h->R = cfg->audio_decim; h->P = P; h->audio_shift = cfg->audio_shift; h->pilot_min = cfg->pilot_min;
+    while ((1u << h->pshift) < P) ++h->pshift;
+    (void)fmd_stereo_pilot_inc(cfg->capture_rate, decim, &h->inc_p);
+    h->HX = n_audio_taps - 1u; h->HXS = h->HX ? h->HX : 1u;
+    const uint32_t na = (fmd_sto::kXCap - 2u * h->Ta) / h->R;   // >= 48: R tile + 2 Ta <= kXCap
+    h->na = na < fmd_sto::kAudioTile ? na : fmd_sto::kAudioTile;
+
+    if (const int rc = fmd_ddc_open(h->core, dev)) { delete h; return rc; }
+    auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_stereo_free(h); return FMD_ERR_HIP; };
+    FmdDeviceGuard guard(h->core.device);
+    if (guard.error() != hipSuccess) return fail("hipSetDevice");
+    if (const char* what = fmd_ddc_upload(h->core, h->plan, (size_t)h->S * (h->HB ? h->HB : 16))) return fail(what);
+    const size_t SK = (size_t)h->S * h->K;
+    if (hipMalloc(&h->d_g, 2u * n_audio_taps) != hipSuccess || hipMemcpy(h->d_g, audio_taps, 2u * n_audio_taps, hipMemcpyHostToDevice) != hipSuccess)
+        return fail("hipMalloc(audio taps)");
+    for (int i = 0; i < 2; ++i) {
+        if (hipMalloc(&h->d_ylast[i], SK * 4) != hipSuccess || hipMemset(h->d_ylast[i], 0, SK * 4) != hipSuccess) return fail("hipMalloc(last y)");
+        if (hipMalloc(&h->d_xh[i], SK * h->HXS * 8) != hipSuccess || hipMemset(h->d_xh[i], 0, SK * h->HXS * 8) != hipSuccess) return fail("hipMalloc(MPX history)");
+        if (hipMalloc(&h->d_carry[i], SK * 32) != hipSuccess || hipMemset(h->d_carry[i], 0, SK * 32) != hipSuccess) return fail("hipMalloc(block carry)");
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
+    *out = h;
+    return FMD_OK;
+}
+
+void fmd_stereo_free(fmd_stereo* h)
+{
+    if (!h) return;
+    FmdDeviceGuard guard(h->core.device);
+    (void)hipDeviceSynchronize();
+    for (void* p : {(void*)h->d_g, (void*)h->d_ylast[0], (void*)h->d_ylast[1], (void*)h->d_xh[0], (void*)h->d_xh[1], (void*)h->d_carry[0],
+                    (void*)h->d_carry[1], h->d_x, h->d_sums})
+        if (p) (void)hipFree(p);
+    fmd_ddc_release(h->core);
+    delete h;
+}
+
+int fmd_stereo_reset(fmd_stereo* h)
+{
+    if (!h) return FMD_ERR_INVALID_ARG;
+    FMD_DDC_ON_DEVICE(h->core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    const size_t SK = (size_t)h->S * h->K;
+    for (int i = 0; i < 2; ++i) {
+        FMD_DDC_TRY(hipMemset(h->d_ylast[i], 0, SK * 4));
+        FMD_DDC_TRY(hipMemset(h->d_xh[i], 0, SK * h->HXS * 8));
+        FMD_DDC_TRY(hipMemset(h->d_carry[i], 0, SK * 32));
+    }
+    FMD_DDC_TRY(fmd_ddc_zero_history(h->core));          // (ends with the device synchronised; position and buffer index to 0)
+    return FMD_OK;
+}
+
+int fmd_stereo_run_device(fmd_stereo* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, void* stream)
+{
+    if (!h || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->core.device);
+    return st_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream));
+}
+
+int fmd_stereo_check(fmd_stereo* h)
+{
+    if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->core.device);
+    if (h->core.order.have_last) FMD_DDC_TRY(hipStreamSynchronize(h->core.order.last));
+    FMD_DDC_TRY(hipGetLastError());
+    return FMD_OK;
+}
+
+int fmd_stereo_run_batch(fmd_stereo* h, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap, size_t* out_len)
+{
+    if (!h || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->core.device);
+    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
+    FmdDdcCore& c = h->core;
+    const size_t rows = (size_t)h->S * h->K;
+    const size_t in_bytes = nbytes * (size_t)h->S, out_bytes = out_cap * rows * sizeof(uint32_t);   // (L, R) pairs
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
+    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
+    size_t n = 0;
+    int rc = st_enqueue(h, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream);
+    if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
+    FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
+    *out_len = n;
+    return FMD_OK;
+}
+
+int fmd_stereo_outputs(const fmd_stereo* h, uint64_t* outputs)
+{
+    if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    *outputs = st_audio(h, st_mpx(h, h->core.pos));
+    return FMD_OK;
+}
+
+int fmd_stereo_pilot(fmd_stereo* h, uint32_t stream, uint32_t station, int* present, uint32_t* level)
+{
+    if (!h || !present || !level) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    if (stream >= h->S || station >= h->K) { fmd_internal_set_err("stream or station out of range"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    long long c[4];
+    FMD_DDC_TRY(hipMemcpy(c, h->d_carry[h->core.cur] + 4ull * ((size_t)stream * h->K + station), sizeof c, hipMemcpyDeviceToHost));
+    const unsigned __int128 e2 = (unsigned __int128)((__int128)c[0] * c[0]) + (unsigned __int128)((__int128)c[1] * c[1]);
+    const uint64_t thr = (uint64_t)h->pilot_min * h->P * 8192u;
+    *present = thr != 0 && e2 >= (unsigned __int128)thr * thr ? 1 : 0;
+    *level = (uint32_t)(isqrt_u128(e2) / ((uint64_t)h->P * 8192u));
+    return FMD_OK;
+}
+
+int fmd_stereo_kernel_name(const fmd_stereo* h, uint32_t pass, char* name, size_t cap)
+{
+    if (!h || !name || cap == 0 || pass > 1) return FMD_ERR_INVALID_ARG;
+    return fmd_ddc_name_rc(snprintf(name, cap, pass == 0 ? "fmd_sto::fmd_stereo_mpx_kernel" : "fmd_sto::fmd_stereo_audio_kernel"), cap);
+}
+
+}  // extern "C"

@@ -21,6 +21,9 @@
 // downsample) is the prototype filter, mixed to each station by fmd_stations_*; audio of station k goes to <prefix>.<k>.s16.
 // With -I the same filter runs through the channelizer (fmd_channelizer_*) instead: station k's complex baseband at
 // capture_rate / downsample goes to <prefix>.<k>.cs16 as interleaved s16 (I, Q) pairs, no demodulation.
+// With -2 the stereo station bank (fmd_stereo_*) instead: station k's pilot-locked stereo, interleaved s16 (L, R) at
+// f_m / R (f_m = capture_rate / downsample, R = max(1, floor(f_m / 48000)); 127 audio taps from fm::stereo_taps, 75 us
+// de-emphasis, blocks of 4096) goes to <prefix>.<k>.s16; the audio rate is printed on stderr.
 //
 // Power spectrum, -P N [-H hop]: the N-bin power spectrum (fmd_spectrum_*, integer Hann window of amplitude 2047, shift 16) of
 // ONE capture file whose sample rate is -s, integrated over the file's complete blocks; one line per bin in frequency order,
@@ -181,7 +184,7 @@ static int run_rtl_tcp(const char* hostport, uint32_t freq, uint32_t rate, uint3
 
 // -S: one capture, K stations (fmd_stations_*; with -I their baseband, fmd_channelizer_*)
 static int run_stations(const char* path, const char* list, const char* prefix, uint32_t freq, uint32_t rate, uint32_t resample,
-                        bool iq_out)
+                        bool iq_out, bool stereo)
 {
     FILE* in = strcmp(path, "-") ? fopen(path, "rb") : stdin;
     if (!in) { perror(path); return 2; }
@@ -203,7 +206,22 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
         while ((512ull * D + (1ull << shift) - 1) >> shift > 16384ull) ++shift;
         std::unique_ptr<fm::StationBank> bank;
         std::unique_ptr<fm::Channelizer> chan;
-        if (iq_out) chan.reset(new fm::Channelizer(std::vector<int16_t>(D, 1), D, shift, incs, 1));
+        std::unique_ptr<fm::StereoBank> st;
+        if (stereo) {
+            // the front end's shift keeps every |y| component <= 256, where the reference's discriminator cannot wrap
+            uint32_t sshift = 0;
+            while ((512ull * D + (1ull << sshift) - 1) >> sshift > 256ull) ++sshift;
+            const uint32_t f_m = capture / D, R = std::max<uint32_t>(1, f_m / 48000);
+            const std::vector<int16_t> g = fm::stereo_taps((double)f_m, 127);
+            int64_t gsum = 0;
+            for (int16_t v : g) gsum += v;
+            const uint64_t peak = (uint64_t)(gsum < 0 ? -gsum : gsum) * 32768ull * 75000ull * D / capture;
+            uint32_t ash = 0;
+            while (ash < 16 && (peak >> (ash + 1)) > 32767) ++ash;
+            const fmd_stereo_config cfg{capture, 4096, R, ash, (uint32_t)((32768ull * 6750 * D) / (4ull * capture))};
+            st.reset(new fm::StereoBank(std::vector<int16_t>(D, 1), D, sshift, incs, 1, g, cfg));
+            fprintf(stderr, "stereo audio: %.3f Hz (interleaved L/R s16)\n", (double)capture / D / R);
+        } else if (iq_out) chan.reset(new fm::Channelizer(std::vector<int16_t>(D, 1), D, shift, incs, 1));
         else bank.reset(new fm::StationBank(std::vector<int16_t>(D, 1), D, shift, incs, 1, dc.rate_out, dc.rate_resample));
         fprintf(stderr, "capture_rate: %u, %zu stations, decimate %u\n", capture, incs.size(), D);
         for (size_t k = 0; k < incs.size(); ++k) {
@@ -219,7 +237,8 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
                 if (fill) fprintf(stderr, "dropped %zu trailing bytes (not a complete %zu-byte block)\n", fill, buf.size());
                 break;
             }
-            const auto rows = iq_out ? chan->run(buf.data(), buf.size()) : bank->demodulate(buf.data(), buf.size());
+            const auto rows = st ? st->run(buf.data(), buf.size())
+                                 : iq_out ? chan->run(buf.data(), buf.size()) : bank->demodulate(buf.data(), buf.size());
             for (size_t k = 0; k < out.size(); ++k) fm::output(rows[k], out[k]);
         }
     } catch (const fm::Error& e) {
@@ -276,6 +295,7 @@ int main(int argc, char** argv)
     const char* rtl_tcp = nullptr;                           // -t host:port: live mode over rtl_tcp
     const char* stations = nullptr;                          // -S off1,off2,...: station bank over one capture
     bool iq_out = false;                                     // -I: with -S, each station's baseband IQ instead of audio
+    bool stereo = false;                                     // -2: with -S, each station's stereo audio (fmd_stereo_*)
     uint32_t power_bins = 0, power_hop = 0;                  // -P N [-H hop]: power spectrum of one capture
     size_t max_blocks = 0;                                   // -n: stop after this many blocks (live mode; 0 = until the stream ends)
     std::vector<const char*> paths;
@@ -288,6 +308,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-t") && i + 1 < argc) rtl_tcp = argv[++i];
         else if (!strcmp(argv[i], "-S") && i + 1 < argc) stations = argv[++i];
         else if (!strcmp(argv[i], "-I")) iq_out = true;
+        else if (!strcmp(argv[i], "-2")) stereo = true;
         else if (!strcmp(argv[i], "-P") && i + 1 < argc) power_bins = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-H") && i + 1 < argc) power_hop = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-n") && i + 1 < argc) max_blocks = strtoul(argv[++i], nullptr, 10);
@@ -298,15 +319,16 @@ int main(int argc, char** argv)
                             "       %s [-f freq_hz] [-s ...] [-r ...] [-n blocks] -t host:port            (live: IQ from an rtl_tcp server)\n"
                             "       %s [-s ...] [-r ...] [-o prefix] -S off1,off2,... <capture.bin | ->   (stations at these offsets in Hz)\n"
                             "       %s [-s ...] [-o prefix] -S off1,off2,... -I <capture.bin | ->        (their baseband: s16 I/Q at capture_rate / downsample)\n"
+                            "       %s [-s ...] [-o prefix] -S off1,off2,... -2 <capture.bin | ->        (their stereo: s16 L/R at capture_rate / downsample / R)\n"
                             "       %s -s capture_rate_hz -P n_bins [-H hop] <capture.bin | ->       (power spectrum: offset_hz power per bin)\n",
-                    argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                    argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else paths.push_back(argv[i]);
     }
     if (rtl_tcp) return run_rtl_tcp(rtl_tcp, freq, rate, resample, max_blocks);
     if (paths.empty()) { fprintf(stderr, "missing input file (use - for stdin)\n"); return 2; }
     if (power_bins) return run_power(paths[0], power_bins, power_hop, rate);
-    if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample, iq_out);
+    if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample, iq_out, stereo);
     if (paths.size() > 1 && gpus > 0) return run_sink(paths, prefix, freq, rate, resample, gpus);
     if (paths.size() > 1) return run_bank(paths, prefix, freq, rate, resample);
     path = paths[0];

@@ -86,6 +86,22 @@ pub struct fmd_channelizer {
 }
 
 #[repr(C)]
+pub struct fmd_stereo {
+    _private: [u8; 0],
+}
+
+/// `fmd_stereo_config` of include/fmd.h (stereo station bank).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_stereo_config {
+    pub capture_rate: u32,
+    pub block: u32,
+    pub audio_decim: u32,
+    pub audio_shift: u32,
+    pub pilot_min: u32,
+}
+
+#[repr(C)]
 pub struct fmd_spectrum {
     _private: [u8; 0],
 }
@@ -175,6 +191,17 @@ extern "C" {
     pub fn fmd_channelizer_check(c: *mut fmd_channelizer) -> c_int;
     pub fn fmd_channelizer_outputs(c: *const fmd_channelizer, outputs: *mut u64) -> c_int;
     pub fn fmd_channelizer_kernel_name(c: *const fmd_channelizer, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_stereo_new(taps: *const i16, n_taps: u32, decim: u32, shift: u32, phase_inc: *const u32, n_stations: u32, audio_taps: *const i16, n_audio_taps: u32, cfg: *const fmd_stereo_config, dev: *const DeviceConfig, out: *mut *mut fmd_stereo) -> c_int;
+    pub fn fmd_stereo_free(s: *mut fmd_stereo);
+    pub fn fmd_stereo_reset(s: *mut fmd_stereo) -> c_int;
+    pub fn fmd_stereo_out_cap(decim: u32, audio_decim: u32, nbytes: usize) -> usize;
+    pub fn fmd_stereo_run_batch(s: *mut fmd_stereo, iq: *const u8, nbytes: usize, out: *mut i16, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn fmd_stereo_run_device(s: *mut fmd_stereo, d_iq: *const c_void, nbytes: usize, d_out: *mut c_void, out_cap: usize, out_len: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_stereo_check(s: *mut fmd_stereo) -> c_int;
+    pub fn fmd_stereo_outputs(s: *const fmd_stereo, outputs: *mut u64) -> c_int;
+    pub fn fmd_stereo_pilot(s: *mut fmd_stereo, stream: u32, station: u32, present: *mut c_int, level: *mut u32) -> c_int;
+    pub fn fmd_stereo_pilot_inc(capture_rate: u32, decim: u32, inc: *mut u32) -> c_int;
+    pub fn fmd_stereo_kernel_name(s: *const fmd_stereo, pass: u32, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_spectrum_hann(n_bins: u32, amplitude: u32, window: *mut i16) -> c_int;
     pub fn fmd_spectrum_bin_inc(bin: u32, n_bins: u32, inc: *mut u32) -> c_int;
     pub fn fmd_spectrum_frames(n_bins: u32, hop: u32, nbytes: usize) -> usize;
