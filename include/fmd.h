@@ -446,6 +446,72 @@ int fmd_stereo_pilot_inc(uint32_t capture_rate, uint32_t decim, uint32_t *inc);
 /* Name of pass 0 (front end + discriminator + pilot sums) or 1 (carrier, FIRs, matrix), as `rocprofv3 --kernel-trace` prints it. */
 int fmd_stereo_kernel_name(const fmd_stereo *s, uint32_t pass, char *name, size_t cap);
 
+/* ---- narrow-band bank: AM, NFM, SSB and IQ channels with squelch --------------------------------------------- */
+/* NEW SURFACE (rtl_fm's -M fm / am / usb / lsb / raw with a squelch, in the rtl-sdr ecosystem; the reference has none).  This is
+ * the project's own operator, not the reference's chain: the channelizer's y, a second, COMPLEX decimating FIR that reaches
+ * channels narrower than capture_rate / 64, one of four detectors and a block-wise squelch.  In IQ mode it is a two-stage
+ * channelizer with total decimation up to 64 x 32.  Definition (integers only; tests/narrow_ref.py), per (stream, station k):
+ *   y[m]    the channelizer's output (above), m counted from creation or reset
+ *   v[n]    = sum_{t < Ta} (gr[t] + j gi[t]) y[R n + t]                                                  (exact in i32)
+ *   u[n]    = (vr >> chan_shift) + j (vi >> chan_shift)                          arithmetic shifts (floor), per component
+ *   a[n]    = isqrt(ur^2 + ui^2)                                                 floor integer square root, exact
+ *   block j = the audio samples n with floor(n / P) = j;  E_j = sum (ur^2 + ui^2),  A_j = sum a[n]          (exact, i64)
+ *   open_j  = squelch == 0 || E_j >= squelch^2 P,  open_{-1} = (squelch == 0);   dc_j = A_j >> log2(P),  dc_{-1} = 0
+ *   w[n]    by mode:  FMD_NARROW_IQ   the pair (ur, ui)
+ *                     FMD_NARROW_FM   (i16) polar_discriminant_fast(u[n], u[n-1])   (simple_fm.rs:377-405; u[-1] = 0; u[n-1]
+ *                                     carries across calls, muted or not)
+ *                     FMD_NARROW_AM   a[n] - dc_{j-1},  j = floor(n / P)
+ *                     FMD_NARROW_SSB  ur                                            (the complex taps choose the sideband)
+ *   out[n]  = 0 (both halves in IQ mode) if !open_{j-1};  (ur, ui) as int16 in IQ mode (gain is not applied);
+ *             sat16((w[n] gain) >> 8) otherwise
+ * Audio sample n comes with the call in which y[R n + Ta - 1] arrives; blocks are counted from reset, so the output does not
+ * depend on how the stream is cut into calls.  The PREVIOUS block's estimates are used: every stage is causal and non-recursive.
+ * out is [n_streams][n_stations][out_cap][width] int16, width = fmd_narrow_out_width(mode): 2 in IQ mode, 1 otherwise, at
+ * capture_rate / (decim R).
+ * Domain (else FMD_ERR_UNSUPPORTED, decided before a device is queried): the channelizer's filter domain, whose bound is
+ * B_y = ceil(256 max_k sum_t (|Wr| + |Wi|) / 2^shift) <= 16384; 1 <= R <= 32; 1 <= Ta <= 256; chan_taps_im may be NULL (real
+ * taps); every |gr|, |gi| <= 16383; G = sum_t (|gr| + |gi|) <= 65535; chan_shift <= 30; ceil(B_y G / 2^chan_shift) <= 16384; P a
+ * power of two in [16, 4096]; squelch <= 23170; 1 <= gain <= 65535; mode <= 3.  Hence |v| <= B_y G < 2^30, |u| <= 16384,
+ * |u|^2 <= 2^29, a <= 23170, E_j <= 2^41, |w gain| < 2^31.  nbytes % 8 != 0 -> FMD_ERR_BAD_LENGTH; a call that completes no
+ * audio sample -> FMD_ERR_TOO_SHORT and changes nothing.  Stream lifetime and completion points: as fmd_channelizer_*. */
+#define FMD_NARROW_IQ 0u
+#define FMD_NARROW_FM 1u
+#define FMD_NARROW_AM 2u
+#define FMD_NARROW_SSB 3u
+typedef struct fmd_narrow fmd_narrow;
+typedef struct fmd_narrow_config {
+    uint32_t mode;           /* FMD_NARROW_*                                                           */
+    uint32_t chan_decim;     /* R                                                                      */
+    uint32_t chan_shift;
+    uint32_t block;          /* P: squelch / carrier-level block length in audio samples               */
+    uint32_t squelch;        /* opens at an RMS |u| of this much (0: always open)                      */
+    uint32_t gain;           /* Q8                                                                     */
+} fmd_narrow_config;
+int fmd_narrow_new(const int16_t *taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t *phase_inc,
+                   uint32_t n_stations, const int16_t *chan_taps_re, const int16_t *chan_taps_im, uint32_t n_chan_taps,
+                   const fmd_narrow_config *cfg, const fmd_device_config *dev, fmd_narrow **out);
+void fmd_narrow_free(fmd_narrow *s);
+int fmd_narrow_reset(fmd_narrow *s);
+/* ceil(nbytes / (2 decim R)): audio samples one call of nbytes can complete per (stream, station), whatever the history;
+ * 0 for decim 0 or R 0. */
+size_t fmd_narrow_out_cap(uint32_t decim, uint32_t chan_decim, size_t nbytes);
+/* int16 values per output sample: 2 in IQ mode, 1 otherwise. */
+uint32_t fmd_narrow_out_width(uint32_t mode);
+/* HOST buffers; *out_len = audio samples per (stream, station) (the same for all). */
+int fmd_narrow_run_batch(fmd_narrow *s, const uint8_t *iq, size_t nbytes, int16_t *out, size_t out_cap, size_t *out_len);
+/* DEVICE buffers (d_iq 4-byte aligned, d_out 4-byte aligned in IQ mode and 2-byte otherwise), enqueued on `stream` without
+ * synchronising; *out_len as above. */
+int fmd_narrow_run_device(fmd_narrow *s, const void *d_iq, size_t nbytes, void *d_out, size_t out_cap, size_t *out_len,
+                          void *stream);
+int fmd_narrow_check(fmd_narrow *s);
+/* Audio samples per (stream, station) produced since creation or the last reset. */
+int fmd_narrow_outputs(const fmd_narrow *s, uint64_t *outputs);
+/* The last completed block: *open = open_j, *rms = isqrt(E_j >> log2 P), the channel's RMS amplitude in units of u (0 and 0
+ * before the first block completes).  Synchronises first. */
+int fmd_narrow_level(fmd_narrow *s, uint32_t stream, uint32_t station, int *open, uint32_t *rms);
+/* Name of pass 0 (front end) or 1 (channel FIR, detector, squelch), as `rocprofv3 --kernel-trace` prints it. */
+int fmd_narrow_kernel_name(const fmd_narrow *s, uint32_t pass, char *name, size_t cap);
+
 /* ---- power spectrum: where the stations are ------------------------------------------------------------------ */
 /* NEW SURFACE (rtl_power's job in the rtl-sdr ecosystem; the reference has none).  The integrated power of N DFT bins of every
  * stream, to find the offsets a station bank is then tuned to.  A bin is a station-bank filter (the taps and the NCO table above)

@@ -150,7 +150,19 @@ PROTOTYPES = {
     "fmd_stereo_pilot": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "fmd_stereo_pilot_inc": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "fmd_stereo_kernel_name": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_size_t]),
-    "fmd_spectrum_hann": (C.c_int, [C.c_uint32, C.c_uint32, _i16p]),
+    "fmd_narrow_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, _i16p, _i16p, C.c_uint32,
+                                 _vp, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_narrow_free": (None, [_vp]),
+    "fmd_narrow_reset": (C.c_int, [_vp]),
+    "fmd_narrow_out_cap": (_sz, [C.c_uint32, C.c_uint32, _sz]),
+    "fmd_narrow_out_width": (C.c_uint32, [C.c_uint32]),
+    "fmd_narrow_run_batch": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "fmd_narrow_run_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_narrow_check": (C.c_int, [_vp]),
+    "fmd_narrow_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "fmd_narrow_level": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "fmd_narrow_kernel_name": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "fmd_spectrum_hann":(C.c_int, [C.c_uint32, C.c_uint32, _i16p]),
     "fmd_spectrum_bin_inc": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "fmd_spectrum_frames": (_sz, [C.c_uint32, C.c_uint32, _sz]),
     "fmd_spectrum_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),

@@ -351,6 +351,93 @@ private:
     fmd_stereo* h_ = nullptr;
 };
 
+// Channel taps of a NarrowBank, as the Python narrow_taps(): a Hamming-windowed complex band-pass from lo_hz to hi_hz at the
+// channelizer's output rate, scaled to sum |gr| + |gi| <= 65535 with every tap within 16383.  The second vector is empty (real
+// taps) when lo_hz == -hi_hz.  USB is e.g. (300, 3000), LSB (-3000, -300).
+inline std::pair<std::vector<int16_t>, std::vector<int16_t>> narrow_taps(double rate, uint32_t n_taps, double lo_hz, double hi_hz)
+{
+    if (n_taps < 1 || n_taps > 256 || !(hi_hz > lo_hz)) throw Error(FMD_ERR_INVALID_ARG);
+    const double pi = 3.14159265358979323846;
+    const uint32_t n = n_taps;
+    const double bw = (hi_hz - lo_hz) / rate, fc = (hi_hz + lo_hz) / (2 * rate);
+    const bool real = lo_hz == -hi_hz;
+    std::vector<double> re(n), im(n, 0.0);
+    double total = 0, peak = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const double t = i - (n - 1) / 2.0, x = pi * (bw * t);
+        const double w = n > 1 ? 0.54 + 0.46 * std::cos(pi * (2.0 * i + 1.0 - n) / (n - 1.0)) : 1.0;
+        const double lp = bw * (t == 0 ? 1.0 : std::sin(x) / x) * w;
+        if (real) re[i] = lp;
+        else {
+            const double ph = 2 * pi * fc * t;          // the correlation sum_t g[t] y[R n + t] passes +fc with g = lp exp(-j ph)
+            re[i] = lp * std::cos(ph);
+            im[i] = -(lp * std::sin(ph));
+        }
+        total += std::fabs(re[i]) + std::fabs(im[i]);
+        peak = std::max(peak, std::max(std::fabs(re[i]), std::fabs(im[i])));
+    }
+    const double scale = std::min((65535.0 - 2.0 * n) / total, 16383.0 / peak);
+    std::vector<int16_t> gr(n), gi(real ? 0 : n);
+    for (uint32_t i = 0; i < n; ++i) {
+        gr[i] = (int16_t)std::floor(re[i] * scale + 0.5);
+        if (!real) gi[i] = (int16_t)std::floor(im[i] * scale + 0.5);
+    }
+    return {gr, gi};
+}
+
+// Narrow-band bank (fmd_narrow_*): run() takes [n_streams][nbytes] and returns [n_streams * n_stations] rows (row stream *
+// n_stations + station) of int16 audio -- interleaved (re, im) in IQ mode -- at capture_rate / (decim chan_decim).
+class NarrowBank {
+public:
+    NarrowBank(const std::vector<int16_t>& taps, uint32_t decim, uint32_t shift, const std::vector<uint32_t>& phase_incs,
+               uint32_t n_streams, const std::vector<int16_t>& chan_taps_re, const std::vector<int16_t>& chan_taps_im,
+               const fmd_narrow_config& cfg, int32_t device_id = -1)
+        : decim_(decim), chan_decim_(cfg.chan_decim), width_(fmd_narrow_out_width(cfg.mode)), n_streams_(n_streams),
+          n_stations_(n_streams ? (uint32_t)(phase_incs.size() / n_streams) : 0u)
+    {
+        if (!chan_taps_im.empty() && chan_taps_im.size() != chan_taps_re.size()) throw Error(FMD_ERR_INVALID_ARG);
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_narrow_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, chan_taps_re.data(),
+                             chan_taps_im.empty() ? nullptr : chan_taps_im.data(), (uint32_t)chan_taps_re.size(), &cfg, &dev, &h_));
+    }
+    ~NarrowBank() { fmd_narrow_free(h_); }
+    NarrowBank(const NarrowBank&) = delete;
+    NarrowBank& operator=(const NarrowBank&) = delete;
+
+    // FMD_ERR_TOO_SHORT (a call that completes no audio sample) returns empty rows and changes nothing.
+    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    {
+        const size_t cap = std::max<size_t>(1, fmd_narrow_out_cap(decim_, chan_decim_, nbytes));
+        const size_t rows = (size_t)n_streams_ * n_stations_;
+        std::vector<int16_t> out(width_ * cap * rows);
+        size_t n = 0;
+        const int rc = fmd_narrow_run_batch(h_, iq, nbytes, out.data(), cap, &n);
+        if (rc == FMD_ERR_TOO_SHORT) return std::vector<std::vector<int16_t>>(rows);
+        check(rc);
+        std::vector<std::vector<int16_t>> res(rows);
+        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + width_ * r * cap, out.begin() + width_ * (r * cap + n));
+        return res;
+    }
+    std::pair<bool, uint32_t> level(uint32_t stream, uint32_t station)
+    {
+        int open = 0;
+        uint32_t rms = 0;
+        check(fmd_narrow_level(h_, stream, station, &open, &rms));
+        return {open != 0, rms};
+    }
+    uint64_t outputs() const
+    {
+        uint64_t n = 0;
+        check(fmd_narrow_outputs(h_, &n));
+        return n;
+    }
+    void reset() { check(fmd_narrow_reset(h_)); }
+
+private:
+    uint32_t decim_, chan_decim_, width_, n_streams_, n_stations_;
+    fmd_narrow* h_ = nullptr;
+};
+
 // Power spectrum (fmd_spectrum_*): power() takes [n_streams][nbytes] and returns u64 [n_streams][n_bins] in natural DFT order.
 inline std::vector<int16_t> hann_window(uint32_t n_bins, uint32_t amplitude = 2047)
 {

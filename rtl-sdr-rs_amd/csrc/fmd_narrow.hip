@@ -1,0 +1,583 @@
+// fmd_narrow.hip -- narrow-band bank: K narrow channels per wideband IQ stream, each through a second, complex decimating FIR and
+// one of four detectors (IQ, NFM, AM, SSB) with a block-wise squelch, in two gfx950 kernels per call.  The project's own operator
+// (like the stereo bank), not the reference's chain.
+//
+// Definition (include/fmd.h, "narrow-band bank"; tests/narrow_ref.py): the channelizer's y, v[n] = sum_t g[t] y[R n + t] with
+// complex taps g, u = v >> chan_shift per component, a = isqrt(|u|^2), the block sums E_j = sum |u|^2 and A_j = sum a over blocks
+// of P audio samples, and per sample the detector's value, the gain and the squelch decided by block j - 1.
+//
+// Pass 1 (fmd_narrow_ddc_kernel): the channelizer's tile -- the fmd_ddc.h front end (staging, contraction on
+//   v_mfma_i32_16x16x64_i8, rotation into LDS rows) over all K stations of one stream; y leaves as packed re | im << 16 dwords
+//   into a buffer the handle owns, rows padded to 16 bytes so that every store is a dwordx4.
+// Pass 2 (fmd_narrow_chan_kernel<complex taps>): one workgroup = one (stream, station) row; it walks the row's tiles of up to 256
+//   audio samples IN ORDER, so the sums of block j - 1 are always complete when a sample of block j is written: no third pass,
+//   no atomics, no intermediate u buffer.  Per tile:
+//   1. y (history first) into LDS, unpacked to (yr, yi) and in POLYPHASE order: sample i of the tile at [i % R][i / R].  Lane l
+//      (audio sample l of the tile) then reads, for tap t = R q + r, the cell [r][l + q]: consecutive lanes read consecutive
+//      8-byte cells for every R, which is free of bank conflicts (a stride-R layout is not, for even R);
+//   2. the FIR with v_mad_i32_i24, the taps in the same polyphase order ([R][Q], Q = ceil(Ta / R) rounded up to a multiple of
+//      4, zero padded) read through the scalar cache (their address is wave-uniform; four taps per s_load_dwordx8), so a tap
+//      step is ONE ds_read_b64 and two (real taps) or four multiply-adds;
+//      the shift, the exact integer square root (v_sqrt_f32 estimate, integer correction);
+//   3. the tile's block sums, one wave per block, wave reduction; thread 0 then steps the (at most 17) blocks of the tile through
+//      the squelch state;
+//   4. the detector, the gain, the squelch; int16 stores (a dword per sample in IQ mode).
+//   After the last tile: the next call's y history and the row's carry (partial sums, last block's estimates, u[n - 1]).
+#include "../../include/fmd.h"
+
+#include <hip/hip_runtime.h>
+
+#include <new>
+#include <vector>
+
+#include "fmd_ddc.h"
+#include "fmd_device.h"
+#include "fmd_internal.h"
+
+namespace fmd_nb {
+
+using fmd_ddc::kThreads;
+using fmd_ddc::kTableBytes;
+
+constexpr uint32_t kTile = 256;                           // audio samples per pass-2 tile (at most)
+constexpr uint32_t kYCap = 6144;                          // (yr, yi) cells a pass-2 tile stages: R pitch <= kYCap
+constexpr uint32_t kMaxBlk = kTile / 16 + 2;              // blocks one tile touches (<= 17: P >= 16)
+constexpr uint32_t kCarry = 6;                            // u64 per row: E part, A part, E last, u[n - 1], dc, open
+
+struct DdcLaunch {
+    const uint8_t* iq;         // [S][nbytes]
+    uint64_t nbytes;
+    const uint8_t* hist_in;    // [S][HB]
+    uint8_t* hist_out;
+    uint32_t HB;
+    uint32_t vb_first;         // virtual byte (history ++ call) of the window of the call's first output
+    uint32_t m0_lo;            // global index of the call's first output, mod 2^32
+    uint32_t M;                // outputs of this call per (stream, station)
+    uint32_t D, T, K, S, shift;
+    uint32_t nrt, nkc, digits;
+    uint32_t tile, ntiles, raw_bytes;
+    const uint32_t* amat;
+    const int32_t* kconst;
+    const uint32_t* dinc;
+    const uint32_t* tab;
+    uint32_t* y;               // [S K][ystride] packed (yr, yi); ystride % 4 == 0, 16-byte aligned
+    uint32_t ystride;
+};
+
+__global__ void __launch_bounds__(kThreads) fmd_narrow_ddc_kernel(const DdcLaunch L)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t s = blockIdx.y, t = blockIdx.x;
+    if (s >= L.S || t >= L.ntiles) return;
+
+    const uint32_t o0 = t * L.tile;                          // first output (of this call) of the tile
+    const uint32_t no = L.M - o0 < L.tile ? L.M - o0 : L.tile;
+    const uint32_t vb = L.vb_first + 2u * L.D * o0;
+    const uint32_t base = vb & ~15u, d0 = vb - base;
+    const uint32_t nq = (d0 + 2u * L.D * (no - 1u) + 2u * L.T + 15u) >> 4;   // <= raw_bytes / 16: host plan
+    int16_t* const tab = reinterpret_cast<int16_t*>(lds + (L.raw_bytes >> 2));
+    uint32_t* const ypk = lds + ((L.raw_bytes + kTableBytes) >> 2);          // [K][tile]
+
+    fmd_ddc::stage(L, s, base, nq, lds, tab, tid, wave);
+    if (t == L.ntiles - 1u) fmd_ddc::write_history(L, s, tid);
+    __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0): the LDS-DMAs have landed
+    __syncthreads();
+
+    fmd_ddc::contract(L, s, wave, lane, d0, no, L.m0_lo + o0, lds, tab, ypk, L.tile, 0u);
+    __syncthreads();
+
+    // whole dwordx4 stores: o0 % 4 == 0 and the rows are padded to a multiple of 4 (the padding takes whatever the LDS row holds)
+    typedef FMD_DDC_GLOBAL fmd_ddc::i4* gqo;
+    const uint32_t n4 = (no + 3u) >> 2;
+    for (uint32_t idx = tid; idx < L.K * n4; idx += kThreads) {
+        const uint32_t k = idx / n4, i = idx - k * n4;
+        ((gqo)(uintptr_t)(L.y + ((uint64_t)s * L.K + k) * L.ystride + o0))[i] = reinterpret_cast<const fmd_ddc::i4*>(ypk + k * L.tile)[i];
+    }
+}
+
+struct ChanLaunch {
+    const uint32_t* y;         // [S K][ystride]: the call's y
+    uint32_t ystride, M;
+    const uint32_t* yh_in;     // [S K][HXS]: y of the HX samples before the call
+    uint32_t* yh_out;
+    uint32_t HX, HXS;          // Ta - 1, row stride (>= 1)
+    const unsigned long long* carry_in;   // [S K][kCarry]
+    unsigned long long* carry_out;
+    uint32_t SK;
+    int32_t yoff0;             // R nS - mS: the first window of the call, relative to the call's first y (> -Ta)
+    uint64_t nS;               // audio samples before the call
+    uint32_t NA, na, ntiles;   // audio samples of the call, per tile, tiles per row
+    uint32_t R, Q, rinv, pitch, Ta;   // Q = ceil(Ta / R) rounded up to a multiple of 4; rinv = ceil(2^32 / R) (R >= 2); LDS row pitch (odd)
+    uint32_t chan_shift, pshift, mode, gain;
+    uint64_t thr;              // squelch^2 P (0: always open)
+    const int2* g;             // [R][Q] (gr, gi), polyphase order, zero padded (32-byte aligned rows)
+    int16_t* out;              // [S K][out_cap][width]
+    uint64_t out_cap;
+};
+
+// floor(sqrt(x)), x <= 2^29: the f32 estimate is within 1 of it
+__device__ __forceinline__ uint32_t isqrt29(uint32_t x)
+{
+    uint32_t r = (uint32_t)__builtin_amdgcn_sqrtf((float)x);
+    r -= (r * r > x) ? 1u : 0u;
+    r += ((r + 1u) * (r + 1u) <= x) ? 1u : 0u;
+    return r;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// acc + g y with 24-bit operands; the tap g is wave-uniform (an SGPR)
+__device__ __forceinline__ int mad24(int g, int y, int acc)
+{
+    int r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "s"(g), "v"(y), "v"(acc));
+    return r;
+}
+
+// one tap (gr + j gi) on one sample: four real multiply-adds, two when the taps are real
+template <bool CPLX>
+__device__ __forceinline__ void fir_step(int gr, int gi, int2 y, int& vr, int& vi)
+{
+    vr = mad24(gr, y.x, vr);
+    vi = mad24(gr, y.y, vi);
+    if (CPLX) {
+        vr = mad24(-gi, y.y, vr);                            // (the negation is scalar)
+        vi = mad24(gi, y.x, vi);
+    }
+}
+
+typedef int tap4 __attribute__((ext_vector_type(8)));       // four (gr, gi) taps
+typedef const __attribute__((address_space(4))) tap4* ctap4;
+
+template <bool CPLX>
+__global__ void __launch_bounds__(kThreads) fmd_narrow_chan_kernel(const ChanLaunch L)
+{
+    __shared__ __attribute__((aligned(16))) int2 ys[kYCap];
+    __shared__ uint32_t ub[kTile + 1];                       // u packed; ub[0] = u of the sample before the tile
+    __shared__ uint32_t ab[kTile];                           // a
+    __shared__ unsigned long long bE[kMaxBlk];               // the tile's share of each block's sums
+    __shared__ uint32_t bA[kMaxBlk];
+    __shared__ uint32_t est[kMaxBlk][2];                     // open, dc of the block BEFORE block jlo + i
+    __shared__ unsigned long long st[kCarry];                // the row's running carry
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t row = blockIdx.x;
+    if (row >= L.SK) return;
+
+    typedef const __attribute__((address_space(4))) int2* ctaps;             // wave-uniform reads: the scalar cache
+    const ctaps g = (ctaps)(uintptr_t)L.g;
+    const uint32_t* const yrow = L.y + (uint64_t)row * L.ystride;
+    const uint32_t* const hin = L.yh_in + (uint64_t)row * L.HXS;
+    if (tid < kCarry) st[tid] = L.carry_in[(uint64_t)row * kCarry + tid];
+    __syncthreads();
+    if (tid == 0u) ub[0] = (uint32_t)st[3];
+
+    for (uint32_t t = 0; t < L.ntiles; ++t) {
+        const uint32_t na0 = t * L.na;                       // first audio sample (of this call) of the tile
+        const uint32_t cnt = L.NA - na0 < L.na ? L.NA - na0 : L.na;
+        const int rel0 = L.yoff0 + (int)(L.R * na0);         // the tile's first y, relative to the call's first
+        const uint32_t nsamp = L.R * (cnt - 1u) + L.Ta;      // <= R pitch: host plan
+
+        // ---- 1. y into LDS, polyphase ---------------------------------------------------------------------------------------
+        for (uint32_t i = tid; i < nsamp; i += kThreads) {
+            const int rel = rel0 + (int)i;
+            const uint32_t p = rel < 0 ? hin[(int)L.HX + rel] : yrow[rel];
+            const uint32_t c = L.R == 1u ? i : __umulhi(i, L.rinv);
+            const uint32_t r = i - c * L.R;
+            ys[r * L.pitch + c] = int2{(int)(int16_t)(p & 0xFFFFu), (int)p >> 16};
+        }
+        __syncthreads();
+
+        // ---- 2. FIR, shift, magnitude ---------------------------------------------------------------------------------------
+        if (tid < cnt) {
+            int vr = 0, vi = 0;
+            const int2* w = ys + tid;
+            ctaps gp = g;
+            for (uint32_t r = 0; r < L.R; ++r) {
+#pragma unroll 2
+                for (uint32_t q = 0; q < L.Q; q += 4u) {     // Q % 4 == 0: four taps per s_load_dwordx8
+                    const tap4 gv = *reinterpret_cast<ctap4>(gp + q);
+                    const int2 y0 = w[q], y1 = w[q + 1u], y2 = w[q + 2u], y3 = w[q + 3u];
+                    fir_step<CPLX>(gv.s0, gv.s1, y0, vr, vi);
+                    fir_step<CPLX>(gv.s2, gv.s3, y1, vr, vi);
+                    fir_step<CPLX>(gv.s4, gv.s5, y2, vr, vi);
+                    fir_step<CPLX>(gv.s6, gv.s7, y3, vr, vi);
+                }
+                w += L.pitch;
+                gp += L.Q;
+            }
+            const int ur = vr >> L.chan_shift, ui = vi >> L.chan_shift;
+            ub[tid + 1u] = ((uint32_t)ur & 0xFFFFu) | ((uint32_t)ui << 16);
+            ab[tid] = isqrt29((uint32_t)(ur * ur + ui * ui));
+        }
+        __syncthreads();
+
+        // ---- 3. block sums and the squelch state ----------------------------------------------------------------------------
+        const uint64_t N0 = L.nS + na0;
+        const uint64_t jlo = N0 >> L.pshift;
+        const uint32_t nblk = (uint32_t)(((N0 + cnt - 1u) >> L.pshift) - jlo) + 1u;   // <= kMaxBlk
+        for (uint32_t b = wave; b < nblk; b += 4u) {
+            const uint64_t bs = (jlo + b) << L.pshift, be = bs + (1ull << L.pshift);
+            const uint32_t i0 = bs > N0 ? (uint32_t)(bs - N0) : 0u;
+            const uint32_t i1 = be < N0 + cnt ? (uint32_t)(be - N0) : cnt;
+            unsigned long long se = 0;
+            uint32_t sa = 0;
+            for (uint32_t i = i0 + lane; i < i1; i += 64u) {
+                const uint32_t p = ub[i + 1u];
+                const int ur = (int16_t)(p & 0xFFFFu), ui = (int)p >> 16;
+                se += (uint32_t)(ur * ur + ui * ui);
+                sa += ab[i];
+            }
+            se = wave_sum64(se);
+            sa = (uint32_t)wave_sum64(sa);
+            if (lane == 0u) { bE[b] = se; bA[b] = sa; }
+        }
+        __syncthreads();
+        if (tid == 0u) {
+            unsigned long long E = st[0], A = st[1], Elast = st[2], dc = st[4], open = st[5];
+            for (uint32_t b = 0; b < nblk; ++b) {
+                est[b][0] = (L.thr == 0u || open) ? 1u : 0u;
+                est[b][1] = (uint32_t)dc;
+                E += bE[b]; A += bA[b];
+                if (((jlo + b + 1u) << L.pshift) <= N0 + cnt) {              // the block is complete
+                    open = E >= L.thr ? 1u : 0u;
+                    dc = A >> L.pshift;
+                    Elast = E;
+                    E = 0; A = 0;
+                }
+            }
+            st[0] = E; st[1] = A; st[2] = Elast; st[4] = dc; st[5] = open;
+        }
+        __syncthreads();
+
+        // ---- 4. detector, gain, squelch -------------------------------------------------------------------------------------
+        if (tid < cnt) {
+            const uint32_t b = (uint32_t)(((N0 + tid) >> L.pshift) - jlo);
+            const bool open = est[b][0] != 0u;
+            const uint32_t cur = ub[tid + 1u];
+            const uint64_t o = (uint64_t)row * L.out_cap + na0 + tid;
+            if (L.mode == FMD_NARROW_IQ) {
+                reinterpret_cast<uint32_t*>(L.out)[o] = open ? cur : 0u;
+            } else {
+                int wv;
+                if (L.mode == FMD_NARROW_FM) wv = (int)(int16_t)fmd_dev::disc_nosel(cur, ub[tid]);
+                else if (L.mode == FMD_NARROW_AM) wv = (int)ab[tid] - (int)est[b][1];
+                else wv = (int)(int16_t)(cur & 0xFFFFu);
+                int v = (wv * (int)L.gain) >> 8;
+                v = v > 32767 ? 32767 : (v < -32768 ? -32768 : v);
+                L.out[o] = open ? (int16_t)v : (int16_t)0;
+            }
+        }
+        __syncthreads();
+        if (tid == 0u) ub[0] = ub[cnt];
+    }
+
+    // ---- the next call's state ----------------------------------------------------------------------------------------------
+    uint32_t* const hout = L.yh_out + (uint64_t)row * L.HXS;
+    for (uint32_t i = tid; i < L.HX; i += kThreads) {        // y of the call's last HX samples: virtual index over history ++ call
+        const uint32_t v = L.M + i;
+        hout[i] = v < L.HX ? hin[v] : yrow[v - L.HX];
+    }
+    if (tid == 0u) {
+        unsigned long long* const c = L.carry_out + (uint64_t)row * kCarry;
+        c[0] = st[0]; c[1] = st[1]; c[2] = st[2]; c[3] = ub[0]; c[4] = st[4]; c[5] = st[5];
+    }
+}
+
+}  // namespace fmd_nb
+
+struct fmd_narrow {
+    uint32_t T = 0, D = 0, K = 0, S = 0, shift = 0, HB = 0;
+    uint32_t groups = 0, tile = 0, raw_bytes = 0;
+    size_t lds = 0;
+    uint32_t Ta = 0, R = 0, Q = 0, P = 0, pshift = 0, chan_shift = 0, mode = 0, squelch = 0, gain = 0, width = 1;
+    uint32_t HX = 0, HXS = 0, na = 0, pitch = 0, rinv = 0;
+    bool cplx = false;
+    FmdDdcPlan plan;
+    FmdDdcCore core;
+    int2* d_g = nullptr;                                  // [R][Q] polyphase taps
+    uint32_t* d_yh[2] = {nullptr, nullptr};               // [S K][HXS] y history, read [core.cur], written [core.cur ^ 1]
+    unsigned long long* d_carry[2] = {nullptr, nullptr};  // [S K][kCarry]
+    void* d_y = nullptr; size_t d_y_cap = 0;              // the call's y
+};
+
+namespace {
+
+using fmd_ddc::kTableBytes;
+
+constexpr size_t kLdsBudget = 40960;
+
+size_t nb_lds(uint32_t D, uint32_t nkc, uint32_t T, uint32_t K, uint32_t G, uint32_t* raw_bytes)
+{
+    const uint64_t cap = 64ull * G;
+    const uint64_t reads = 12 + 6ull * D + 8ull * D * (16 * G - 1) + 64ull * nkc;
+    const uint64_t staged = 12 + 2ull * D * (cap - 1) + 2ull * T + 15;
+    const uint64_t raw = ((reads > staged ? reads : staged) + 15) & ~15ull;
+    *raw_bytes = (uint32_t)raw;
+    return (size_t)(raw + kTableBytes + 4ull * K * cap);
+}
+
+uint64_t nb_y(const fmd_narrow* h, uint64_t S) { return S >= h->T ? (S - h->T) / h->D + 1 : 0; }
+uint64_t nb_audio(const fmd_narrow* h, uint64_t m) { return m >= h->Ta ? (m - h->Ta) / h->R + 1 : 0; }
+
+uint32_t isqrt_u64(uint64_t v)
+{
+    uint64_t r = (uint64_t)std::sqrt((double)v);
+    while (r * r > v) --r;
+    while ((r + 1) * (r + 1) <= v) ++r;
+    return (uint32_t)r;
+}
+
+int nb_enqueue(fmd_narrow* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
+{
+    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
+    if (nbytes > (1ull << 31) - (1ull << 20)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
+    if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & (2u * h->width - 1u)) != 0) {
+        fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG;
+    }
+    FmdDdcCore& c = h->core;
+    const uint64_t ns = nbytes / 2;
+    const uint64_t mS = nb_y(h, c.pos), mE = nb_y(h, c.pos + ns), M = mE - mS;
+    const uint64_t nS = nb_audio(h, mS), NA = nb_audio(h, mE) - nS;
+    if (NA < 1) { fmd_internal_set_err("the call completes no audio sample"); return FMD_ERR_TOO_SHORT; }
+    if (NA > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
+    const uint64_t SK = (uint64_t)h->S * h->K;
+    const uint64_t nt1 = (M + h->tile - 1) / h->tile, nt2 = (NA + h->na - 1) / h->na;
+    if (nt1 > (1u << 30) || h->S > 65535u) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
+    const uint64_t ystride = (M + 3) & ~3ull;
+    FMD_DDC_TRY(fmd_ddc_grow(h->d_y, h->d_y_cap, (size_t)(SK * ystride * 4)));
+    const int cur = c.cur;
+
+    fmd_nb::DdcLaunch A{};
+    A.iq = static_cast<const uint8_t*>(d_iq);
+    A.nbytes = nbytes;
+    A.hist_in = c.d_hist[cur]; A.hist_out = c.d_hist[cur ^ 1];
+    A.HB = h->HB;
+    A.vb_first = (uint32_t)(2ull * (h->D * mS + h->HB / 2 - c.pos));
+    A.m0_lo = (uint32_t)mS; A.M = (uint32_t)M;
+    A.D = h->D; A.T = h->T; A.K = h->K; A.S = h->S; A.shift = h->shift;
+    A.nrt = h->plan.nrt; A.nkc = h->plan.nkc; A.digits = h->plan.digits;
+    A.tile = h->tile; A.ntiles = (uint32_t)nt1; A.raw_bytes = h->raw_bytes;
+    A.amat = c.d_amat; A.kconst = c.d_kconst; A.dinc = c.d_dinc; A.tab = c.d_tab;
+    A.y = static_cast<uint32_t*>(h->d_y); A.ystride = (uint32_t)ystride;
+
+    fmd_nb::ChanLaunch B{};
+    B.y = A.y; B.ystride = A.ystride; B.M = (uint32_t)M;
+    B.yh_in = h->d_yh[cur]; B.yh_out = h->d_yh[cur ^ 1];
+    B.HX = h->HX; B.HXS = h->HXS;
+    B.carry_in = h->d_carry[cur]; B.carry_out = h->d_carry[cur ^ 1];
+    B.SK = (uint32_t)SK;
+    B.yoff0 = (int32_t)((int64_t)(h->R * nS) - (int64_t)mS);
+    B.nS = nS; B.NA = (uint32_t)NA; B.na = h->na; B.ntiles = (uint32_t)nt2;
+    B.R = h->R; B.Q = h->Q; B.rinv = h->rinv; B.pitch = h->pitch; B.Ta = h->Ta;
+    B.chan_shift = h->chan_shift; B.pshift = h->pshift; B.mode = h->mode; B.gain = h->gain;
+    B.thr = (uint64_t)h->squelch * h->squelch * h->P;
+    B.g = h->d_g;
+    B.out = static_cast<int16_t*>(d_out); B.out_cap = out_cap;   // samples per row: int16 each, a dword each in IQ mode
+
+    FMD_DDC_TRY(c.order.before(stream));
+    hipLaunchKernelGGL(fmd_nb::fmd_narrow_ddc_kernel, dim3(A.ntiles, h->S), dim3(fmd_nb::kThreads), h->lds, stream, A);
+    FMD_DDC_TRY(hipGetLastError());
+    if (h->cplx) hipLaunchKernelGGL(fmd_nb::fmd_narrow_chan_kernel<true>, dim3((uint32_t)SK), dim3(fmd_nb::kThreads), 0, stream, B);
+    else hipLaunchKernelGGL(fmd_nb::fmd_narrow_chan_kernel<false>, dim3((uint32_t)SK), dim3(fmd_nb::kThreads), 0, stream, B);
+    FMD_DDC_TRY(hipGetLastError());
+    (void)c.order.after(stream);
+    c.cur ^= 1;
+    c.pos += ns;
+    if (out_len) *out_len = (size_t)NA;
+    return FMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fmd_narrow_out_cap(uint32_t decim, uint32_t chan_decim, size_t nbytes)
+{
+    if (!decim || !chan_decim) return 0;
+    const uint64_t d = 2ull * decim * chan_decim;
+    return (size_t)((nbytes + d - 1) / d);
+}
+
+uint32_t fmd_narrow_out_width(uint32_t mode) { return mode == FMD_NARROW_IQ ? 2u : 1u; }
+
+int fmd_narrow_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t* phase_inc,
+                   uint32_t n_stations, const int16_t* chan_taps_re, const int16_t* chan_taps_im, uint32_t n_chan_taps,
+                   const fmd_narrow_config* cfg, const fmd_device_config* dev, fmd_narrow** out)
+{
+    if (!taps || !phase_inc || !chan_taps_re || !cfg || !dev || !out || dev->n_channels == 0) {
+        fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    if (n_taps == 0 || n_taps > 256 || decim < 2 || decim % 2 != 0 || decim > 64 || shift > 24 || n_stations == 0 || n_stations > 32 ||
+        dev->n_channels > 65535u) {
+        fmd_internal_set_err("need 1 <= n_taps <= 256, an even 2 <= decim <= 64, shift <= 24, 1 <= n_stations <= 32, n_streams <= 65535");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    for (uint32_t t = 0; t < n_taps; ++t)
+        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
+    const uint32_t R = cfg->chan_decim, P = cfg->block, Ta = n_chan_taps;
+    if (cfg->mode > FMD_NARROW_SSB || R < 1u || R > 32u || Ta < 1u || Ta > 256u || cfg->chan_shift > 30u || cfg->squelch > 23170u ||
+        cfg->gain < 1u || cfg->gain > 65535u) {
+        fmd_internal_set_err("need mode <= 3, 1 <= chan_decim <= 32, 1 <= n_chan_taps <= 256, chan_shift <= 30, squelch <= 23170, 1 <= gain <= 65535");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    if (P < 16u || P > 4096u || (P & (P - 1u)) != 0) { fmd_internal_set_err("block must be a power of two in [16, 4096]"); return FMD_ERR_UNSUPPORTED; }
+    uint64_t gsum = 0;
+    bool cplx = false;
+    for (uint32_t t = 0; t < Ta; ++t) {
+        const int gr = chan_taps_re[t], gi = chan_taps_im ? chan_taps_im[t] : 0;
+        if (gr > 16383 || gr < -16383 || gi > 16383 || gi < -16383) { fmd_internal_set_err("|chan tap| > 16383"); return FMD_ERR_UNSUPPORTED; }
+        gsum += (uint64_t)(gr < 0 ? -gr : gr) + (uint64_t)(gi < 0 ? -gi : gi);
+        if (gi) cplx = true;
+    }
+    if (gsum > 65535u) { fmd_internal_set_err("sum |gr| + |gi| > 65535"); return FMD_ERR_UNSUPPORTED; }
+    fmd_narrow* h = new (std::nothrow) fmd_narrow();
+    if (!h) return FMD_ERR_NOMEM;
+    h->T = n_taps; h->D = decim; h->K = n_stations; h->S = dev->n_channels; h->shift = shift;
+    fmd_st_build_plan(taps, n_taps, decim, phase_inc, h->S, h->K, h->plan);
+    const uint64_t bound = (256ull * h->plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
+    if (bound > 16384ull) {
+        delete h;
+        fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    if (((bound * gsum + ((1ull << cfg->chan_shift) - 1ull)) >> cfg->chan_shift) > 16384ull) {
+        delete h;
+        fmd_internal_set_err("channel filter gain too large: need ceil(B_y * sum(|gr| + |gi|) / 2^chan_shift) <= 16384");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    for (uint32_t G = fmd_ddc::kGroups; G >= 1; --G) {
+        uint32_t rb;
+        const size_t l = nb_lds(decim, h->plan.nkc, n_taps, n_stations, G, &rb);
+        if (l <= kLdsBudget || G == 1) { h->groups = G; h->tile = 64u * G; h->raw_bytes = rb; h->lds = l; break; }
+    }
+    h->HB = 2u * ((n_taps - 1u + 7u) & ~7u);
+    h->Ta = Ta; h->R = R; h->Q = ((Ta + R - 1u) / R + 3u) & ~3u; h->P = P; h->chan_shift = cfg->chan_shift; h->mode = cfg->mode;
+    h->squelch = cfg->squelch; h->gain = cfg->gain; h->width = fmd_narrow_out_width(cfg->mode); h->cplx = cplx;
+    while ((1u << h->pshift) < P) ++h->pshift;
+    h->HX = Ta - 1u; h->HXS = h->HX ? h->HX : 1u;
+    h->rinv = R >= 2u ? (uint32_t)(((1ull << 32) + R - 1u) / R) : 0u;
+    const uint32_t pmax = (fmd_nb::kYCap / R - 1u) | 1u;  // the largest odd pitch with R pitch <= kYCap (>= 191)
+    const uint32_t na = pmax - h->Q;                      // >= 183
+    h->na = na < fmd_nb::kTile ? na : fmd_nb::kTile;
+    h->pitch = (h->na + h->Q) | 1u;                       // <= pmax
+
+    if (const int rc = fmd_ddc_open(h->core, dev)) { delete h; return rc; }
+    auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_narrow_free(h); return FMD_ERR_HIP; };
+    FmdDeviceGuard guard(h->core.device);
+    if (guard.error() != hipSuccess) return fail("hipSetDevice");
+    if (const char* what = fmd_ddc_upload(h->core, h->plan, (size_t)h->S * (h->HB ? h->HB : 16))) return fail(what);
+    std::vector<int2> gp((size_t)R * h->Q, int2{0, 0});
+    for (uint32_t t = 0; t < Ta; ++t) gp[(size_t)(t % R) * h->Q + t / R] = int2{chan_taps_re[t], chan_taps_im ? chan_taps_im[t] : 0};
+    if (hipMalloc(&h->d_g, gp.size() * sizeof(int2)) != hipSuccess || hipMemcpy(h->d_g, gp.data(), gp.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess)
+        return fail("hipMalloc(channel taps)");
+    const size_t SK = (size_t)h->S * h->K;
+    for (int i = 0; i < 2; ++i) {
+        if (hipMalloc(&h->d_yh[i], SK * h->HXS * 4) != hipSuccess || hipMemset(h->d_yh[i], 0, SK * h->HXS * 4) != hipSuccess) return fail("hipMalloc(y history)");
+        if (hipMalloc(&h->d_carry[i], SK * fmd_nb::kCarry * 8) != hipSuccess || hipMemset(h->d_carry[i], 0, SK * fmd_nb::kCarry * 8) != hipSuccess)
+            return fail("hipMalloc(block carry)");
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
+    *out = h;
+    return FMD_OK;
+}
+
+void fmd_narrow_free(fmd_narrow* h)
+{
+    if (!h) return;
+    FmdDeviceGuard guard(h->core.device);
+    (void)hipDeviceSynchronize();
+    for (void* p : {(void*)h->d_g, (void*)h->d_yh[0], (void*)h->d_yh[1], (void*)h->d_carry[0], (void*)h->d_carry[1], h->d_y})
+        if (p) (void)hipFree(p);
+    fmd_ddc_release(h->core);
+    delete h;
+}
+
+int fmd_narrow_reset(fmd_narrow* h)
+{
+    if (!h) return FMD_ERR_INVALID_ARG;
+    FMD_DDC_ON_DEVICE(h->core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    const size_t SK = (size_t)h->S * h->K;
+    for (int i = 0; i < 2; ++i) {
+        FMD_DDC_TRY(hipMemset(h->d_yh[i], 0, SK * h->HXS * 4));
+        FMD_DDC_TRY(hipMemset(h->d_carry[i], 0, SK * fmd_nb::kCarry * 8));
+    }
+    FMD_DDC_TRY(fmd_ddc_zero_history(h->core));          // (ends with the device synchronised; position and buffer index to 0)
+    return FMD_OK;
+}
+
+int fmd_narrow_run_device(fmd_narrow* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, void* stream)
+{
+    if (!h || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->core.device);
+    return nb_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream));
+}
+
+int fmd_narrow_check(fmd_narrow* h)
+{
+    if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->core.device);
+    if (h->core.order.have_last) FMD_DDC_TRY(hipStreamSynchronize(h->core.order.last));
+    FMD_DDC_TRY(hipGetLastError());
+    return FMD_OK;
+}
+
+int fmd_narrow_run_batch(fmd_narrow* h, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap, size_t* out_len)
+{
+    if (!h || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->core.device);
+    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
+    FmdDdcCore& c = h->core;
+    const size_t rows = (size_t)h->S * h->K;
+    const size_t in_bytes = nbytes * (size_t)h->S, out_bytes = out_cap * rows * h->width * sizeof(int16_t);
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
+    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
+    size_t n = 0;
+    int rc = nb_enqueue(h, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream);
+    if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
+    FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
+    *out_len = n;
+    return FMD_OK;
+}
+
+int fmd_narrow_outputs(const fmd_narrow* h, uint64_t* outputs)
+{
+    if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    *outputs = nb_audio(h, nb_y(h, h->core.pos));
+    return FMD_OK;
+}
+
+int fmd_narrow_level(fmd_narrow* h, uint32_t stream, uint32_t station, int* open, uint32_t* rms)
+{
+    if (!h || !open || !rms) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    if (stream >= h->S || station >= h->K) { fmd_internal_set_err("stream or station out of range"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    *open = 0; *rms = 0;
+    if ((nb_audio(h, nb_y(h, h->core.pos)) >> h->pshift) == 0) return FMD_OK;   // no block has completed
+    unsigned long long c[fmd_nb::kCarry];
+    FMD_DDC_TRY(hipMemcpy(c, h->d_carry[h->core.cur] + (size_t)fmd_nb::kCarry * ((size_t)stream * h->K + station), sizeof c, hipMemcpyDeviceToHost));
+    *open = (h->squelch == 0u || c[5]) ? 1 : 0;
+    *rms = isqrt_u64(c[2] >> h->pshift);
+    return FMD_OK;
+}
+
+int fmd_narrow_kernel_name(const fmd_narrow* h, uint32_t pass, char* name, size_t cap)
+{
+    if (!h || !name || cap == 0 || pass > 1) return FMD_ERR_INVALID_ARG;
+    return fmd_ddc_name_rc(snprintf(name, cap, pass == 0 ? "fmd_nb::fmd_narrow_ddc_kernel" :
+                                    (h->cplx ? "fmd_nb::fmd_narrow_chan_kernel<true>" : "fmd_nb::fmd_narrow_chan_kernel<false>")), cap);
+}
+
+}  // extern "C"

@@ -21,6 +21,8 @@
 // downsample) is the prototype filter, mixed to each station by fmd_stations_*; audio of station k goes to <prefix>.<k>.s16.
 // With -I the same filter runs through the channelizer (fmd_channelizer_*) instead: station k's complex baseband at
 // capture_rate / downsample goes to <prefix>.<k>.cs16 as interleaved s16 (I, Q) pairs, no demodulation.
+// With -N mode[:R[:lo:hi]] [-q squelch] the narrow-band bank (fmd_narrow_*) instead: station k's channel from lo to hi Hz around its
+// offset through 256 channel taps at stride R, detected as iq / fm / am / usb / lsb, s16 (interleaved I/Q as .cs16 in iq mode).
 // With -2 the stereo station bank (fmd_stereo_*) instead: station k's pilot-locked stereo, interleaved s16 (L, R) at
 // f_m / R (f_m = capture_rate / downsample, R = max(1, floor(f_m / 48000)); 127 audio taps from fm::stereo_taps, 75 us
 // de-emphasis, blocks of 4096) goes to <prefix>.<k>.s16; the audio rate is printed on stderr.
@@ -184,7 +186,7 @@ static int run_rtl_tcp(const char* hostport, uint32_t freq, uint32_t rate, uint3
 
 // -S: one capture, K stations (fmd_stations_*; with -I their baseband, fmd_channelizer_*)
 static int run_stations(const char* path, const char* list, const char* prefix, uint32_t freq, uint32_t rate, uint32_t resample,
-                        bool iq_out, bool stereo)
+                        bool iq_out, bool stereo, const char* narrow, uint32_t squelch)
 {
     FILE* in = strcmp(path, "-") ? fopen(path, "rb") : stdin;
     if (!in) { perror(path); return 2; }
@@ -207,7 +209,39 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
         std::unique_ptr<fm::StationBank> bank;
         std::unique_ptr<fm::Channelizer> chan;
         std::unique_ptr<fm::StereoBank> st;
-        if (stereo) {
+        std::unique_ptr<fm::NarrowBank> nb;
+        if (narrow) {
+            // -N mode[:R[:lo:hi]]: 256 channel taps from fm::narrow_taps; chan_shift keeps |u| <= 256 in fm mode (where the
+            // reference's discriminator cannot wrap), <= 16384 otherwise; squelch blocks of 256 samples, gain 1.0
+            char mode[8] = {0};
+            unsigned R = 0;
+            double lo = 0, hi = 0;
+            const int got = sscanf(narrow, "%7[a-z]:%u:%lf:%lf", mode, &R, &lo, &hi);
+            const uint32_t f_m = capture / D;
+            uint32_t m;
+            if (!strcmp(mode, "iq") || !strcmp(mode, "raw")) m = FMD_NARROW_IQ;
+            else if (!strcmp(mode, "fm")) m = FMD_NARROW_FM;
+            else if (!strcmp(mode, "am")) m = FMD_NARROW_AM;
+            else if (!strcmp(mode, "usb") || !strcmp(mode, "lsb")) m = FMD_NARROW_SSB;
+            else { fprintf(stderr, "bad -N mode: %s (iq, fm, am, usb, lsb)\n", narrow); return 2; }
+            if (got < 2 || R == 0) R = std::max<uint32_t>(1, f_m / 12000);
+            if (got < 4) {
+                if (!strcmp(mode, "usb")) { lo = 300; hi = 3000; }
+                else if (!strcmp(mode, "lsb")) { lo = -3000; hi = -300; }
+                else { hi = m == FMD_NARROW_AM ? 4000 : 6000; lo = -hi; }
+            }
+            iq_out = m == FMD_NARROW_IQ;
+            const auto g = fm::narrow_taps((double)f_m, 256, lo, hi);
+            uint64_t gsum = 0;
+            for (int16_t v : g.first) gsum += (uint64_t)std::abs((int)v);
+            for (int16_t v : g.second) gsum += (uint64_t)std::abs((int)v);
+            const uint64_t peak = ((512ull * D + (1ull << shift) - 1) >> shift) * gsum, limit = m == FMD_NARROW_FM ? 256 : 16384;
+            uint32_t cs = 0;
+            while (cs < 30 && ((peak + (1ull << cs) - 1) >> cs) > limit) ++cs;
+            const fmd_narrow_config cfg{m, R, cs, 256, squelch, 256};
+            nb.reset(new fm::NarrowBank(std::vector<int16_t>(D, 1), D, shift, incs, 1, g.first, g.second, cfg));
+            fprintf(stderr, "narrow-band %s: %.3f Hz (%s)\n", mode, (double)capture / D / R, iq_out ? "interleaved I/Q s16" : "s16");
+        } else if (stereo) {
             // the front end's shift keeps every |y| component <= 256, where the reference's discriminator cannot wrap
             uint32_t sshift = 0;
             while ((512ull * D + (1ull << sshift) - 1) >> sshift > 256ull) ++sshift;
@@ -237,7 +271,7 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
                 if (fill) fprintf(stderr, "dropped %zu trailing bytes (not a complete %zu-byte block)\n", fill, buf.size());
                 break;
             }
-            const auto rows = st ? st->run(buf.data(), buf.size())
+            const auto rows = nb ? nb->run(buf.data(), buf.size()) : st ? st->run(buf.data(), buf.size())
                                  : iq_out ? chan->run(buf.data(), buf.size()) : bank->demodulate(buf.data(), buf.size());
             for (size_t k = 0; k < out.size(); ++k) fm::output(rows[k], out[k]);
         }
@@ -296,6 +330,8 @@ int main(int argc, char** argv)
     const char* stations = nullptr;                          // -S off1,off2,...: station bank over one capture
     bool iq_out = false;                                     // -I: with -S, each station's baseband IQ instead of audio
     bool stereo = false;                                     // -2: with -S, each station's stereo audio (fmd_stereo_*)
+    const char* narrow = nullptr;                            // -N mode[:R[:lo:hi]]: with -S, narrow-band channels (fmd_narrow_*)
+    uint32_t squelch = 0;                                    // -q: their squelch (RMS amplitude; 0 = always open)
     uint32_t power_bins = 0, power_hop = 0;                  // -P N [-H hop]: power spectrum of one capture
     size_t max_blocks = 0;                                   // -n: stop after this many blocks (live mode; 0 = until the stream ends)
     std::vector<const char*> paths;
@@ -309,6 +345,8 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-S") && i + 1 < argc) stations = argv[++i];
         else if (!strcmp(argv[i], "-I")) iq_out = true;
         else if (!strcmp(argv[i], "-2")) stereo = true;
+        else if (!strcmp(argv[i], "-N") && i + 1 < argc) narrow = argv[++i];
+        else if (!strcmp(argv[i], "-q") && i + 1 < argc) squelch = (uint32_t)strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-P") && i + 1 < argc) power_bins = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-H") && i + 1 < argc) power_hop = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-n") && i + 1 < argc) max_blocks = strtoul(argv[++i], nullptr, 10);
@@ -320,15 +358,16 @@ int main(int argc, char** argv)
                             "       %s [-s ...] [-r ...] [-o prefix] -S off1,off2,... <capture.bin | ->   (stations at these offsets in Hz)\n"
                             "       %s [-s ...] [-o prefix] -S off1,off2,... -I <capture.bin | ->        (their baseband: s16 I/Q at capture_rate / downsample)\n"
                             "       %s [-s ...] [-o prefix] -S off1,off2,... -2 <capture.bin | ->        (their stereo: s16 L/R at capture_rate / downsample / R)\n"
+                            "       %s [-s ...] [-o prefix] -S off1,off2,... -N mode[:R[:lo:hi]] [-q squelch] <capture.bin | ->   (narrow-band channels: iq, fm, am, usb, lsb at capture_rate / downsample / R)\n"
                             "       %s -s capture_rate_hz -P n_bins [-H hop] <capture.bin | ->       (power spectrum: offset_hz power per bin)\n",
-                    argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                    argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else paths.push_back(argv[i]);
     }
     if (rtl_tcp) return run_rtl_tcp(rtl_tcp, freq, rate, resample, max_blocks);
     if (paths.empty()) { fprintf(stderr, "missing input file (use - for stdin)\n"); return 2; }
     if (power_bins) return run_power(paths[0], power_bins, power_hop, rate);
-    if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample, iq_out, stereo);
+    if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample, iq_out, stereo, narrow, squelch);
     if (paths.size() > 1 && gpus > 0) return run_sink(paths, prefix, freq, rate, resample, gpus);
     if (paths.size() > 1) return run_bank(paths, prefix, freq, rate, resample);
     path = paths[0];

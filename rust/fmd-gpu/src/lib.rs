@@ -102,6 +102,28 @@ pub struct fmd_stereo_config {
 }
 
 #[repr(C)]
+pub struct fmd_narrow {
+    _private: [u8; 0],
+}
+
+/// `fmd_narrow_config` of include/fmd.h (narrow-band bank); `mode` is FMD_NARROW_IQ / _FM / _AM / _SSB.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_narrow_config {
+    pub mode: u32,
+    pub chan_decim: u32,
+    pub chan_shift: u32,
+    pub block: u32,
+    pub squelch: u32,
+    pub gain: u32,
+}
+
+pub const FMD_NARROW_IQ: u32 = 0;
+pub const FMD_NARROW_FM: u32 = 1;
+pub const FMD_NARROW_AM: u32 = 2;
+pub const FMD_NARROW_SSB: u32 = 3;
+
+#[repr(C)]
 pub struct fmd_spectrum {
     _private: [u8; 0],
 }
@@ -202,6 +224,17 @@ extern "C" {
     pub fn fmd_stereo_pilot(s: *mut fmd_stereo, stream: u32, station: u32, present: *mut c_int, level: *mut u32) -> c_int;
     pub fn fmd_stereo_pilot_inc(capture_rate: u32, decim: u32, inc: *mut u32) -> c_int;
     pub fn fmd_stereo_kernel_name(s: *const fmd_stereo, pass: u32, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_narrow_new(taps: *const i16, n_taps: u32, decim: u32, shift: u32, phase_inc: *const u32, n_stations: u32, chan_taps_re: *const i16, chan_taps_im: *const i16, n_chan_taps: u32, cfg: *const fmd_narrow_config, dev: *const DeviceConfig, out: *mut *mut fmd_narrow) -> c_int;
+    pub fn fmd_narrow_free(s: *mut fmd_narrow);
+    pub fn fmd_narrow_reset(s: *mut fmd_narrow) -> c_int;
+    pub fn fmd_narrow_out_cap(decim: u32, chan_decim: u32, nbytes: usize) -> usize;
+    pub fn fmd_narrow_out_width(mode: u32) -> u32;
+    pub fn fmd_narrow_run_batch(s: *mut fmd_narrow, iq: *const u8, nbytes: usize, out: *mut i16, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn fmd_narrow_run_device(s: *mut fmd_narrow, d_iq: *const c_void, nbytes: usize, d_out: *mut c_void, out_cap: usize, out_len: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_narrow_check(s: *mut fmd_narrow) -> c_int;
+    pub fn fmd_narrow_outputs(s: *const fmd_narrow, outputs: *mut u64) -> c_int;
+    pub fn fmd_narrow_level(s: *mut fmd_narrow, stream: u32, station: u32, open: *mut c_int, rms: *mut u32) -> c_int;
+    pub fn fmd_narrow_kernel_name(s: *const fmd_narrow, pass: u32, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_spectrum_hann(n_bins: u32, amplitude: u32, window: *mut i16) -> c_int;
     pub fn fmd_spectrum_bin_inc(bin: u32, n_bins: u32, inc: *mut u32) -> c_int;
     pub fn fmd_spectrum_frames(n_bins: u32, hop: u32, nbytes: usize) -> usize;
