@@ -1,0 +1,529 @@
+"""Case generators of the *_domain GPU tests of the stereo bank, the narrow-band bank and the channelizer: shapes, tap sets and
+call-size sequences, in plain numpy, with the host-side plan arithmetic (tile sizes) copied from DESIGN.md so that a case can say
+which kernel path it reaches.  tests/test_domain_cases.py runs these against the references alone and asserts what each case
+claims; the GPU files feed the same cases to the handles."""
+import os
+from types import SimpleNamespace as NS
+
+import numpy as np
+
+import stations_ref as sr
+
+DECIMS = (2, 4, 6, 30, 62, 64)
+TAPS = (1, 2, 26, 27, 58, 59, 250, 256)
+K_TWO = (4, 5, 8, 9, 28, 29, 32)                                   # row tiles of 4 stations (two-digit taps)
+K_ONE = (8, 9, 16, 17, 24, 25, 32)                                 # row tiles of 8 (one-digit taps)
+K_EDGES = [(k, 2) for k in K_TWO] + [(k, 1) for k in K_ONE]
+
+
+def fuzz(default, offset):
+    n = max(default, int(os.environ.get("FMD_FUZZ_CASES", str(default))))
+    return n, np.random.default_rng(int(os.environ.get("FMD_FUZZ_SEED", "20260101")) + offset)
+
+
+def groups(D, T, K):
+    """G, the 16-column MFMA groups per wave of the first pass (st_lds / nb_lds / ch_lds): the largest G in 4 ... 1 with
+    raw + 2048 + 4 K 64 G <= 40960, raw = max(12 + 6 D + 8 D (16 G - 1) + 64 nkc, 12 + 2 D (64 G - 1) + 2 T + 15) rounded up to
+    16, nkc = ceil((12 + 2 T) / 64)."""
+    nkc = (12 + 2 * T + 63) // 64
+    for G in (4, 3, 2, 1):
+        reads = 12 + 6 * D + 8 * D * (16 * G - 1) + 64 * nkc
+        staged = 12 + 2 * D * (64 * G - 1) + 2 * T + 15
+        raw = (max(reads, staged) + 15) & ~15
+        if raw + 2048 + 4 * K * 64 * G <= 40960 or G == 1:
+            return G
+
+
+def stereo_na(Ta, R):
+    return min(256, (2048 - 2 * Ta) // R)
+
+
+def narrow_q(Ta, R):
+    return (-(-Ta // R) + 3) & ~3
+
+
+def narrow_na(Ta, R):
+    return min(256, ((6144 // R - 1) | 1) - narrow_q(Ta, R))
+
+
+def incs(rng, S, K):
+    """[S, K] phase_incs, every (stream, station) its own: an index slip between streams or stations cannot pass."""
+    while True:
+        v = rng.integers(0, 1 << 32, S * K, dtype=np.uint64)
+        if np.unique(v).size == v.size:
+            return v.reshape(S, K).astype(np.uint32)
+
+
+def front(rng, T, S, K, digits):
+    """Front-end taps and phase_incs of the wanted digit form: inc[0][0] = 0 makes that station's taps h itself."""
+    if digits == 2:
+        h = rng.integers(-2047, 2048, T).astype(np.int16)
+        h[int(rng.integers(0, T))] = 2047 * int(rng.choice([-1, 1]))
+    else:
+        h = rng.integers(-127, 128, T).astype(np.int16)
+    ii = incs(rng, S, K)
+    ii[0, 0] = 0
+    return h, ii
+
+
+def digits_of(h, ii):
+    w = [sr.complex_taps(h, int(x)) for x in np.asarray(ii).ravel()]
+    return 1 if max(max(np.abs(a).max(), np.abs(b).max()) for a, b in w) <= 127 else 2
+
+
+def shift_for(h, ii, limit):
+    """The smallest shift with ceil(256 max_gain / 2^shift) <= limit."""
+    g = sr.max_gain(h, np.unique(np.asarray(ii, dtype=np.uint64)))
+    s = 0
+    while -(-256 * g >> s) > limit:
+        s += 1
+    return s
+
+
+def y_bound(h, ii, shift):
+    return -(-256 * sr.max_gain(h, np.unique(np.asarray(ii, dtype=np.uint64))) >> shift)
+
+
+def bytes_(rng, S, n):
+    b = rng.integers(0, 256, (S, n), dtype=np.uint8)
+    if n >= 64:                                                    # a full-scale stretch
+        a = int(rng.integers(0, n - n // 4)) & ~1
+        b[:, a:a + n // 4] = np.where(rng.random((S, n // 4)) < 0.5, 0, 255)
+    return b
+
+
+def loud_quiet(rng, S, n, run):
+    """Random bytes in stretches of about `run` bytes, alternately full range and within 8 of the centre."""
+    b = rng.integers(0, 256, (S, n), dtype=np.uint8)
+    a, quiet = 0, False
+    while a < n:
+        e = a + 2 * int(rng.integers(run // 4, run))
+        if quiet:
+            b[:, a:e] = rng.integers(120, 136, b[:, a:e].shape, dtype=np.uint8)
+        a, quiet = e, not quiet
+    return b
+
+
+def audio_taps(rng, Ta, total=16383, sign=0):
+    """int16 taps with sum |g| == total exactly; sign +1 / -1: all of one sign, 0: random signs."""
+    mag = rng.multinomial(total - min(Ta, total), np.ones(Ta) / Ta) + (np.arange(Ta) < total)
+    sg = rng.choice([-1, 1], Ta) if sign == 0 else np.full(Ta, sign)
+    g = (mag * sg).astype(np.int16)
+    assert int(np.abs(g.astype(np.int64)).sum()) == total
+    return g
+
+
+def chan_taps(rng, Ta, cplx, peak=300):
+    """Random channel taps scaled to the rule: sum |gr| + |gi| <= 65535, every tap within 16383."""
+    gr = rng.integers(-peak, peak + 1, Ta).astype(np.int64)
+    gi = rng.integers(-peak, peak + 1, Ta).astype(np.int64) if cplx else np.zeros(Ta, np.int64)
+    gr[0] = gr[0] or 1
+    if cplx:
+        gi[-1] = gi[-1] or 1
+    f = min(65535 / int(np.abs(gr).sum() + np.abs(gi).sum()), 16383 / int(max(np.abs(gr).max(), np.abs(gi).max())))
+    if f < 1:
+        gr, gi = np.trunc(gr * f).astype(np.int64), np.trunc(gi * f).astype(np.int64)
+        gr[0] = gr[0] or 1
+        if cplx:
+            gi[-1] = gi[-1] or 1
+    return gr.astype(np.int16), (gi.astype(np.int16) if cplx else None)
+
+
+def chan_shift_for(h, ii, shift, gr, gi, limit):
+    peak = y_bound(h, ii, shift) * int(np.abs(gr.astype(np.int64)).sum() + (0 if gi is None else np.abs(gi.astype(np.int64)).sum()))
+    s = 0
+    while -(-peak >> s) > limit:
+        s += 1
+    return s
+
+
+def pos_for_outputs(T, D, m):
+    """The smallest sample count, a multiple of 4 (nbytes % 8 == 0), after which exactly m front-end outputs exist (D >= 4)."""
+    assert D >= 4 and m >= 1
+    p = -(-(T + (m - 1) * D) // 4) * 4
+    assert (p - T) // D + 1 == m
+    return p
+
+
+def sizes_for_outputs(T, D, ends):
+    """Byte counts of consecutive calls after which the front end has produced ends[0], ends[1], ... outputs in all."""
+    out, pos = [], 0
+    for m in ends:
+        p = pos_for_outputs(T, D, m)
+        assert p > pos
+        out.append(2 * (p - pos))
+        pos = p
+    return out
+
+
+def y_for_audio(Ta, R, n):
+    """The smallest count of second-stage inputs after which exactly n audio samples exist."""
+    return Ta + (n - 1) * R
+
+
+def short_ends(Ta, R, Ms):
+    """Second-stage input counts after consecutive calls: a call of M inputs for every M in Ms, each completing audio (a call
+    that re-aligns to one input before a completion comes first where needed), then a long call."""
+    m = Ta + 40 * R + R - 1
+    ends = [m]
+    for M in Ms:
+        if (m - Ta) % R != R - 1:
+            m = Ta + ((m - Ta) // R + 2) * R - 1
+            ends.append(m)
+        m += M
+        ends.append(m)
+    return ends + [m + 3000]
+
+
+# ---- stereo bank ---------------------------------------------------------------------------------------------------------------
+
+ST_BLOCKS = (1024, 4096, 16384)
+ST_TA = (1, 2, 63, 64, 255, 256)
+
+
+def stereo_handle(c, fmd, S=None):
+    return fmd.StereoBank(c.h, c.D, c.incs, c.rate, c.g, c.R, n_streams=c.S if S is None else S, block=c.P, pilot_min=c.pilot_min,
+                          audio_shift=c.audio_shift, shift=c.shift, device_id=0)
+
+
+def stereo_refs(c, st, check=None, z=sr.z_corr, pilot_min=None):
+    return {s: st.StereoRef(c.h, c.D, c.incs[s], c.shift, c.rate, c.g, c.R, c.P, c.pilot_min if pilot_min is None else pilot_min,
+                            c.audio_shift, z=z) for s in (range(c.S) if check is None else check)}
+
+
+def default_pilot_min(rate, D):
+    return (32768 * 6750 * D) // (4 * rate)
+
+
+def stereo_sweep():
+    """Every R in 1 ... 32 (case i has R = i % 32 + 1); Ta from ST_TA or chosen against R; D, K edges of both digit forms, P,
+    pilot_min, audio_shift spread over the sweep; every fourth case a call of more than three audio tiles."""
+    n_cases, rng = fuzz(32, 1101)
+    for i in range(n_cases):
+        R = i % 32 + 1
+        K, digits = K_EDGES[i % 14] if i % 2 == 0 or i < 28 else (int(rng.integers(1, 4)), 2)
+        D = DECIMS[(i + i // 6) % 6]
+        if i % 16 == 7:
+            D, K, digits = 64, 8, 2                                # G = 3
+        if i % 16 == 15:
+            D, K, digits = 64, (24, 28, 32)[(i // 16) % 3], 2      # G = 2
+        T = TAPS[(3 * i + i // 8) % 8]
+        Ta = (ST_TA + (R, R + 1, max(1, R - 1), min(256, 4 * R + 1), 256, 255))[(i + i // 12) % 12]
+        if i % 8 == 3 or R == 32:
+            Ta = 256                                               # na < 256 from R = 7 on
+        S = 1 if K > 9 else 2
+        h, ii = front(rng, T, S, K, digits)
+        P = ST_BLOCKS[i % 3] if ST_BLOCKS[i % 3] * D <= 65536 else 1024
+        rate = 106000 * D + int(rng.integers(0, 50000)) * D
+        pm = (0, 1, None, 16384, 1, None)[i % 6]
+        pm = default_pilot_min(rate, D) if pm is None else pm
+        g = audio_taps(rng, Ta, int(rng.integers(max(Ta, 8000), 16384)) if Ta < 16383 else 16383)
+        c = NS(kind="stereo", i=i, R=R, K=K, digits=digits, D=D, T=T, Ta=Ta, S=S, h=h, incs=ii, P=P, rate=rate, pilot_min=pm, g=g,
+               audio_shift=int(rng.integers(0, 17)), shift=shift_for(h, ii, int(rng.choice([256, 2048, 16384]))),
+               G=groups(D, T, K), na=stereo_na(Ta, R))
+        first = 8 * -(-(T + D * (Ta + 2 * R)) // 4)                 # completes audio
+        tiles = 3 * c.na + 5 if i % 4 == 3 else int(rng.integers(8, 200))
+        c.long_tiles = tiles > 3 * c.na
+        c.sizes = [8 * int(rng.integers(1, 30)), first, 8 * int(rng.integers(1, 3 + D * R // 4)), 8 * -(-D * R * tiles // 4),
+                   8 * -(-D * (P + 300) // 4), 8 * int(rng.integers(1, 3 + D * R // 2))]
+        c.seed = int(rng.integers(0, 1 << 31))
+        yield c
+
+
+def stereo_edges(P, D=4, T=27, Ta=9, R=1, K=3):
+    """A call sequence whose MPX end lands on j P - 1, j P and j P + 1; block 1 stays open over 4 calls; one call holds 4 whole
+    blocks; one starts exactly on an edge; first-pass tiles straddle an edge at their first and at their last column."""
+    rng = np.random.default_rng(1202 + P)
+    h, ii = front(rng, T, 2, K, 2)
+    G = groups(D, T, K)
+    tile = 64 * G - 1
+    ends = [P - 1, P, P + 1, P + P // 3, P + 2 * (P // 3), 2 * P - 1, 2 * P, 6 * P, 6 * P + 1, 7 * P - tile + 1, 7 * P + 40, 8 * P - 1,
+            8 * P + 1, 9 * P]
+    rate = 110000 * D
+    c = NS(kind="stereo", R=R, K=K, D=D, T=T, Ta=Ta, S=2, h=h, incs=ii, P=P, rate=rate, pilot_min=1, g=audio_taps(rng, Ta, 16000),
+           audio_shift=9, shift=shift_for(h, ii, 256), G=G, tile=tile, ends=ends, sizes=sizes_for_outputs(T, D, ends),
+           seed=int(rng.integers(0, 1 << 31)))
+    return c
+
+
+def stereo_short(R):
+    """Ta = 256: calls that complete audio with 1, 2, Ta - 2, Ta - 1 and Ta MPX samples (the (x, s) history is rebuilt from old
+    history plus new samples), then a long call."""
+    rng = np.random.default_rng(1303 + R)
+    D, T, Ta, K, P = 4, 26, 256, 5, 1024
+    h, ii = front(rng, T, 2, K, 2)
+    ends = short_ends(Ta, R, (1, 2, Ta - 2, Ta - 1, Ta, 1, Ta - 1, 2))
+    c = NS(kind="stereo", R=R, K=K, D=D, T=T, Ta=Ta, S=2, h=h, incs=ii, P=P, rate=120000 * D, pilot_min=1, g=audio_taps(rng, Ta),
+           audio_shift=8, shift=shift_for(h, ii, 2048), G=groups(D, T, K), ends=ends, sizes=sizes_for_outputs(T, D, ends),
+           seed=int(rng.integers(0, 1 << 31)))
+    return c
+
+
+def stereo_threshold():
+    """T = 1, h = [1], decim 2, inc = 0, shift 0: y is the centred byte pair of every second sample.  capture_rate = 8 * 19000 *
+    decim makes the pilot step 2^29 exactly, so theta = 0 at every m = 8 i: cosq = 16384, sinq = 0.  y constant (100, 0) up to
+    m = 7 and (100, 100) from m = 8 on gives x = 0 everywhere except x[8] = 4096 (a turn of 45 degrees, where the discriminator
+    is exact), so block 0 has I = 2^26, Q = 0 and I^2 + Q^2 == (8 * 1024 * 8192)^2: exact equality at pilot_min = 8.  Random
+    bytes follow, whose audio differs between L and R only where block 0 counted as present."""
+    rng = np.random.default_rng(1404)
+    P, D = 1024, 2
+    b = np.empty(2 * D * P + 8 * 3000, np.uint8)
+    b[0::2], b[1::2] = 227, 127
+    b[2 * D * 8 + 1:2 * D * P:2] = 227
+    b[2 * D * P:] = rng.integers(0, 256, b.size - 2 * D * P, dtype=np.uint8)
+    ii = np.array([[0]], np.uint32)
+    c = NS(kind="stereo", R=1, K=1, D=D, T=1, Ta=3, S=1, h=np.ones(1, np.int16), incs=ii, P=P, rate=8 * 19000 * D, pilot_min=8,
+           g=np.array([5000, 6000, 5383], np.int16), audio_shift=6, shift=0, data=b[None, :],
+           sizes=[2 * D * 600, 2 * D * 424, 8 * 3000])
+    return c
+
+
+def stereo_extreme(limit, sign):
+    """sum |g| = 16383 over taps of one sign or of alternating signs, audio_shift 0, the front-end shift at `limit`; a strong
+    synthetic station with pilot, then bytes at the rails."""
+    import stereo_ref as st
+    rng = np.random.default_rng(1505 + limit + sign)
+    fs, D, T, Ta, R, P = 1200000, 4, 32, 8, 3, 1024
+    h = st.lowpass(T, 130000 / fs)
+    ii = np.array([[sr.phase_inc(200000, fs), sr.phase_inc(-310000, fs)]], np.uint32)
+    g = audio_taps(rng, Ta, 16383, sign=sign)
+    if sign == 0:
+        g = (np.abs(g) * np.where(np.arange(Ta) % 2, -1, 1)).astype(np.int16)
+    n = D * 3 * P
+    tone = lambda t: 0.4 * np.sin(2 * np.pi * 1000 * t)
+    other = lambda t: 0.3 * np.sin(2 * np.pi * 3100 * t)
+    iq = st.synth_iq(n, fs, [(200000, tone, other, 0.7, True), (-310000, other, tone, 2.1, True)], amp=60.0, noise=1.0, seed=limit)
+    rails = np.where(rng.random(8 * 2000) < 0.5, 0, 255).astype(np.uint8)
+    data = np.concatenate([iq, rails])[None, :]
+    return NS(kind="stereo", R=R, K=2, D=D, T=T, Ta=Ta, S=1, h=h, incs=ii, P=P, rate=fs, pilot_min=1 if limit == 16384 else default_pilot_min(fs, D),
+              g=g, audio_shift=0, shift=shift_for(h, ii, limit), data=data, sizes=[2 * n // 2, 2 * n // 2, 8 * 2000], limit=limit)
+
+
+# ---- narrow-band bank ----------------------------------------------------------------------------------------------------------
+
+NB_BLOCKS = (16, 64, 4096)
+
+
+def narrow_handle(c, fmd, squelch=None):
+    return fmd.NarrowBank(c.h, c.D, c.incs, (c.gr, c.gi), c.R, mode=c.mode, n_streams=c.S, block=c.P,
+                          squelch=c.squelch if squelch is None else squelch, gain=c.gain, chan_shift=c.chan_shift, shift=c.shift,
+                          device_id=0)
+
+
+def narrow_refs(c, nr, check=None, z=sr.z_corr, squelch=None, mode=None):
+    return {s: nr.NarrowRef(c.h, c.D, c.incs[s], c.shift, c.gr, c.gi, c.mode if mode is None else mode, c.R, c.chan_shift, c.P,
+                            c.squelch if squelch is None else squelch, c.gain, z=z) for s in (range(c.S) if check is None else check)}
+
+
+def probe_squelch(c, nr, data):
+    """A squelch between the loud and the quiet block RMS of stream 0, station 0 (0 when fewer than two blocks complete)."""
+    p = nr.NarrowRef(c.h, c.D, c.incs[0][:1], c.shift, c.gr, c.gi, nr.IQ, c.R, c.chan_shift, c.P, 0, 256, z=sr.z_corr)
+    u = p.feed(data)[0]
+    nblk = u.shape[0] // c.P
+    if nblk < 2:
+        return 0
+    rms = np.sqrt((u[:nblk * c.P].astype(np.float64) ** 2).sum(axis=1).reshape(nblk, c.P).mean(axis=1))
+    return min(23170, int(np.sqrt(max(1.0, rms.min()) * rms.max())))
+
+
+def narrow_sweep():
+    """For every R in 1 ... 32: four Ta with ceil(Ta / R) mod 4 = 0, 1, 2, 3 and a fifth that is below R or 256.  Modes, real and
+    complex taps, D, K edges of both digit forms and P spread over the sweep; R >= 24 gets a call of more than three tiles."""
+    _, rng = fuzz(160, 2101)
+    i = 0
+    for R in range(1, 33):
+        for res in (0, 1, 2, 3, 4):
+            if res < 4:
+                qs = [q for q in range(1, -(-256 // R) + 1) if q % 4 == res]
+                q = int(rng.choice(qs))
+                Ta = int(rng.integers((q - 1) * R + 1, min(256, q * R) + 1))
+            else:
+                Ta = int(rng.integers(1, R)) if R % 2 == 0 else 256
+            heavy = i % 5 == res % 5 and i < 5 * 28                # 28 cases with a K edge; the rest K = 1 ... 3
+            K, digits = K_EDGES[(i // 5) % 14] if heavy else (int(rng.integers(1, 4)), 1 + i % 2)
+            D = DECIMS[(i // 5 + i) % 6] if heavy else DECIMS[i % 4]
+            if i in (33, 98):
+                D, K, digits = 64, 8, 2                            # G = 3
+            if i in (66, 131):
+                D, K, digits = 64, 32, 1 + (i == 131)              # G = 2
+            T = TAPS[(3 * i + i // 8) % 8]
+            S = 1 if K > 5 else 2
+            h, ii = front(rng, T, S, K, digits)
+            mode, cplx = i % 4, (i // 4) % 2 == 1
+            gr, gi = chan_taps(rng, Ta, cplx)
+            shift = shift_for(h, ii, int(rng.choice([256, 2048, 16384])))
+            P = NB_BLOCKS[i % 3]
+            c = NS(kind="narrow", i=i, R=R, K=K, digits=digits, D=D, T=T, Ta=Ta, S=S, h=h, incs=ii, P=P, mode=mode, cplx=cplx, gr=gr,
+                   gi=gi, shift=shift, chan_shift=chan_shift_for(h, ii, shift, gr, gi, int(rng.choice([256, 4096, 16384]))),
+                   gain=int(rng.integers(1, 65536)), G=groups(D, T, K), na=narrow_na(Ta, R), Q=narrow_q(Ta, R), squelch=0)
+            first = 8 * -(-(T + D * (Ta + 2 * R)) // 4)
+            c.long_tiles = R >= 24 and res == 1
+            aud = 3 * c.na + 7 if c.long_tiles else int(rng.integers(20, 300 if D > 6 else 700))
+            if D * R * aud > 400000:
+                aud = max(4, 400000 // (D * R))
+            c.sizes = [8 * int(rng.integers(1, 20)), first, 8 * -(-D * R * aud // 4), 8 * int(rng.integers(1, 3 + D * R // 2)),
+                       8 * -(-D * R * int(rng.integers(5, 80)) // 4)]
+            c.seed = int(rng.integers(0, 1 << 31))
+            c.use_squelch = i % 3 != 2
+            i += 1
+            yield c
+
+
+def narrow_edges(P, mode):
+    """Audio ends on j P - 1, j P, j P + 1.  P = 16: calls of several 256-sample tiles that start inside a block (17 blocks in a
+    tile).  P = 4096: one block open across many calls.  Loud and quiet stretches around a squelch between them."""
+    rng = np.random.default_rng(2202 + P + mode)
+    D, T, Ta, R, K = 4, 27, 9, 2, 3
+    h, ii = front(rng, T, 2, K, 2)
+    if P == 16:
+        ends = [P - 1, P, P + 1, 3 * P - 1, 3 * P + 5 + 3 * 256, 3 * P + 5 + 3 * 256 + 11, 64 * P, 64 * P + 1, 70 * P - 1, 70 * P + 600, 112 * P]
+    else:
+        ends = [300, 1000, 2000, 3000, P - 1, P, P + 1, P + 500, P + 2500, 2 * P - 1, 2 * P + 1, 3 * P, 3 * P + 700]
+    gr, gi = chan_taps(rng, Ta, mode != 2)
+    shift = shift_for(h, ii, 16384)
+    ys = [y_for_audio(Ta, R, n) for n in ends]
+    c = NS(kind="narrow", R=R, K=K, D=D, T=T, Ta=Ta, S=2, h=h, incs=ii, P=P, mode=mode, gr=gr, gi=gi, shift=shift,
+           chan_shift=chan_shift_for(h, ii, shift, gr, gi, 16384), gain=300, G=groups(D, T, K), na=narrow_na(Ta, R), ends=ends,
+           sizes=sizes_for_outputs(T, D, ys))
+    c.data = loud_quiet(rng, 2, sum(c.sizes), 2 * D * R * (40 if P == 16 else 3000))
+    c.data[1] = c.data[1][::-1]
+    c.squelch = 0
+    return c
+
+
+def narrow_short(R):
+    """Ta = 256: calls that complete audio with 1, Ta - 1 and Ta second-stage inputs, then a long call."""
+    rng = np.random.default_rng(2303 + R)
+    D, T, Ta, K, P = 4, 26, 256, 5, 16
+    h, ii = front(rng, T, 2, K, 2)
+    ends = short_ends(Ta, R, (1, Ta - 1, Ta, 1))
+    gr, gi = chan_taps(rng, Ta, True)
+    shift = shift_for(h, ii, 2048)
+    return NS(kind="narrow", R=R, K=K, D=D, T=T, Ta=Ta, S=2, h=h, incs=ii, P=P, mode=1, gr=gr, gi=gi, shift=shift,
+              chan_shift=chan_shift_for(h, ii, shift, gr, gi, 256), gain=256, squelch=0, ends=ends, sizes=sizes_for_outputs(T, D, ends),
+              seed=int(rng.integers(0, 1 << 31)))
+
+
+def narrow_threshold(mode):
+    """T = 1, h = [1], decim 2, shift 0, one channel tap 1, chan_shift 0: u is the centred byte pair of every second sample.
+    Blocks of 16 samples with |u|^2 = 25 each ((3, 4), (5, 0), (4, 3)) have E = 400 = 5^2 * 16: exact equality at squelch 5.  A
+    block with (7, 0) and (0, 0) in place of two of them has E = 399, one with (5, 1) in place of one has E = 401."""
+    rng = np.random.default_rng(2404 + mode)
+    P = 16
+    kinds = [0, -1, 1, 0, 0, 1, -1, -1, 0, 1, 1, 0]
+    u = []
+    for kd in kinds:
+        blk = [[(3, 4), (5, 0), (4, 3), (0, 5), (-3, 4), (-5, 0), (4, -3)][int(x)] for x in rng.integers(0, 7, P)]
+        if kd == -1:
+            blk[3], blk[9] = (7, 0), (0, 0)
+        if kd == 1:
+            blk[6] = (5, 1)
+        u += blk
+    u = np.array(u)
+    b = np.empty(4 * u.shape[0], np.uint8)
+    b[0::4], b[1::4] = u[:, 0] + 127, u[:, 1] + 127
+    b[2::4], b[3::4] = rng.integers(0, 256, u.shape[0]), rng.integers(0, 256, u.shape[0])       # never read: decim 2, one tap
+    ii = np.array([[0, 1 << 31]], np.uint32)
+    want = [kd >= 0 for kd in kinds]
+    return NS(kind="narrow", R=1, K=2, D=2, T=1, Ta=1, S=1, h=np.ones(1, np.int16), incs=ii, P=P, mode=mode, gr=np.ones(1, np.int16),
+              gi=None, shift=0, chan_shift=0, gain=4000, squelch=5, data=b[None, :], kinds=kinds, want_open=want,
+              sizes=[4 * P * 2 + 8, 4 * P * 3 - 8, 4 * P * 4 + 16, 4 * P * 3 - 16])
+
+
+def narrow_extreme(mode):
+    """FM: gain 65535 and |u| up to 16384, where the discriminator's i32 arithmetic wraps and its i16 value takes every value,
+    -32768 among them.  AM: full-scale bytes through maximal taps at the smallest shifts, a = isqrt(ur^2 + ui^2) near 23170."""
+    rng = np.random.default_rng(2505 + mode)
+    D, T, R, P = 2, 16, 1, 16
+    h = np.full(T, 2047, np.int16)
+    ii = np.zeros((1, 1), np.uint32)
+    shift = shift_for(h, ii, 16384)
+    gr = np.array([16383, 16383, 16383, 16383], np.int16)
+    n = 8 * 6000
+    b = np.empty((1, n), np.uint8)
+    if mode == 2:
+        r = np.repeat(np.where(rng.random(n // 128 + 1) < 0.5, 0, 255), 64)[:n // 2]
+        b[0, 0::2], b[0, 1::2] = r, np.where(rng.random(n // 2) < 0.03, 255 - r, r)
+    else:
+        b[0, 0::2] = np.repeat(np.where(rng.random(n // 16 + 1) < 0.5, 0, 255), 8)[:n // 2]
+        b[0, 1::2] = np.repeat(np.where(rng.random(n // 24 + 1) < 0.5, 0, 255), 12)[:n // 2]
+    return NS(kind="narrow", R=R, K=1, D=D, T=T, Ta=4, S=1, h=h, incs=ii, P=P, mode=mode, gr=gr, gi=None, shift=shift,
+              chan_shift=chan_shift_for(h, ii, shift, gr, None, 16384), gain=65535, squelch=0, data=b, sizes=[n // 2, n // 2])
+
+
+# ---- channelizer ---------------------------------------------------------------------------------------------------------------
+
+def channelizer_sweep():
+    """The K edges x both digit forms, with D and T walking their lists so that G = 4, 3 and 2 all occur; one call of several
+    tiles in every case."""
+    n_cases, rng = fuzz(28, 3101)
+    for i in range(n_cases):
+        K, digits = K_EDGES[i % 14]
+        D = DECIMS[(i + i // 14 + i // 6) % 6]
+        T = TAPS[(3 * i + i // 8) % 8]
+        if i % 14 == 2:
+            D, K, digits = 64, 8, 1 + (i // 14) % 2                # G = 3
+        if i % 14 == 13:
+            D = 64                                                 # K = 32: G = 2
+        S = 1 if K > 9 else 2
+        h, ii = front(rng, T, S, K, digits)
+        G = groups(D, T, K)
+        c = NS(kind="channelizer", i=i, K=K, digits=digits, D=D, T=T, S=S, h=h, incs=ii, G=G,
+               shift=shift_for(h, ii, 16384 if i % 3 else 2048))
+        tiles = int(rng.integers(3, 7))
+        c.sizes = [8 * int(rng.integers(1, (T + 2 * D) // 4 + 3)), 8 * -(-(T + D * (64 * G * tiles + int(rng.integers(1, 64)))) // 4),
+                   8 * int(rng.integers(1, 40)), 8 * -(-D * (64 * G + int(rng.integers(1, 64))) // 4)]
+        c.tiles = tiles
+        c.seed = int(rng.integers(0, 1 << 31))
+        yield c
+
+
+# ---- what a case reaches -------------------------------------------------------------------------------------------------------
+
+def calls(c):
+    """The byte arrays [S, n] of the case's calls: slices of c.data where the case brings its own, seeded random bytes otherwise."""
+    if hasattr(c, "data"):
+        assert c.data.shape[1] == sum(c.sizes)
+        cuts = np.cumsum([0] + list(c.sizes))
+        return [c.data[:, a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+    rng = np.random.default_rng(c.seed)
+    return [bytes_(rng, c.S, n) for n in c.sizes]
+
+
+def plan(c):
+    """(mS, mE, nS, nE) of every accepted call of a stereo or narrow case -- second-stage inputs and audio samples before and after
+    it -- by the arithmetic of include/fmd.h alone; a call that completes no audio sample is refused and changes nothing."""
+    out_of = lambda p: (p - c.T) // c.D + 1 if p >= c.T else 0
+    aud_of = lambda m: (m - c.Ta) // c.R + 1 if m >= c.Ta else 0
+    pos, acc = 0, []
+    for n in c.sizes:
+        mS, mE = out_of(pos), out_of(pos + n // 2)
+        if aud_of(mE) - aud_of(mS) < 1:
+            continue
+        acc.append((mS, mE, aud_of(mS), aud_of(mE)))
+        pos += n // 2
+    return acc
+
+
+def edge_facts(ends_pairs, P):
+    """Of (start, end) counts per call: which of j P - 1, j P, j P + 1 the ends land on, the most calls that end inside one block,
+    the most whole blocks in one call, whether a call starts exactly on an edge."""
+    rel = {e - P * round(e / P) for _, e in ends_pairs if e >= P - 1 and abs(e - P * round(e / P)) <= 1}
+    inside = {}
+    for _, e in ends_pairs:
+        if e % P:
+            inside[e // P] = inside.get(e // P, 0) + 1
+    whole = max(e // P - -(-s // P) for s, e in ends_pairs)
+    return NS(rel=rel, open_calls=max(inside.values()), whole=whole, starts_on_edge=any(s % P == 0 and s > 0 for s, _ in ends_pairs))
+
+
+def straddles(c):
+    """(first, last): a first-pass tile of the stereo case c whose FIRST column is the last sample of a block, and a full tile
+    whose LAST column is the first sample of a block."""
+    first = last = False
+    for mS, mE, _, _ in plan(c):
+        for o0 in range(0, mE - mS, c.tile):
+            no = min(c.tile, mE - mS - o0)
+            first |= no >= 2 and (mS + o0) % c.P == c.P - 1
+            last |= no == c.tile and (mS + o0 + no - 1) % c.P == 0
+    return first, last

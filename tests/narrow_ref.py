@@ -47,6 +47,7 @@ class NarrowRef:
         self.a = [np.zeros(0, np.int64) for _ in range(self.K)]
         self.n_next = 0
         self.v_max = 0
+        self.a_max = 0
 
     def audio_after(self, m):
         return (m - self.Ta) // self.R + 1 if m >= self.Ta else 0
@@ -84,6 +85,7 @@ class NarrowRef:
             self.v_max = max(self.v_max, int(np.abs(vr).max()), int(np.abs(vi).max()))
             u = np.stack([vr >> self.chan_shift, vi >> self.chan_shift], axis=1)
             a = isqrt_vec((u * u).sum(axis=1))
+            self.a_max = max(self.a_max, int(a.max()))
             uprev = self.u[k][-1] if n0 else np.zeros(2, np.int64)
             self.u[k] = np.concatenate([self.u[k], u])
             self.a[k] = np.concatenate([self.a[k], a])

@@ -97,7 +97,10 @@ class StereoRef:
         self.yprev = np.zeros((self.K, 2), dtype=np.int64)
         self.x = [np.zeros(0, np.int64) for _ in range(self.K)]
         self.s = [np.zeros(0, np.int64) for _ in range(self.K)]
-        self.kc_max = 0
+        self.kc_max = 0                                      # max |kc|, |s|, |M| + |S| and correlation since reset
+        self.s_max = 0
+        self.ms_max = 0
+        self.corr_max = 0
         self.n_next = 0
 
     def audio_after(self, m):
@@ -135,13 +138,16 @@ class StereoRef:
             for jp in np.unique(jprev):
                 if jp < 0:
                     continue
-                present, c2, s2 = estimate(*self.block_iq(k, int(jp)), self.pilot_min, self.P)
+                I, Q = self.block_iq(k, int(jp))
+                present, c2, s2 = estimate(I, Q, self.pilot_min, self.P)
                 if present:
+                    self.corr_max = max(self.corr_max, abs(I), abs(Q))
                     sel = jprev == jp
                     th2 = (self.theta(m[sel]) * np.uint64(2)) & 0xFFFFFFFF
                     kc[sel] = (sr.sinq(th2) * c2 + sr.cosq(th2) * s2) >> 13
             self.kc_max = max(self.kc_max, int(np.abs(kc).max()))
             self.s[k] = np.concatenate([self.s[k], (x * kc) >> 14])
+            self.s_max = max(self.s_max, int(np.abs((x * kc) >> 14).max()))
             n1 = self.audio_after(self.x[k].size)
             lo, hi = self.R * self.n_next, self.R * (n1 - 1) + self.Ta
             Mf = np.correlate(self.x[k][lo:hi], self.g, "valid")[::self.R]
@@ -149,6 +155,7 @@ class StereoRef:
             sh = self.audio_shift + 1
             out.append(np.stack([sat16((Mf + Sf) >> sh), sat16((Mf - Sf) >> sh)], axis=1))
             self.last_MS = (Mf, Sf)
+            self.ms_max = max(self.ms_max, int((np.abs(Mf) + np.abs(Sf)).max()))
         self.n_next = self.audio_after(self.x[0].size)
         return np.stack(out)
 
