@@ -446,6 +446,89 @@ int fmd_stereo_pilot_inc(uint32_t capture_rate, uint32_t decim, uint32_t *inc);
 /* Name of pass 0 (front end + discriminator + pilot sums) or 1 (carrier, FIRs, matrix), as `rocprofv3 --kernel-trace` prints it. */
 int fmd_stereo_kernel_name(const fmd_stereo *s, uint32_t pass, char *name, size_t cap);
 
+/* ---- RDS bank: each FM station's 57 kHz subcarrier as a low-rate complex baseband --------------------------- */
+/* NEW SURFACE (the reference has none).  The wideband half of RDS reception, feed-forward and in integers; the sequential half
+ * (carrier and symbol timing, block synchronisation, groups) is fmd_rds_decoder_* below, on the host.  Definition (integers only;
+ * tests/rds_ref.py), per (stream, station k):
+ *   y[m], x[m], inc_p, theta_m, I_j, Q_j   exactly the stereo station bank's (above); m counted from creation or reset, y[m-1]
+ *                                          carried across calls
+ *   phi_m  = 3 m inc_p mod 2^32                                (the free-running 57 kHz carrier: three times the pilot step)
+ *   qr[m]  = (x[m] cosq(phi_m)) >> 14,   qi[m] = (-x[m] sinq(phi_m)) >> 14                                    (|q| <= 32768)
+ *   vr[n]  = sum_{t < Ta} g[t] qr[R n + t],   vi[n] likewise            (exact in i32: sum |g| <= 16383, so |v| < 2^29)
+ *   u[n]   = (vr >> rds_shift, vi >> rds_shift)                          stored as the int16 pair (ur, ui)
+ * Shifts are arithmetic (floor).  Sample n comes with the call in which x[R n + Ta - 1] arrives; out is
+ * [n_streams][n_stations][out_cap][2] int16 at capture_rate / (decim R).  The carrier is NOT corrected by the pilot estimate: the
+ * residual (three times the transmitter's pilot error plus the rounding of inc_p, a few Hz) is left to the host decoder, which
+ * keeps the device operator free of per-block divisions.  The output does not depend on how the stream is cut into calls.
+ * Domain (else FMD_ERR_UNSUPPORTED, decided before a device is queried): the channelizer's filter domain; capture_rate >=
+ * 120000 decim (the subcarrier's upper sideband at 59.4 kHz lies below half the multiplex rate); P a power of two in
+ * [1024, 16384]; 1 <= R <= 32; 1 <= Ta <= 256; sum |g| <= 16383; rds_shift <= 24 and ceil(32768 sum |g| / 2^rds_shift) <= 32767,
+ * so the int16 store is exact; pilot_min <= 16384.  nbytes % 8 != 0 -> FMD_ERR_BAD_LENGTH; a call that completes no output ->
+ * FMD_ERR_TOO_SHORT and changes nothing.  Stream lifetime and completion points: as fmd_channelizer_* (fmd_rds_check). */
+typedef struct fmd_rds fmd_rds;
+typedef struct fmd_rds_config {
+    uint32_t capture_rate;   /* Hz: sets the pilot step inc_p                                         */
+    uint32_t block;          /* P: pilot block length in MPX samples (fmd_rds_pilot)                  */
+    uint32_t out_decim;      /* R                                                                     */
+    uint32_t rds_shift;
+    uint32_t pilot_min;      /* presence threshold of fmd_rds_pilot, in discriminator units           */
+} fmd_rds_config;
+int fmd_rds_new(const int16_t *taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t *phase_inc,
+                uint32_t n_stations, const int16_t *rds_taps, uint32_t n_rds_taps, const fmd_rds_config *cfg,
+                const fmd_device_config *dev, fmd_rds **out);
+void fmd_rds_free(fmd_rds *s);
+int fmd_rds_reset(fmd_rds *s);
+/* ceil(nbytes / (2 decim R)): outputs one call of nbytes can complete per (stream, station), whatever the history; 0 for decim 0
+ * or R 0. */
+size_t fmd_rds_out_cap(uint32_t decim, uint32_t out_decim, size_t nbytes);
+/* HOST buffers; *out_len = outputs per (stream, station) (the same for all). */
+int fmd_rds_run_batch(fmd_rds *s, const uint8_t *iq, size_t nbytes, int16_t *out, size_t out_cap, size_t *out_len);
+/* DEVICE buffers (d_iq and d_out 4-byte aligned), enqueued on `stream` without synchronising; *out_len as above. */
+int fmd_rds_run_device(fmd_rds *s, const void *d_iq, size_t nbytes, void *d_out, size_t out_cap, size_t *out_len,
+                       void *stream);
+int fmd_rds_check(fmd_rds *s);
+/* Outputs per (stream, station) produced since creation or the last reset. */
+int fmd_rds_outputs(const fmd_rds *s, uint64_t *outputs);
+/* The last completed block's pilot, with the semantics of fmd_stereo_pilot: a station without a pilot has no multiplex to decode.
+ * Synchronises first. */
+int fmd_rds_pilot(fmd_rds *s, uint32_t stream, uint32_t station, int *present, uint32_t *level);
+/* Name of pass 0 (the stereo bank's multiplex pass) or 1 (carrier, FIRs, shift), as `rocprofv3 --kernel-trace` prints it. */
+int fmd_rds_kernel_name(const fmd_rds *s, uint32_t pass, char *name, size_t cap);
+
+/* ---- RDS decoder (host): groups, PI, PS and RadioText from one station's RDS baseband ----------------------- */
+/* No GPU.  One decoder handles one (stream, station) of an RDS bank and keeps its state across pushes; what it returns does not
+ * depend on how the samples are cut into pushes.  Floating point inside: this layer is defined by what it decodes (IEC 62106:
+ * 1187.5 bit/s, biphase symbols, differential coding, 26-bit blocks with the generator x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1 and
+ * the offset words A 0x0FC, B 0x198, C 0x168, C' 0x350, D 0x1B4), not bit for bit.
+ *   carrier   a Costas loop on the matched-filter output (residual up to +-20 Hz; the pi ambiguity is harmless)
+ *   timing    the 1187.5 Hz line of the squared matched-filter envelope (feed-forward), linear interpolation at the bit centre
+ *   blocks    a block is used only when its syndrome -- the remainder of the 26 bits by the generator -- equals its offset word; no
+ *             error correction.  Lock on two consecutive valid blocks in sequence; lock is dropped after 10 bad blocks in a row.
+ *   groups    PI from block A; PS from 0A / 0B; RadioText from 2A / 2B (a change of the text A/B flag clears the buffer, 0x0D ends
+ *             the text); every group completed while locked is delivered raw, whatever its type.
+ * rate_num / rate_den Hz is the sample rate: 4 kHz ... 32 kHz, else FMD_ERR_UNSUPPORTED. */
+typedef struct fmd_rds_decoder fmd_rds_decoder;
+typedef struct fmd_rds_group {
+    uint16_t block[4];       /* the 16 information bits of blocks A, B, C / C', D                      */
+    uint8_t ok_mask;         /* bit i: block i passed its check                                        */
+    uint64_t first_sample;   /* index, since creation or reset, of the sample at the group's first bit */
+} fmd_rds_group;
+typedef struct fmd_rds_info {
+    uint16_t pi;             /* 0 until a block A (or a C' of a B group) passed                         */
+    char ps[9];              /* 8 characters, spaces where nothing arrived yet, NUL-terminated         */
+    char rt[65];             /* the text up to 0x0D or the first segment not yet received, NUL-terminated */
+    uint64_t groups_ok;      /* groups with all four blocks valid                                      */
+    uint64_t blocks_bad;     /* blocks that failed their check while locked                            */
+    int synced;
+} fmd_rds_info;
+int fmd_rds_decoder_new(uint32_t rate_num, uint32_t rate_den, fmd_rds_decoder **out);
+void fmd_rds_decoder_free(fmd_rds_decoder *d);
+int fmd_rds_decoder_reset(fmd_rds_decoder *d);
+/* n (ur, ui) pairs in; up to `cap` groups out, oldest first.  Groups that do not fit stay queued and come with the next push
+ * (n may be 0, iq then NULL). */
+int fmd_rds_decoder_push(fmd_rds_decoder *d, const int16_t *iq, size_t n, fmd_rds_group *groups, size_t cap, size_t *n_groups);
+int fmd_rds_decoder_info(const fmd_rds_decoder *d, fmd_rds_info *info);
+
 /* ---- narrow-band bank: AM, NFM, SSB and IQ channels with squelch --------------------------------------------- */
 /* NEW SURFACE (rtl_fm's -M fm / am / usb / lsb / raw with a squelch, in the rtl-sdr ecosystem; the reference has none).  This is
  * the project's own operator, not the reference's chain: the channelizer's y, a second, COMPLEX decimating FIR that reaches

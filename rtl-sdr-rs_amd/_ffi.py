@@ -150,6 +150,22 @@ PROTOTYPES = {
     "fmd_stereo_pilot": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "fmd_stereo_pilot_inc": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "fmd_stereo_kernel_name": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "fmd_rds_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, _i16p, C.c_uint32,
+                              _vp, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_rds_free": (None, [_vp]),
+    "fmd_rds_reset": (C.c_int, [_vp]),
+    "fmd_rds_out_cap": (_sz, [C.c_uint32, C.c_uint32, _sz]),
+    "fmd_rds_run_batch": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "fmd_rds_run_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_rds_check": (C.c_int, [_vp]),
+    "fmd_rds_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "fmd_rds_pilot": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "fmd_rds_kernel_name": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "fmd_rds_decoder_new": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "fmd_rds_decoder_free": (None, [_vp]),
+    "fmd_rds_decoder_reset": (C.c_int, [_vp]),
+    "fmd_rds_decoder_push": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "fmd_rds_decoder_info": (C.c_int, [_vp, _vp]),
     "fmd_narrow_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, _i16p, _i16p, C.c_uint32,
                                  _vp, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
     "fmd_narrow_free": (None, [_vp]),

@@ -351,6 +351,115 @@ private:
     fmd_stereo* h_ = nullptr;
 };
 
+// Taps of an RdsBank, as the Python rds_taps(): a Hamming-windowed sinc low-pass at +-cutoff_hz around the subcarrier, scaled to
+// sum |g| <= 16383, and the smallest rds_shift at which the int16 store is exact.
+inline std::pair<std::vector<int16_t>, uint32_t> rds_taps(double mpx_rate, uint32_t n_taps, double cutoff_hz = 2400)
+{
+    if (n_taps < 1 || n_taps > 256) throw Error(FMD_ERR_INVALID_ARG);
+    const double pi = 3.14159265358979323846, fc = 2 * cutoff_hz / mpx_rate;
+    std::vector<double> g(n_taps);
+    double sum = 0;
+    for (uint32_t i = 0; i < n_taps; ++i) {
+        const double t = i - (n_taps - 1) / 2.0, x = pi * fc * t;
+        const double w = n_taps > 1 ? 0.54 - 0.46 * std::cos(2 * pi * i / (n_taps - 1)) : 1.0;
+        g[i] = fc * (t == 0 ? 1.0 : std::sin(x) / x) * w;
+        sum += std::fabs(g[i]);
+    }
+    std::vector<int16_t> out(n_taps);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_taps; ++i) {
+        out[i] = (int16_t)std::floor(g[i] / sum * (16383.0 - n_taps) + 0.5);
+        total += (uint64_t)std::abs((int)out[i]);
+    }
+    uint32_t shift = 0;
+    while (((32768ull * total + (1ull << shift) - 1) >> shift) > 32767ull) ++shift;
+    return {out, shift};
+}
+
+// RDS bank (fmd_rds_*): run() takes [n_streams][nbytes] and returns interleaved (ur, ui) baseband
+// [n_streams * n_stations] (row stream * n_stations + station) at capture_rate / (decim out_decim).
+class RdsBank {
+public:
+    RdsBank(const std::vector<int16_t>& taps, uint32_t decim, uint32_t shift, const std::vector<uint32_t>& phase_incs,
+            uint32_t n_streams, const std::vector<int16_t>& rds_taps, const fmd_rds_config& cfg, int32_t device_id = -1)
+        : decim_(decim), out_decim_(cfg.out_decim), n_streams_(n_streams),
+          n_stations_(n_streams ? (uint32_t)(phase_incs.size() / n_streams) : 0u)
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_rds_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, rds_taps.data(),
+                          (uint32_t)rds_taps.size(), &cfg, &dev, &h_));
+    }
+    ~RdsBank() { fmd_rds_free(h_); }
+    RdsBank(const RdsBank&) = delete;
+    RdsBank& operator=(const RdsBank&) = delete;
+
+    // FMD_ERR_TOO_SHORT (a call that completes no output) returns empty rows and changes nothing.
+    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    {
+        const size_t cap = std::max<size_t>(1, fmd_rds_out_cap(decim_, out_decim_, nbytes));
+        const size_t rows = (size_t)n_streams_ * n_stations_;
+        std::vector<int16_t> out(2 * cap * rows);
+        size_t n = 0;
+        const int rc = fmd_rds_run_batch(h_, iq, nbytes, out.data(), cap, &n);
+        if (rc == FMD_ERR_TOO_SHORT) return std::vector<std::vector<int16_t>>(rows);
+        check(rc);
+        std::vector<std::vector<int16_t>> res(rows);
+        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + 2 * r * cap, out.begin() + 2 * (r * cap + n));
+        return res;
+    }
+    std::pair<bool, uint32_t> pilot(uint32_t stream, uint32_t station)
+    {
+        int present = 0;
+        uint32_t level = 0;
+        check(fmd_rds_pilot(h_, stream, station, &present, &level));
+        return {present != 0, level};
+    }
+    uint64_t outputs() const
+    {
+        uint64_t n = 0;
+        check(fmd_rds_outputs(h_, &n));
+        return n;
+    }
+    void reset() { check(fmd_rds_reset(h_)); }
+
+private:
+    uint32_t decim_, out_decim_, n_streams_, n_stations_;
+    fmd_rds* h_ = nullptr;
+};
+
+// RDS decoder of one (stream, station) (fmd_rds_decoder_*, host only): push() takes interleaved (ur, ui) pairs at rate_num / rate_den
+// Hz and returns the groups completed since.
+class RdsDecoder {
+public:
+    RdsDecoder(uint32_t rate_num, uint32_t rate_den) { check(fmd_rds_decoder_new(rate_num, rate_den, &h_)); }
+    ~RdsDecoder() { fmd_rds_decoder_free(h_); }
+    RdsDecoder(const RdsDecoder&) = delete;
+    RdsDecoder& operator=(const RdsDecoder&) = delete;
+
+    std::vector<fmd_rds_group> push(const std::vector<int16_t>& iq)
+    {
+        std::vector<fmd_rds_group> res;
+        fmd_rds_group buf[64];
+        size_t n = 0;
+        check(fmd_rds_decoder_push(h_, iq.data(), iq.size() / 2, buf, 64, &n));
+        for (;;) {
+            res.insert(res.end(), buf, buf + n);
+            if (n < 64) return res;
+            check(fmd_rds_decoder_push(h_, nullptr, 0, buf, 64, &n));
+        }
+    }
+    fmd_rds_info info() const
+    {
+        fmd_rds_info i;
+        check(fmd_rds_decoder_info(h_, &i));
+        return i;
+    }
+    void reset() { check(fmd_rds_decoder_reset(h_)); }
+
+private:
+    fmd_rds_decoder* h_ = nullptr;
+};
+
 // Channel taps of a NarrowBank, as the Python narrow_taps(): a Hamming-windowed complex band-pass from lo_hz to hi_hz at the
 // channelizer's output rate, scaled to sum |gr| + |gi| <= 65535 with every tap within 16383.  The second vector is empty (real
 // taps) when lo_hz == -hi_hz.  USB is e.g. (300, 3000), LSB (-3000, -300).

@@ -29,6 +29,7 @@
 #include "fmd_ddc.h"
 #include "fmd_device.h"
 #include "fmd_internal.h"
+#include "fmd_stereo_mpx.h"
 
 namespace fmd_sto {
 
@@ -38,31 +39,6 @@ using fmd_ddc::kTableBytes;
 constexpr uint32_t kAudioTile = 256;                      // audio samples per pass-2 tile (at most)
 constexpr uint32_t kXCap = 2048;                          // (x, s) pairs a pass-2 tile stages: R tile + 2 Ta <= kXCap
 constexpr uint32_t kMaxBlocks = 4;                        // blocks one pass-2 tile touches (<= 3: kXCap / 1024 + 1)
-
-struct MpxLaunch {
-    const uint8_t* iq;         // [S][nbytes]
-    uint64_t nbytes;
-    const uint8_t* hist_in;    // [S][HB]
-    uint8_t* hist_out;
-    uint32_t HB;
-    uint32_t vb_first;         // virtual byte of the window of the call's first output
-    uint64_t m0;               // global index of the call's first output
-    uint32_t M;                // outputs of this call per (stream, station)
-    uint32_t D, T, K, S, shift;
-    uint32_t nrt, nkc, digits;
-    uint32_t tile, cols;       // outputs per tile (cols - 1), LDS row length
-    uint32_t ntiles, raw_bytes;
-    uint32_t pshift, inc_p;    // log2 P, pilot step
-    uint64_t jfirst;           // block of the call's first output
-    const uint32_t* amat;
-    const int32_t* kconst;
-    const uint32_t* dinc;
-    const uint32_t* tab;
-    const uint32_t* ylast_in;  // [S K]: y[m0 - 1], packed
-    uint32_t* ylast_out;
-    int16_t* x;                // [S K][M]
-    unsigned long long* sums;  // [nbc][S K][2]: I, Q of block jfirst + i, this call's samples only
-};
 
 __device__ __forceinline__ long long wave_sum(long long v)
 {
@@ -132,6 +108,12 @@ __global__ void __launch_bounds__(kThreads) fmd_stereo_mpx_kernel(const MpxLaunc
             }
         }
     }
+}
+
+hipError_t launch_mpx(const MpxLaunch& A, size_t lds, hipStream_t stream)
+{
+    hipLaunchKernelGGL(fmd_stereo_mpx_kernel, dim3(A.ntiles, A.S), dim3(kThreads), lds, stream, A);
+    return hipGetLastError();
 }
 
 struct AudioLaunch {
@@ -303,18 +285,6 @@ namespace {
 
 using fmd_ddc::kTableBytes;
 
-constexpr size_t kLdsBudget = 40960;
-
-size_t st_lds(uint32_t D, uint32_t nkc, uint32_t T, uint32_t K, uint32_t G, uint32_t* raw_bytes)
-{
-    const uint64_t cap = 64ull * G;                       // contracted outputs per tile (the tile's and the one before)
-    const uint64_t reads = 12 + 6ull * D + 8ull * D * (16 * G - 1) + 64ull * nkc;
-    const uint64_t staged = 12 + 2ull * D * (cap - 1) + 2ull * T + 15;
-    const uint64_t raw = ((reads > staged ? reads : staged) + 15) & ~15ull;
-    *raw_bytes = (uint32_t)raw;
-    return (size_t)(raw + kTableBytes + 4ull * K * cap);
-}
-
 uint64_t st_mpx(const fmd_stereo* h, uint64_t S) { return S >= h->T ? (S - h->T) / h->D + 1 : 0; }
 uint64_t st_audio(const fmd_stereo* h, uint64_t m) { return m >= h->Ta ? (m - h->Ta) / h->R + 1 : 0; }
 
@@ -371,8 +341,7 @@ int st_enqueue(fmd_stereo* h, const void* d_iq, size_t nbytes, void* d_out, size
 
     FMD_DDC_TRY(c.order.before(stream));
     FMD_DDC_TRY(hipMemsetAsync(h->d_sums, 0, sums_bytes, stream));
-    hipLaunchKernelGGL(fmd_sto::fmd_stereo_mpx_kernel, dim3(A.ntiles, h->S), dim3(fmd_sto::kThreads), h->lds, stream, A);
-    FMD_DDC_TRY(hipGetLastError());
+    FMD_DDC_TRY(fmd_sto::launch_mpx(A, h->lds, stream));
     hipLaunchKernelGGL(fmd_sto::fmd_stereo_audio_kernel, dim3((uint32_t)(nt2 * SK)), dim3(fmd_sto::kThreads), 0, stream, B);
     FMD_DDC_TRY(hipGetLastError());
     (void)c.order.after(stream);
@@ -380,14 +349,6 @@ int st_enqueue(fmd_stereo* h, const void* d_iq, size_t nbytes, void* d_out, size
     c.pos += ns;
     if (out_len) *out_len = (size_t)NA;
     return FMD_OK;
-}
-
-uint64_t isqrt_u128(unsigned __int128 v)
-{
-    uint64_t r = (uint64_t)std::sqrt((double)v);
-    while ((unsigned __int128)r * r > v) --r;
-    while ((unsigned __int128)(r + 1) * (r + 1) <= v) ++r;
-    return r;
 }
 
 }  // namespace
@@ -445,11 +406,8 @@ int fmd_stereo_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
         fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
         return FMD_ERR_UNSUPPORTED;
     }
-    for (uint32_t G = fmd_ddc::kGroups; G >= 1; --G) {
-        uint32_t rb;
-        const size_t l = st_lds(decim, h->plan.nkc, n_taps, n_stations, G, &rb);
-        if (l <= kLdsBudget || G == 1) { h->groups = G; h->cols = 64u * G; h->tile = 64u * G - 1u; h->raw_bytes = rb; h->lds = l; break; }
-    }
+    const fmd_sto::MpxTiling tl = fmd_sto::mpx_tiling(decim, h->plan.nkc, n_taps, n_stations);
+    h->groups = tl.groups; h->cols = tl.cols; h->tile = tl.tile; h->raw_bytes = tl.raw_bytes; h->lds = tl.lds;
     h->HB = 2u * ((n_taps - 1u + 7u) & ~7u);
     h->Ta = n_audio_taps; h->R = cfg->audio_decim; h->P = P; h->audio_shift = cfg->audio_shift; h->pilot_min = cfg->pilot_min;
     while ((1u << h->pshift) < P) ++h->pshift;
@@ -554,10 +512,7 @@ int fmd_stereo_pilot(fmd_stereo* h, uint32_t stream, uint32_t station, int* pres
     FMD_DDC_TRY(hipDeviceSynchronize());
     long long c[4];
     FMD_DDC_TRY(hipMemcpy(c, h->d_carry[h->core.cur] + 4ull * ((size_t)stream * h->K + station), sizeof c, hipMemcpyDeviceToHost));
-    const unsigned __int128 e2 = (unsigned __int128)((__int128)c[0] * c[0]) + (unsigned __int128)((__int128)c[1] * c[1]);
-    const uint64_t thr = (uint64_t)h->pilot_min * h->P * 8192u;
-    *present = thr != 0 && e2 >= (unsigned __int128)thr * thr ? 1 : 0;
-    *level = (uint32_t)(isqrt_u128(e2) / ((uint64_t)h->P * 8192u));
+    fmd_sto::pilot_report(c[0], c[1], h->pilot_min, h->P, present, level);
     return FMD_OK;
 }
 

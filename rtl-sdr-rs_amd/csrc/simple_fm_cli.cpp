@@ -26,6 +26,10 @@
 // With -2 the stereo station bank (fmd_stereo_*) instead: station k's pilot-locked stereo, interleaved s16 (L, R) at
 // f_m / R (f_m = capture_rate / downsample, R = max(1, floor(f_m / 48000)); 127 audio taps from fm::stereo_taps, 75 us
 // de-emphasis, blocks of 4096) goes to <prefix>.<k>.s16; the audio rate is printed on stderr.
+// With -R the RDS bank (fmd_rds_*) and one host decoder per station (fmd_rds_decoder_*) instead: a 64-tap low-pass of +-62 kHz in
+// front (the boxcar would cut the 57 kHz subcarrier), 255 taps from fm::rds_taps at stride R = max(1, floor(f_m / 7500)); at the end
+// one line per station on stdout, `offset_hz PI PS "radiotext" groups_ok blocks_bad` (PI in hex).  With -I also station k's RDS
+// baseband as interleaved s16 (ur, ui) in <prefix>.<k>.rds.cs16.
 //
 // Power spectrum, -P N [-H hop]: the N-bin power spectrum (fmd_spectrum_*, integer Hann window of amplitude 2047, shift 16) of
 // ONE capture file whose sample rate is -s, integrated over the file's complete blocks; one line per bin in frequency order,
@@ -186,7 +190,7 @@ static int run_rtl_tcp(const char* hostport, uint32_t freq, uint32_t rate, uint3
 
 // -S: one capture, K stations (fmd_stations_*; with -I their baseband, fmd_channelizer_*)
 static int run_stations(const char* path, const char* list, const char* prefix, uint32_t freq, uint32_t rate, uint32_t resample,
-                        bool iq_out, bool stereo, const char* narrow, uint32_t squelch)
+                        bool iq_out, bool stereo, const char* narrow, uint32_t squelch, bool rds)
 {
     FILE* in = strcmp(path, "-") ? fopen(path, "rb") : stdin;
     if (!in) { perror(path); return 2; }
@@ -197,11 +201,13 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
         const fm::DemodConfig& dc = settings.second;
         const uint32_t capture = settings.first.capture_rate, D = dc.downsample;
         std::vector<uint32_t> incs;
+        std::vector<long> offsets;
         for (const char* p = list; *p;) {
             char* end = nullptr;
             const long off = strtol(p, &end, 10);
             if (end == p) { fprintf(stderr, "bad -S list: %s\n", list); return 2; }
             incs.push_back(fm::phase_inc((int32_t)off, capture));
+            offsets.push_back(off);
             p = *end == ',' ? end + 1 : end;
         }
         uint32_t shift = 0;                                  // |W| <= 1 for a boxcar: sum(|Wr| + |Wi|) <= 2 n_taps
@@ -210,7 +216,29 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
         std::unique_ptr<fm::Channelizer> chan;
         std::unique_ptr<fm::StereoBank> st;
         std::unique_ptr<fm::NarrowBank> nb;
-        if (narrow) {
+        std::unique_ptr<fm::RdsBank> rb;
+        std::vector<std::unique_ptr<fm::RdsDecoder>> decoders;
+        if (rds) {
+            // a Hamming-windowed sinc of +-62 kHz, peak 2047; the front end's shift keeps every |y| component <= 256, where the
+            // reference's discriminator cannot wrap
+            const uint32_t f_m = capture / D, R = std::max<uint32_t>(1, f_m / 7500);
+            const double pi = 3.14159265358979323846, fc = 2.0 * 62000.0 / capture;
+            std::vector<int16_t> h(64);
+            uint64_t hsum = 0;
+            for (int i = 0; i < 64; ++i) {
+                const double t = i - 31.5, x = pi * fc * t;
+                const double v = std::sin(x) / x * (0.54 - 0.46 * std::cos(2 * pi * i / 63.0)), peak = std::sin(pi * fc * 0.5) / (pi * fc * 0.5) * (0.54 - 0.46 * std::cos(2 * pi * 31 / 63.0));
+                h[i] = (int16_t)std::lround(v / peak * 2047.0);
+                hsum += (uint64_t)std::abs((int)h[i]);
+            }
+            uint32_t rshift = 0;                             // sum(|Wr| + |Wi|) <= 2 sum |h| + 2 n_taps (rounding)
+            while ((256ull * (2 * hsum + 128) + (1ull << rshift) - 1) >> rshift > 256ull) ++rshift;
+            const auto g = fm::rds_taps((double)f_m, 255);
+            const fmd_rds_config cfg{capture, 4096, R, g.second, (uint32_t)((32768ull * 6750 * D) / (4ull * capture))};
+            rb.reset(new fm::RdsBank(h, D, rshift, incs, 1, g.first, cfg));
+            for (size_t k = 0; k < incs.size(); ++k) decoders.emplace_back(new fm::RdsDecoder(capture, D * R));
+            fprintf(stderr, "RDS baseband: %.3f Hz\n", (double)capture / D / R);
+        } else if (narrow) {
             // -N mode[:R[:lo:hi]]: 256 channel taps from fm::narrow_taps; chan_shift keeps |u| <= 256 in fm mode (where the
             // reference's discriminator cannot wrap), <= 16384 otherwise; squelch blocks of 256 samples, gain 1.0
             char mode[8] = {0};
@@ -258,8 +286,8 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
         } else if (iq_out) chan.reset(new fm::Channelizer(std::vector<int16_t>(D, 1), D, shift, incs, 1));
         else bank.reset(new fm::StationBank(std::vector<int16_t>(D, 1), D, shift, incs, 1, dc.rate_out, dc.rate_resample));
         fprintf(stderr, "capture_rate: %u, %zu stations, decimate %u\n", capture, incs.size(), D);
-        for (size_t k = 0; k < incs.size(); ++k) {
-            const std::string name = std::string(prefix) + "." + std::to_string(k) + (iq_out ? ".cs16" : ".s16");
+        for (size_t k = 0; k < incs.size() && (!rds || iq_out); ++k) {
+            const std::string name = std::string(prefix) + "." + std::to_string(k) + (rds ? ".rds.cs16" : iq_out ? ".cs16" : ".s16");
             out.push_back(fopen(name.c_str(), "wb"));
             if (!out.back()) { perror(name.c_str()); rc = 2; break; }
         }
@@ -268,12 +296,22 @@ static int run_stations(const char* path, const char* list, const char* prefix, 
             size_t fill = 0, n;
             while (fill < buf.size() && (n = fread(buf.data() + fill, 1, buf.size() - fill, in)) > 0) fill += n;
             if (fill < buf.size()) {
-                if (fill) fprintf(stderr, "dropped %zu trailing bytes (not a complete %zu-byte block)\n", fill, buf.size());
+                if (rb && fill >= 8) {                       // RDS is slow: the tail of a short capture may hold its last group
+                    const auto rows = rb->run(buf.data(), fill & ~(size_t)7);
+                    for (size_t k = 0; k < out.size(); ++k) fm::output(rows[k], out[k]);
+                    for (size_t k = 0; k < decoders.size(); ++k) (void)decoders[k]->push(rows[k]);
+                } else if (fill) fprintf(stderr, "dropped %zu trailing bytes (not a complete %zu-byte block)\n", fill, buf.size());
                 break;
             }
-            const auto rows = nb ? nb->run(buf.data(), buf.size()) : st ? st->run(buf.data(), buf.size())
+            const auto rows = rb ? rb->run(buf.data(), buf.size()) : nb ? nb->run(buf.data(), buf.size()) : st ? st->run(buf.data(), buf.size())
                                  : iq_out ? chan->run(buf.data(), buf.size()) : bank->demodulate(buf.data(), buf.size());
             for (size_t k = 0; k < out.size(); ++k) fm::output(rows[k], out[k]);
+            for (size_t k = 0; k < decoders.size(); ++k) (void)decoders[k]->push(rows[k]);
+        }
+        for (size_t k = 0; k < decoders.size() && !rc; ++k) {
+            const fmd_rds_info i = decoders[k]->info();
+            printf("%ld %04X %s \"%s\" %llu %llu\n", offsets[k], (unsigned)i.pi, i.ps, i.rt, (unsigned long long)i.groups_ok,
+                   (unsigned long long)i.blocks_bad);
         }
     } catch (const fm::Error& e) {
         fprintf(stderr, "error: %s\n", e.what());
@@ -329,6 +367,7 @@ int main(int argc, char** argv)
     const char* rtl_tcp = nullptr;                           // -t host:port: live mode over rtl_tcp
     const char* stations = nullptr;                          // -S off1,off2,...: station bank over one capture
     bool iq_out = false;                                     // -I: with -S, each station's baseband IQ instead of audio
+    bool rds = false;                                        // -R: with -S, each station's RDS (fmd_rds_*, fmd_rds_decoder_*)
     bool stereo = false;                                     // -2: with -S, each station's stereo audio (fmd_stereo_*)
     const char* narrow = nullptr;                            // -N mode[:R[:lo:hi]]: with -S, narrow-band channels (fmd_narrow_*)
     uint32_t squelch = 0;                                    // -q: their squelch (RMS amplitude; 0 = always open)
@@ -345,6 +384,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-S") && i + 1 < argc) stations = argv[++i];
         else if (!strcmp(argv[i], "-I")) iq_out = true;
         else if (!strcmp(argv[i], "-2")) stereo = true;
+        else if (!strcmp(argv[i], "-R")) rds = true;
         else if (!strcmp(argv[i], "-N") && i + 1 < argc) narrow = argv[++i];
         else if (!strcmp(argv[i], "-q") && i + 1 < argc) squelch = (uint32_t)strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-P") && i + 1 < argc) power_bins = strtoul(argv[++i], nullptr, 10);
@@ -359,15 +399,16 @@ int main(int argc, char** argv)
                             "       %s [-s ...] [-o prefix] -S off1,off2,... -I <capture.bin | ->        (their baseband: s16 I/Q at capture_rate / downsample)\n"
                             "       %s [-s ...] [-o prefix] -S off1,off2,... -2 <capture.bin | ->        (their stereo: s16 L/R at capture_rate / downsample / R)\n"
                             "       %s [-s ...] [-o prefix] -S off1,off2,... -N mode[:R[:lo:hi]] [-q squelch] <capture.bin | ->   (narrow-band channels: iq, fm, am, usb, lsb at capture_rate / downsample / R)\n"
+                            "       %s [-s ...] [-o prefix] -S off1,off2,... -R [-I] <capture.bin | ->   (their RDS: offset_hz PI PS \"radiotext\" groups_ok blocks_bad; -I: baseband to prefix.k.rds.cs16)\n"
                             "       %s -s capture_rate_hz -P n_bins [-H hop] <capture.bin | ->       (power spectrum: offset_hz power per bin)\n",
-                    argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                    argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else paths.push_back(argv[i]);
     }
     if (rtl_tcp) return run_rtl_tcp(rtl_tcp, freq, rate, resample, max_blocks);
     if (paths.empty()) { fprintf(stderr, "missing input file (use - for stdin)\n"); return 2; }
     if (power_bins) return run_power(paths[0], power_bins, power_hop, rate);
-    if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample, iq_out, stereo, narrow, squelch);
+    if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample, iq_out, stereo, narrow, squelch, rds);
     if (paths.size() > 1 && gpus > 0) return run_sink(paths, prefix, freq, rate, resample, gpus);
     if (paths.size() > 1) return run_bank(paths, prefix, freq, rate, resample);
     path = paths[0];

@@ -1,0 +1,178 @@
+"""Host-side wrapper of the RDS bank (include/fmd.h, fmd_rds_*) and the RDS decoder (fmd_rds_decoder_*): K FM stations per wideband
+IQ stream, each station's 57 kHz subcarrier returned as a complex baseband of a few kHz (int16 (ur, ui) pairs at capture_rate /
+(decim R)), and the host decoder that turns one station's baseband into groups, PI, PS and RadioText."""
+import ctypes as C
+
+import numpy as np
+
+from ._ffi import DeviceConfig, CheckedHandle, check, lib, stream_phase_incs
+from .channelizer import as_complex
+from .stations import stations_auto_shift
+from .stereo import FRONT_END_LIMIT, default_pilot_min
+
+
+class RdsConfig(C.Structure):
+    _fields_ = [("capture_rate", C.c_uint32), ("block", C.c_uint32), ("out_decim", C.c_uint32), ("rds_shift", C.c_uint32),
+                ("pilot_min", C.c_uint32)]
+
+
+class RdsGroup(C.Structure):
+    _fields_ = [("block", C.c_uint16 * 4), ("ok_mask", C.c_uint8), ("first_sample", C.c_uint64)]
+
+
+class RdsInfo(C.Structure):
+    _fields_ = [("pi", C.c_uint16), ("ps", C.c_char * 9), ("rt", C.c_char * 65), ("groups_ok", C.c_uint64), ("blocks_bad", C.c_uint64),
+                ("synced", C.c_int)]
+
+
+def rds_taps(mpx_rate, out_decim, n_taps, cutoff_hz=2400):
+    """(g, rds_shift) for an RdsBank: a Hamming-windowed sinc low-pass at +-`cutoff_hz` around the subcarrier, scaled so that
+    sum |g| <= 16383, int16, and the smallest rds_shift at which the int16 store is exact (ceil(32768 sum|g| / 2^shift) <= 32767).
+    `out_decim` is the stride the taps are used with; it does not change them."""
+    n = int(n_taps)
+    if n < 1 or n > 256 or int(out_decim) < 1:
+        raise ValueError("need 1 <= n_taps <= 256 and out_decim >= 1")
+    fc = float(cutoff_hz) / float(mpx_rate)
+    t = np.arange(n) - (n - 1) / 2
+    g = 2 * fc * np.sinc(2 * fc * t) * (np.hamming(n) if n > 1 else np.ones(1))
+    g = g / np.abs(g).sum() * (16383 - n)                    # rounding adds at most n / 2 to sum |g|
+    g = np.floor(g + 0.5).astype(np.int16)
+    return g, rds_shift_for(g)
+
+
+def rds_shift_for(g):
+    total = 32768 * int(np.abs(np.asarray(g, dtype=np.int64)).sum())
+    s = 0
+    while -(-total >> s) > 32767:
+        s += 1
+    return s
+
+
+class RdsBank(CheckedHandle):
+    """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream).  `shift=None` takes the smallest
+    front-end shift with every |y| component <= 256 (stereo.FRONT_END_LIMIT); `pilot_min=None` a quarter of a nominal pilot;
+    `rds_shift=None` the smallest exact one."""
+    _prefix = "rds"
+
+    def __init__(self, taps, decim, phase_incs, capture_rate, rds_taps, out_decim, n_streams=1, block=4096, pilot_min=None,
+                 rds_shift=None, shift=None, device_id=-1):
+        self.taps = np.ascontiguousarray(taps, dtype=np.int16)
+        self.rds_taps = np.ascontiguousarray(rds_taps, dtype=np.int16)
+        self.decim, self.n_streams, self.capture_rate = int(decim), int(n_streams), int(capture_rate)
+        self.out_decim, self.block = int(out_decim), int(block)
+        self.phase_incs = stream_phase_incs(phase_incs, self.n_streams)
+        self.n_stations = self.phase_incs.shape[1]
+        self.shift = stations_auto_shift(self.taps, self.phase_incs, limit=FRONT_END_LIMIT) if shift is None else int(shift)
+        self.pilot_min = default_pilot_min(self.capture_rate, self.decim) if pilot_min is None else int(pilot_min)
+        self.rds_shift = rds_shift_for(self.rds_taps) if rds_shift is None else int(rds_shift)
+        self.rate_num, self.rate_den = self.capture_rate, self.decim * self.out_decim
+        self.out_rate = self.rate_num / self.rate_den
+        cfg = RdsConfig(self.capture_rate, self.block, self.out_decim, self.rds_shift, self.pilot_min)
+        self._h = C.c_void_p()
+        dev = DeviceConfig(self.n_streams, device_id, 0)
+        check(lib().fmd_rds_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim, self.shift,
+                                self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations,
+                                self.rds_taps.ctypes.data_as(C.POINTER(C.c_int16)), self.rds_taps.size, C.byref(cfg),
+                                C.byref(dev), C.byref(self._h)))
+
+    def kernel_name(self, which=0):
+        """Pass 0 (the stereo bank's multiplex pass) or 1 (carrier, FIRs, shift), as rocprofv3 --kernel-trace prints it."""
+        buf = C.create_string_buffer(128)
+        check(lib().fmd_rds_kernel_name(self._h, int(which), buf, len(buf)))
+        return buf.value.decode()
+
+    def reset(self):
+        check(lib().fmd_rds_reset(self._h))
+
+    def out_cap(self, nbytes):
+        return int(lib().fmd_rds_out_cap(self.decim, self.out_decim, nbytes))
+
+    def outputs(self):
+        """Outputs per (stream, station) produced since creation or reset."""
+        n = C.c_uint64(0)
+        check(lib().fmd_rds_outputs(self._h, C.byref(n)))
+        return n.value
+
+    def pilot(self, stream=0, station=0):
+        """(present, level) of the last completed block, as StereoBank.pilot."""
+        p, lv = C.c_int(0), C.c_uint32(0)
+        check(lib().fmd_rds_pilot(self._h, int(stream), int(station), C.byref(p), C.byref(lv)))
+        return bool(p.value), lv.value
+
+    def run_batch(self, iq):
+        """iq uint8 [n_streams, nbytes] -> int16 array [n_streams, n_stations, n, 2] of (ur, ui)."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        if iq.ndim != 2 or iq.shape[0] != self.n_streams:
+            raise ValueError("iq must be [n_streams, nbytes]")
+        cap = max(1, self.out_cap(iq.shape[1]))
+        out = np.empty((self.n_streams, self.n_stations, cap, 2), dtype=np.int16)
+        n = C.c_size_t(0)
+        check(lib().fmd_rds_run_batch(self._h, iq.ctypes.data, iq.shape[1], out.ctypes.data, cap, C.byref(n)))
+        return out[:, :, :n.value].copy()
+
+    def run_complex(self, iq):
+        """run_batch as complex64 [n_streams, n_stations, n]."""
+        return as_complex(self.run_batch(iq))
+
+    def run_device(self, d_iq, nbytes, d_out, out_cap, stream=None):
+        """Enqueue on device pointers (d_out [n_streams][n_stations][out_cap][2] int16); returns the outputs per (stream, station).
+        `stream` must stay alive until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
+        n = C.c_size_t(0)
+        check(lib().fmd_rds_run_device(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
+        return n.value
+
+
+class RdsDecoder:
+    """The host decoder of one (stream, station): push() takes int16 [n, 2] (ur, ui) at rate_num / rate_den Hz and returns the
+    groups completed since, as dicts {"blocks": (A, B, C, D), "ok_mask", "first_sample"}; info() the station's PI, PS and text."""
+
+    def __init__(self, rate_num, rate_den=1):
+        self._h = C.c_void_p()
+        check(lib().fmd_rds_decoder_new(int(rate_num), int(rate_den), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().fmd_rds_decoder_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(lib().fmd_rds_decoder_reset(self._h))
+
+    def push(self, u):
+        u = np.ascontiguousarray(u, dtype=np.int16)
+        if u.ndim != 2 or u.shape[1] != 2:
+            raise ValueError("u must be [n, 2] (ur, ui)")
+        buf = (RdsGroup * 64)()
+        n = C.c_size_t(0)
+        groups = []
+        check(lib().fmd_rds_decoder_push(self._h, u.ctypes.data, u.shape[0], buf, 64, C.byref(n)))
+        while True:
+            groups += [{"blocks": tuple(buf[i].block), "ok_mask": buf[i].ok_mask, "first_sample": buf[i].first_sample} for i in range(n.value)]
+            if n.value < 64:
+                return groups
+            check(lib().fmd_rds_decoder_push(self._h, None, 0, buf, 64, C.byref(n)))
+
+    def info(self):
+        i = RdsInfo()
+        check(lib().fmd_rds_decoder_info(self._h, C.byref(i)))
+        return {"pi": i.pi, "ps": i.ps.decode("latin-1"), "rt": i.rt.decode("latin-1"), "groups_ok": i.groups_ok,
+                "blocks_bad": i.blocks_bad, "synced": bool(i.synced)}
+
+
+def decode_stations(bank, iq_calls):
+    """Every call of `iq_calls` (uint8 [n_streams, nbytes] each) through `bank`, every (stream, station) through a decoder of its own:
+    a list [n_streams][n_stations] of RdsDecoder.info() dicts with the delivered groups under "groups"."""
+    decs = [[RdsDecoder(bank.rate_num, bank.rate_den) for _ in range(bank.n_stations)] for _ in range(bank.n_streams)]
+    groups = [[[] for _ in range(bank.n_stations)] for _ in range(bank.n_streams)]
+    for iq in iq_calls:
+        u = bank.run_batch(iq)
+        for s in range(bank.n_streams):
+            for k in range(bank.n_stations):
+                groups[s][k] += decs[s][k].push(u[s, k])
+    return [[dict(decs[s][k].info(), groups=groups[s][k]) for k in range(bank.n_stations)] for s in range(bank.n_streams)]

@@ -102,6 +102,48 @@ pub struct fmd_stereo_config {
 }
 
 #[repr(C)]
+pub struct fmd_rds {
+    _private: [u8; 0],
+}
+
+/// `fmd_rds_config` of include/fmd.h (RDS bank).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_rds_config {
+    pub capture_rate: u32,
+    pub block: u32,
+    pub out_decim: u32,
+    pub rds_shift: u32,
+    pub pilot_min: u32,
+}
+
+#[repr(C)]
+pub struct fmd_rds_decoder {
+    _private: [u8; 0],
+}
+
+/// `fmd_rds_group` of include/fmd.h: one RDS group as the host decoder delivers it.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_rds_group {
+    pub block: [u16; 4],
+    pub ok_mask: u8,
+    pub first_sample: u64,
+}
+
+/// `fmd_rds_info` of include/fmd.h: PI, PS (8 characters + NUL), RadioText (up to 64 + NUL) and the decoder's counters.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct fmd_rds_info {
+    pub pi: u16,
+    pub ps: [c_char; 9],
+    pub rt: [c_char; 65],
+    pub groups_ok: u64,
+    pub blocks_bad: u64,
+    pub synced: c_int,
+}
+
+#[repr(C)]
 pub struct fmd_narrow {
     _private: [u8; 0],
 }
@@ -224,6 +266,21 @@ extern "C" {
     pub fn fmd_stereo_pilot(s: *mut fmd_stereo, stream: u32, station: u32, present: *mut c_int, level: *mut u32) -> c_int;
     pub fn fmd_stereo_pilot_inc(capture_rate: u32, decim: u32, inc: *mut u32) -> c_int;
     pub fn fmd_stereo_kernel_name(s: *const fmd_stereo, pass: u32, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_rds_new(taps: *const i16, n_taps: u32, decim: u32, shift: u32, phase_inc: *const u32, n_stations: u32, rds_taps: *const i16, n_rds_taps: u32, cfg: *const fmd_rds_config, dev: *const DeviceConfig, out: *mut *mut fmd_rds) -> c_int;
+    pub fn fmd_rds_free(s: *mut fmd_rds);
+    pub fn fmd_rds_reset(s: *mut fmd_rds) -> c_int;
+    pub fn fmd_rds_out_cap(decim: u32, out_decim: u32, nbytes: usize) -> usize;
+    pub fn fmd_rds_run_batch(s: *mut fmd_rds, iq: *const u8, nbytes: usize, out: *mut i16, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn fmd_rds_run_device(s: *mut fmd_rds, d_iq: *const c_void, nbytes: usize, d_out: *mut c_void, out_cap: usize, out_len: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_rds_check(s: *mut fmd_rds) -> c_int;
+    pub fn fmd_rds_outputs(s: *const fmd_rds, outputs: *mut u64) -> c_int;
+    pub fn fmd_rds_pilot(s: *mut fmd_rds, stream: u32, station: u32, present: *mut c_int, level: *mut u32) -> c_int;
+    pub fn fmd_rds_kernel_name(s: *const fmd_rds, pass: u32, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_rds_decoder_new(rate_num: u32, rate_den: u32, out: *mut *mut fmd_rds_decoder) -> c_int;
+    pub fn fmd_rds_decoder_free(d: *mut fmd_rds_decoder);
+    pub fn fmd_rds_decoder_reset(d: *mut fmd_rds_decoder) -> c_int;
+    pub fn fmd_rds_decoder_push(d: *mut fmd_rds_decoder, iq: *const i16, n: usize, groups: *mut fmd_rds_group, cap: usize, n_groups: *mut usize) -> c_int;
+    pub fn fmd_rds_decoder_info(d: *const fmd_rds_decoder, info: *mut fmd_rds_info) -> c_int;
     pub fn fmd_narrow_new(taps: *const i16, n_taps: u32, decim: u32, shift: u32, phase_inc: *const u32, n_stations: u32, chan_taps_re: *const i16, chan_taps_im: *const i16, n_chan_taps: u32, cfg: *const fmd_narrow_config, dev: *const DeviceConfig, out: *mut *mut fmd_narrow) -> c_int;
     pub fn fmd_narrow_free(s: *mut fmd_narrow);
     pub fn fmd_narrow_reset(s: *mut fmd_narrow) -> c_int;

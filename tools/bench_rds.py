@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""RDS bank (fmd_rds_*): S streams x 262144 B per call at 2.4 Msps, decimate 10 (f_m = 240 kHz), 64 front-end taps, output
+decimation 32 (7.5 kHz) with 255 RDS taps, pilot blocks of 4096, K stations.  Per K (--k 1,4,8,16): ms per call (HIP events, both
+passes and the block-sum reset), a parity bit against the test-side definition (tests/rds_ref.py) on a seeded sample of streams, and
+two baselines timed in the same process at the same K and front-end shift: the stereo station bank (R = 5, 127 audio taps) and the
+channelizer.  Then the host decoder: fmd_rds_decoder_push in samples per second on one thread, on the definition's baseband of a
+synthesized station.  Writes every line to --out (profiles/rds_bench.json)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+
+import rtl_sdr_rs_amd as fmd
+
+FS, D, T, R, TA, P = 2400000, 10, 64, 32, 255, 4096
+
+
+def time_calls(launch, iters, reps=3):
+    for _ in range(3):
+        launch(0)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(iters):
+            launch(i)
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) / iters)
+    return sorted(ts)[len(ts) // 2], ts
+
+
+def run(K, S, n, iters, parity_streams):
+    import rds_ref as rr
+    import stations_ref as sr
+    import stereo_ref as st
+    h = st.lowpass(T, 130000 / FS)
+    g, rs = fmd.rds_taps(FS // D, R, TA)
+    rng = np.random.default_rng(K)
+    offs = np.linspace(-1000000, 1000000, K) if K > 1 else np.array([300000.0])
+    incs = np.array([[fmd.phase_inc(int(o) + int(rng.integers(-5000, 5000)), FS) for o in offs] for _ in range(S)], np.uint32)
+    rb = fmd.RdsBank(h, D, incs, FS, g, R, n_streams=S, block=P, rds_shift=rs, device_id=0)
+    stream = torch.cuda.current_stream().cuda_stream
+    bufs = []
+    for b in range(2):
+        t = torch.empty((S, n), dtype=torch.uint8, device="cuda")
+        fmd.synth.fill_device(t.data_ptr(), S, n, sample_offset=b * (n // 2), stream=stream)
+        bufs.append(t)
+    cap = rb.out_cap(n)
+    out = torch.empty((S, K, cap, 2), dtype=torch.int16, device="cuda")
+    got = {}
+
+    def launch(i):
+        got["n"] = rb.run_device(bufs[i % 2].data_ptr(), n, out.data_ptr(), cap, stream)
+
+    ms, ts = time_calls(launch, iters)
+    rb.check()
+    # baseline 1: the stereo station bank at the same K and shift (the same pass 0; its pass 1 at R = 5 with 127 taps)
+    sb = fmd.StereoBank(h, D, incs, FS, fmd.stereo_taps(FS // D, 5, 127), 5, n_streams=S, block=P, shift=rb.shift, device_id=0)
+    scap = sb.out_cap(n)
+    sout = torch.empty((S, K, scap, 2), dtype=torch.int16, device="cuda")
+    ms_st, ts_st = time_calls(lambda i: sb.run_device(bufs[i % 2].data_ptr(), n, sout.data_ptr(), scap, stream), iters)
+    sb.check()
+    del sb, sout
+    # baseline 2: the channelizer at the same K and shift
+    ch = fmd.Channelizer(h, D, incs, n_streams=S, shift=rb.shift, device_id=0)
+    ccap = ch.out_cap(n)
+    cout = torch.empty((S, K, ccap, 2), dtype=torch.int16, device="cuda")
+    ms_ch, ts_ch = time_calls(lambda i: ch.run_device(bufs[i % 2].data_ptr(), n, cout.data_ptr(), ccap, stream), iters)
+    ch.check()
+    del ch, cout
+    torch.cuda.empty_cache()
+    # parity: a fresh bank, two calls, sampled streams against the definition
+    pb = fmd.RdsBank(h, D, incs, FS, g, R, n_streams=S, block=P, rds_shift=rs, device_id=0)
+    sample = sorted(np.random.default_rng(7).choice(S, min(parity_streams, S), replace=False).tolist())
+    refs = {s: rr.RdsRef(h, D, incs[s], pb.shift, FS, g, R, rs, P, pb.pilot_min, z=sr.z_corr) for s in sample}
+    ok = True
+    for b in range(2):
+        host = bufs[b].cpu().numpy()
+        pout = torch.empty((S, K, cap, 2), dtype=torch.int16, device="cuda")
+        m = pb.run_device(bufs[b].data_ptr(), n, pout.data_ptr(), cap, stream)
+        pb.check()
+        a = pout[sample, :, :m].cpu().numpy()
+        for i, s in enumerate(sample):
+            ok &= bool(np.array_equal(a[i], refs[s].feed(host[s])))
+    return {"tool": "bench_rds", "K": K, "streams": S, "nbytes": n, "decim": D, "taps": T, "out_decim": R, "rds_taps": TA,
+            "block": P, "shift": rb.shift, "rds_shift": rb.rds_shift, "kernels": [rb.kernel_name(0), rb.kernel_name(1)],
+            "out_per_station": got["n"], "ms": round(ms, 4), "ms_all": [round(t, 4) for t in ts], "in_bytes": S * n,
+            "out_bytes": S * K * got["n"] * 4,
+            "stereo_ms": round(ms_st, 4), "stereo_ms_all": [round(t, 4) for t in ts_st], "ratio_vs_stereo": round(ms / ms_st, 3),
+            "channelizer_ms": round(ms_ch, 4), "channelizer_ms_all": [round(t, 4) for t in ts_ch],
+            "ratio_vs_channelizer": round(ms / ms_ch, 3), "parity": bool(ok), "parity_streams": sample}
+
+
+def decoder_rate(seconds=2.0, reps=5):
+    """fmd_rds_decoder_push on one thread: samples per second over `seconds` of the test station's baseband (the definition's)."""
+    import rds_ref as rr
+    import stations_ref as sr
+    iq, _ = rr.station_capture(seconds)
+    h = rr.front_taps()
+    incs = [sr.phase_inc(40000, rr.FS)]
+    g, rs = fmd.rds_taps(rr.FS // rr.D, rr.R, rr.T_RDS)
+    ref = rr.RdsRef(h, rr.D, incs, fmd.stations_auto_shift(h, incs, limit=256), rr.FS, g, rr.R, rs, z=sr.z_corr)
+    u = np.ascontiguousarray(ref.feed(iq)[0].astype(np.int16))
+    ts, info = [], None
+    for _ in range(reps):
+        dec = fmd.RdsDecoder(rr.FS, rr.D * rr.R)
+        t0 = time.perf_counter()
+        dec.push(u)
+        ts.append(time.perf_counter() - t0)
+        info = dec.info()
+    t = sorted(ts)[len(ts) // 2]
+    return {"tool": "bench_rds", "decoder": True, "samples": int(u.shape[0]), "sample_rate": rr.FS / (rr.D * rr.R),
+            "push_seconds": round(t, 6), "samples_per_second": round(u.shape[0] / t), "realtime_stations_per_thread": round(u.shape[0] / t / (rr.FS / (rr.D * rr.R))),
+            "groups_ok": info["groups_ok"], "blocks_bad": info["blocks_bad"], "ps": info["ps"], "rt": info["rt"]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--k", default="1,4,8,16")
+    ap.add_argument("--streams", type=int, default=512)
+    ap.add_argument("--nbytes", type=int, default=fmd.DEFAULT_BUF_LENGTH)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--parity-streams", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rds_bench.json"))
+    a = ap.parse_args()
+    rows = []
+    for K in [int(x) for x in a.k.split(",")]:
+        rows.append(run(K, a.streams, a.nbytes, a.iters, a.parity_streams))
+        print(json.dumps(rows[-1]), flush=True)
+    dec = decoder_rate()
+    print(json.dumps(dec), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows, "decoder": dec}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
