@@ -106,66 +106,34 @@ __global__ void __launch_bounds__(kThreads) fmd_channelizer_kernel(const ChLaunc
 }  // namespace fmd_ch
 
 struct fmd_channelizer {
-    uint32_t T = 0, D = 0, K = 0, S = 0, shift = 0, HB = 0;
-    uint32_t groups = 0, tile = 0, raw_bytes = 0;
-    size_t lds = 0;
-    FmdDdcPlan plan;
-    FmdDdcCore core;
+    FmdDdcBank bank;
+    FmdDdcTiling tl;
 };
 
 namespace {
 
-using fmd_ddc::kTableBytes;
-
-constexpr size_t kLdsBudget = 40960;                      // 4 tiles per CU
-
-// LDS of a tile of G groups per wave (64 G outputs): raw bytes the matrix phase may read + NCO table + one row per station
-size_t ch_lds(uint32_t D, uint32_t nkc, uint32_t T, uint32_t K, uint32_t G, uint32_t* raw_bytes)
-{
-    const uint64_t cap = 64ull * G;
-    const uint64_t reads = 12 + 6ull * D + 8ull * D * (16 * G - 1) + 64ull * nkc;
-    const uint64_t staged = 12 + 2ull * D * (cap - 1) + 2ull * T + 15;
-    const uint64_t raw = ((reads > staged ? reads : staged) + 15) & ~15ull;
-    *raw_bytes = (uint32_t)raw;
-    return (size_t)(raw + kTableBytes + 4ull * K * cap);
-}
-
-// outputs completed once `S` samples per stream have arrived
-uint64_t ch_outputs(const fmd_channelizer* h, uint64_t S) { return S >= h->T ? (S - h->T) / h->D + 1 : 0; }
-
 int ch_enqueue(fmd_channelizer* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
 {
-    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    if (nbytes > (1ull << 31) - (1ull << 20)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
-    if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & 3u) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
+    if (const int rc = fmd_ddc_check_call(nbytes, d_iq, d_out, 4u)) return rc;
+    const FmdDdcBank& b = h->bank;
+    FmdDdcCore& c = h->bank.core;
     const uint64_t ns = nbytes / 2;
-    FmdDdcCore& c = h->core;
-    const uint64_t m0 = ch_outputs(h, c.pos), m1 = ch_outputs(h, c.pos + ns);
-    const uint64_t M = m1 - m0;
+    const uint64_t m0 = fmd_ddc_outputs(b.T, b.D, c.pos), M = fmd_ddc_outputs(b.T, b.D, c.pos + ns) - m0;
     if (M < 1) { fmd_internal_set_err("the call completes no filter output"); return FMD_ERR_TOO_SHORT; }
     if (M > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
-    const uint64_t ntiles = (M + h->tile - 1) / h->tile;
-    if (ntiles > (1u << 30) || h->S > 65535u) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
+    const uint64_t ntiles = (M + h->tl.tile - 1) / h->tl.tile;
+    if (ntiles > (1u << 30) || b.S > 65535u) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
     fmd_ch::ChLaunch L{};
-    L.iq = static_cast<const uint8_t*>(d_iq);
-    L.nbytes = nbytes;
-    L.hist_in = c.d_hist[c.cur]; L.hist_out = c.d_hist[c.cur ^ 1];
-    L.HB = h->HB;
-    L.vb_first = (uint32_t)(2ull * (h->D * m0 + h->HB / 2 - c.pos));   // >= 0: the window of output m0 starts at most n_taps - 1 samples back
+    fmd_ddc_fill_front(L, b, d_iq, nbytes, m0);
     L.m0_lo = (uint32_t)m0;
     L.M = (uint32_t)M;
-    L.D = h->D; L.T = h->T; L.K = h->K; L.S = h->S; L.shift = h->shift;
-    L.nrt = h->plan.nrt; L.nkc = h->plan.nkc; L.digits = h->plan.digits;
-    L.groups = h->groups; L.tile = h->tile; L.ntiles = (uint32_t)ntiles; L.raw_bytes = h->raw_bytes;
+    L.groups = h->tl.groups; L.tile = h->tl.tile; L.ntiles = (uint32_t)ntiles; L.raw_bytes = h->tl.raw_bytes;
     L.vec4 = (((uintptr_t)d_out & 15u) == 0 && out_cap % 4 == 0) ? 1u : 0u;
-    L.amat = c.d_amat; L.kconst = c.d_kconst; L.dinc = c.d_dinc; L.tab = c.d_tab;
     L.out = static_cast<uint32_t*>(d_out); L.out_stride = out_cap;
     FMD_DDC_TRY(c.order.before(stream));
-    hipLaunchKernelGGL(fmd_ch::fmd_channelizer_kernel, dim3(L.ntiles, h->S), dim3(fmd_ch::kThreads), h->lds, stream, L);
+    hipLaunchKernelGGL(fmd_ch::fmd_channelizer_kernel, dim3(L.ntiles, b.S), dim3(fmd_ch::kThreads), h->tl.lds, stream, L);
     FMD_DDC_TRY(hipGetLastError());
-    (void)c.order.after(stream);
-    c.cur ^= 1;
-    c.pos += ns;
+    fmd_ddc_commit(c, stream, ns);
     if (out_len) *out_len = (size_t)M;
     return FMD_OK;
 }
@@ -185,37 +153,17 @@ int fmd_channelizer_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, ui
 {
     if (!taps || !phase_inc || !dev || !out || dev->n_channels == 0) { fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG; }
     *out = nullptr;
-    if (n_taps == 0 || n_taps > 256 || decim < 2 || decim % 2 != 0 || decim > 64 || shift > 24 || n_stations == 0 || n_stations > 32 ||
-        dev->n_channels > 65535u) {
-        fmd_internal_set_err("need 1 <= n_taps <= 256, an even 2 <= decim <= 64, shift <= 24, 1 <= n_stations <= 32, n_streams <= 65535");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    for (uint32_t t = 0; t < n_taps; ++t)
-        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
     fmd_channelizer* h = new (std::nothrow) fmd_channelizer();
     if (!h) return FMD_ERR_NOMEM;
-    h->T = n_taps; h->D = decim; h->K = n_stations; h->S = dev->n_channels; h->shift = shift;
-    fmd_st_build_plan(taps, n_taps, decim, phase_inc, h->S, h->K, h->plan);
-    // |y| <= 256 G / 2^shift (|z| <= 128 G per component, the rotation adds two of them): exact in int16 while <= 16384
-    const uint64_t bound = (256ull * h->plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
-    if (bound > 16384ull) {
-        delete h;
-        fmd_internal_set_err("filter gain too large for int16 output: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    for (uint32_t G = fmd_ddc::kGroups; G >= 1; --G) {     // the largest tile within the budget (G = 1 always fits: <= 19 KB)
-        uint32_t rb;
-        const size_t l = ch_lds(decim, h->plan.nkc, n_taps, n_stations, G, &rb);
-        if (l <= kLdsBudget || G == 1) { h->groups = G; h->tile = 64u * G; h->raw_bytes = rb; h->lds = l; break; }
-    }
-    h->HB = 2u * ((n_taps - 1u + 7u) & ~7u);
+    uint64_t bound;
+    if (const int rc = fmd_ddc_bank_front(h->bank, taps, n_taps, decim, shift, phase_inc, n_stations, dev, &bound)) { delete h; return rc; }
+    h->tl = fmd_ddc_tiling(decim, h->bank.plan.nkc, n_taps, n_stations);
 
-    if (const int rc = fmd_ddc_open(h->core, dev)) { delete h; return rc; }
-    auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_channelizer_free(h); return FMD_ERR_HIP; };
-    FmdDeviceGuard guard(h->core.device);
-    if (guard.error() != hipSuccess) return fail("hipSetDevice");
-    if (const char* what = fmd_ddc_upload(h->core, h->plan, (size_t)h->S * (h->HB ? h->HB : 16))) return fail(what);
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
+    const char* what;
+    if (const int rc = fmd_ddc_bank_device(h->bank, dev, &what)) {
+        if (!what) { delete h; return rc; }
+        fmd_internal_set_err(what); fmd_channelizer_free(h); return rc;
+    }
     *out = h;
     return FMD_OK;
 }
@@ -223,61 +171,40 @@ int fmd_channelizer_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, ui
 void fmd_channelizer_free(fmd_channelizer* h)
 {
     if (!h) return;
-    FmdDeviceGuard guard(h->core.device);
-    fmd_ddc_release(h->core);
+    fmd_ddc_free(h->bank.core);
     delete h;
 }
 
 int fmd_channelizer_reset(fmd_channelizer* h)
 {
     if (!h) return FMD_ERR_INVALID_ARG;
-    FMD_DDC_ON_DEVICE(h->core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    FMD_DDC_TRY(fmd_ddc_zero_history(h->core));          // (ends with the device synchronised)
-    return FMD_OK;
+    return fmd_ddc_reset(h->bank.core);
 }
 
 int fmd_channelizer_run_device(fmd_channelizer* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len,
                                void* stream)
 {
-    if (!h || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    return ch_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream));
+    return fmd_ddc_run_device(h ? &h->bank.core : nullptr, d_iq, d_out,
+                              [&] { return ch_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream)); });
 }
 
 int fmd_channelizer_check(fmd_channelizer* h)
 {
     if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    if (h->core.order.have_last) FMD_DDC_TRY(hipStreamSynchronize(h->core.order.last));
-    FMD_DDC_TRY(hipGetLastError());
-    return FMD_OK;
+    return fmd_ddc_check(h->bank.core);
 }
 
 int fmd_channelizer_run_batch(fmd_channelizer* h, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap, size_t* out_len)
 {
     if (!h || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    FmdDdcCore& c = h->core;
-    const size_t rows = (size_t)h->S * h->K;
-    const size_t in_bytes = nbytes * (size_t)h->S, out_bytes = out_cap * rows * sizeof(uint32_t);   // (yr, yi) pairs
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
-    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
-    size_t n = 0;
-    int rc = ch_enqueue(h, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream);
-    if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
-    FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
-    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
-    *out_len = n;
-    return FMD_OK;
+    const size_t out_bytes = out_cap * h->bank.S * h->bank.K * sizeof(uint32_t);   // (yr, yi) pairs
+    return fmd_ddc_run_batch(h->bank, iq, nbytes, out, out_bytes, out_cap, out_len, [h](auto... a) { return ch_enqueue(h, a...); });
 }
 
 int fmd_channelizer_outputs(const fmd_channelizer* h, uint64_t* outputs)
 {
     if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *outputs = ch_outputs(h, h->core.pos);
+    *outputs = fmd_ddc_outputs(h->bank.T, h->bank.D, h->bank.core.pos);
     return FMD_OK;
 }
 

@@ -1,9 +1,12 @@
-// fmd_ddc.h -- what the three matrix-core handles share: the station bank (fmd_stations.hip), the channelizer
-// (fmd_channelizer.hip) and the power-spectrum scanner (fmd_spectrum.hip).
+// fmd_ddc.h -- what the matrix-core handles share: the five down-converter banks (fmd_stations.hip, fmd_channelizer.hip,
+// fmd_stereo.hip, fmd_narrow.hip, fmd_rds.hip) and the power-spectrum scanner (fmd_spectrum.hip).
 //   plan (host):        the NCO table, the complex taps of every row, the matrix-core A fragments and their centring constants;
-//   front end (device): the bank's and the channelizer's digital down-converter -- staging of the filter windows and the NCO
-//                       table in LDS, the history write, the contraction on the matrix cores, the rotation back to baseband;
-//   handle core (host): device, stream, uploaded plan, double-buffered history, batch staging buffers.
+//   front end (device): the banks' digital down-converter -- staging of the filter windows and the NCO table in LDS, the
+//                       history write, the contraction on the matrix cores, the rotation back to baseband;
+//   handle core (host): device, stream, uploaded plan, double-buffered history, per-row ping-pong state, batch staging buffers;
+//   bank (host):        what a down-converter's entry points do around its own kernels -- the constructor's front-end checks and
+//                       device step, the tile sizing, the output counters, the call checks, the launch fields the front end
+//                       reads, the batch path, check, reset and free.
 // Definitions: include/fmd.h, "station bank", "channelizer", "power spectrum".
 #pragma once
 
@@ -13,6 +16,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -301,7 +305,23 @@ __device__ __forceinline__ void contract(const Launch& L, uint32_t s, uint32_t w
     FmdDeviceGuard dev_guard_(dev);                                                         \
     if (dev_guard_.error() != hipSuccess) { fmd_internal_set_err("hipSetDevice failed"); return FMD_ERR_HIP; }
 
-// What each of fmd_stations, fmd_channelizer and fmd_spectrum holds on the device.
+// Per-row state that one call reads and the next call's copy is written to: read [core.cur], written [core.cur ^ 1].
+struct FmdDdcPair {
+    void* p[2] = {nullptr, nullptr};
+    size_t bytes = 0;
+    template <class T> T* in(int cur) const { return static_cast<T*>(p[cur]); }
+    template <class T> T* out(int cur) const { return static_cast<T*>(p[cur ^ 1]); }
+};
+
+// A further device buffer of the handle: a constant uploaded by the constructor (src != nullptr) or call-sized scratch that
+// fmd_ddc_grow allocates in the calls (src == nullptr).
+struct FmdDdcOwned {
+    void** slot = nullptr;
+    const void* src = nullptr;
+    size_t bytes = 0;
+};
+
+// What every handle holds on the device.
 struct FmdDdcCore {
     int device = 0;
     hipStream_t stream = nullptr;                         // the host entry points' own stream
@@ -316,7 +336,26 @@ struct FmdDdcCore {
     uint64_t pos = 0;                                     // samples consumed per stream
     void* d_iq = nullptr; size_t d_iq_cap = 0;            // batch staging (bytes)
     void* d_out = nullptr; size_t d_out_cap = 0;
+    // what the handle registered (members of the handle itself): the constructor's device step allocates them, reset zeroes the
+    // pairs, release frees all of them
+    FmdDdcPair* pairs[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t n_pairs = 0;
+    FmdDdcOwned owned[4];
+    uint32_t n_owned = 0;
 };
+
+inline void fmd_ddc_add_pair(FmdDdcCore& c, FmdDdcPair& pr, size_t bytes)
+{
+    assert(c.n_pairs < 4u);
+    pr.bytes = bytes;
+    c.pairs[c.n_pairs++] = &pr;
+}
+// `src` must stay valid until the constructor's device step
+inline void fmd_ddc_add_owned(FmdDdcCore& c, void*& slot, const void* src = nullptr, size_t bytes = 0)
+{
+    assert(c.n_owned < 4u);
+    c.owned[c.n_owned++] = FmdDdcOwned{&slot, src, bytes};
+}
 
 // The device of `dev` (device_id < 0: the current one) if it is a gfx950; FMD_ERR_NO_DEVICE otherwise.  Touches no allocation.
 inline int fmd_ddc_open(FmdDdcCore& c, const fmd_device_config* dev)
@@ -334,7 +373,7 @@ inline int fmd_ddc_open(FmdDdcCore& c, const fmd_device_config* dev)
 }
 
 // On c.device: the plan's buffers (the NCO table with the phase steps), a zeroed history of `hist_bytes` twice when non-zero,
-// the stream.  nullptr, or what failed.
+// the stream, the registered pairs zeroed and the registered constants.  nullptr, or what failed.
 inline const char* fmd_ddc_upload(FmdDdcCore& c, const FmdDdcPlan& P, size_t hist_bytes)
 {
     if (hipMalloc(&c.d_amat, P.amat.size() * 4) != hipSuccess || hipMemcpy(c.d_amat, P.amat.data(), P.amat.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
@@ -353,13 +392,29 @@ inline const char* fmd_ddc_upload(FmdDdcCore& c, const FmdDdcPlan& P, size_t his
     for (int i = 0; i < 2 && hist_bytes; ++i)
         if (hipMalloc(&c.d_hist[i], hist_bytes) != hipSuccess || hipMemset(c.d_hist[i], 0, hist_bytes) != hipSuccess) return "hipMalloc(history)";
     if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate";
+    for (uint32_t k = 0; k < c.n_pairs; ++k)
+        for (int i = 0; i < 2; ++i) {
+            FmdDdcPair& pr = *c.pairs[k];
+            if (hipMalloc(&pr.p[i], pr.bytes) != hipSuccess || hipMemset(pr.p[i], 0, pr.bytes) != hipSuccess) return "hipMalloc(per-row state)";
+        }
+    for (uint32_t k = 0; k < c.n_owned; ++k) {
+        FmdDdcOwned& o = c.owned[k];
+        if (o.src && (hipMalloc(o.slot, o.bytes) != hipSuccess || hipMemcpy(*o.slot, o.src, o.bytes, hipMemcpyHostToDevice) != hipSuccess))
+            return "hipMalloc(second-stage taps)";
+        o.src = nullptr;
+    }
     return nullptr;
 }
 
-// Back to position 0 with an all-zero history (the caller has synchronised the device).  The position, the buffer index and the
-// stream order change only once the device has finished the memsets, so a failure leaves them as they were.
+// Back to position 0 with an all-zero history and all-zero pairs (the caller has synchronised the device).  The position, the
+// buffer index and the stream order change only once the device has finished the memsets, so a failure leaves them as they were.
 inline hipError_t fmd_ddc_zero_history(FmdDdcCore& c)
 {
+    for (uint32_t k = 0; k < c.n_pairs; ++k)
+        for (int i = 0; i < 2; ++i) {
+            const hipError_t e = hipMemset(c.pairs[k]->p[i], 0, c.pairs[k]->bytes);
+            if (e != hipSuccess) return e;
+        }
     for (int i = 0; i < 2; ++i) {
         const hipError_t e = hipMemset(c.d_hist[i], 0, c.hist_bytes);
         if (e != hipSuccess) return e;
@@ -371,17 +426,21 @@ inline hipError_t fmd_ddc_zero_history(FmdDdcCore& c)
     return hipSuccess;
 }
 
-// Everything the core holds (on c.device: the caller holds the device guard).
+// Everything the core holds and the handle registered (on c.device: the caller holds the device guard).
 inline void fmd_ddc_release(FmdDdcCore& c)
 {
     (void)hipDeviceSynchronize();
     c.order.destroy();
+    for (uint32_t k = 0; k < c.n_pairs; ++k)
+        for (void* p : c.pairs[k]->p) if (p) (void)hipFree(p);
+    for (uint32_t k = 0; k < c.n_owned; ++k)
+        if (*c.owned[k].slot) (void)hipFree(*c.owned[k].slot);
     for (void* p : {(void*)c.d_amat, (void*)c.d_kconst, (void*)c.d_dinc, (void*)c.d_tab, (void*)c.d_hist[0], (void*)c.d_hist[1], c.d_iq, c.d_out})
         if (p) (void)hipFree(p);
     if (c.stream) (void)hipStreamDestroy(c.stream);
 }
 
-// A batch staging buffer of at least `bytes` (at least 1) bytes, reallocated only when it grows.
+// A batch staging or scratch buffer of at least `bytes` (at least 1) bytes, reallocated only when it grows.
 inline hipError_t fmd_ddc_grow(void*& p, size_t& cap, size_t bytes)
 {
     if (bytes <= cap) return hipSuccess;
@@ -397,3 +456,196 @@ inline hipError_t fmd_ddc_grow(void*& p, size_t& cap, size_t bytes)
 
 // snprintf's result in a `_kernel_name` entry point -> FMD_OK / FMD_ERR_CAPACITY
 inline int fmd_ddc_name_rc(int n, size_t cap) { return n < 0 || (size_t)n >= cap ? FMD_ERR_CAPACITY : FMD_OK; }
+
+// The handle's most recent launch has completed without an error.
+inline int fmd_ddc_check(FmdDdcCore& c)
+{
+    FMD_DDC_ON_DEVICE(c.device);
+    FMD_DDC_TRY(c.order.wait_last());
+    FMD_DDC_TRY(hipGetLastError());
+    return FMD_OK;
+}
+
+// ---- bank (host): a down-converter handle around its own kernels ------------------------------------------------------------------
+
+// The front end's parameters, its plan and the core.  Every down-converter handle embeds one.
+struct FmdDdcBank {
+    uint32_t T = 0, D = 0, K = 0, S = 0, shift = 0;       // taps, decimation, stations per stream, streams, normalising shift
+    uint32_t HB = 0;                                      // history bytes per stream (multiple of 16)
+    FmdDdcPlan plan;
+    FmdDdcCore core;
+};
+
+// The front end's argument checks, in a *_new: the ranges, then |tap| <= 2047.
+inline int fmd_ddc_front_args(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t shift, uint32_t n_stations,
+                              const fmd_device_config* dev)
+{
+    if (n_taps == 0 || n_taps > 256 || decim < 2 || decim % 2 != 0 || decim > 64 || shift > 24 || n_stations == 0 || n_stations > 32 ||
+        dev->n_channels > 65535u) {
+        fmd_internal_set_err("need 1 <= n_taps <= 256, an even 2 <= decim <= 64, shift <= 24, 1 <= n_stations <= 32, n_streams <= 65535");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    for (uint32_t t = 0; t < n_taps; ++t)
+        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
+    return FMD_OK;
+}
+
+// The front end's constructor step: the argument checks (again, for a caller whose own checks came after them), the bank's
+// fields, the plan and the gain bound.  *bound = B_y = ceil(256 max_gain / 2^shift), the largest |y| component: |z| <= 128 G per
+// component and the rotation adds two of them; the int16 outputs and the discriminator are exact while B_y <= 16384.
+inline int fmd_ddc_bank_front(FmdDdcBank& b, const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t shift,
+                              const uint32_t* phase_inc, uint32_t n_stations, const fmd_device_config* dev, uint64_t* bound)
+{
+    if (const int rc = fmd_ddc_front_args(taps, n_taps, decim, shift, n_stations, dev)) return rc;
+    b.T = n_taps; b.D = decim; b.K = n_stations; b.S = dev->n_channels; b.shift = shift;
+    b.HB = 2u * ((n_taps - 1u + 7u) & ~7u);
+    fmd_st_build_plan(taps, n_taps, decim, phase_inc, b.S, b.K, b.plan);
+    *bound = (256ull * b.plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
+    if (*bound > 16384ull) {
+        fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    return FMD_OK;
+}
+
+// The constructor's device step: the device, the plan, the history, the stream, and what the handle registered on the core.
+// FMD_OK; the device's refusal with *what == nullptr (nothing was allocated: the caller deletes the handle); or FMD_ERR_HIP and
+// what failed (the caller sets the error text and calls its *_free).
+inline int fmd_ddc_bank_device(FmdDdcBank& b, const fmd_device_config* dev, const char** what)
+{
+    *what = nullptr;
+    if (const int rc = fmd_ddc_open(b.core, dev)) return rc;
+    FmdDeviceGuard guard(b.core.device);
+    if (guard.error() != hipSuccess) *what = "hipSetDevice";
+    if (!*what) *what = fmd_ddc_upload(b.core, b.plan, (size_t)b.S * (b.HB ? b.HB : 16));
+    if (!*what && hipDeviceSynchronize() != hipSuccess) *what = "hipDeviceSynchronize";
+    return *what ? FMD_ERR_HIP : FMD_OK;
+}
+
+namespace fmd_ddc {
+constexpr size_t kLdsBudget = 40960;                      // 4 tiles per CU
+}
+
+// Raw bytes of a tile of `cap` outputs, G 16-column groups per wave: what the matrix phase may read or the staging writes.
+inline uint32_t fmd_ddc_raw_bytes(uint32_t D, uint32_t nkc, uint32_t T, uint32_t G, uint32_t cap)
+{
+    const uint64_t reads = 12 + 6ull * D + 8ull * D * (16 * G - 1) + 64ull * nkc;
+    const uint64_t staged = 12 + 2ull * D * (cap - 1) + 2ull * T + 15;
+    return (uint32_t)(((reads > staged ? reads : staged) + 15) & ~15ull);
+}
+
+// LDS of a tile of G groups per wave (64 G outputs): the raw bytes + the NCO table + one row of packed outputs per station
+inline size_t fmd_ddc_tile_lds(uint32_t D, uint32_t nkc, uint32_t T, uint32_t K, uint32_t G, uint32_t* raw_bytes)
+{
+    *raw_bytes = fmd_ddc_raw_bytes(D, nkc, T, G, 64u * G);
+    return (size_t)*raw_bytes + fmd_ddc::kTableBytes + 4ull * K * 64u * G;
+}
+
+// the largest tile (tile = 64 groups outputs) within the budget; G = 1 always fits (<= 19 KB)
+struct FmdDdcTiling { uint32_t groups = 0, tile = 0, raw_bytes = 0; size_t lds = 0; };
+inline FmdDdcTiling fmd_ddc_tiling(uint32_t D, uint32_t nkc, uint32_t T, uint32_t K)
+{
+    FmdDdcTiling t;
+    for (t.groups = fmd_ddc::kGroups; t.groups >= 1; --t.groups) {
+        t.lds = fmd_ddc_tile_lds(D, nkc, T, K, t.groups, &t.raw_bytes);
+        if (t.lds <= fmd_ddc::kLdsBudget || t.groups == 1) break;
+    }
+    t.tile = 64u * t.groups;
+    return t;
+}
+
+// front-end outputs completed once `samples` samples per stream have arrived
+inline uint64_t fmd_ddc_outputs(uint32_t T, uint32_t D, uint64_t samples) { return samples >= T ? (samples - T) / D + 1 : 0; }
+// outputs of a second filter of Ta taps at stride R over m inputs
+inline uint64_t fmd_ddc_fir_outputs(uint32_t Ta, uint32_t R, uint64_t m) { return fmd_ddc_outputs(Ta, R, m); }
+
+// The checks every enqueue starts with; d_out must be aligned to `out_align` (a power of two) bytes.
+inline int fmd_ddc_check_call(size_t nbytes, const void* d_iq, const void* d_out, uint32_t out_align)
+{
+    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
+    if (nbytes > (1ull << 31) - (1ull << 20)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
+    if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & (out_align - 1u)) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
+    return FMD_OK;
+}
+
+// The launch fields the device front end reads (same names in every launch struct), for a call whose first output has the global
+// index m0.  The index itself (m0 / m0_lo) and the call's output count differ in name and width: the caller sets them.
+template <class Launch>
+inline void fmd_ddc_fill_front(Launch& L, const FmdDdcBank& b, const void* d_iq, size_t nbytes, uint64_t m0)
+{
+    const FmdDdcCore& c = b.core;
+    L.iq = static_cast<const uint8_t*>(d_iq);
+    L.nbytes = nbytes;
+    L.hist_in = c.d_hist[c.cur]; L.hist_out = c.d_hist[c.cur ^ 1];
+    L.HB = b.HB;
+    L.vb_first = (uint32_t)(2ull * (b.D * m0 + b.HB / 2 - c.pos));   // >= 0: the window of output m0 starts at most n_taps - 1 samples back
+    L.D = b.D; L.T = b.T; L.K = b.K; L.S = b.S; L.shift = b.shift;
+    L.nrt = b.plan.nrt; L.nkc = b.plan.nkc; L.digits = b.plan.digits;
+    L.amat = c.d_amat; L.kconst = c.d_kconst; L.dinc = c.d_dinc; L.tab = c.d_tab;
+}
+
+// The end of an enqueue whose launches were accepted: the stream order, the buffer index, the position.
+inline void fmd_ddc_commit(FmdDdcCore& c, hipStream_t stream, uint64_t ns)
+{
+    (void)c.order.after(stream);
+    c.cur ^= 1;
+    c.pos += ns;
+}
+
+// A `_device` entry point: `enqueue()` on the handle's device.
+template <class Enqueue>
+inline int fmd_ddc_run_device(const FmdDdcCore* c, const void* d_iq, const void* d_out, Enqueue enqueue)
+{
+    if (!c || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(c->device);
+    return enqueue();
+}
+
+// The first half of a `_batch` entry point (on the handle's device): the input of every stream into the staging buffer and
+// enqueue(d_iq, nbytes, d_out, out_cap, &n, stream) on the handle's own stream, into a staging buffer of `out_bytes`.
+template <class Enqueue>
+inline int fmd_ddc_batch_enqueue(FmdDdcBank& b, const uint8_t* iq, size_t nbytes, size_t out_bytes, size_t out_cap, size_t* n,
+                                 Enqueue enqueue)
+{
+    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
+    FmdDdcCore& c = b.core;
+    const size_t in_bytes = nbytes * (size_t)b.S;
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
+    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
+    return enqueue(c.d_iq, nbytes, c.d_out, out_cap, n, c.stream);
+}
+
+// A `_batch` entry point: host in, host out (`out_bytes` for all rows), the call's outputs per row in *out_len.
+template <class Enqueue>
+inline int fmd_ddc_run_batch(FmdDdcBank& b, const uint8_t* iq, size_t nbytes, void* out, size_t out_bytes, size_t out_cap,
+                             size_t* out_len, Enqueue enqueue)
+{
+    FmdDdcCore& c = b.core;
+    FMD_DDC_ON_DEVICE(c.device);
+    size_t n = 0;
+    if (const int rc = fmd_ddc_batch_enqueue(b, iq, nbytes, out_bytes, out_cap, &n, enqueue)) {
+        (void)hipStreamSynchronize(c.stream);
+        return rc;
+    }
+    FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
+    *out_len = n;
+    return FMD_OK;
+}
+
+// A `_reset` entry point: position 0, an all-zero history, all-zero pairs.
+inline int fmd_ddc_reset(FmdDdcCore& c)
+{
+    FMD_DDC_ON_DEVICE(c.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    FMD_DDC_TRY(fmd_ddc_zero_history(c));                 // (ends with the device synchronised)
+    return FMD_OK;
+}
+
+// A `_free` entry point's device side: everything but the handle itself.
+inline void fmd_ddc_free(FmdDdcCore& c)
+{
+    FmdDeviceGuard guard(c.device);
+    fmd_ddc_release(c);
+}

@@ -294,38 +294,24 @@ __global__ void __launch_bounds__(kThreads) fmd_narrow_chan_kernel(const ChanLau
 }  // namespace fmd_nb
 
 struct fmd_narrow {
-    uint32_t T = 0, D = 0, K = 0, S = 0, shift = 0, HB = 0;
-    uint32_t groups = 0, tile = 0, raw_bytes = 0;
-    size_t lds = 0;
+    FmdDdcBank bank;
+    FmdDdcTiling tl;
     uint32_t Ta = 0, R = 0, Q = 0, P = 0, pshift = 0, chan_shift = 0, mode = 0, squelch = 0, gain = 0, width = 1;
     uint32_t HX = 0, HXS = 0, na = 0, pitch = 0, rinv = 0;
     bool cplx = false;
-    FmdDdcPlan plan;
-    FmdDdcCore core;
-    int2* d_g = nullptr;                                  // [R][Q] polyphase taps
-    uint32_t* d_yh[2] = {nullptr, nullptr};               // [S K][HXS] y history, read [core.cur], written [core.cur ^ 1]
-    unsigned long long* d_carry[2] = {nullptr, nullptr};  // [S K][kCarry]
+    void* d_g = nullptr;                                  // [R][Q] polyphase taps (int2)
+    FmdDdcPair yh;                                        // [S K][HXS] y history (packed dwords)
+    FmdDdcPair carry;                                     // [S K][kCarry] (u64)
     void* d_y = nullptr; size_t d_y_cap = 0;              // the call's y
 };
 
 namespace {
 
-using fmd_ddc::kTableBytes;
-
-constexpr size_t kLdsBudget = 40960;
-
-size_t nb_lds(uint32_t D, uint32_t nkc, uint32_t T, uint32_t K, uint32_t G, uint32_t* raw_bytes)
+// audio samples completed once `samples` samples per stream have arrived
+uint64_t nb_audio(const fmd_narrow* h, uint64_t samples)
 {
-    const uint64_t cap = 64ull * G;
-    const uint64_t reads = 12 + 6ull * D + 8ull * D * (16 * G - 1) + 64ull * nkc;
-    const uint64_t staged = 12 + 2ull * D * (cap - 1) + 2ull * T + 15;
-    const uint64_t raw = ((reads > staged ? reads : staged) + 15) & ~15ull;
-    *raw_bytes = (uint32_t)raw;
-    return (size_t)(raw + kTableBytes + 4ull * K * cap);
+    return fmd_ddc_fir_outputs(h->Ta, h->R, fmd_ddc_outputs(h->bank.T, h->bank.D, samples));
 }
-
-uint64_t nb_y(const fmd_narrow* h, uint64_t S) { return S >= h->T ? (S - h->T) / h->D + 1 : 0; }
-uint64_t nb_audio(const fmd_narrow* h, uint64_t m) { return m >= h->Ta ? (m - h->Ta) / h->R + 1 : 0; }
 
 uint32_t isqrt_u64(uint64_t v)
 {
@@ -337,60 +323,47 @@ uint32_t isqrt_u64(uint64_t v)
 
 int nb_enqueue(fmd_narrow* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
 {
-    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    if (nbytes > (1ull << 31) - (1ull << 20)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
-    if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & (2u * h->width - 1u)) != 0) {
-        fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG;
-    }
-    FmdDdcCore& c = h->core;
+    if (const int rc = fmd_ddc_check_call(nbytes, d_iq, d_out, 2u * h->width)) return rc;
+    const FmdDdcBank& b = h->bank;
+    FmdDdcCore& c = h->bank.core;
     const uint64_t ns = nbytes / 2;
-    const uint64_t mS = nb_y(h, c.pos), mE = nb_y(h, c.pos + ns), M = mE - mS;
-    const uint64_t nS = nb_audio(h, mS), NA = nb_audio(h, mE) - nS;
+    const uint64_t mS = fmd_ddc_outputs(b.T, b.D, c.pos), M = fmd_ddc_outputs(b.T, b.D, c.pos + ns) - mS;
+    const uint64_t nS = nb_audio(h, c.pos), NA = nb_audio(h, c.pos + ns) - nS;
     if (NA < 1) { fmd_internal_set_err("the call completes no audio sample"); return FMD_ERR_TOO_SHORT; }
     if (NA > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
-    const uint64_t SK = (uint64_t)h->S * h->K;
-    const uint64_t nt1 = (M + h->tile - 1) / h->tile, nt2 = (NA + h->na - 1) / h->na;
-    if (nt1 > (1u << 30) || h->S > 65535u) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
+    const uint64_t SK = (uint64_t)b.S * b.K;
+    const uint64_t nt1 = (M + h->tl.tile - 1) / h->tl.tile, nt2 = (NA + h->na - 1) / h->na;
+    if (nt1 > (1u << 30) || b.S > 65535u) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
     const uint64_t ystride = (M + 3) & ~3ull;
     FMD_DDC_TRY(fmd_ddc_grow(h->d_y, h->d_y_cap, (size_t)(SK * ystride * 4)));
-    const int cur = c.cur;
 
     fmd_nb::DdcLaunch A{};
-    A.iq = static_cast<const uint8_t*>(d_iq);
-    A.nbytes = nbytes;
-    A.hist_in = c.d_hist[cur]; A.hist_out = c.d_hist[cur ^ 1];
-    A.HB = h->HB;
-    A.vb_first = (uint32_t)(2ull * (h->D * mS + h->HB / 2 - c.pos));
+    fmd_ddc_fill_front(A, b, d_iq, nbytes, mS);
     A.m0_lo = (uint32_t)mS; A.M = (uint32_t)M;
-    A.D = h->D; A.T = h->T; A.K = h->K; A.S = h->S; A.shift = h->shift;
-    A.nrt = h->plan.nrt; A.nkc = h->plan.nkc; A.digits = h->plan.digits;
-    A.tile = h->tile; A.ntiles = (uint32_t)nt1; A.raw_bytes = h->raw_bytes;
-    A.amat = c.d_amat; A.kconst = c.d_kconst; A.dinc = c.d_dinc; A.tab = c.d_tab;
+    A.tile = h->tl.tile; A.ntiles = (uint32_t)nt1; A.raw_bytes = h->tl.raw_bytes;
     A.y = static_cast<uint32_t*>(h->d_y); A.ystride = (uint32_t)ystride;
 
     fmd_nb::ChanLaunch B{};
     B.y = A.y; B.ystride = A.ystride; B.M = (uint32_t)M;
-    B.yh_in = h->d_yh[cur]; B.yh_out = h->d_yh[cur ^ 1];
+    B.yh_in = h->yh.in<uint32_t>(c.cur); B.yh_out = h->yh.out<uint32_t>(c.cur);
     B.HX = h->HX; B.HXS = h->HXS;
-    B.carry_in = h->d_carry[cur]; B.carry_out = h->d_carry[cur ^ 1];
+    B.carry_in = h->carry.in<unsigned long long>(c.cur); B.carry_out = h->carry.out<unsigned long long>(c.cur);
     B.SK = (uint32_t)SK;
     B.yoff0 = (int32_t)((int64_t)(h->R * nS) - (int64_t)mS);
     B.nS = nS; B.NA = (uint32_t)NA; B.na = h->na; B.ntiles = (uint32_t)nt2;
     B.R = h->R; B.Q = h->Q; B.rinv = h->rinv; B.pitch = h->pitch; B.Ta = h->Ta;
     B.chan_shift = h->chan_shift; B.pshift = h->pshift; B.mode = h->mode; B.gain = h->gain;
     B.thr = (uint64_t)h->squelch * h->squelch * h->P;
-    B.g = h->d_g;
+    B.g = static_cast<const int2*>(h->d_g);
     B.out = static_cast<int16_t*>(d_out); B.out_cap = out_cap;   // samples per row: int16 each, a dword each in IQ mode
 
     FMD_DDC_TRY(c.order.before(stream));
-    hipLaunchKernelGGL(fmd_nb::fmd_narrow_ddc_kernel, dim3(A.ntiles, h->S), dim3(fmd_nb::kThreads), h->lds, stream, A);
+    hipLaunchKernelGGL(fmd_nb::fmd_narrow_ddc_kernel, dim3(A.ntiles, b.S), dim3(fmd_nb::kThreads), h->tl.lds, stream, A);
     FMD_DDC_TRY(hipGetLastError());
     if (h->cplx) hipLaunchKernelGGL(fmd_nb::fmd_narrow_chan_kernel<true>, dim3((uint32_t)SK), dim3(fmd_nb::kThreads), 0, stream, B);
     else hipLaunchKernelGGL(fmd_nb::fmd_narrow_chan_kernel<false>, dim3((uint32_t)SK), dim3(fmd_nb::kThreads), 0, stream, B);
     FMD_DDC_TRY(hipGetLastError());
-    (void)c.order.after(stream);
-    c.cur ^= 1;
-    c.pos += ns;
+    fmd_ddc_commit(c, stream, ns);
     if (out_len) *out_len = (size_t)NA;
     return FMD_OK;
 }
@@ -416,13 +389,7 @@ int fmd_narrow_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
         fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG;
     }
     *out = nullptr;
-    if (n_taps == 0 || n_taps > 256 || decim < 2 || decim % 2 != 0 || decim > 64 || shift > 24 || n_stations == 0 || n_stations > 32 ||
-        dev->n_channels > 65535u) {
-        fmd_internal_set_err("need 1 <= n_taps <= 256, an even 2 <= decim <= 64, shift <= 24, 1 <= n_stations <= 32, n_streams <= 65535");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    for (uint32_t t = 0; t < n_taps; ++t)
-        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
+    if (const int rc = fmd_ddc_front_args(taps, n_taps, decim, shift, n_stations, dev)) return rc;
     const uint32_t R = cfg->chan_decim, P = cfg->block, Ta = n_chan_taps;
     if (cfg->mode > FMD_NARROW_SSB || R < 1u || R > 32u || Ta < 1u || Ta > 256u || cfg->chan_shift > 30u || cfg->squelch > 23170u ||
         cfg->gain < 1u || cfg->gain > 65535u) {
@@ -441,25 +408,14 @@ int fmd_narrow_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
     if (gsum > 65535u) { fmd_internal_set_err("sum |gr| + |gi| > 65535"); return FMD_ERR_UNSUPPORTED; }
     fmd_narrow* h = new (std::nothrow) fmd_narrow();
     if (!h) return FMD_ERR_NOMEM;
-    h->T = n_taps; h->D = decim; h->K = n_stations; h->S = dev->n_channels; h->shift = shift;
-    fmd_st_build_plan(taps, n_taps, decim, phase_inc, h->S, h->K, h->plan);
-    const uint64_t bound = (256ull * h->plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
-    if (bound > 16384ull) {
-        delete h;
-        fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
-        return FMD_ERR_UNSUPPORTED;
-    }
+    uint64_t bound;
+    if (const int rc = fmd_ddc_bank_front(h->bank, taps, n_taps, decim, shift, phase_inc, n_stations, dev, &bound)) { delete h; return rc; }
     if (((bound * gsum + ((1ull << cfg->chan_shift) - 1ull)) >> cfg->chan_shift) > 16384ull) {
         delete h;
         fmd_internal_set_err("channel filter gain too large: need ceil(B_y * sum(|gr| + |gi|) / 2^chan_shift) <= 16384");
         return FMD_ERR_UNSUPPORTED;
     }
-    for (uint32_t G = fmd_ddc::kGroups; G >= 1; --G) {
-        uint32_t rb;
-        const size_t l = nb_lds(decim, h->plan.nkc, n_taps, n_stations, G, &rb);
-        if (l <= kLdsBudget || G == 1) { h->groups = G; h->tile = 64u * G; h->raw_bytes = rb; h->lds = l; break; }
-    }
-    h->HB = 2u * ((n_taps - 1u + 7u) & ~7u);
+    h->tl = fmd_ddc_tiling(decim, h->bank.plan.nkc, n_taps, n_stations);
     h->Ta = Ta; h->R = R; h->Q = ((Ta + R - 1u) / R + 3u) & ~3u; h->P = P; h->chan_shift = cfg->chan_shift; h->mode = cfg->mode;
     h->squelch = cfg->squelch; h->gain = cfg->gain; h->width = fmd_narrow_out_width(cfg->mode); h->cplx = cplx;
     while ((1u << h->pshift) < P) ++h->pshift;
@@ -470,22 +426,18 @@ int fmd_narrow_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
     h->na = na < fmd_nb::kTile ? na : fmd_nb::kTile;
     h->pitch = (h->na + h->Q) | 1u;                       // <= pmax
 
-    if (const int rc = fmd_ddc_open(h->core, dev)) { delete h; return rc; }
-    auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_narrow_free(h); return FMD_ERR_HIP; };
-    FmdDeviceGuard guard(h->core.device);
-    if (guard.error() != hipSuccess) return fail("hipSetDevice");
-    if (const char* what = fmd_ddc_upload(h->core, h->plan, (size_t)h->S * (h->HB ? h->HB : 16))) return fail(what);
     std::vector<int2> gp((size_t)R * h->Q, int2{0, 0});
     for (uint32_t t = 0; t < Ta; ++t) gp[(size_t)(t % R) * h->Q + t / R] = int2{chan_taps_re[t], chan_taps_im ? chan_taps_im[t] : 0};
-    if (hipMalloc(&h->d_g, gp.size() * sizeof(int2)) != hipSuccess || hipMemcpy(h->d_g, gp.data(), gp.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess)
-        return fail("hipMalloc(channel taps)");
-    const size_t SK = (size_t)h->S * h->K;
-    for (int i = 0; i < 2; ++i) {
-        if (hipMalloc(&h->d_yh[i], SK * h->HXS * 4) != hipSuccess || hipMemset(h->d_yh[i], 0, SK * h->HXS * 4) != hipSuccess) return fail("hipMalloc(y history)");
-        if (hipMalloc(&h->d_carry[i], SK * fmd_nb::kCarry * 8) != hipSuccess || hipMemset(h->d_carry[i], 0, SK * fmd_nb::kCarry * 8) != hipSuccess)
-            return fail("hipMalloc(block carry)");
+    const size_t SK = (size_t)h->bank.S * h->bank.K;
+    fmd_ddc_add_pair(h->bank.core, h->yh, SK * h->HXS * 4);
+    fmd_ddc_add_pair(h->bank.core, h->carry, SK * fmd_nb::kCarry * 8);
+    fmd_ddc_add_owned(h->bank.core, h->d_g, gp.data(), gp.size() * sizeof(int2));
+    fmd_ddc_add_owned(h->bank.core, h->d_y);
+    const char* what;
+    if (const int rc = fmd_ddc_bank_device(h->bank, dev, &what)) {
+        if (!what) { delete h; return rc; }
+        fmd_internal_set_err(what); fmd_narrow_free(h); return rc;
     }
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
     *out = h;
     return FMD_OK;
 }
@@ -493,81 +445,52 @@ int fmd_narrow_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
 void fmd_narrow_free(fmd_narrow* h)
 {
     if (!h) return;
-    FmdDeviceGuard guard(h->core.device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)h->d_g, (void*)h->d_yh[0], (void*)h->d_yh[1], (void*)h->d_carry[0], (void*)h->d_carry[1], h->d_y})
-        if (p) (void)hipFree(p);
-    fmd_ddc_release(h->core);
+    fmd_ddc_free(h->bank.core);
     delete h;
 }
 
 int fmd_narrow_reset(fmd_narrow* h)
 {
     if (!h) return FMD_ERR_INVALID_ARG;
-    FMD_DDC_ON_DEVICE(h->core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    const size_t SK = (size_t)h->S * h->K;
-    for (int i = 0; i < 2; ++i) {
-        FMD_DDC_TRY(hipMemset(h->d_yh[i], 0, SK * h->HXS * 4));
-        FMD_DDC_TRY(hipMemset(h->d_carry[i], 0, SK * fmd_nb::kCarry * 8));
-    }
-    FMD_DDC_TRY(fmd_ddc_zero_history(h->core));          // (ends with the device synchronised; position and buffer index to 0)
-    return FMD_OK;
+    return fmd_ddc_reset(h->bank.core);
 }
 
 int fmd_narrow_run_device(fmd_narrow* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, void* stream)
 {
-    if (!h || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    return nb_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream));
+    return fmd_ddc_run_device(h ? &h->bank.core : nullptr, d_iq, d_out,
+                              [&] { return nb_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream)); });
 }
 
 int fmd_narrow_check(fmd_narrow* h)
 {
     if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    if (h->core.order.have_last) FMD_DDC_TRY(hipStreamSynchronize(h->core.order.last));
-    FMD_DDC_TRY(hipGetLastError());
-    return FMD_OK;
+    return fmd_ddc_check(h->bank.core);
 }
 
 int fmd_narrow_run_batch(fmd_narrow* h, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap, size_t* out_len)
 {
     if (!h || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    FmdDdcCore& c = h->core;
-    const size_t rows = (size_t)h->S * h->K;
-    const size_t in_bytes = nbytes * (size_t)h->S, out_bytes = out_cap * rows * h->width * sizeof(int16_t);
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
-    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
-    size_t n = 0;
-    int rc = nb_enqueue(h, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream);
-    if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
-    FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
-    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
-    *out_len = n;
-    return FMD_OK;
+    const size_t out_bytes = out_cap * h->bank.S * h->bank.K * h->width * sizeof(int16_t);
+    return fmd_ddc_run_batch(h->bank, iq, nbytes, out, out_bytes, out_cap, out_len, [h](auto... a) { return nb_enqueue(h, a...); });
 }
 
 int fmd_narrow_outputs(const fmd_narrow* h, uint64_t* outputs)
 {
     if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *outputs = nb_audio(h, nb_y(h, h->core.pos));
+    *outputs = nb_audio(h, h->bank.core.pos);
     return FMD_OK;
 }
 
 int fmd_narrow_level(fmd_narrow* h, uint32_t stream, uint32_t station, int* open, uint32_t* rms)
 {
     if (!h || !open || !rms) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    if (stream >= h->S || station >= h->K) { fmd_internal_set_err("stream or station out of range"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
+    if (stream >= h->bank.S || station >= h->bank.K) { fmd_internal_set_err("stream or station out of range"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->bank.core.device);
     FMD_DDC_TRY(hipDeviceSynchronize());
     *open = 0; *rms = 0;
-    if ((nb_audio(h, nb_y(h, h->core.pos)) >> h->pshift) == 0) return FMD_OK;   // no block has completed
+    if ((nb_audio(h, h->bank.core.pos) >> h->pshift) == 0) return FMD_OK;   // no block has completed
     unsigned long long c[fmd_nb::kCarry];
-    FMD_DDC_TRY(hipMemcpy(c, h->d_carry[h->core.cur] + (size_t)fmd_nb::kCarry * ((size_t)stream * h->K + station), sizeof c, hipMemcpyDeviceToHost));
+    FMD_DDC_TRY(hipMemcpy(c, h->carry.in<unsigned long long>(h->bank.core.cur) + (size_t)fmd_nb::kCarry * ((size_t)stream * h->bank.K + station), sizeof c, hipMemcpyDeviceToHost));
     *open = (h->squelch == 0u || c[5]) ? 1 : 0;
     *rms = isqrt_u64(c[2] >> h->pshift);
     return FMD_OK;

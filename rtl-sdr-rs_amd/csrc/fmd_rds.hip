@@ -55,17 +55,6 @@ struct BasebandLaunch {
     uint64_t out_stride;
 };
 
-// I, Q of block j (>= jfirst - 1, every sample of it already in the sums)
-__device__ __forceinline__ void block_iq(const BasebandLaunch& L, uint32_t row, int64_t j, long long& I, long long& Q)
-{
-    const int64_t jf = (int64_t)L.jfirst;
-    if (j < 0) { I = 0; Q = 0; return; }
-    if (j == jf - 1) { I = L.carry_in[4u * row]; Q = L.carry_in[4u * row + 1u]; return; }
-    const long long* p = L.sums + ((uint64_t)(j - jf) * L.SK + row) * 2u;
-    I = p[0]; Q = p[1];
-    if (j == jf) { I += L.carry_in[4u * row + 2u]; Q += L.carry_in[4u * row + 3u]; }
-}
-
 __device__ __forceinline__ uint32_t slot(uint32_t i) { return i + (i >> 5); }
 
 __global__ void __launch_bounds__(kThreads) fmd_rds_baseband_kernel(const BasebandLaunch L)
@@ -116,14 +105,7 @@ __global__ void __launch_bounds__(kThreads) fmd_rds_baseband_kernel(const Baseba
             hout[2u * i] = p.x; hout[2u * i + 1u] = p.y;
         }
     }
-    if (t == 0u && tid == 0u) {                              // the next call's block carry
-        const int64_t jn = (int64_t)(L.mE >> L.pshift);
-        long long I = 0, Q = 0, Ip = 0, Qp = 0;
-        if (jn >= 1) block_iq(L, row, jn - 1, I, Q);
-        if (L.mE & ((1ull << L.pshift) - 1u)) block_iq(L, row, jn, Ip, Qp);
-        long long* const c = L.carry_out + 4u * row;
-        c[0] = I; c[1] = Q; c[2] = Ip; c[3] = Qp;
-    }
+    if (t == 0u && tid == 0u) fmd_sto::write_block_carry(L, row);   // the next call's block carry
 
     // ---- 3. FIRs, shift -----------------------------------------------------------------------------------------------------------
     uint32_t* const out = L.out + (uint64_t)row * L.out_stride + na0;
@@ -143,84 +125,38 @@ __global__ void __launch_bounds__(kThreads) fmd_rds_baseband_kernel(const Baseba
 }  // namespace fmd_rdsk
 
 struct fmd_rds {
-    uint32_t T = 0, D = 0, K = 0, S = 0, shift = 0, HB = 0;
-    fmd_sto::MpxTiling tl;
-    uint32_t Ta = 0, R = 0, P = 0, pshift = 0, rds_shift = 0, pilot_min = 0, inc_p = 0;
+    FmdDdcBank bank;
+    fmd_sto::MpxState mpx;
+    uint32_t Ta = 0, R = 0, rds_shift = 0;
     uint32_t HX = 0, HXS = 0, na = 0;
-    FmdDdcPlan plan;
-    FmdDdcCore core;
-    int16_t* d_g = nullptr;
-    uint32_t* d_ylast[2] = {nullptr, nullptr};            // [S K] packed y, read [core.cur], written [core.cur ^ 1]
-    int32_t* d_qh[2] = {nullptr, nullptr};                // [S K][HXS][2] (qr, qi) history
-    long long* d_carry[2] = {nullptr, nullptr};           // [S K][4] block carry
-    void* d_x = nullptr; size_t d_x_cap = 0;              // the call's MPX samples
-    void* d_sums = nullptr; size_t d_sums_cap = 0;        // the call's block sums
+    void* d_g = nullptr;                                  // int16 RDS taps
+    FmdDdcPair qh;                                        // [S K][HXS][2] (qr, qi) history (int32)
 };
 
 namespace {
 
-uint64_t rd_mpx(const fmd_rds* h, uint64_t S) { return S >= h->T ? (S - h->T) / h->D + 1 : 0; }
-uint64_t rd_out(const fmd_rds* h, uint64_t m) { return m >= h->Ta ? (m - h->Ta) / h->R + 1 : 0; }
-
 int rd_enqueue(fmd_rds* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
 {
-    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    if (nbytes > (1ull << 31) - (1ull << 20)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
-    if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & 3u) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
-    FmdDdcCore& c = h->core;
-    const uint64_t ns = nbytes / 2;
-    const uint64_t mS = rd_mpx(h, c.pos), mE = rd_mpx(h, c.pos + ns), M = mE - mS;
-    const uint64_t nS = rd_out(h, mS), NA = rd_out(h, mE) - nS;
-    if (NA < 1) { fmd_internal_set_err("the call completes no output"); return FMD_ERR_TOO_SHORT; }
-    if (NA > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
-    const uint64_t SK = (uint64_t)h->S * h->K;
-    const uint64_t nt1 = (M + h->tl.tile - 1) / h->tl.tile, nt2 = (NA + h->na - 1) / h->na;
-    if (nt1 > (1u << 30) || h->S > 65535u || nt2 * SK > 0x7FFFFFFFull) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
-    const uint64_t jfirst = mS >> h->pshift, nbc = ((mE - 1) >> h->pshift) - jfirst + 1;
-    const size_t sums_bytes = (size_t)(nbc * SK * 16);
-    FMD_DDC_TRY(fmd_ddc_grow(h->d_x, h->d_x_cap, (size_t)(SK * M * 2)));
-    FMD_DDC_TRY(fmd_ddc_grow(h->d_sums, h->d_sums_cap, sums_bytes));
-    const int cur = c.cur;
-
+    FmdDdcCore& c = h->bank.core;
+    fmd_sto::MpxCall q;
     fmd_sto::MpxLaunch A{};
-    A.iq = static_cast<const uint8_t*>(d_iq);
-    A.nbytes = nbytes;
-    A.hist_in = c.d_hist[cur]; A.hist_out = c.d_hist[cur ^ 1];
-    A.HB = h->HB;
-    A.vb_first = (uint32_t)(2ull * (h->D * mS + h->HB / 2 - c.pos));
-    A.m0 = mS; A.M = (uint32_t)M;
-    A.D = h->D; A.T = h->T; A.K = h->K; A.S = h->S; A.shift = h->shift;
-    A.nrt = h->plan.nrt; A.nkc = h->plan.nkc; A.digits = h->plan.digits;
-    A.tile = h->tl.tile; A.cols = h->tl.cols; A.ntiles = (uint32_t)nt1; A.raw_bytes = h->tl.raw_bytes;
-    A.pshift = h->pshift; A.inc_p = h->inc_p; A.jfirst = jfirst;
-    A.amat = c.d_amat; A.kconst = c.d_kconst; A.dinc = c.d_dinc; A.tab = c.d_tab;
-    A.ylast_in = h->d_ylast[cur]; A.ylast_out = h->d_ylast[cur ^ 1];
-    A.x = static_cast<int16_t*>(h->d_x);
-    A.sums = static_cast<unsigned long long*>(h->d_sums);
+    if (const int rc = fmd_sto::mpx_plan_call(h->bank, h->mpx, h->Ta, h->R, h->na, d_iq, nbytes, d_out, out_cap, q, A)) return rc;
 
     fmd_rdsk::BasebandLaunch B{};
-    B.x = A.x; B.M = (uint32_t)M;
-    B.qh_in = h->d_qh[cur]; B.qh_out = h->d_qh[cur ^ 1];
+    fmd_sto::mpx_fill_blocks(B, h->bank, h->mpx, q);
+    B.qh_in = h->qh.in<int32_t>(c.cur); B.qh_out = h->qh.out<int32_t>(c.cur);
     B.HX = h->HX; B.HXS = h->HXS;
-    B.sums = static_cast<const long long*>(h->d_sums);
-    B.carry_in = h->d_carry[cur]; B.carry_out = h->d_carry[cur ^ 1];
-    B.SK = (uint32_t)SK;
-    B.mS = mS; B.mE = mE; B.jfirst = jfirst; B.nS = nS;
-    B.NA = (uint32_t)NA; B.na = h->na; B.ntiles = (uint32_t)nt2;
+    B.na = h->na;
     B.R = h->R; B.Ta = h->Ta; B.rds_shift = h->rds_shift;
-    B.pshift = h->pshift; B.inc3 = 3u * h->inc_p;
-    B.g = h->d_g; B.tab = c.d_tab;
+    B.inc3 = 3u * h->mpx.inc_p;
+    B.g = static_cast<const int16_t*>(h->d_g);
     B.out = static_cast<uint32_t*>(d_out); B.out_stride = out_cap;
 
-    FMD_DDC_TRY(c.order.before(stream));
-    FMD_DDC_TRY(hipMemsetAsync(h->d_sums, 0, sums_bytes, stream));
-    FMD_DDC_TRY(fmd_sto::launch_mpx(A, h->tl.lds, stream));
-    hipLaunchKernelGGL(fmd_rdsk::fmd_rds_baseband_kernel, dim3((uint32_t)(nt2 * SK)), dim3(fmd_rdsk::kThreads), 0, stream, B);
+    if (const int rc = fmd_sto::mpx_enqueue(h->bank, h->mpx, q, A, stream)) return rc;
+    hipLaunchKernelGGL(fmd_rdsk::fmd_rds_baseband_kernel, dim3((uint32_t)(q.nt2 * q.SK)), dim3(fmd_rdsk::kThreads), 0, stream, B);
     FMD_DDC_TRY(hipGetLastError());
-    (void)c.order.after(stream);
-    c.cur ^= 1;
-    c.pos += ns;
-    if (out_len) *out_len = (size_t)NA;
+    fmd_ddc_commit(c, stream, q.ns);
+    if (out_len) *out_len = (size_t)q.NA;
     return FMD_OK;
 }
 
@@ -242,13 +178,7 @@ int fmd_rds_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t s
         fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG;
     }
     *out = nullptr;
-    if (n_taps == 0 || n_taps > 256 || decim < 2 || decim % 2 != 0 || decim > 64 || shift > 24 || n_stations == 0 || n_stations > 32 ||
-        dev->n_channels > 65535u) {
-        fmd_internal_set_err("need 1 <= n_taps <= 256, an even 2 <= decim <= 64, shift <= 24, 1 <= n_stations <= 32, n_streams <= 65535");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    for (uint32_t t = 0; t < n_taps; ++t)
-        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
+    if (const int rc = fmd_ddc_front_args(taps, n_taps, decim, shift, n_stations, dev)) return rc;
     if ((uint64_t)cfg->capture_rate < 120000ull * decim) { fmd_internal_set_err("need capture_rate >= 120000 * decim"); return FMD_ERR_UNSUPPORTED; }
     const uint32_t P = cfg->block;
     if (P < 1024u || P > 16384u || (P & (P - 1u)) != 0) { fmd_internal_set_err("block must be a power of two in [1024, 16384]"); return FMD_ERR_UNSUPPORTED; }
@@ -265,37 +195,21 @@ int fmd_rds_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t s
     }
     fmd_rds* h = new (std::nothrow) fmd_rds();
     if (!h) return FMD_ERR_NOMEM;
-    h->T = n_taps; h->D = decim; h->K = n_stations; h->S = dev->n_channels; h->shift = shift;
-    fmd_st_build_plan(taps, n_taps, decim, phase_inc, h->S, h->K, h->plan);
-    const uint64_t bound = (256ull * h->plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
-    if (bound > 16384ull) {
-        delete h;
-        fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    h->tl = fmd_sto::mpx_tiling(decim, h->plan.nkc, n_taps, n_stations);
-    h->HB = 2u * ((n_taps - 1u + 7u) & ~7u);
-    h->Ta = n_rds_taps; h->R = cfg->out_decim; h->P = P; h->rds_shift = cfg->rds_shift; h->pilot_min = cfg->pilot_min;
-    while ((1u << h->pshift) < P) ++h->pshift;
-    (void)fmd_stereo_pilot_inc(cfg->capture_rate, decim, &h->inc_p);
+    uint64_t bound;
+    if (const int rc = fmd_ddc_bank_front(h->bank, taps, n_taps, decim, shift, phase_inc, n_stations, dev, &bound)) { delete h; return rc; }
+    fmd_sto::mpx_init(h->bank, h->mpx, P, cfg->pilot_min, cfg->capture_rate);
+    h->Ta = n_rds_taps; h->R = cfg->out_decim; h->rds_shift = cfg->rds_shift;
     h->HX = n_rds_taps - 1u; h->HXS = h->HX ? h->HX : 1u;
     const uint32_t na = (fmd_rdsk::kQCap - h->Ta) / h->R;   // >= 54: R tile + Ta <= kQCap
     h->na = na < fmd_rdsk::kTile ? na : fmd_rdsk::kTile;
+    fmd_ddc_add_pair(h->bank.core, h->qh, (size_t)h->bank.S * h->bank.K * h->HXS * 8);
+    fmd_ddc_add_owned(h->bank.core, h->d_g, rds_taps, 2u * n_rds_taps);
 
-    if (const int rc = fmd_ddc_open(h->core, dev)) { delete h; return rc; }
-    auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_rds_free(h); return FMD_ERR_HIP; };
-    FmdDeviceGuard guard(h->core.device);
-    if (guard.error() != hipSuccess) return fail("hipSetDevice");
-    if (const char* what = fmd_ddc_upload(h->core, h->plan, (size_t)h->S * (h->HB ? h->HB : 16))) return fail(what);
-    const size_t SK = (size_t)h->S * h->K;
-    if (hipMalloc(&h->d_g, 2u * n_rds_taps) != hipSuccess || hipMemcpy(h->d_g, rds_taps, 2u * n_rds_taps, hipMemcpyHostToDevice) != hipSuccess)
-        return fail("hipMalloc(RDS taps)");
-    for (int i = 0; i < 2; ++i) {
-        if (hipMalloc(&h->d_ylast[i], SK * 4) != hipSuccess || hipMemset(h->d_ylast[i], 0, SK * 4) != hipSuccess) return fail("hipMalloc(last y)");
-        if (hipMalloc(&h->d_qh[i], SK * h->HXS * 8) != hipSuccess || hipMemset(h->d_qh[i], 0, SK * h->HXS * 8) != hipSuccess) return fail("hipMalloc(q history)");
-        if (hipMalloc(&h->d_carry[i], SK * 32) != hipSuccess || hipMemset(h->d_carry[i], 0, SK * 32) != hipSuccess) return fail("hipMalloc(block carry)");
+    const char* what;
+    if (const int rc = fmd_ddc_bank_device(h->bank, dev, &what)) {
+        if (!what) { delete h; return rc; }
+        fmd_internal_set_err(what); fmd_rds_free(h); return rc;
     }
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
     *out = h;
     return FMD_OK;
 }
@@ -303,83 +217,46 @@ int fmd_rds_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t s
 void fmd_rds_free(fmd_rds* h)
 {
     if (!h) return;
-    FmdDeviceGuard guard(h->core.device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)h->d_g, (void*)h->d_ylast[0], (void*)h->d_ylast[1], (void*)h->d_qh[0], (void*)h->d_qh[1], (void*)h->d_carry[0],
-                    (void*)h->d_carry[1], h->d_x, h->d_sums})
-        if (p) (void)hipFree(p);
-    fmd_ddc_release(h->core);
+    fmd_ddc_free(h->bank.core);
     delete h;
 }
 
 int fmd_rds_reset(fmd_rds* h)
 {
     if (!h) return FMD_ERR_INVALID_ARG;
-    FMD_DDC_ON_DEVICE(h->core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    const size_t SK = (size_t)h->S * h->K;
-    for (int i = 0; i < 2; ++i) {
-        FMD_DDC_TRY(hipMemset(h->d_ylast[i], 0, SK * 4));
-        FMD_DDC_TRY(hipMemset(h->d_qh[i], 0, SK * h->HXS * 8));
-        FMD_DDC_TRY(hipMemset(h->d_carry[i], 0, SK * 32));
-    }
-    FMD_DDC_TRY(fmd_ddc_zero_history(h->core));          // (ends with the device synchronised; position and buffer index to 0)
-    return FMD_OK;
+    return fmd_ddc_reset(h->bank.core);
 }
 
 int fmd_rds_run_device(fmd_rds* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, void* stream)
 {
-    if (!h || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    return rd_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream));
+    return fmd_ddc_run_device(h ? &h->bank.core : nullptr, d_iq, d_out,
+                              [&] { return rd_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream)); });
 }
 
 int fmd_rds_check(fmd_rds* h)
 {
     if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    if (h->core.order.have_last) FMD_DDC_TRY(hipStreamSynchronize(h->core.order.last));
-    FMD_DDC_TRY(hipGetLastError());
-    return FMD_OK;
+    return fmd_ddc_check(h->bank.core);
 }
 
 int fmd_rds_run_batch(fmd_rds* h, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap, size_t* out_len)
 {
     if (!h || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    FmdDdcCore& c = h->core;
-    const size_t rows = (size_t)h->S * h->K;
-    const size_t in_bytes = nbytes * (size_t)h->S, out_bytes = out_cap * rows * sizeof(uint32_t);   // (ur, ui) pairs
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
-    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
-    size_t n = 0;
-    int rc = rd_enqueue(h, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream);
-    if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
-    FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
-    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
-    *out_len = n;
-    return FMD_OK;
+    const size_t out_bytes = out_cap * h->bank.S * h->bank.K * sizeof(uint32_t);   // (ur, ui) pairs
+    return fmd_ddc_run_batch(h->bank, iq, nbytes, out, out_bytes, out_cap, out_len, [h](auto... a) { return rd_enqueue(h, a...); });
 }
 
 int fmd_rds_outputs(const fmd_rds* h, uint64_t* outputs)
 {
     if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *outputs = rd_out(h, rd_mpx(h, h->core.pos));
+    *outputs = fmd_ddc_fir_outputs(h->Ta, h->R, fmd_ddc_outputs(h->bank.T, h->bank.D, h->bank.core.pos));
     return FMD_OK;
 }
 
 int fmd_rds_pilot(fmd_rds* h, uint32_t stream, uint32_t station, int* present, uint32_t* level)
 {
-    if (!h || !present || !level) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    if (stream >= h->S || station >= h->K) { fmd_internal_set_err("stream or station out of range"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    long long c[4];
-    FMD_DDC_TRY(hipMemcpy(c, h->d_carry[h->core.cur] + 4ull * ((size_t)stream * h->K + station), sizeof c, hipMemcpyDeviceToHost));
-    fmd_sto::pilot_report(c[0], c[1], h->pilot_min, h->P, present, level);
-    return FMD_OK;
+    if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    return fmd_sto::mpx_pilot(h->bank, h->mpx, stream, station, present, level);
 }
 
 int fmd_rds_kernel_name(const fmd_rds* h, uint32_t pass, char* name, size_t cap)

@@ -334,10 +334,7 @@ int fmd_spectrum_power_device(fmd_spectrum* h, const void* d_iq, size_t nbytes, 
 int fmd_spectrum_check(fmd_spectrum* h)
 {
     if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    FMD_DDC_TRY(h->core.order.wait_last());
-    FMD_DDC_TRY(hipGetLastError());
-    return FMD_OK;
+    return fmd_ddc_check(h->core);
 }
 
 int fmd_spectrum_tap_digits(const fmd_spectrum* h)

@@ -185,11 +185,9 @@ __global__ void __launch_bounds__(kThreads) fmd_stations_kernel(const StLaunch L
 }  // namespace fmd_st
 
 struct fmd_stations {
-    uint32_t T = 0, D = 0, K = 0, S = 0, shift = 0, HB = 0;
+    FmdDdcBank bank;
     uint32_t lp_bound = 0;                                // ceil(256 max_gain / 2^shift): the largest |y| component
-    FmdDdcPlan plan;
-    FmdDdcCore core;
-    FmdChanState* d_state[2] = {nullptr, nullptr};        // read [core.cur], written [core.cur ^ 1]
+    FmdDdcPair state;                                     // [S * K] FmdChanState
     FmdRates r{};
     uint32_t i0r = 0;                                     // resampler phase (identical for every station)
     uint32_t lp_cap = 0, raw_bytes = 0;
@@ -207,41 +205,29 @@ namespace {
 using fmd_st::kMaxOutputs;
 using fmd_ddc::kTableBytes;
 
-constexpr size_t kLdsBudget = 40960;                      // 4 tiles per CU
-
 // LDS of a tile of `kt` audio samples: raw bytes the matrix phase may read + NCO table + packed outputs + group table
 bool st_sizes(const fmd_stations* b, uint32_t kt, uint32_t* lp_cap, uint32_t* raw_bytes, size_t* lds)
 {
     FmdRates r = b->r; r.kt = kt;
     const uint32_t cap = fmd_tile_lp_cap(r);
     if (cap > kMaxOutputs) return false;
-    const uint64_t D = b->D;
-    const uint64_t groups = ((cap + 3u) / 4u + 15u) / 16u;           // 16-column groups of a wave
-    const uint64_t reads = 12 + 6 * D + 8 * D * (16 * groups - 1) + 64ull * b->plan.nkc;
-    const uint64_t staged = 12 + 2 * D * (cap - 1) + 2ull * b->T + 15;
-    const uint64_t raw = ((reads > staged ? reads : staged) + 15) & ~15ull;
-    const uint64_t total = raw + kTableBytes + 4ull * b->K * cap + 8ull * (kt + 2);
+    const uint32_t groups = ((cap + 3u) / 4u + 15u) / 16u;           // 16-column groups of a wave
+    const uint32_t raw = fmd_ddc_raw_bytes(b->bank.D, b->bank.plan.nkc, b->bank.T, groups, cap);
+    const uint64_t total = raw + kTableBytes + 4ull * b->bank.K * cap + 8ull * (kt + 2);
     if (total > 64 * 1024) return false;
-    *lp_cap = cap; *raw_bytes = (uint32_t)raw; *lds = (size_t)total;
+    *lp_cap = cap; *raw_bytes = raw; *lds = (size_t)total;
     return true;
-}
-
-void st_counts(const fmd_stations* b, uint64_t ns, uint64_t* m0, uint64_t* m1)
-{
-    const uint64_t S = b->core.pos, T = b->T, M = b->D;
-    *m0 = S >= T ? (S - T) / M + 1 : 0;
-    *m1 = S + ns >= T ? (S + ns - T) / M + 1 : 0;
 }
 
 int st_enqueue(fmd_stations* b, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* n_each, hipStream_t stream)
 {
     if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0 (simple_fm.rs:286 would panic)"); return FMD_ERR_BAD_LENGTH; }
-    if (nbytes == 0 || nbytes > (1ull << 31) - (1ull << 20)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
-    if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & 1u) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
+    if (nbytes == 0) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
+    if (const int rc = fmd_ddc_check_call(nbytes, d_iq, d_out, 2u)) return rc;
+    const FmdDdcBank& bk = b->bank;
+    FmdDdcCore& c = b->bank.core;
     const uint64_t ns = nbytes / 2;
-    uint64_t m0, m1;
-    st_counts(b, ns, &m0, &m1);
-    const uint64_t Mdec = m1 - m0;
+    const uint64_t m0 = fmd_ddc_outputs(bk.T, bk.D, c.pos), Mdec = fmd_ddc_outputs(bk.T, bk.D, c.pos + ns) - m0;
     if (Mdec < 2) { fmd_internal_set_err("the call yields fewer than 2 filter outputs (simple_fm.rs:356 asserts > 1)"); return FMD_ERR_TOO_SHORT; }
     const FmdRates r = b->r;
     if (!fmd_ranges_fit32(r, Mdec * r.D)) { fmd_internal_set_err("call exceeds the 32-bit index range for these rates"); return FMD_ERR_UNSUPPORTED; }
@@ -251,17 +237,9 @@ int st_enqueue(fmd_stations* b, const void* d_iq, size_t nbytes, void* d_out, si
     L.P.K = fmd_num_audio(r, b->i0r, L.P.M);
     L.P.nt = fmd_num_tiles(r, L.P.K);
     if (L.P.K > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
-    if (L.P.nt > (1u << 30) || b->S > 65535u) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
-    L.iq = static_cast<const uint8_t*>(d_iq);
-    L.nbytes = nbytes;
-    FmdDdcCore& c = b->core;
-    L.hist_in = c.d_hist[c.cur]; L.hist_out = c.d_hist[c.cur ^ 1];
-    L.HB = b->HB;
-    L.vb_first = (uint32_t)(2ull * (b->D * m0 + b->HB / 2 - c.pos));   // >= 0: the window of output m0 starts at most n_taps - 1 samples back
+    if (L.P.nt > (1u << 30) || bk.S > 65535u) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
+    fmd_ddc_fill_front(L, bk, d_iq, nbytes, m0);
     L.m0_lo = (uint32_t)m0;
-    L.D = b->D; L.T = b->T; L.K = b->K; L.S = b->S; L.shift = b->shift;
-    L.nrt = b->plan.nrt; L.nkc = b->plan.nkc; L.digits = b->plan.digits;
-    L.amat = c.d_amat; L.kconst = c.d_kconst; L.dinc = c.d_dinc; L.tab = c.d_tab;
     L.r = r; L.tl = fmd_make_tiling(r);
     L.fa = r.fr / r.sr; L.fb = r.fr % r.sr;
     L.sr_shift = 32u;
@@ -269,24 +247,22 @@ int st_enqueue(fmd_stations* b, const void* d_iq, size_t nbytes, void* d_out, si
     L.inv_sr = 1.0f / (float)r.sr; L.inv_R = 1.0f / (float)r.R;
     L.lp_cap = b->lp_cap; L.raw_bytes = b->raw_bytes;
     L.f32_disc = b->lp_bound <= 2048u ? 1u : 0u;
-    L.st_in = b->d_state[c.cur]; L.st_out = b->d_state[c.cur ^ 1];
+    L.st_in = b->state.in<FmdChanState>(c.cur); L.st_out = b->state.out<FmdChanState>(c.cur);
     L.out = static_cast<int16_t*>(d_out); L.out_stride = out_cap;
     L.exc = b->d_exc; L.f64_guard = b->f64_guard; L.seq = b->seq + 1; L.f64_skew = b->f64_skew;
     FMD_DDC_TRY(c.order.before(stream));
-    hipLaunchKernelGGL(fmd_st::fmd_stations_kernel, dim3(L.P.nt, b->S), dim3(fmd_st::kThreads), b->lds, stream, L);
+    hipLaunchKernelGGL(fmd_st::fmd_stations_kernel, dim3(L.P.nt, bk.S), dim3(fmd_st::kThreads), b->lds, stream, L);
     FMD_DDC_TRY(hipGetLastError());
-    (void)c.order.after(stream);
+    fmd_ddc_commit(c, stream, ns);
     b->seq += 1;
-    c.cur ^= 1;
     b->i0r = fmd_next_lpr_index_r(r, b->i0r, L.P.M, L.P.K);
-    c.pos += ns;
     if (n_each) *n_each = L.P.K;
     return FMD_OK;
 }
 
 int st_settle(fmd_stations* b, int16_t* host_out, size_t host_cap)
 {
-    return fmd_internal_resolve_exc(b->d_exc, b->r.R, b->seq, b->seq, b->d_state[b->core.cur], host_out, host_cap, &b->f64_guarded,
+    return fmd_internal_resolve_exc(b->d_exc, b->r.R, b->seq, b->seq, b->state.in<FmdChanState>(b->bank.core.cur), host_out, host_cap, &b->f64_guarded,
                                     &b->f64_patched);
 }
 
@@ -327,28 +303,15 @@ int fmd_stations_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint3
 {
     if (!taps || !phase_inc || !dev || !out || dev->n_channels == 0) { fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG; }
     *out = nullptr;
-    if (n_taps == 0 || n_taps > 256 || decim < 2 || decim % 2 != 0 || decim > 64 || shift > 24 || n_stations == 0 || n_stations > 32 ||
-        dev->n_channels > 65535u) {
-        fmd_internal_set_err("need 1 <= n_taps <= 256, an even 2 <= decim <= 64, shift <= 24, 1 <= n_stations <= 32, n_streams <= 65535");
-        return FMD_ERR_UNSUPPORTED;
-    }
+    if (const int rc = fmd_ddc_front_args(taps, n_taps, decim, shift, n_stations, dev)) return rc;
     if (rate_resample == 0 || rate_out < rate_resample) {
         fmd_internal_set_err("need rate_out >= rate_resample >= 1 (simple_fm.rs:421 divides by rate_out / rate_resample)");
         return FMD_ERR_BAD_RATES;
     }
-    for (uint32_t t = 0; t < n_taps; ++t)
-        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
     fmd_stations* b = new (std::nothrow) fmd_stations();
     if (!b) return FMD_ERR_NOMEM;
-    b->T = n_taps; b->D = decim; b->K = n_stations; b->S = dev->n_channels; b->shift = shift;
-    fmd_st_build_plan(taps, n_taps, decim, phase_inc, b->S, b->K, b->plan);
-    // |y| <= 256 G / 2^shift (|z| <= 128 G per component, the rotation adds two of them) must stay in the discriminator's range
-    const uint64_t bound = (256ull * b->plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
-    if (bound > 16384ull) {
-        delete b;
-        fmd_internal_set_err("filter gain too large for the discriminator: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
-        return FMD_ERR_UNSUPPORTED;
-    }
+    uint64_t bound;                                          // must stay in the discriminator's range
+    if (const int rc = fmd_ddc_bank_front(b->bank, taps, n_taps, decim, shift, phase_inc, n_stations, dev, &bound)) { delete b; return rc; }
     b->lp_bound = (uint32_t)bound;
     FmdRates& r = b->r;
     r.D = decim; r.fast = rate_out; r.slow = rate_resample;
@@ -358,7 +321,7 @@ int fmd_stations_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint3
     if (r.fr > FMD_MAX_RATE_REDUCED || (fa + 2) * 32768ull >= (1u << 24) || (uint32_t)r.R >= (1u << 24)) {
         delete b; fmd_internal_set_err("rate ratio outside the exact-small-divide range"); return FMD_ERR_UNSUPPORTED;
     }
-    const size_t budget = (size_t)fmd_knob_u32("FMD_ST_LDS", (uint32_t)kLdsBudget);
+    const size_t budget = (size_t)fmd_knob_u32("FMD_ST_LDS", (uint32_t)fmd_ddc::kLdsBudget);
     uint32_t best = 0;
     for (uint32_t kt = 1; kt <= 1024; ++kt) {
         if ((uint64_t)r.sr * (kt + 2) >= (1u << 24)) break;
@@ -370,18 +333,18 @@ int fmd_stations_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint3
     if (!best) { delete b; fmd_internal_set_err("one audio sample does not fit a tile: rate_out / rate_resample x decim too large"); return FMD_ERR_UNSUPPORTED; }
     r.kt = best;
     if (!st_sizes(b, r.kt, &b->lp_cap, &b->raw_bytes, &b->lds)) { delete b; return FMD_ERR_UNSUPPORTED; }
-    b->HB = 2u * ((n_taps - 1u + 7u) & ~7u);
     if (const char* g = fmd_knob("FMD_F64_GUARD_LOG2")) b->f64_guard = ldexp(1.0, atoi(g));   // experiment build only
     b->f64_skew = fmd_knob_i32("FMD_F64_SKEW", 0);
 
-    if (const int rc = fmd_ddc_open(b->core, dev)) { delete b; return rc; }
-    auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_stations_free(b); return FMD_ERR_HIP; };
-    FmdDeviceGuard guard(b->core.device);
+    fmd_ddc_add_pair(b->bank.core, b->state, (size_t)n_stations * dev->n_channels * sizeof(FmdChanState));
+    const char* what;
+    if (const int rc = fmd_ddc_bank_device(b->bank, dev, &what)) {
+        if (!what) { delete b; return rc; }
+        fmd_internal_set_err(what); fmd_stations_free(b); return rc;
+    }
+    auto fail = [&](const char* w) { fmd_internal_set_err(w); fmd_stations_free(b); return FMD_ERR_HIP; };
+    FmdDeviceGuard guard(b->bank.core.device);
     if (guard.error() != hipSuccess) return fail("hipSetDevice");
-    if (const char* what = fmd_ddc_upload(b->core, b->plan, (size_t)b->S * (b->HB ? b->HB : 16))) return fail(what);
-    const size_t sb = (size_t)b->S * b->K * sizeof(FmdChanState);
-    for (int i = 0; i < 2; ++i)
-        if (hipMalloc(&b->d_state[i], sb) != hipSuccess || hipMemset(b->d_state[i], 0, sb) != hipSuccess) return fail("hipMalloc(state)");
     if (hipMalloc(&b->d_exc, sizeof(FmdExcBuf)) != hipSuccess || hipMemset(b->d_exc, 0, sizeof(FmdExcBuf)) != hipSuccess) return fail("hipMalloc(reports)");
     if (hipHostMalloc(reinterpret_cast<void**>(&b->h_head), 16, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc(report head)");
     if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
@@ -392,9 +355,8 @@ int fmd_stations_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint3
 void fmd_stations_free(fmd_stations* b)
 {
     if (!b) return;
-    FmdDeviceGuard guard(b->core.device);
-    fmd_ddc_release(b->core);
-    for (int i = 0; i < 2; ++i) if (b->d_state[i]) (void)hipFree(b->d_state[i]);
+    FmdDeviceGuard guard(b->bank.core.device);
+    fmd_ddc_release(b->bank.core);
     if (b->d_exc) (void)hipFree(b->d_exc);
     if (b->h_head) (void)hipHostFree(b->h_head);
     delete b;
@@ -403,12 +365,10 @@ void fmd_stations_free(fmd_stations* b)
 int fmd_stations_reset(fmd_stations* b)
 {
     if (!b) return FMD_ERR_INVALID_ARG;
-    FMD_DDC_ON_DEVICE(b->core.device);
+    FMD_DDC_ON_DEVICE(b->bank.core.device);
     FMD_DDC_TRY(hipDeviceSynchronize());
-    const size_t sb = (size_t)b->S * b->K * sizeof(FmdChanState);
-    for (int i = 0; i < 2; ++i) FMD_DDC_TRY(hipMemset(b->d_state[i], 0, sb));
     FMD_DDC_TRY(hipMemset(b->d_exc, 0, 16));
-    FMD_DDC_TRY(fmd_ddc_zero_history(b->core));          // (ends with the device synchronised)
+    FMD_DDC_TRY(fmd_ddc_zero_history(b->bank.core));     // (the state too; ends with the device synchronised)
     b->i0r = 0;
     return FMD_OK;
 }
@@ -416,16 +376,15 @@ int fmd_stations_reset(fmd_stations* b)
 int fmd_stations_demodulate_device(fmd_stations* b, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap,
                                    size_t* out_len_each, void* stream)
 {
-    if (!b || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(b->core.device);
-    return st_enqueue(b, d_iq, nbytes, d_out, out_cap, out_len_each, static_cast<hipStream_t>(stream));
+    return fmd_ddc_run_device(b ? &b->bank.core : nullptr, d_iq, d_out,
+                              [&] { return st_enqueue(b, d_iq, nbytes, d_out, out_cap, out_len_each, static_cast<hipStream_t>(stream)); });
 }
 
 int fmd_stations_check(fmd_stations* b)
 {
     if (!b) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(b->core.device);
-    const FmdStreamOrder& order = b->core.order;
+    FMD_DDC_ON_DEVICE(b->bank.core.device);
+    const FmdStreamOrder& order = b->bank.core.order;
     if (order.have_last && b->h_head) {                      // one stream synchronisation in the common case (see fmd_demod_check)
         b->h_head[0] = b->h_head[1] = ~0u;
         hipError_t e = hipMemcpyAsync(b->h_head, b->d_exc, 16, hipMemcpyDeviceToHost, order.last);
@@ -440,17 +399,12 @@ int fmd_stations_check(fmd_stations* b)
 int fmd_stations_demodulate_batch(fmd_stations* b, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap, size_t* out_len)
 {
     if (!b || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(b->core.device);
-    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    FmdDdcCore& c = b->core;
-    const size_t rows = (size_t)b->S * b->K;
-    const size_t in_bytes = nbytes * (size_t)b->S, out_bytes = out_cap * rows * sizeof(int16_t);
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
-    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
+    FmdDdcCore& c = b->bank.core;
+    FMD_DDC_ON_DEVICE(c.device);
+    const size_t rows = (size_t)b->bank.S * b->bank.K, out_bytes = out_cap * rows * sizeof(int16_t);
     size_t n = 0;
-    int rc = st_enqueue(b, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream);
-    if (rc) return rc;
+    // (a refused call returns without waiting for the stream)
+    if (const int rc = fmd_ddc_batch_enqueue(b->bank, iq, nbytes, out_bytes, out_cap, &n, [b](auto... a) { return st_enqueue(b, a...); })) return rc;
     if (n) FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
     FMD_DDC_TRY(hipStreamSynchronize(c.stream));
     for (size_t row = 0; row < rows; ++row) out_len[row] = n;
@@ -459,13 +413,13 @@ int fmd_stations_demodulate_batch(fmd_stations* b, const uint8_t* iq, size_t nby
 
 int fmd_stations_get_state(fmd_stations* b, uint32_t stream, uint32_t station, fmd_demod_state* state)
 {
-    if (!b || !state || stream >= b->S || station >= b->K) { fmd_internal_set_err("bad argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(b->core.device);
+    if (!b || !state || stream >= b->bank.S || station >= b->bank.K) { fmd_internal_set_err("bad argument"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(b->bank.core.device);
     FMD_DDC_TRY(hipDeviceSynchronize());
     int rc = st_settle(b, nullptr, 0);
     if (rc) return rc;
     FmdChanState s;
-    FMD_DDC_TRY(hipMemcpy(&s, b->d_state[b->core.cur] + ((size_t)stream * b->K + station), sizeof(s), hipMemcpyDeviceToHost));
+    FMD_DDC_TRY(hipMemcpy(&s, b->state.in<FmdChanState>(b->bank.core.cur) + ((size_t)stream * b->bank.K + station), sizeof(s), hipMemcpyDeviceToHost));
     memset(state, 0, sizeof(*state));
     state->now_lpr = s.now_lpr;
     state->prev_lpr_index = (int32_t)(s.lpr_index_r * b->r.g);

@@ -138,17 +138,6 @@ struct AudioLaunch {
     uint64_t out_stride;
 };
 
-// I, Q of block j (>= jfirst - 1, every sample of it already in the sums)
-__device__ __forceinline__ void block_iq(const AudioLaunch& L, uint32_t row, int64_t j, long long& I, long long& Q)
-{
-    const int64_t jf = (int64_t)L.jfirst;
-    if (j < 0) { I = 0; Q = 0; return; }
-    if (j == jf - 1) { I = L.carry_in[4u * row]; Q = L.carry_in[4u * row + 1u]; return; }
-    const long long* p = L.sums + ((uint64_t)(j - jf) * L.SK + row) * 2u;
-    I = p[0]; Q = p[1];
-    if (j == jf) { I += L.carry_in[4u * row + 2u]; Q += L.carry_in[4u * row + 3u]; }
-}
-
 // a^2 + b^2 >= thr^2 in 128 bits (|a|, |b| <= 2^43, thr <= 2^41)
 __device__ __forceinline__ bool pilot_present(long long I, long long Q, uint64_t thr)
 {
@@ -235,14 +224,7 @@ __global__ void __launch_bounds__(kThreads) fmd_stereo_audio_kernel(const AudioL
             hout[2u * i] = p.x; hout[2u * i + 1u] = p.y;
         }
     }
-    if (t == 0u && tid == 0u) {                              // the next call's block carry
-        const int64_t jn = (int64_t)(L.mE >> L.pshift);
-        long long I = 0, Q = 0, Ip = 0, Qp = 0;
-        if (jn >= 1) block_iq(L, row, jn - 1, I, Q);
-        if (L.mE & ((1ull << L.pshift) - 1u)) block_iq(L, row, jn, Ip, Qp);
-        long long* const c = L.carry_out + 4u * row;
-        c[0] = I; c[1] = Q; c[2] = Ip; c[3] = Qp;
-    }
+    if (t == 0u && tid == 0u) write_block_carry(L, row);     // the next call's block carry
 
     // ---- 3. FIRs, matrix, saturation ------------------------------------------------------------------------------------------
     uint32_t* const out = L.out + (uint64_t)row * L.out_stride + na0;
@@ -266,88 +248,39 @@ __global__ void __launch_bounds__(kThreads) fmd_stereo_audio_kernel(const AudioL
 }  // namespace fmd_sto
 
 struct fmd_stereo {
-    uint32_t T = 0, D = 0, K = 0, S = 0, shift = 0, HB = 0;
-    uint32_t groups = 0, tile = 0, cols = 0, raw_bytes = 0;
-    size_t lds = 0;
-    uint32_t Ta = 0, R = 0, P = 0, pshift = 0, audio_shift = 0, pilot_min = 0, inc_p = 0;
+    FmdDdcBank bank;
+    fmd_sto::MpxState mpx;
+    uint32_t Ta = 0, R = 0, audio_shift = 0;
     uint32_t HX = 0, HXS = 0, na = 0;
-    FmdDdcPlan plan;
-    FmdDdcCore core;
-    int16_t* d_g = nullptr;
-    uint32_t* d_ylast[2] = {nullptr, nullptr};            // [S K] packed y, read [core.cur], written [core.cur ^ 1]
-    int32_t* d_xh[2] = {nullptr, nullptr};                // [S K][HXS][2] (x, s) history
-    long long* d_carry[2] = {nullptr, nullptr};           // [S K][4] block carry
-    void* d_x = nullptr; size_t d_x_cap = 0;              // the call's MPX samples
-    void* d_sums = nullptr; size_t d_sums_cap = 0;        // the call's block sums
+    void* d_g = nullptr;                                  // int16 audio taps
+    FmdDdcPair xh;                                        // [S K][HXS][2] (x, s) history (int32)
 };
 
 namespace {
 
-using fmd_ddc::kTableBytes;
-
-uint64_t st_mpx(const fmd_stereo* h, uint64_t S) { return S >= h->T ? (S - h->T) / h->D + 1 : 0; }
-uint64_t st_audio(const fmd_stereo* h, uint64_t m) { return m >= h->Ta ? (m - h->Ta) / h->R + 1 : 0; }
-
 int st_enqueue(fmd_stereo* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
 {
-    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    if (nbytes > (1ull << 31) - (1ull << 20)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
-    if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & 3u) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
-    FmdDdcCore& c = h->core;
-    const uint64_t ns = nbytes / 2;
-    const uint64_t mS = st_mpx(h, c.pos), mE = st_mpx(h, c.pos + ns), M = mE - mS;
-    const uint64_t nS = st_audio(h, mS), NA = st_audio(h, mE) - nS;
-    if (NA < 1) { fmd_internal_set_err("the call completes no audio sample"); return FMD_ERR_TOO_SHORT; }
-    if (NA > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
-    const uint64_t SK = (uint64_t)h->S * h->K;
-    const uint64_t nt1 = (M + h->tile - 1) / h->tile, nt2 = (NA + h->na - 1) / h->na;
-    if (nt1 > (1u << 30) || h->S > 65535u || nt2 * SK > 0x7FFFFFFFull) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
-    const uint64_t jfirst = mS >> h->pshift, nbc = ((mE - 1) >> h->pshift) - jfirst + 1;
-    const size_t sums_bytes = (size_t)(nbc * SK * 16);
-    FMD_DDC_TRY(fmd_ddc_grow(h->d_x, h->d_x_cap, (size_t)(SK * M * 2)));
-    FMD_DDC_TRY(fmd_ddc_grow(h->d_sums, h->d_sums_cap, sums_bytes));
-    const int cur = c.cur;
-
+    FmdDdcCore& c = h->bank.core;
+    fmd_sto::MpxCall q;
     fmd_sto::MpxLaunch A{};
-    A.iq = static_cast<const uint8_t*>(d_iq);
-    A.nbytes = nbytes;
-    A.hist_in = c.d_hist[cur]; A.hist_out = c.d_hist[cur ^ 1];
-    A.HB = h->HB;
-    A.vb_first = (uint32_t)(2ull * (h->D * mS + h->HB / 2 - c.pos));
-    A.m0 = mS; A.M = (uint32_t)M;
-    A.D = h->D; A.T = h->T; A.K = h->K; A.S = h->S; A.shift = h->shift;
-    A.nrt = h->plan.nrt; A.nkc = h->plan.nkc; A.digits = h->plan.digits;
-    A.tile = h->tile; A.cols = h->cols; A.ntiles = (uint32_t)nt1; A.raw_bytes = h->raw_bytes;
-    A.pshift = h->pshift; A.inc_p = h->inc_p; A.jfirst = jfirst;
-    A.amat = c.d_amat; A.kconst = c.d_kconst; A.dinc = c.d_dinc; A.tab = c.d_tab;
-    A.ylast_in = h->d_ylast[cur]; A.ylast_out = h->d_ylast[cur ^ 1];
-    A.x = static_cast<int16_t*>(h->d_x);
-    A.sums = static_cast<unsigned long long*>(h->d_sums);
+    if (const int rc = fmd_sto::mpx_plan_call(h->bank, h->mpx, h->Ta, h->R, h->na, d_iq, nbytes, d_out, out_cap, q, A)) return rc;
 
     fmd_sto::AudioLaunch B{};
-    B.x = A.x; B.M = (uint32_t)M;
-    B.xh_in = h->d_xh[cur]; B.xh_out = h->d_xh[cur ^ 1];
+    fmd_sto::mpx_fill_blocks(B, h->bank, h->mpx, q);
+    B.xh_in = h->xh.in<int32_t>(c.cur); B.xh_out = h->xh.out<int32_t>(c.cur);
     B.HX = h->HX; B.HXS = h->HXS;
-    B.sums = static_cast<const long long*>(h->d_sums);
-    B.carry_in = h->d_carry[cur]; B.carry_out = h->d_carry[cur ^ 1];
-    B.SK = (uint32_t)SK;
-    B.mS = mS; B.mE = mE; B.jfirst = jfirst; B.nS = nS;
-    B.NA = (uint32_t)NA; B.na = h->na; B.ntiles = (uint32_t)nt2;
+    B.na = h->na;
     B.R = h->R; B.Ta = h->Ta; B.audio_shift = h->audio_shift;
-    B.pshift = h->pshift; B.inc_p = h->inc_p;
-    B.thr = (uint64_t)h->pilot_min * h->P * 8192u;
-    B.g = h->d_g; B.tab = c.d_tab;
+    B.inc_p = h->mpx.inc_p;
+    B.thr = (uint64_t)h->mpx.pilot_min * h->mpx.P * 8192u;
+    B.g = static_cast<const int16_t*>(h->d_g);
     B.out = static_cast<uint32_t*>(d_out); B.out_stride = out_cap;
 
-    FMD_DDC_TRY(c.order.before(stream));
-    FMD_DDC_TRY(hipMemsetAsync(h->d_sums, 0, sums_bytes, stream));
-    FMD_DDC_TRY(fmd_sto::launch_mpx(A, h->lds, stream));
-    hipLaunchKernelGGL(fmd_sto::fmd_stereo_audio_kernel, dim3((uint32_t)(nt2 * SK)), dim3(fmd_sto::kThreads), 0, stream, B);
+    if (const int rc = fmd_sto::mpx_enqueue(h->bank, h->mpx, q, A, stream)) return rc;
+    hipLaunchKernelGGL(fmd_sto::fmd_stereo_audio_kernel, dim3((uint32_t)(q.nt2 * q.SK)), dim3(fmd_sto::kThreads), 0, stream, B);
     FMD_DDC_TRY(hipGetLastError());
-    (void)c.order.after(stream);
-    c.cur ^= 1;
-    c.pos += ns;
-    if (out_len) *out_len = (size_t)NA;
+    fmd_ddc_commit(c, stream, q.ns);
+    if (out_len) *out_len = (size_t)q.NA;
     return FMD_OK;
 }
 
@@ -378,13 +311,7 @@ int fmd_stereo_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
         fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG;
     }
     *out = nullptr;
-    if (n_taps == 0 || n_taps > 256 || decim < 2 || decim % 2 != 0 || decim > 64 || shift > 24 || n_stations == 0 || n_stations > 32 ||
-        dev->n_channels > 65535u) {
-        fmd_internal_set_err("need 1 <= n_taps <= 256, an even 2 <= decim <= 64, shift <= 24, 1 <= n_stations <= 32, n_streams <= 65535");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    for (uint32_t t = 0; t < n_taps; ++t)
-        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
+    if (const int rc = fmd_ddc_front_args(taps, n_taps, decim, shift, n_stations, dev)) return rc;
     if ((uint64_t)cfg->capture_rate < 106000ull * decim) { fmd_internal_set_err("need capture_rate >= 106000 * decim"); return FMD_ERR_UNSUPPORTED; }
     const uint32_t P = cfg->block;
     if (P < 1024u || P > 16384u || (P & (P - 1u)) != 0) { fmd_internal_set_err("block must be a power of two in [1024, 16384]"); return FMD_ERR_UNSUPPORTED; }
@@ -398,38 +325,21 @@ int fmd_stereo_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
     if (gsum > 16383u) { fmd_internal_set_err("sum |audio_taps| > 16383"); return FMD_ERR_UNSUPPORTED; }
     fmd_stereo* h = new (std::nothrow) fmd_stereo();
     if (!h) return FMD_ERR_NOMEM;
-    h->T = n_taps; h->D = decim; h->K = n_stations; h->S = dev->n_channels; h->shift = shift;
-    fmd_st_build_plan(taps, n_taps, decim, phase_inc, h->S, h->K, h->plan);
-    const uint64_t bound = (256ull * h->plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
-    if (bound > 16384ull) {
-        delete h;
-        fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    const fmd_sto::MpxTiling tl = fmd_sto::mpx_tiling(decim, h->plan.nkc, n_taps, n_stations);
-    h->groups = tl.groups; h->cols = tl.cols; h->tile = tl.tile; h->raw_bytes = tl.raw_bytes; h->lds = tl.lds;
-    h->HB = 2u * ((n_taps - 1u + 7u) & ~7u);
-    h->Ta = n_audio_taps; h->R = cfg->audio_decim; h->P = P; h->audio_shift = cfg->audio_shift; h->pilot_min = cfg->pilot_min;
-    while ((1u << h->pshift) < P) ++h->pshift;
-    (void)fmd_stereo_pilot_inc(cfg->capture_rate, decim, &h->inc_p);
+    uint64_t bound;
+    if (const int rc = fmd_ddc_bank_front(h->bank, taps, n_taps, decim, shift, phase_inc, n_stations, dev, &bound)) { delete h; return rc; }
+    fmd_sto::mpx_init(h->bank, h->mpx, P, cfg->pilot_min, cfg->capture_rate);
+    h->Ta = n_audio_taps; h->R = cfg->audio_decim; h->audio_shift = cfg->audio_shift;
     h->HX = n_audio_taps - 1u; h->HXS = h->HX ? h->HX : 1u;
     const uint32_t na = (fmd_sto::kXCap - 2u * h->Ta) / h->R;   // >= 48: R tile + 2 Ta <= kXCap
     h->na = na < fmd_sto::kAudioTile ? na : fmd_sto::kAudioTile;
+    fmd_ddc_add_pair(h->bank.core, h->xh, (size_t)h->bank.S * h->bank.K * h->HXS * 8);
+    fmd_ddc_add_owned(h->bank.core, h->d_g, audio_taps, 2u * n_audio_taps);
 
-    if (const int rc = fmd_ddc_open(h->core, dev)) { delete h; return rc; }
-    auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_stereo_free(h); return FMD_ERR_HIP; };
-    FmdDeviceGuard guard(h->core.device);
-    if (guard.error() != hipSuccess) return fail("hipSetDevice");
-    if (const char* what = fmd_ddc_upload(h->core, h->plan, (size_t)h->S * (h->HB ? h->HB : 16))) return fail(what);
-    const size_t SK = (size_t)h->S * h->K;
-    if (hipMalloc(&h->d_g, 2u * n_audio_taps) != hipSuccess || hipMemcpy(h->d_g, audio_taps, 2u * n_audio_taps, hipMemcpyHostToDevice) != hipSuccess)
-        return fail("hipMalloc(audio taps)");
-    for (int i = 0; i < 2; ++i) {
-        if (hipMalloc(&h->d_ylast[i], SK * 4) != hipSuccess || hipMemset(h->d_ylast[i], 0, SK * 4) != hipSuccess) return fail("hipMalloc(last y)");
-        if (hipMalloc(&h->d_xh[i], SK * h->HXS * 8) != hipSuccess || hipMemset(h->d_xh[i], 0, SK * h->HXS * 8) != hipSuccess) return fail("hipMalloc(MPX history)");
-        if (hipMalloc(&h->d_carry[i], SK * 32) != hipSuccess || hipMemset(h->d_carry[i], 0, SK * 32) != hipSuccess) return fail("hipMalloc(block carry)");
+    const char* what;
+    if (const int rc = fmd_ddc_bank_device(h->bank, dev, &what)) {
+        if (!what) { delete h; return rc; }
+        fmd_internal_set_err(what); fmd_stereo_free(h); return rc;
     }
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
     *out = h;
     return FMD_OK;
 }
@@ -437,83 +347,46 @@ int fmd_stereo_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
 void fmd_stereo_free(fmd_stereo* h)
 {
     if (!h) return;
-    FmdDeviceGuard guard(h->core.device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)h->d_g, (void*)h->d_ylast[0], (void*)h->d_ylast[1], (void*)h->d_xh[0], (void*)h->d_xh[1], (void*)h->d_carry[0],
-                    (void*)h->d_carry[1], h->d_x, h->d_sums})
-        if (p) (void)hipFree(p);
-    fmd_ddc_release(h->core);
+    fmd_ddc_free(h->bank.core);
     delete h;
 }
 
 int fmd_stereo_reset(fmd_stereo* h)
 {
     if (!h) return FMD_ERR_INVALID_ARG;
-    FMD_DDC_ON_DEVICE(h->core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    const size_t SK = (size_t)h->S * h->K;
-    for (int i = 0; i < 2; ++i) {
-        FMD_DDC_TRY(hipMemset(h->d_ylast[i], 0, SK * 4));
-        FMD_DDC_TRY(hipMemset(h->d_xh[i], 0, SK * h->HXS * 8));
-        FMD_DDC_TRY(hipMemset(h->d_carry[i], 0, SK * 32));
-    }
-    FMD_DDC_TRY(fmd_ddc_zero_history(h->core));          // (ends with the device synchronised; position and buffer index to 0)
-    return FMD_OK;
+    return fmd_ddc_reset(h->bank.core);
 }
 
 int fmd_stereo_run_device(fmd_stereo* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, void* stream)
 {
-    if (!h || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    return st_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream));
+    return fmd_ddc_run_device(h ? &h->bank.core : nullptr, d_iq, d_out,
+                              [&] { return st_enqueue(h, d_iq, nbytes, d_out, out_cap, out_len, static_cast<hipStream_t>(stream)); });
 }
 
 int fmd_stereo_check(fmd_stereo* h)
 {
     if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    if (h->core.order.have_last) FMD_DDC_TRY(hipStreamSynchronize(h->core.order.last));
-    FMD_DDC_TRY(hipGetLastError());
-    return FMD_OK;
+    return fmd_ddc_check(h->bank.core);
 }
 
 int fmd_stereo_run_batch(fmd_stereo* h, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap, size_t* out_len)
 {
     if (!h || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    FmdDdcCore& c = h->core;
-    const size_t rows = (size_t)h->S * h->K;
-    const size_t in_bytes = nbytes * (size_t)h->S, out_bytes = out_cap * rows * sizeof(uint32_t);   // (L, R) pairs
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
-    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
-    size_t n = 0;
-    int rc = st_enqueue(h, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream);
-    if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
-    FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
-    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
-    *out_len = n;
-    return FMD_OK;
+    const size_t out_bytes = out_cap * h->bank.S * h->bank.K * sizeof(uint32_t);   // (L, R) pairs
+    return fmd_ddc_run_batch(h->bank, iq, nbytes, out, out_bytes, out_cap, out_len, [h](auto... a) { return st_enqueue(h, a...); });
 }
 
 int fmd_stereo_outputs(const fmd_stereo* h, uint64_t* outputs)
 {
     if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *outputs = st_audio(h, st_mpx(h, h->core.pos));
+    *outputs = fmd_ddc_fir_outputs(h->Ta, h->R, fmd_ddc_outputs(h->bank.T, h->bank.D, h->bank.core.pos));
     return FMD_OK;
 }
 
 int fmd_stereo_pilot(fmd_stereo* h, uint32_t stream, uint32_t station, int* present, uint32_t* level)
 {
-    if (!h || !present || !level) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    if (stream >= h->S || station >= h->K) { fmd_internal_set_err("stream or station out of range"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    long long c[4];
-    FMD_DDC_TRY(hipMemcpy(c, h->d_carry[h->core.cur] + 4ull * ((size_t)stream * h->K + station), sizeof c, hipMemcpyDeviceToHost));
-    fmd_sto::pilot_report(c[0], c[1], h->pilot_min, h->P, present, level);
-    return FMD_OK;
+    if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    return fmd_sto::mpx_pilot(h->bank, h->mpx, stream, station, present, level);
 }
 
 int fmd_stereo_kernel_name(const fmd_stereo* h, uint32_t pass, char* name, size_t cap)

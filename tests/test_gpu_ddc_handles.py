@@ -1,0 +1,102 @@
+"""The five down-converter handles (station bank, channelizer, stereo, narrow-band and RDS bank) alive at once on the MI355X: they
+share one host layer (csrc/fmd_ddc.h), so each is checked bit for bit against its own definition while the others run, are reset,
+refuse a call and are freed around it."""
+import numpy as np
+import pytest
+
+import channelizer_ref as cr
+import narrow_ref as nr
+import rds_ref as rr
+import stations_ref as sr
+import stereo_ref as st
+
+pytestmark = pytest.mark.gpu
+
+TOO_SHORT = -3
+S, K, D, T = 2, 3, 4, 33
+RATE = 480000                                                # >= 120000 * D, the RDS bank's floor (the stereo bank's is lower)
+FAST, SLOW = RATE // D, 30000                                # the station bank's rates: 4 filter outputs per audio sample
+TA, R = 9, 2                                                 # every second filter: 9 taps at stride 2
+CUTS = (8 * 601, 8 * 513, 8 * 389)                           # 2404 + 2052 + 1556 samples: cut 2 crosses the first 1024-sample pilot block
+
+
+def _same(got, exp):
+    """got [S, K, ...] from a bank, exp[s] the definition's [K, ...] of stream s"""
+    return all(np.array_equal(got[s, k], exp[s][k]) for s in range(S) for k in range(K))
+
+
+def test_five_handles_interleaved_reset_refusal_and_free(fmd, oracle):
+    rng = np.random.default_rng(515)
+    h = rng.integers(-900, 901, T).astype(np.int16)          # |W| > 127: the two-digit tap form
+    incs = np.array([[int(x) for x in rng.integers(0, 1 << 32, K)] for _ in range(S)], np.uint32)
+    assert max(np.abs(w).max() for i in incs.ravel() for w in sr.complex_taps(h, int(i))) > 127
+    g = rng.integers(-1500, 1501, TA).astype(np.int16)       # sum |g| <= 13500
+    data = rng.integers(0, 256, (S, sum(CUTS)), dtype=np.uint8)
+    cuts = np.split(data, np.cumsum(CUTS)[:-1], axis=1)
+
+    bank = fmd.StationBank(h, D, incs, FAST, SLOW, n_streams=S, device_id=0)
+    ch = fmd.Channelizer(h, D, incs, n_streams=S, device_id=0)
+    sb = fmd.StereoBank(h, D, incs, RATE, g, R, n_streams=S, block=1024, pilot_min=1, device_id=0)
+    nb = fmd.NarrowBank(h, D, incs, g, R, n_streams=S, block=16, device_id=0)
+    rb = fmd.RdsBank(h, D, incs, RATE, g, R, n_streams=S, block=1024, pilot_min=1, device_id=0)
+
+    def refs(kind):
+        if kind == "bank":
+            return [sr.StationsRef(oracle, h, D, incs[s], FAST, SLOW, bank.shift, z=sr.z_corr) for s in range(S)]
+        if kind == "ch":
+            return [cr.ChannelizerRef(h, D, incs[s], ch.shift, z=sr.z_corr) for s in range(S)]
+        if kind == "sb":
+            return [st.StereoRef(h, D, incs[s], sb.shift, RATE, g, R, 1024, 1, sb.audio_shift, z=sr.z_corr) for s in range(S)]
+        if kind == "nb":
+            return [nr.NarrowRef(h, D, incs[s], nb.shift, nb.gr, nb.gi, nb.mode, R, nb.chan_shift, 16, nb.squelch, nb.gain, z=sr.z_corr)
+                    for s in range(S)]
+        return [rr.RdsRef(h, D, incs[s], rb.shift, RATE, g, R, rb.rds_shift, 1024, 1, z=sr.z_corr) for s in range(S)]
+
+    ref = {kind: refs(kind) for kind in ("bank", "ch", "sb", "nb", "rb")}
+    run = {"bank": bank.demodulate_batch, "ch": ch.run_batch, "sb": sb.run_batch, "nb": nb.run_batch, "rb": rb.run_batch}
+
+    def step(kind, cut):
+        """one call of one handle, against its definition; every call completes at least one output"""
+        exp = [ref[kind][s].feed(cut[s]) for s in range(S)]
+        got = run[kind](cut)
+        assert got.shape[2] == len(exp[0][0]) >= 1 and _same(got, exp), kind
+        return got
+
+    # cut 1, the handles interleaved call by call
+    first = {kind: step(kind, cuts[0]) for kind in ("bank", "ch", "sb", "nb", "rb")}
+
+    # two of them back to the start: the other three continue unbroken, the two reproduce their first outputs
+    sb.reset()
+    nb.reset()
+    assert sb.outputs() == 0 and nb.outputs() == 0
+    ref["sb"], ref["nb"] = refs("sb"), refs("nb")
+    step("bank", cuts[1])
+    assert np.array_equal(step("sb", cuts[0]), first["sb"])
+    step("ch", cuts[1])
+    assert np.array_equal(step("nb", cuts[0]), first["nb"])
+    # a refused call on one handle between good calls on the others: nothing changes, there or elsewhere.  8 bytes are 4 samples,
+    # one front-end output; after cut 1 (593 of them) that completes no output of the stride-2 second filter
+    before = rb.outputs()
+    assert ref["rb"][0].completes(8) < 1
+    with pytest.raises(fmd.FmdError) as e:
+        rb.run_batch(data[:, :8])
+    assert e.value.status == TOO_SHORT and rb.outputs() == before
+    step("sb", cuts[1])
+    step("rb", cuts[1])
+    step("nb", cuts[1])
+
+    step("bank", cuts[2])
+    step("ch", cuts[2])
+    step("sb", cuts[2])
+    step("rb", cuts[2])
+    step("nb", cuts[2])
+    assert ch.outputs() == ref["ch"][0].m_next and rb.outputs() == ref["rb"][0].n_next
+    assert sb.outputs() == ref["sb"][0].n_next and nb.outputs() == ref["nb"][0].n_next
+
+    # freed in another order than created; a handle created afterwards starts clean
+    for hd in (sb, bank, rb, ch, nb):
+        hd.close()
+    ch2 = fmd.Channelizer(h, D, incs, n_streams=S, device_id=0)
+    ref2 = [cr.ChannelizerRef(h, D, incs[s], ch2.shift, z=sr.z_corr) for s in range(S)]
+    assert _same(ch2.run_batch(cuts[0]), [ref2[s].feed(cuts[0][s]) for s in range(S)])
+    ch2.close()
