@@ -66,10 +66,10 @@ struct fmd_rds_decoder {
     // blocks
     bool synced = false;
     int pos = 0, bits_in_block = 0, bad_run = 0;
-    bool have_cand = false;
-    uint64_t cand_bit = 0;
-    int cand_pos = 0;
-    uint16_t cand_data = 0;
+    // a valid block seen while searching, one per bit phase (nbits mod 26): a chance match between two true blocks must not
+    // displace the first of them, or the lock would not be taken on two consecutive valid blocks
+    struct Cand { uint64_t bit = 0; int pos = 0; uint16_t data = 0; bool have = false; };
+    Cand cand[26];
     fmd_rds_group cur{};
     // groups
     std::deque<fmd_rds_group> queue;
@@ -87,7 +87,7 @@ struct fmd_rds_decoder {
         prev_sym = 0; reg = 0; nbits = 0;
         memset(strobes, 0, sizeof strobes);
         synced = false; pos = bits_in_block = bad_run = 0;
-        have_cand = false;
+        drop_cands();
         cur = fmd_rds_group{};
         queue.clear();
         info = fmd_rds_info{};
@@ -95,6 +95,8 @@ struct fmd_rds_decoder {
         memset(rtbuf, 0, sizeof rtbuf);
         rt_flag = -1;
     }
+
+    void drop_cands() { for (Cand& c : cand) c = Cand{}; }
 
     uint64_t bit_sample(uint64_t bits_back) const         // sample index of the bit `bits_back` before the newest (0 if before the start)
     {
@@ -153,8 +155,11 @@ struct fmd_rds_decoder {
         if (!synced) {
             const int p = position_of(remainder26(reg));
             if (p < 0) return;
-            if (have_cand && nbits - cand_bit == 26 && p == (cand_pos + 1) % 4) {
-                synced = true; bad_run = 0; bits_in_block = 0; have_cand = false;
+            Cand& c = cand[nbits % 26u];
+            if (c.have && nbits - c.bit == 26 && p == (c.pos + 1) % 4) {
+                const int cand_pos = c.pos;
+                const uint16_t cand_data = c.data;
+                synced = true; bad_run = 0; bits_in_block = 0; drop_cands();
                 cur = fmd_rds_group{};
                 cur.first_sample = bit_sample(26u * (unsigned)(p + 1) - 1u);
                 if (p == 0) {                               // D then A: the group that starts here
@@ -166,7 +171,7 @@ struct fmd_rds_decoder {
                 pos = (p + 1) % 4;
                 return;
             }
-            have_cand = true; cand_bit = nbits; cand_pos = p; cand_data = data;
+            c = Cand{nbits, p, data, true};
             return;
         }
         if (++bits_in_block < 26) return;
@@ -178,7 +183,7 @@ struct fmd_rds_decoder {
         else { ++info.blocks_bad; ++bad_run; }
         block_done(pos, ok, data);
         pos = (pos + 1) % 4;
-        if (bad_run >= kBadRun) { synced = false; have_cand = false; cur = fmd_rds_group{}; }
+        if (bad_run >= kBadRun) { synced = false; drop_cands(); cur = fmd_rds_group{}; }
     }
 
     void push_sample(double xr, double xi)

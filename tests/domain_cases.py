@@ -1,6 +1,6 @@
-"""Case generators of the *_domain GPU tests of the stereo bank, the narrow-band bank and the channelizer: shapes, tap sets and
-call-size sequences, in plain numpy, with the host-side plan arithmetic (tile sizes) copied from DESIGN.md so that a case can say
-which kernel path it reaches.  tests/test_domain_cases.py runs these against the references alone and asserts what each case
+"""Case generators of the *_domain GPU tests of the stereo bank, the RDS bank, the narrow-band bank and the channelizer: shapes,
+tap sets and call-size sequences, in plain numpy, with the host-side plan arithmetic (tile sizes) copied from DESIGN.md so that a
+case can say which kernel path it reaches.  tests/test_domain_cases.py runs these against the references alone and asserts what each case
 claims; the GPU files feed the same cases to the handles."""
 import os
 from types import SimpleNamespace as NS
@@ -297,6 +297,149 @@ def stereo_extreme(limit, sign):
     data = np.concatenate([iq, rails])[None, :]
     return NS(kind="stereo", R=R, K=2, D=D, T=T, Ta=Ta, S=1, h=h, incs=ii, P=P, rate=fs, pilot_min=1 if limit == 16384 else default_pilot_min(fs, D),
               g=g, audio_shift=0, shift=shift_for(h, ii, limit), data=data, sizes=[2 * n // 2, 2 * n // 2, 8 * 2000], limit=limit)
+
+
+# ---- RDS bank ------------------------------------------------------------------------------------------------------------------
+
+def rds_na(Ta, R):
+    """Outputs per tile of the baseband pass: R na + Ta <= 1984 staged pairs."""
+    return min(256, (1984 - Ta) // R)
+
+
+def rds_shift_for(g):
+    """The smallest rds_shift with ceil(32768 sum |g| / 2^s) <= 32767."""
+    total = 32768 * int(np.abs(np.asarray(g, dtype=np.int64)).sum())
+    s = 0
+    while -(-total >> s) > 32767:
+        s += 1
+    return s
+
+
+def rds_handle(c, fmd):
+    return fmd.RdsBank(c.h, c.D, c.incs, c.rate, c.g, c.R, n_streams=c.S, block=c.P, pilot_min=c.pilot_min, rds_shift=c.rds_shift,
+                       shift=c.shift, device_id=0)
+
+
+def rds_refs(c, rr, check=None, cls=None, stations=None):
+    """The definition of the streams in `check` (all by default); `cls`: a variant of rr.RdsRef, `stations`: only these k."""
+    pick = (lambda row: row) if stations is None else (lambda row: [row[k] for k in stations])
+    return {s: (cls or rr.RdsRef)(c.h, c.D, pick(c.incs[s]), c.shift, c.rate, c.g, c.R, c.rds_shift, c.P, c.pilot_min, z=sr.z_corr)
+            for s in (range(c.S) if check is None else check)}
+
+
+def rds_sweep():
+    """Every R in 1 ... 32 (case i has R = i % 32 + 1); Ta from the list below or chosen against R; D, K edges of both digit forms,
+    P, pilot_min spread over the sweep; rds_shift alternately the smallest allowed and a value up to 24 (the alternation slips by
+    one every four cases, so the cases with many tiles get both); every fourth case a call of more than three tiles; every case a
+    call of more than P MPX samples."""
+    n_cases, rng = fuzz(32, 4101)
+    for i in range(n_cases):
+        R = i % 32 + 1
+        K, digits = K_EDGES[i % 14] if i % 2 == 0 or i < 28 else (int(rng.integers(1, 4)), 2)
+        D = DECIMS[(i + i // 6) % 6]
+        if i % 16 == 7:
+            D, K, digits = 64, 8, 2                                # G = 3
+        if i % 16 == 15:
+            D, K, digits = 64, (24, 28, 32)[(i // 16) % 3], 2      # G = 2
+        T = TAPS[(3 * i + i // 8) % 8]
+        Ta = (1, 2, 63, 64, 255, 256, R, R + 1, max(1, R - 1), min(256, 4 * R + 1))[(i + i // 10) % 10]
+        if i % 8 == 3 or R == 32:
+            Ta = 256
+        S = 1 if K > 9 else 2
+        h, ii = front(rng, T, S, K, digits)
+        P = ST_BLOCKS[i % 3] if ST_BLOCKS[i % 3] * D <= 65536 else 1024
+        rate = 120000 * D + int(rng.integers(0, 50000)) * D
+        pm = (0, 1, None, 16384, 1, None)[i % 6]
+        pm = default_pilot_min(rate, D) if pm is None else pm
+        g = audio_taps(rng, Ta, int(rng.integers(max(Ta, 8000), 16384)))
+        smin = rds_shift_for(g)
+        c = NS(kind="rds", i=i, R=R, K=K, digits=digits, D=D, T=T, Ta=Ta, S=S, h=h, incs=ii, P=P, rate=rate, pilot_min=pm, g=g,
+               rds_shift=smin if (i + i // 4) % 2 == 0 else int(rng.integers(smin + 1, 25)), rds_shift_min=smin,
+               shift=shift_for(h, ii, int(rng.choice([256, 2048, 16384]))), G=groups(D, T, K), na=rds_na(Ta, R))
+        first = 8 * -(-(T + D * (Ta + 2 * R)) // 4)                 # completes an output
+        c.long_tiles = i % 4 == 3
+        outs = 3 * c.na + 5 if c.long_tiles else int(rng.integers(8, 200))
+        if not c.long_tiles and D * R * outs > 200000:             # keeps the reference quick; the long calls stay whole
+            outs = max(4, 200000 // (D * R))
+        c.sizes = [8 * int(rng.integers(1, 30)), first, 8 * int(rng.integers(1, 3 + D * R // 4)), 8 * -(-D * R * outs // 4),
+                   8 * -(-D * (P + 300) // 4), 8 * int(rng.integers(1, 3 + D * R // 2))]
+        c.seed = int(rng.integers(0, 1 << 31))
+        yield c
+
+
+def rds_full_tiles(R):
+    """Ta = 256 and R in (8, 16, 32): R na + Ta == 1984 exactly.  Two calls of 2 na outputs each, both ending one MPX sample before
+    the next output would complete: the last tile then stages R na + Ta - 1 pairs, the most any tile can (its highest LDS slot is
+    1982 + 61 = 2043), and the second call reads back all Ta - 1 pairs of the history the first one wrote.  A short third call
+    reads the second one's."""
+    rng = np.random.default_rng(4202 + R)
+    D, T, Ta, K, P = 4, 26, 256, 5, 1024
+    na = rds_na(Ta, R)
+    h, ii = front(rng, T, 2, K, 2)
+    g = audio_taps(rng, Ta)
+    m1 = Ta + 2 * na * R - 1
+    ends = [m1, m1 + 2 * na * R, m1 + 2 * na * R + 3 * R]
+    return NS(kind="rds", R=R, K=K, D=D, T=T, Ta=Ta, S=2, h=h, incs=ii, P=P, rate=125000 * D, pilot_min=1, g=g,
+              rds_shift=rds_shift_for(g), shift=shift_for(h, ii, 2048), G=groups(D, T, K), na=na, ends=ends,
+              sizes=sizes_for_outputs(T, D, ends), seed=int(rng.integers(0, 1 << 31)))
+
+
+def rds_short(R):
+    """Ta = 256: calls that complete outputs with 1, 2, Ta - 2, Ta - 1 and Ta MPX samples (the (qr, qi) history is rebuilt from
+    old history plus new samples), then a long call."""
+    rng = np.random.default_rng(4303 + R)
+    D, T, Ta, K, P = 4, 26, 256, 5, 1024
+    h, ii = front(rng, T, 2, K, 2)
+    g = audio_taps(rng, Ta)
+    ends = short_ends(Ta, R, (1, 2, Ta - 2, Ta - 1, Ta, 1, Ta - 1, 2))
+    return NS(kind="rds", R=R, K=K, D=D, T=T, Ta=Ta, S=2, h=h, incs=ii, P=P, rate=125000 * D, pilot_min=1, g=g,
+              rds_shift=rds_shift_for(g), shift=shift_for(h, ii, 2048), G=groups(D, T, K), na=rds_na(Ta, R), ends=ends,
+              sizes=sizes_for_outputs(T, D, ends), seed=int(rng.integers(0, 1 << 31)))
+
+
+def rds_edges(P):
+    """The call ends of stereo_edges (MPX ends on j P - 1, j P, j P + 1; a block open over four calls; four whole blocks in one
+    call; a call that starts on an edge) with Ta = 9, R = 1.  Two synthetic stations: the one at +110 kHz carries a pilot up to the
+    middle of block 5 and none after, the one at -110 kHz the other way round; random bytes from block 8 on.  Station 2 tunes
+    to nothing.  Stream 1 has the same bytes half a block later and the stations in another order."""
+    import stereo_ref as st
+    rng = np.random.default_rng(4404 + P)
+    D, T, Ta, R, K = 4, 27, 9, 1, 3
+    fs = 120000 * D
+    e = stereo_edges(P, D=D, T=T, Ta=Ta, R=R, K=K)
+    h = st.lowpass(T, 90000 / fs)
+    a, b, x = sr.phase_inc(110000, fs), sr.phase_inc(-110000, fs), sr.phase_inc(5000, fs)
+    ii = np.array([[a, b, x], [x, a, b]], np.uint32)
+    n = sum(e.sizes) // 2
+    cut, tail = D * (5 * P + P // 2), D * 8 * P
+    tone = lambda t: 0.4 * np.sin(2 * np.pi * 1000 * t)
+    other = lambda t: 0.3 * np.sin(2 * np.pi * 3100 * t)
+    d0 = np.concatenate([st.synth_iq(cut, fs, [(110000, tone, other, 0.7, True), (-110000, other, tone, 2.1, False)], seed=P),
+                         st.synth_iq(tail - cut, fs, [(110000, tone, other, 0.7, False), (-110000, other, tone, 2.1, True)], seed=P + 1),
+                         rng.integers(0, 256, 2 * (n - tail), dtype=np.uint8)])
+    g = audio_taps(rng, Ta, 16000)
+    return NS(kind="rds", R=R, K=K, D=D, T=T, Ta=Ta, S=2, h=h, incs=ii, P=P, rate=fs, pilot_min=default_pilot_min(fs, D), g=g,
+              rds_shift=rds_shift_for(g), shift=shift_for(h, ii, 256), G=e.G, tile=e.tile, na=rds_na(Ta, R), ends=e.ends, sizes=e.sizes,
+              data=np.stack([d0, np.roll(d0, 2 * D * (P // 2))]))
+
+
+RDS_EXTREMES = (("plus", 14), ("minus", 14), ("256", 14), ("256", 24))
+
+
+def rds_extreme(g, rds_shift):
+    """The front end and the bytes of narrow_extreme(FM): D = 2, T = 16, every tap 2047, inc 0, the front-end shift at limit
+    16384, bytes at the rails.  `g`: "plus" = [16383], "minus" = [-16383], "256" = 256 taps of one sign with sum 16383.  The
+    one-tap sets reach v = +-16384 * 16383, the largest |v| bytes can produce, and u = v >> 14 spans exactly -16383 ... 16383; at
+    rds_shift 24 a small negative v must give u = -1, where a shift that truncates toward zero gives 0.
+
+    |x| never exceeds 16384: the discriminator's range is +-16384 (a half turn), so |q| <= 16384 as well and the bound
+    |q| <= 32768 of include/fmd.h (any int16 x) is never met through bytes."""
+    e = narrow_extreme(1)
+    rng = np.random.default_rng(4505)                              # the same 256 taps at both shifts
+    taps = {"plus": np.array([16383], np.int16), "minus": np.array([-16383], np.int16)}
+    gg = taps[g] if g in taps else audio_taps(rng, 256, 16383, sign=+1)
+    return NS(kind="rds", R=1, K=1, D=e.D, T=e.T, Ta=gg.size, S=1, h=e.h, incs=e.incs, P=1024, rate=304000, pilot_min=1, g=gg,
+              rds_shift=rds_shift, shift=e.shift, na=rds_na(gg.size, 1), data=e.data, sizes=e.sizes)
 
 
 # ---- narrow-band bank ----------------------------------------------------------------------------------------------------------

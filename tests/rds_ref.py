@@ -1,7 +1,7 @@
 """Test-side definition of the RDS bank (include/fmd.h, "RDS bank"), in numpy int64: the channelizer's y (tests/channelizer_ref.py),
 the stereo bank's discriminator and pilot sums (tests/stereo_ref.py), the free-running 57 kHz carrier, the FIR and the shift.
 Independent of the library.  Also an RDS encoder and a synthesizer of FM stations that carry RDS, as u8 IQ bytes, for the decoder
-tests: groups 0A and 2A -> 26-bit blocks (checkword by polynomial division, offset word XORed in) -> differential coding ->
+tests: groups 0A / 0B, 2A / 2B or raw -> 26-bit blocks (checkword by polynomial division, offset word XORed in) -> differential coding ->
 biphase impulse pairs -> shaping -> 57 kHz subcarrier in the multiplex -> FM -> u8 IQ."""
 import numpy as np
 
@@ -34,8 +34,8 @@ class RdsRef:
         self.x = [np.zeros(0, np.int64) for _ in range(self.K)]
         self.qr = [np.zeros(0, np.int64) for _ in range(self.K)]
         self.qi = [np.zeros(0, np.int64) for _ in range(self.K)]
-        self.q_max = 0                                       # max |q| and |v| since reset
-        self.v_max = 0
+        self.x_max = self.q_max = self.v_max = 0             # max |x|, |q| and |v| since reset
+        self.cuts = [0]                                      # MPX samples after every accepted call
         self.n_next = 0
 
     def out_after(self, m):
@@ -44,6 +44,28 @@ class RdsRef:
     def completes(self, nbytes):
         """Outputs a call of nbytes completes (0: refused)."""
         return self.out_after(self.ch.outputs_after(nbytes // 2)) - self.n_next
+
+    # The four steps below are methods of their own so that tests/test_domain_cases.py can derive deliberately wrong variants and
+    # show that the domain cases tell them from the definition.
+
+    def carrier_index(self, m0):
+        """Index of the call's first MPX sample as the carrier counts it: m since creation or reset."""
+        return m0
+
+    def shifted(self, v):
+        return v >> self.rds_shift                           # arithmetic: floor
+
+    def window(self, q, lo, hi, m0):
+        """q[lo:hi], the samples the call's outputs read; those below m0 came with earlier calls."""
+        return q[lo:hi]
+
+    def block_span(self, j):
+        """The samples summed for block j."""
+        return j * self.P, (j + 1) * self.P
+
+    def blocks_done(self, m):
+        """Blocks complete after m MPX samples."""
+        return m // self.P
 
     def feed(self, buf):
         b = np.asarray(buf, dtype=np.uint8)
@@ -58,30 +80,33 @@ class RdsRef:
             self.yprev[k] = y[k, -1]
             m0 = self.x[k].size
             self.x[k] = np.concatenate([self.x[k], x])
-            phi = (np.arange(m0, m0 + M, dtype=np.uint64) * np.uint64((3 * self.inc_p) & 0xFFFFFFFF)) & 0xFFFFFFFF
+            self.x_max = max(self.x_max, int(np.abs(x).max()))
+            phi = (np.arange(self.carrier_index(m0), self.carrier_index(m0) + M, dtype=np.uint64) * np.uint64((3 * self.inc_p) & 0xFFFFFFFF)) & 0xFFFFFFFF
             qr, qi = (x * sr.cosq(phi)) >> 14, (-x * sr.sinq(phi)) >> 14
             self.q_max = max(self.q_max, int(np.abs(qr).max()), int(np.abs(qi).max()))
             self.qr[k] = np.concatenate([self.qr[k], qr])
             self.qi[k] = np.concatenate([self.qi[k], qi])
             n1 = self.out_after(self.x[k].size)
             lo, hi = self.R * self.n_next, self.R * (n1 - 1) + self.Ta
-            vr = np.correlate(self.qr[k][lo:hi], self.g, "valid")[::self.R]
-            vi = np.correlate(self.qi[k][lo:hi], self.g, "valid")[::self.R]
+            vr = np.correlate(self.window(self.qr[k], lo, hi, m0), self.g, "valid")[::self.R]
+            vi = np.correlate(self.window(self.qi[k], lo, hi, m0), self.g, "valid")[::self.R]
             self.v_max = max(self.v_max, int(np.abs(vr).max()), int(np.abs(vi).max()))
-            u = np.stack([vr >> self.rds_shift, vi >> self.rds_shift], axis=1)
+            u = np.stack([self.shifted(vr), self.shifted(vi)], axis=1)
             assert np.abs(u).max() <= 32767                  # the int16 store is exact
             out.append(u)
         self.n_next = self.out_after(self.x[0].size)
+        self.cuts.append(self.x[0].size)
         return np.stack(out)
 
     def pilot(self, k):
         """(present, level) of the last completed block, as StereoRef.pilot."""
-        jn = self.x[k].size // self.P
+        jn = self.blocks_done(self.x[k].size)
         if jn == 0:
             return False, 0
-        m = np.arange((jn - 1) * self.P, jn * self.P, dtype=np.uint64)
+        a, b = self.block_span(jn - 1)
+        m = np.arange(a, b, dtype=np.uint64)
         th = (m * np.uint64(self.inc_p)) & 0xFFFFFFFF
-        x = self.x[k][(jn - 1) * self.P:jn * self.P]
+        x = self.x[k][a:b]
         I, Q = int((x * sr.cosq(th)).sum()), int((x * sr.sinq(th)).sum())
         present = self.pilot_min > 0 and I * I + Q * Q >= (self.pilot_min * self.P * 8192) ** 2
         return present, st.isqrt(I * I + Q * Q) // (self.P * 8192)
@@ -119,11 +144,35 @@ def groups_0a_2a(pi, ps, rt, flag=0):
     return out
 
 
+def groups_0b_2b(pi, ps, rt, flag=0):
+    """The version-B cycle: four 0B groups (PS) and one 2B group per TWO characters of `rt` (at most 32, padded with spaces to an
+    even count), interleaved as in groups_0a_2a.  Bit 11 of block B is set and block C repeats the PI, sent with offset C'."""
+    assert len(ps) == 8 and len(rt) <= 32
+    rt = rt + " " * (len(rt) % 2)
+    b0 = [(pi, 0 << 12 | 1 << 11 | 1 << 3 | a, pi, ord(ps[2 * a]) << 8 | ord(ps[2 * a + 1])) for a in range(4)]
+    b2 = [(pi, 2 << 12 | 1 << 11 | flag << 4 | a, pi, ord(rt[2 * a]) << 8 | ord(rt[2 * a + 1])) for a in range(len(rt) // 2)]
+    out = []
+    for i in range(max(len(b0), len(b2))):
+        out += b0[i:i + 1] + b2[i:i + 1]
+    return out
+
+
+def raw_group(a, b, c, d):
+    """Any group from its four 16-bit words; group_bits sends block C with offset C' when b says version B (bit 11)."""
+    assert all(0 <= v < 1 << 16 for v in (a, b, c, d))
+    return a, b, c, d
+
+
+def group_offsets(group):
+    """The offset words of the group's four blocks: C' in place of C in a version-B group."""
+    return "A", "B", "C'" if group[1] >> 11 & 1 else "C", "D"
+
+
 def group_bits(groups):
     """Groups (A, B, C, D) -> the transmitted bit stream (before differential coding), MSB of block A first."""
     bits = []
     for g in groups:
-        for info, off in zip(g, ("A", "B", "C", "D")):
+        for info, off in zip(g, group_offsets(g)):
             blk = encode_block(info, off)
             bits += [blk >> i & 1 for i in range(25, -1, -1)]
     return np.array(bits, dtype=np.int64)
@@ -150,6 +199,20 @@ def biphase_waveform(ebits, t, bit_rate=BIT_RATE):
             d = u - (k + half)
             r += np.where(np.abs(d) < 0.5, sign * a[k % n] * 0.5 * (1 + np.cos(2 * np.pi * d)), 0.0)
     return r
+
+
+def baseband_direct(bits, fs, f_res=0.0, phase=0.0, amp=97.0, noise=1.0, seed=0, start_bit=0.0, bit_rate=BIT_RATE):
+    """The RDS bank's output without the bank: int16 [n, 2] at fs of amp * biphase_waveform(differential(bits), t) * exp(j (2 pi
+    f_res t + phase)) plus white noise of `noise` per component (the defaults are about the level of the full chain's baseband of the decoder
+    tests' station), from `start_bit` bit periods into the stream to its end.  Takes the
+    BIT stream, so a test can damage bits before the differential coding: one flipped bit is exactly one wrong decoded bit.  Bit k
+    is centred at sample ((k + 1/2 - start_bit) / bit_rate) fs."""
+    n = int((len(bits) - start_bit) * fs / bit_rate)
+    t = np.arange(n) / fs
+    r = amp * biphase_waveform(differential(bits), t + start_bit / bit_rate, bit_rate)
+    rng = np.random.default_rng(seed)
+    z = r * np.exp(1j * (2 * np.pi * f_res * t + phase)) + rng.normal(0, noise, n) + 1j * rng.normal(0, noise, n)
+    return np.ascontiguousarray(np.stack([np.round(z.real), np.round(z.imag)], axis=1).astype(np.int16))
 
 
 def synth_rds_iq(n, fs, stations, amp=50.0, noise=0.5, seed=0, start_bit=0.0):
