@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import fir_cases
 import oracle_lib
 from conftest import run_in_exp_child
 
@@ -238,6 +239,8 @@ def test_gpu_fir_fuzz(fmd, oracle):
         nch = int(rng.integers(1, 5))
         bank = fmd.FirBank(taps, M, nch)
         assert bank.tap_digits() == (0 if M > 64 else 1 if np.abs(taps).max() <= 127 else 2), (T, M, bank.tap_digits())
+        want = fir_cases.fir_select(T, M, bool(np.abs(taps).max() <= 127))      # the planner's arithmetic, restated (tests/fir_cases.py)
+        assert (bank.kernel_name(), bank.tap_digits()) == (want.kernel, want.digits), (T, M, bank.kernel_name(), want.kernel)
         hs = [oracle.fir_new(taps, M) for _ in range(nch)]
         for _ in range(int(rng.integers(1, 5))):
             n = 8 * int(rng.integers(1, 3000))

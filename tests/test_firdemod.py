@@ -10,6 +10,8 @@ import math
 import numpy as np
 import pytest
 
+import fir_cases
+
 
 @pytest.mark.parametrize("D,fast,slow", [(6, 170000, 32000), (10, 240000, 32000), (2, 48000, 48000), (16, 150000, 32000)])
 def test_oracle_composition_reduces_to_reference_chain(oracle, D, fast, slow):
@@ -61,8 +63,12 @@ def test_gpu_all_ones_is_the_boxcar_kernel_and_the_reference(fmd, oracle, D, fas
                                            (16, 16, 48000, 48000), (129, 64, 37500, 8000), (1, 2, 500000, 32000),
                                            (127, 16, 1250000, 48000), (200, 16, 625000, 44100), (255, 16, 625000, 48000)])
 def test_gpu_fused_matches_composition(fmd, oracle, T, M, fast, slow):
-    """Decimate 8 with all k-steps in one pass runs the operand-fragment-reuse mapping; every other shape the plain one."""
-    fused_case(fmd, oracle, T, M, fast, slow)
+    """Decimate 8 with all k-steps in one pass runs the operand-fragment-reuse mapping; every other shape the plain one.  Both
+    discriminator forms per shape, each fixed (not drawn): |lp| <= 2048 runs the f32 form -- at decimate 8 with audio groups of >= 16
+    outputs that is a register form --, a larger bound the integer form of the LDS-array kernel.  The kernel is the one the planner's
+    arithmetic (tests/fir_cases.py) names."""
+    for disc in ("f32", "int"):
+        fused_case(fmd, oracle, T, M, fast, slow, disc=disc)
 
 
 @pytest.mark.gpu
@@ -169,17 +175,29 @@ def test_gpu_fused_digit_and_sparse_variants(fmd, oracle, request, knobs):
         assert kn2.startswith(reg_kernel_prefix(fast, slow, False, knobs)), (knobs, kn2)
 
 
-def fused_case(fmd, oracle, T, M, fast, slow, f32_only=False, taps_max=2047):
+def fused_case(fmd, oracle, T, M, fast, slow, f32_only=False, taps_max=2047, disc=None):
+    """disc "f32" / "int": that discriminator form (|lp| <= 2048 or beyond), and the kernel name is held to the planner's restatement."""
     rng = np.random.default_rng(T * 11 + M)
     taps = rng.integers(-taps_max, taps_max + 1, T).astype(np.int16)
     if taps_max < 2047:
         taps[rng.integers(0, T)] = taps_max
         taps[rng.integers(0, T)] = -taps_max
     shift = fmd.auto_shift(taps, 16384) + int(rng.integers(0, 6))     # both discriminator forms (|lp| <= 2048: f32)
-    if f32_only:
+    if f32_only or disc == "f32":
         shift = fmd.auto_shift(taps, 2048) + int(rng.integers(0, 3))
+    if disc == "f32" and fir_cases.lp_bound(taps, shift) > 2048:          # (the library rounds the bound up: 2049 is the integer form)
+        shift += 1
+    if disc == "int":
+        if 128 * int(np.abs(taps.astype(np.int64)).sum()) <= 2048:        # (a single small tap: no shift takes it beyond the f32 range)
+            taps[0] = 2047
+        shift = fmd.auto_shift(taps, 16384)
     nch = 5
     fd = fmd.FirDemodBank(taps, M, fast, slow, nch, shift=shift)
+    if disc:
+        bound = fir_cases.lp_bound(taps, shift)
+        assert (bound <= 2048) == (disc == "f32"), (disc, bound)
+        want = fir_cases.fused_select(T, M, bool(np.abs(taps).max() <= 127), bound <= 2048, fast, slow)
+        assert fd.kernel_name() == fir_cases.fused_name(want) and fd.tiling()["audio_per_tile"] == want.kt, (fd.kernel_name(), fir_cases.fused_name(want))
     hs = [oracle.firdemod_new(taps, M, shift, fast, slow) for _ in range(nch)]
     first = 8 * ((T + 2 * M) // 4 + 2)                                            # >= 2 filter outputs
     for call in range(6):
@@ -197,6 +215,8 @@ def fused_case(fmd, oracle, T, M, fast, slow, f32_only=False, taps_max=2047):
     for c in range(nch):
         assert state_tuple(fd.get_state(c).as_dict()) == state_tuple(oracle.firdemod_state(hs[c]))
         oracle.lib.fmo_firdemod_free(hs[c])
+    if disc:
+        assert fd.kernel_name() == fir_cases.fused_name(want), (fd.kernel_name(), fir_cases.fused_name(want))   # (every call here has a per-tile table)
     fd.reset()
     assert fd.get_state(0).as_dict()["demod_pre"] == [0, 0]
     return fd.kernel_name()
@@ -273,6 +293,8 @@ def test_gpu_fused_fuzz(fmd, oracle):
             assert e.status == -6, (T, M, fast, slow, e)                     # outside the documented domain only
             n_refused += 1
             continue
+        want = fir_cases.fused_select(T, M, bool(np.abs(taps).max() <= 127), fir_cases.lp_bound(taps, shift) <= 2048, fast, slow)
+        assert want is not None and fd.kernel_name() == fir_cases.fused_name(want), (case, T, M, shift, fast, slow, fd.kernel_name())
         hs = [oracle.firdemod_new(taps, M, shift, fast, slow) for _ in range(nch)]
         first = 8 * ((T + 2 * M) // 4 + 2)
         for call in range(int(rng.integers(2, 6))):
@@ -287,6 +309,7 @@ def test_gpu_fused_fuzz(fmd, oracle):
         for c in range(nch):
             assert state_tuple(fd.get_state(c).as_dict()) == state_tuple(oracle.firdemod_state(hs[c])), (case, c)
             oracle.lib.fmo_firdemod_free(hs[c])
+        assert fd.kernel_name() == fir_cases.fused_name(want), (case, fd.kernel_name(), fir_cases.fused_name(want))   # (calls of at most 160 tiles)
         kn = fd.kernel_name().split("::")[-1].split("<")[0]
         kernels[kn] = kernels.get(kn, 0) + 1
         fd.close()
