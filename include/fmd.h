@@ -637,6 +637,51 @@ int fmd_spectrum_tap_digits(const fmd_spectrum *s);
 /* Name of the kernel this handle launches, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_spectrum_kernel_name(const fmd_spectrum *s, char *name, size_t cap);
 
+/* ---- uniform channelizer: every channel of a band plan in one pass --------------------------------------------- */
+/* NEW SURFACE (the reference has none).  One prototype filter, longer than a frame step, applied to all N equally spaced channels
+ * of every stream (or a selection of them): each channel's decimated complex baseband.  Definition (integers only;
+ * tests/uniform_ref.py): the channelizer's steps, unchanged, with decim = hop and a fixed grid of phase steps:
+ *   inc_k     = floor((k 2^33 / N + 1) / 2) mod 2^32                  channel k of N: centre (k < N/2 ? k : k - N) capture_rate / N Hz
+ *                                                                     (for a power-of-two N: fmd_spectrum_bin_inc(k, N))
+ *   c, TAB, cosq, sinq, W[k][t] = rnd(h[t] cosq(t inc_k)) + j rnd(-h[t] sinq(t inc_k))      exactly the station bank's
+ *   z[k][m]   = sum_{t < n_taps} W[k][t] c[hop m + t]                 (exact in i32)
+ *   y[k][m]   = (z * (cosq(psi) + j sinq(psi))) >> (14 + shift),  psi = m hop inc_k mod 2^32 (floor, per component, in i64)
+ * Output m comes with the call in which sample hop m + n_taps - 1 arrives; m and the filter history carry across calls.
+ * Domain (else FMD_ERR_UNSUPPORTED, decided before a device is queried): 2 <= n_channels <= 256, any integer; hop a multiple of
+ * 8 in 8 ... 256, not tied to n_channels (the caller chooses the oversampling); 1 <= n_taps <= 2048; |h| <= 2047; shift <= 24;
+ * ceil(256 G / 2^shift) <= 16384 with G = max over the selected channels of sum_t (|Wr| + |Wi|), so |y| <= 16384 (and, G <= 2^23,
+ * |z| < 2^31); n_streams <= 65535.  `channels` [n_selected]: strictly increasing, each < n_channels, 1 <= n_selected <=
+ * n_channels -- only these rows are computed and stored; NULL means all n_channels (n_selected is then ignored).
+ * Calls: nbytes % (2 hop) != 0 -> FMD_ERR_BAD_LENGTH (every power-of-two hop divides a 262144-byte read_sync buffer); a call that
+ * completes no output -> FMD_ERR_TOO_SHORT and nothing changes, exactly as the channelizer.  With whole hops per call the carried
+ * history is a constant hop (ceil(n_taps / hop) - 1) samples, and every frame start stays 16-byte aligned relative to d_iq.
+ * Where both are defined (hop even and <= 64, n_taps <= 256, at most 32 selected channels) the handle returns exactly what
+ * fmd_channelizer_* returns for decim = hop and phase_inc = inc_k, call by call.
+ * Layouts: iq [n_streams][nbytes], out [n_streams][selected channel][out_cap][2] int16 (yr, yi); n_streams is dev->n_channels.
+ * Stream lifetime and completion points: as fmd_channelizer_* (fmd_uniform_check). */
+typedef struct fmd_uniform fmd_uniform;
+/* inc_k above; FMD_ERR_UNSUPPORTED unless 2 <= n_channels <= 256 and channel < n_channels. */
+int fmd_uniform_channel_inc(uint32_t channel, uint32_t n_channels, uint32_t *inc);
+/* nbytes / (2 hop): bounds the outputs of every call of nbytes per (stream, channel); 0 for hop 0. */
+size_t fmd_uniform_out_cap(uint32_t hop, size_t nbytes);
+int fmd_uniform_new(const int16_t *taps, uint32_t n_taps, uint32_t n_channels, uint32_t hop, uint32_t shift,
+                    const uint32_t *channels, uint32_t n_selected, const fmd_device_config *dev, fmd_uniform **out);
+void fmd_uniform_free(fmd_uniform *u);
+/* Position 0 and an all-zero history, after the device has finished. */
+int fmd_uniform_reset(fmd_uniform *u);
+/* HOST buffers; *out_len = outputs per (stream, channel) (the same for all). */
+int fmd_uniform_run_batch(fmd_uniform *u, const uint8_t *iq, size_t nbytes, int16_t *out, size_t out_cap, size_t *out_len);
+/* DEVICE buffers (d_iq and d_out 4-byte aligned, any out_cap), enqueued on `stream` without synchronising; *out_len as above. */
+int fmd_uniform_run_device(fmd_uniform *u, const void *d_iq, size_t nbytes, void *d_out, size_t out_cap, size_t *out_len,
+                           void *stream);
+int fmd_uniform_check(fmd_uniform *u);
+/* Outputs per (stream, channel) produced since creation or the last reset: the next output's index m. */
+int fmd_uniform_outputs(const fmd_uniform *u, uint64_t *outputs);
+/* 1 or 2: the i8 digits per tap on the matrix cores (1 when every |W| of the selected channels <= 127). */
+int fmd_uniform_tap_digits(const fmd_uniform *u);
+/* Name of the kernel this handle launches, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_uniform_kernel_name(const fmd_uniform *u, char *name, size_t cap);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

@@ -188,6 +188,18 @@ PROTOTYPES = {
     "fmd_spectrum_check": (C.c_int, [_vp]),
     "fmd_spectrum_tap_digits": (C.c_int, [_vp]),
     "fmd_spectrum_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_uniform_channel_inc": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fmd_uniform_out_cap": (_sz, [C.c_uint32, _sz]),
+    "fmd_uniform_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                                  C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_uniform_free": (None, [_vp]),
+    "fmd_uniform_reset": (C.c_int, [_vp]),
+    "fmd_uniform_run_batch": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "fmd_uniform_run_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_uniform_check": (C.c_int, [_vp]),
+    "fmd_uniform_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "fmd_uniform_tap_digits": (C.c_int, [_vp]),
+    "fmd_uniform_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

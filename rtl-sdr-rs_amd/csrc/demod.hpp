@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <stdexcept>
 #include <string>
@@ -589,6 +590,96 @@ public:
 private:
     uint32_t n_bins_, n_streams_;
     fmd_spectrum* h_ = nullptr;
+};
+
+// Uniform channelizer (fmd_uniform_*).  The prototype, as the Python uniform_taps(): h[t] = floor(amplitude s[t] / max|s| + 1/2),
+// s[t] = sinc((t - (T - 1) / 2) / N) hamming(T), T = N taps_per_channel.
+inline std::vector<int16_t> uniform_taps(uint32_t n_channels, uint32_t taps_per_channel, uint32_t amplitude = 2047)
+{
+    const size_t T = (size_t)n_channels * taps_per_channel;
+    const double pi = 3.14159265358979323846;
+    std::vector<double> s(T);
+    double peak = 0;
+    for (size_t t = 0; t < T; ++t) {
+        const double x = pi * (((double)t - ((double)T - 1) / 2.0) / n_channels);
+        const double w = T > 1 ? 0.54 - 0.46 * std::cos(2.0 * pi * (double)t / ((double)T - 1)) : 1.0;
+        s[t] = (x == 0.0 ? 1.0 : std::sin(x) / x) * w;
+        peak = std::max(peak, std::fabs(s[t]));
+    }
+    std::vector<int16_t> h(T);
+    for (size_t t = 0; t < T; ++t) h[t] = (int16_t)std::floor(amplitude * s[t] / peak + 0.5);
+    return h;
+}
+
+inline uint32_t uniform_channel_inc(uint32_t channel, uint32_t n_channels)
+{
+    uint32_t inc = 0;
+    check(fmd_uniform_channel_inc(channel, n_channels, &inc));
+    return inc;
+}
+
+// The smallest shift with ceil(256 G / 2^shift) <= 16384, G = max over `channels` (empty: all) of sum_t |Wr| + |Wi|.
+inline uint32_t uniform_auto_shift(const std::vector<int16_t>& taps, uint32_t n_channels, const std::vector<uint32_t>& channels = {})
+{
+    int16_t tab[1024];
+    check(fmd_stations_nco_table(tab));
+    uint64_t gain = 0;
+    const size_t rows = channels.empty() ? n_channels : channels.size();
+    for (size_t i = 0; i < rows; ++i) {
+        const uint32_t inc = uniform_channel_inc(channels.empty() ? (uint32_t)i : channels[i], n_channels);
+        uint64_t g = 0;
+        for (size_t t = 0; t < taps.size(); ++t) {
+            const uint32_t ix = ((uint32_t)t * inc) >> 22;
+            const int32_t wr = (taps[t] * tab[ix] + 8192) >> 14, wi = (-taps[t] * tab[(ix - 256u) & 1023u] + 8192) >> 14;
+            g += (uint64_t)std::abs(wr) + (uint64_t)std::abs(wi);
+        }
+        gain = std::max(gain, g);
+    }
+    uint32_t shift = 0;
+    while (((256 * gain + ((1ull << shift) - 1)) >> shift) > 16384) ++shift;
+    return shift;
+}
+
+// run() takes [n_streams][nbytes] (whole hops) and returns interleaved (yr, yi) baseband, row stream * n_selected + selected channel.
+class UniformChannelizer {
+public:
+    // `channels` empty: all n_channels
+    UniformChannelizer(const std::vector<int16_t>& taps, uint32_t n_channels, uint32_t hop, uint32_t shift,
+                       const std::vector<uint32_t>& channels = {}, uint32_t n_streams = 1, int32_t device_id = -1)
+        : hop_(hop), n_streams_(n_streams), n_selected_(channels.empty() ? n_channels : (uint32_t)channels.size())
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_uniform_new(taps.data(), (uint32_t)taps.size(), n_channels, hop, shift, channels.empty() ? nullptr : channels.data(),
+                              n_selected_, &dev, &h_));
+    }
+    ~UniformChannelizer() { fmd_uniform_free(h_); }
+    UniformChannelizer(const UniformChannelizer&) = delete;
+    UniformChannelizer& operator=(const UniformChannelizer&) = delete;
+
+    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    {
+        const size_t cap = std::max<size_t>(1, fmd_uniform_out_cap(hop_, nbytes));
+        const size_t rows = (size_t)n_streams_ * n_selected_;
+        std::vector<int16_t> out(2 * cap * rows);
+        size_t n = 0;
+        check(fmd_uniform_run_batch(h_, iq, nbytes, out.data(), cap, &n));
+        std::vector<std::vector<int16_t>> res(rows);
+        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + 2 * r * cap, out.begin() + 2 * (r * cap + n));
+        return res;
+    }
+    uint64_t outputs() const
+    {
+        uint64_t n = 0;
+        check(fmd_uniform_outputs(h_, &n));
+        return n;
+    }
+    void reset() { check(fmd_uniform_reset(h_)); }
+    int tap_digits() const { return fmd_uniform_tap_digits(h_); }
+    uint32_t n_selected() const { return n_selected_; }
+
+private:
+    uint32_t hop_, n_streams_, n_selected_;
+    fmd_uniform* h_ = nullptr;
 };
 
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.

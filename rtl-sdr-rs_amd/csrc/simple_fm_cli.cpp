@@ -35,6 +35,11 @@
 // ONE capture file whose sample rate is -s, integrated over the file's complete blocks; one line per bin in frequency order,
 // "offset_hz power" with the exact u64 power -- the offsets are where the stations are (-S).
 //
+// Uniform channelizer, -U N:hop[:taps_per_channel] [-C k1,k2,...]: all N channels of a band plan (or the listed ones) out of ONE
+// capture file whose sample rate is -s (fmd_uniform_*; prototype fm::uniform_taps(N, taps_per_channel = 8), the smallest
+// admissible shift): channel k's complex baseband at capture_rate / hop goes to <prefix>.<k>.cs16 as interleaved s16 (I, Q) pairs;
+// the channels' offsets and the output rate are printed on stderr.  Trailing bytes that do not fill a hop are dropped with a note.
+//
 // EOF policy (the reference ignores the read count and never terminates at EOF): only COMPLETE
 // blocks are demodulated; a trailing partial block is dropped with a note on stderr.  Logging goes to stderr
 // because stdout carries audio (:37-38).
@@ -357,6 +362,63 @@ static int run_power(const char* path, uint32_t n_bins, uint32_t hop, uint32_t r
     return rc;
 }
 
+// -U: one capture, every channel of a band plan (fmd_uniform_*)
+static int run_uniform(const char* path, const char* spec, const char* select, const char* prefix, uint32_t rate)
+{
+    unsigned N = 0, hop = 0, P = 8;
+    if (sscanf(spec, "%u:%u:%u", &N, &hop, &P) < 2 || !N || !hop || !P) { fprintf(stderr, "bad -U N:hop[:taps_per_channel]: %s\n", spec); return 2; }
+    std::vector<uint32_t> sel;
+    for (const char* p = select; p && *p;) {
+        char* end = nullptr;
+        const unsigned long k = strtoul(p, &end, 10);
+        if (end == p) { fprintf(stderr, "bad -C list: %s\n", select); return 2; }
+        sel.push_back((uint32_t)k);
+        p = *end == ',' ? end + 1 : end;
+    }
+    FILE* in = strcmp(path, "-") ? fopen(path, "rb") : stdin;
+    if (!in) { perror(path); return 2; }
+    std::vector<FILE*> out;
+    int rc = 0;
+    try {
+        const std::vector<int16_t> taps = fm::uniform_taps(N, P);
+        const uint32_t shift = fm::uniform_auto_shift(taps, N, sel);
+        fm::UniformChannelizer uc(taps, N, hop, shift, sel);
+        fprintf(stderr, "%u of %u channels of %.1f Hz, %zu taps, shift %u, output at %.1f Hz\n", uc.n_selected(), N, (double)rate / N,
+                taps.size(), shift, (double)rate / hop);
+        for (uint32_t i = 0; i < uc.n_selected(); ++i) {
+            const uint32_t k = sel.empty() ? i : sel[i];
+            const std::string name = std::string(prefix) + "." + std::to_string(k) + ".cs16";
+            fprintf(stderr, "channel %u at %+.1f Hz -> %s\n", k, (2 * k < N ? (double)k : (double)k - N) * rate / N, name.c_str());
+            FILE* f = fopen(name.c_str(), "wb");
+            if (!f) { perror(name.c_str()); throw 2; }
+            out.push_back(f);
+        }
+        const size_t frame = 2 * (size_t)hop;
+        std::vector<uint8_t> buf(std::max<size_t>(1, fm::DEFAULT_BUF_LENGTH / frame) * frame);   // whole hops per call
+        for (;;) {
+            size_t fill = 0, n;
+            while (fill < buf.size() && (n = fread(buf.data() + fill, 1, buf.size() - fill, in)) > 0) fill += n;
+            const size_t whole = fill / frame * frame;
+            if (whole) {
+                const auto rows = uc.run(buf.data(), whole);
+                for (size_t k = 0; k < out.size(); ++k) fm::output(rows[k], out[k]);
+            }
+            if (fill < buf.size()) {
+                if (fill - whole) fprintf(stderr, "dropped %zu trailing bytes (not a complete hop of %zu bytes)\n", fill - whole, frame);
+                break;
+            }
+        }
+    } catch (const fm::Error& e) {
+        fprintf(stderr, "error: %s\n", e.what());
+        rc = 1;
+    } catch (int e) {
+        rc = e;
+    }
+    for (FILE* f : out) if (f) fclose(f);
+    if (in != stdin) fclose(in);
+    return rc;
+}
+
 int main(int argc, char** argv)
 {
     uint32_t rate = 170000, resample = 32000, freq = 94900000;
@@ -372,6 +434,8 @@ int main(int argc, char** argv)
     const char* narrow = nullptr;                            // -N mode[:R[:lo:hi]]: with -S, narrow-band channels (fmd_narrow_*)
     uint32_t squelch = 0;                                    // -q: their squelch (RMS amplitude; 0 = always open)
     uint32_t power_bins = 0, power_hop = 0;                  // -P N [-H hop]: power spectrum of one capture
+    const char* uniform = nullptr;                           // -U N:hop[:taps_per_channel]: uniform channelizer over one capture
+    const char* uniform_sel = nullptr;                       // -C k1,k2,...: with -U, only these channels
     size_t max_blocks = 0;                                   // -n: stop after this many blocks (live mode; 0 = until the stream ends)
     std::vector<const char*> paths;
     for (int i = 1; i < argc; ++i) {
@@ -389,6 +453,8 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-q") && i + 1 < argc) squelch = (uint32_t)strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-P") && i + 1 < argc) power_bins = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-H") && i + 1 < argc) power_hop = strtoul(argv[++i], nullptr, 10);
+        else if (!strcmp(argv[i], "-U") && i + 1 < argc) uniform = argv[++i];
+        else if (!strcmp(argv[i], "-C") && i + 1 < argc) uniform_sel = argv[++i];
         else if (!strcmp(argv[i], "-n") && i + 1 < argc) max_blocks = strtoul(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "-b") && i + 1 < argc) { per_launch = strtoul(argv[++i], nullptr, 10); if (!per_launch) per_launch = 1; }
         else if (!strcmp(argv[i], "-h") || !strcmp(argv[i], "--help")) {
@@ -400,14 +466,16 @@ int main(int argc, char** argv)
                             "       %s [-s ...] [-o prefix] -S off1,off2,... -2 <capture.bin | ->        (their stereo: s16 L/R at capture_rate / downsample / R)\n"
                             "       %s [-s ...] [-o prefix] -S off1,off2,... -N mode[:R[:lo:hi]] [-q squelch] <capture.bin | ->   (narrow-band channels: iq, fm, am, usb, lsb at capture_rate / downsample / R)\n"
                             "       %s [-s ...] [-o prefix] -S off1,off2,... -R [-I] <capture.bin | ->   (their RDS: offset_hz PI PS \"radiotext\" groups_ok blocks_bad; -I: baseband to prefix.k.rds.cs16)\n"
-                            "       %s -s capture_rate_hz -P n_bins [-H hop] <capture.bin | ->       (power spectrum: offset_hz power per bin)\n",
-                    argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                            "       %s -s capture_rate_hz -P n_bins [-H hop] <capture.bin | ->       (power spectrum: offset_hz power per bin)\n"
+                            "       %s -s capture_rate_hz [-o prefix] -U N:hop[:taps_per_channel] [-C k1,k2,...] <capture.bin | ->   (band plan: channel k's s16 I/Q at capture_rate / hop to prefix.k.cs16)\n",
+                    argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else paths.push_back(argv[i]);
     }
     if (rtl_tcp) return run_rtl_tcp(rtl_tcp, freq, rate, resample, max_blocks);
     if (paths.empty()) { fprintf(stderr, "missing input file (use - for stdin)\n"); return 2; }
     if (power_bins) return run_power(paths[0], power_bins, power_hop, rate);
+    if (uniform) return run_uniform(paths[0], uniform, uniform_sel, prefix, rate);
     if (stations) return run_stations(paths[0], stations, prefix, freq, rate, resample, iq_out, stereo, narrow, squelch, rds);
     if (paths.size() > 1 && gpus > 0) return run_sink(paths, prefix, freq, rate, resample, gpus);
     if (paths.size() > 1) return run_bank(paths, prefix, freq, rate, resample);

@@ -171,6 +171,11 @@ pub struct fmd_spectrum {
 }
 
 #[repr(C)]
+pub struct fmd_uniform {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
 }
@@ -302,6 +307,18 @@ extern "C" {
     pub fn fmd_spectrum_check(s: *mut fmd_spectrum) -> c_int;
     pub fn fmd_spectrum_tap_digits(s: *const fmd_spectrum) -> c_int;
     pub fn fmd_spectrum_kernel_name(s: *const fmd_spectrum, name: *mut c_char, cap: usize) -> c_int;
+    // uniform channelizer: the declarations only (no safe wrapper yet)
+    pub fn fmd_uniform_channel_inc(channel: u32, n_channels: u32, inc: *mut u32) -> c_int;
+    pub fn fmd_uniform_out_cap(hop: u32, nbytes: usize) -> usize;
+    pub fn fmd_uniform_new(taps: *const i16, n_taps: u32, n_channels: u32, hop: u32, shift: u32, channels: *const u32, n_selected: u32, dev: *const DeviceConfig, out: *mut *mut fmd_uniform) -> c_int;
+    pub fn fmd_uniform_free(u: *mut fmd_uniform);
+    pub fn fmd_uniform_reset(u: *mut fmd_uniform) -> c_int;
+    pub fn fmd_uniform_run_batch(u: *mut fmd_uniform, iq: *const u8, nbytes: usize, out: *mut i16, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn fmd_uniform_run_device(u: *mut fmd_uniform, d_iq: *const c_void, nbytes: usize, d_out: *mut c_void, out_cap: usize, out_len: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_uniform_check(u: *mut fmd_uniform) -> c_int;
+    pub fn fmd_uniform_outputs(u: *const fmd_uniform, outputs: *mut u64) -> c_int;
+    pub fn fmd_uniform_tap_digits(u: *const fmd_uniform) -> c_int;
+    pub fn fmd_uniform_kernel_name(u: *const fmd_uniform, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
