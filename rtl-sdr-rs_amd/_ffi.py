@@ -306,6 +306,53 @@ class CheckedHandle(Handle):
         check(self._fn("check")(self._h))
 
 
+class BankHandle(CheckedHandle):
+    """A CheckedHandle with state carried across calls, which fmd_<_prefix>_reset clears."""
+
+    def reset(self):
+        check(self._fn("reset")(self._h))
+
+
+class DownConverter(BankHandle):
+    """Base of the down-converter handles that run through fmd_<_prefix>_run_*: `n_streams` streams in, and for each of them
+    `_rows` rows (the attribute named so: stations or selected channels) of `width` int16 per output.  A subclass gives
+    out_cap(nbytes); its kernel_name takes the pass where `_passes` is 2."""
+    _rows = "n_stations"
+    _passes = 1
+    width = 2
+
+    def kernel_name(self, which=0):
+        """The kernel this handle launches (in pass `which` of `_passes`), as rocprofv3 --kernel-trace prints it."""
+        buf = C.create_string_buffer(128)
+        which = (int(which),) if self._passes == 2 else ()
+        check(self._fn("kernel_name")(self._h, *which, buf, len(buf)))
+        return buf.value.decode()
+
+    def outputs(self):
+        """Outputs per row produced since creation or reset: the index m of the next one."""
+        n = C.c_uint64(0)
+        check(self._fn("outputs")(self._h, C.byref(n)))
+        return n.value
+
+    def run_batch(self, iq):
+        """iq uint8 [n_streams, nbytes] -> int16 array [n_streams, rows, n_out, width]."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        if iq.ndim != 2 or iq.shape[0] != self.n_streams:
+            raise ValueError("iq must be [n_streams, nbytes]")
+        cap = max(1, self.out_cap(iq.shape[1]))
+        out = np.empty((self.n_streams, getattr(self, self._rows), cap, self.width), dtype=np.int16)
+        n = C.c_size_t(0)
+        check(self._fn("run_batch")(self._h, iq.ctypes.data, iq.shape[1], out.ctypes.data, cap, C.byref(n)))
+        return out[:, :, :n.value].copy()
+
+    def run_device(self, d_iq, nbytes, d_out, out_cap, stream=None):
+        """Enqueue on device pointers (d_out [n_streams][rows][out_cap][width] int16); returns the outputs per row.  `stream` must
+        stay alive until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
+        n = C.c_size_t(0)
+        check(self._fn("run_device")(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
+        return n.value
+
+
 def stream_phase_incs(phase_incs, n_streams):
     """`phase_incs` as a contiguous uint32 [n_streams, n_stations] (a flat list of n_stations is taken for every stream)."""
     incs = np.asarray(phase_incs, dtype=np.uint32)

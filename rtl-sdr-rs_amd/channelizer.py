@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DeviceConfig, CheckedHandle, check, lib, stream_phase_incs
+from ._ffi import DeviceConfig, DownConverter, check, lib, stream_phase_incs
 from .stations import stations_auto_shift
 
 
@@ -17,9 +17,9 @@ def as_complex(x):
     return (x[..., 0].astype(np.float32) + 1j * x[..., 1].astype(np.float32)).astype(np.complex64)
 
 
-class Channelizer(CheckedHandle):
+class Channelizer(DownConverter):
     """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream).  `shift=None` takes the
-    smallest normalisation shift with |y| <= 16384."""
+    smallest normalisation shift with |y| <= 16384.  run_batch returns [n_streams, n_stations, n_out, 2] of (yr, yi)."""
     _prefix = "channelizer"
 
     def __init__(self, taps, decim, phase_incs, n_streams=1, shift=None, device_id=-1):
@@ -34,32 +34,5 @@ class Channelizer(CheckedHandle):
                                         self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations, C.byref(dev),
                                         C.byref(self._h)))
 
-    def reset(self):
-        check(lib().fmd_channelizer_reset(self._h))
-
     def out_cap(self, nbytes):
         return int(lib().fmd_channelizer_out_cap(self.decim, nbytes))
-
-    def outputs(self):
-        """Outputs per (stream, station) produced since creation or reset: the index m of the next one."""
-        n = C.c_uint64(0)
-        check(lib().fmd_channelizer_outputs(self._h, C.byref(n)))
-        return n.value
-
-    def run_batch(self, iq):
-        """iq uint8 [n_streams, nbytes] -> int16 array [n_streams, n_stations, n_out, 2] of (yr, yi)."""
-        iq = np.ascontiguousarray(iq, dtype=np.uint8)
-        if iq.ndim != 2 or iq.shape[0] != self.n_streams:
-            raise ValueError("iq must be [n_streams, nbytes]")
-        cap = max(1, self.out_cap(iq.shape[1]))
-        out = np.empty((self.n_streams, self.n_stations, cap, 2), dtype=np.int16)
-        n = C.c_size_t(0)
-        check(lib().fmd_channelizer_run_batch(self._h, iq.ctypes.data, iq.shape[1], out.ctypes.data, cap, C.byref(n)))
-        return out[:, :, :n.value].copy()
-
-    def run_device(self, d_iq, nbytes, d_out, out_cap, stream=None):
-        """Enqueue on device pointers (d_out [n_streams][n_stations][out_cap][2] int16); returns the outputs per (stream, station).
-        `stream` must stay alive until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
-        n = C.c_size_t(0)
-        check(lib().fmd_channelizer_run_device(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
-        return n.value

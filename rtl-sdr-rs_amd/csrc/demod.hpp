@@ -38,6 +38,62 @@ struct Error : std::runtime_error {
 
 inline void check(int status) { if (status != FMD_OK) throw Error(status); }
 
+// Owner of a C handle: `h.out()` receives it from fmd_*_new, the destructor gives it to `Free`; not copyable, and so is no class
+// that holds one.
+template <class T, void (*Free)(T*)>
+class Owned {
+public:
+    Owned() = default;
+    ~Owned() { Free(h_); }
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    operator T*() const { return h_; }
+    T** out() { return &h_; }
+
+private:
+    T* h_ = nullptr;
+};
+
+// Rows of a flat batch result [rows][cap][width]: row r is its first lens[r] (or, for every row, n) outputs of `width` int16 each.
+using Rows = std::vector<std::vector<int16_t>>;
+
+inline Rows cut_rows(const std::vector<int16_t>& flat, size_t rows, size_t cap, const std::vector<size_t>& lens, size_t width = 1)
+{
+    Rows res(rows);
+    for (size_t r = 0; r < rows; ++r) res[r].assign(flat.begin() + width * r * cap, flat.begin() + width * (r * cap + lens[r]));
+    return res;
+}
+inline Rows cut_rows(const std::vector<int16_t>& flat, size_t rows, size_t cap, size_t n, size_t width = 1)
+{
+    return cut_rows(flat, rows, cap, std::vector<size_t>(rows, n), width);
+}
+
+// What an fmd_* getter writes through its last argument: outputs() of the five down-converters, and the other one-value getters.
+template <class R, class Fn, class... Args>
+inline R value_of(Fn getter, const Args&... args)
+{
+    R r{};
+    check(getter(args..., &r));
+    return r;
+}
+
+// (present, level) of a pilot, (open, rms) of a squelch: the last completed block of one (stream, station)
+template <class Fn, class H>
+inline std::pair<bool, uint32_t> flag_and_level(Fn getter, const H& h, uint32_t stream, uint32_t station)
+{
+    int flag = 0;
+    uint32_t level = 0;
+    check(getter(h, stream, station, &flag, &level));
+    return {flag != 0, level};
+}
+
+// sin(x) / x and point i of an n-point Hamming window, for the windowed-sinc designers below
+namespace detail {
+constexpr double pi = 3.14159265358979323846;
+inline double sinc(double x) { return x == 0 ? 1.0 : std::sin(x) / x; }
+inline double hamming(size_t i, size_t n) { return n > 1 ? 0.54 - 0.46 * std::cos(2 * pi * (double)i / (double)(n - 1)) : 1.0; }
+}  // namespace detail
+
 // optimal_settings(freq, rate), simple_fm.rs:189-214 (rate_resample = RATE_RESAMPLE, :27).
 inline std::pair<RadioConfig, DemodConfig> optimal_settings(uint32_t freq, uint32_t rate, uint32_t rate_resample = 32000)
 {
@@ -53,11 +109,8 @@ public:
     explicit Demod(const DemodConfig& config, int device_id = -1) : config_(config)
     {
         fmd_device_config dev{1u, device_id, 0u};
-        check(fmd_demod_new(&config_, &dev, &h_));
+        check(fmd_demod_new(&config_, &dev, h_.out()));
     }
-    ~Demod() { fmd_demod_free(h_); }
-    Demod(const Demod&) = delete;
-    Demod& operator=(const Demod&) = delete;
 
     // demodulate(&mut self, buf: Vec<u8>) -> Vec<i16>
     std::vector<int16_t> demodulate(const std::vector<uint8_t>& buf) { return demodulate(buf.data(), buf.size()); }
@@ -70,12 +123,7 @@ public:
         return out;
     }
 
-    fmd_demod_state state()
-    {
-        fmd_demod_state s{};
-        check(fmd_demod_get_state(h_, 0, &s));
-        return s;
-    }
+    fmd_demod_state state() { return value_of<fmd_demod_state>(fmd_demod_get_state, h_, 0u); }
     void set_state(const fmd_demod_state& s) { check(fmd_demod_set_state(h_, 0, &s)); }
     // treat every buffer as consecutive reference calls of block_bytes each (0 = off); see fmd_demod_set_block_len
     void set_block_len(size_t block_bytes) { check(fmd_demod_set_block_len(h_, block_bytes)); }
@@ -83,7 +131,7 @@ public:
 
 private:
     DemodConfig config_;
-    fmd_demod* h_ = nullptr;
+    Owned<fmd_demod, fmd_demod_free> h_;
 };
 
 // n independent Demods on one GPU behind one handle (one `Demod` per stream, simple_fm.rs:137): `iq` holds
@@ -93,22 +141,17 @@ public:
     DemodBank(const DemodConfig& config, uint32_t n_channels, int device_id = -1) : config_(config), n_(n_channels)
     {
         fmd_device_config dev{n_channels, device_id, 0u};
-        check(fmd_demod_new(&config_, &dev, &h_));
+        check(fmd_demod_new(&config_, &dev, h_.out()));
     }
-    ~DemodBank() { fmd_demod_free(h_); }
-    DemodBank(const DemodBank&) = delete;
-    DemodBank& operator=(const DemodBank&) = delete;
 
     // out[c] = Demod::demodulate(channel c's buffer); `len` bytes per channel
-    std::vector<std::vector<int16_t>> demodulate(const uint8_t* iq, size_t len)
+    Rows demodulate(const uint8_t* iq, size_t len)
     {
         const size_t cap = fmd_out_cap(&config_, len) + 1;
         std::vector<int16_t> flat(cap * n_);
         std::vector<size_t> lens(n_);
         check(fmd_demod_demodulate_batch(h_, iq, len, flat.data(), cap, lens.data()));
-        std::vector<std::vector<int16_t>> out(n_);
-        for (uint32_t c = 0; c < n_; ++c) out[c].assign(flat.begin() + c * cap, flat.begin() + c * cap + lens[c]);
-        return out;
+        return cut_rows(flat, n_, cap, lens);
     }
     uint32_t channels() const { return n_; }
     const DemodConfig& config() const { return config_; }
@@ -116,7 +159,7 @@ public:
 private:
     DemodConfig config_;
     uint32_t n_;
-    fmd_demod* h_ = nullptr;
+    Owned<fmd_demod, fmd_demod_free> h_;
 };
 
 // The receive -> mpsc -> process -> output hand-off of the example (simple_fm.rs:55-60,114-127,150-156) with the GPU(s)
@@ -131,11 +174,8 @@ public:
         : n_(n_channels), nbytes_(nbytes), cb_(std::move(on_audio))
     {
         check(fmd_sink_new(&config, n_channels, device_ids.data(), (uint32_t)device_ids.size(), nbytes, depth, &Sink::trampoline,
-                           this, &h_));
+                           this, h_.out()));
     }
-    ~Sink() { fmd_sink_free(h_); }
-    Sink(const Sink&) = delete;
-    Sink& operator=(const Sink&) = delete;
 
     // the next slot to fill: n_channels buffers of nbytes back to back (page-locked; read_sync writes straight into it)
     uint8_t* acquire() { uint8_t* p = nullptr; check(fmd_sink_acquire(h_, &p)); return p; }
@@ -156,7 +196,7 @@ private:
     size_t nbytes_;
     Callback cb_;
     int status_ = FMD_OK;
-    fmd_sink* h_ = nullptr;
+    Owned<fmd_sink, fmd_sink_free> h_;
 };
 
 // An rtl_tcp server (the reference's examples/rtl_tcp.rs) as the producer: `read_sync` has the shape of
@@ -166,12 +206,9 @@ class RtlTcpSource {
 public:
     RtlTcpSource(const std::string& host, uint16_t port, uint32_t timeout_ms = 10000)
     {
-        check(fmd_rtltcp_open(host.c_str(), port, timeout_ms, &h_));
+        check(fmd_rtltcp_open(host.c_str(), port, timeout_ms, h_.out()));
         check(fmd_rtltcp_info(h_, &tuner_type_, &gain_count_));
     }
-    ~RtlTcpSource() { fmd_rtltcp_close(h_); }
-    RtlTcpSource(const RtlTcpSource&) = delete;
-    RtlTcpSource& operator=(const RtlTcpSource&) = delete;
 
     size_t read_sync(uint8_t* buf, size_t nbytes) { size_t n = 0; check(fmd_rtltcp_read_sync(h_, buf, nbytes, &n)); return n; }
     void command(uint8_t opcode, uint32_t param) { check(fmd_rtltcp_command(h_, opcode, param)); }
@@ -184,7 +221,7 @@ public:
     uint32_t gain_count() const { return gain_count_; }
 
 private:
-    fmd_rtltcp* h_ = nullptr;
+    Owned<fmd_rtltcp, fmd_rtltcp_close> h_;
     uint32_t tuner_type_ = 0, gain_count_ = 0;
 };
 
@@ -192,9 +229,18 @@ private:
 // returns audio [n_streams * n_stations] (row stream * n_stations + station).
 inline uint32_t phase_inc(int32_t offset_hz, uint32_t capture_rate)
 {
-    uint32_t inc = 0;
-    check(fmd_stations_phase_inc(offset_hz, capture_rate, &inc));
-    return inc;
+    return value_of<uint32_t>(fmd_stations_phase_inc, offset_hz, capture_rate);
+}
+
+// The boxcar prototype (h = 1...1, n_taps = decim: the reference's own low_pass) has |W| <= 1, so sum(|Wr| + |Wi|) <= 2 decim and
+// every |y| component stays within ceil(512 decim / 2^shift); the smallest shift that keeps it within `limit` (the Python
+// stations_auto_shift(taps, phase_incs, limit) works from the taps' exact gain instead).
+inline uint64_t boxcar_y_bound(uint32_t decim, uint32_t shift) { return (512ull * decim + (1ull << shift) - 1) >> shift; }
+inline uint32_t boxcar_shift(uint32_t decim, uint64_t limit)
+{
+    uint32_t shift = 0;
+    while (boxcar_y_bound(decim, shift) > limit) ++shift;
+    return shift;
 }
 
 class StationBank {
@@ -206,29 +252,24 @@ public:
     {
         fmd_device_config dev{n_streams, device_id, 0};
         check(fmd_stations_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, rate_out,
-                               rate_resample, &dev, &h_));
+                               rate_resample, &dev, h_.out()));
     }
-    ~StationBank() { fmd_stations_free(h_); }
-    StationBank(const StationBank&) = delete;
-    StationBank& operator=(const StationBank&) = delete;
 
-    std::vector<std::vector<int16_t>> demodulate(const uint8_t* iq, size_t nbytes)
+    Rows demodulate(const uint8_t* iq, size_t nbytes)
     {
         const size_t cap = std::max<size_t>(1, fmd_stations_out_cap(decim_, rate_out_, rate_resample_, nbytes));
         const size_t rows = (size_t)n_streams_ * n_stations_;
         std::vector<int16_t> out(cap * rows);
         std::vector<size_t> lens(rows);
         check(fmd_stations_demodulate_batch(h_, iq, nbytes, out.data(), cap, lens.data()));
-        std::vector<std::vector<int16_t>> res(rows);
-        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + r * cap, out.begin() + r * cap + lens[r]);
-        return res;
+        return cut_rows(out, rows, cap, lens);
     }
     void reset() { check(fmd_stations_reset(h_)); }
     uint32_t n_stations() const { return n_stations_; }
 
 private:
     uint32_t decim_, rate_out_, rate_resample_, n_streams_, n_stations_;
-    fmd_stations* h_ = nullptr;
+    Owned<fmd_stations, fmd_stations_free> h_;
 };
 
 // Channelizer (fmd_channelizer_*): `phase_incs` is [n_streams][n_stations]; run() takes [n_streams][nbytes] and returns
@@ -240,35 +281,25 @@ public:
         : decim_(decim), n_streams_(n_streams), n_stations_(n_streams ? (uint32_t)(phase_incs.size() / n_streams) : 0u)
     {
         fmd_device_config dev{n_streams, device_id, 0};
-        check(fmd_channelizer_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, &dev, &h_));
+        check(fmd_channelizer_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, &dev, h_.out()));
     }
-    ~Channelizer() { fmd_channelizer_free(h_); }
-    Channelizer(const Channelizer&) = delete;
-    Channelizer& operator=(const Channelizer&) = delete;
 
-    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    Rows run(const uint8_t* iq, size_t nbytes)
     {
         const size_t cap = std::max<size_t>(1, fmd_channelizer_out_cap(decim_, nbytes));
         const size_t rows = (size_t)n_streams_ * n_stations_;
         std::vector<int16_t> out(2 * cap * rows);
         size_t n = 0;
         check(fmd_channelizer_run_batch(h_, iq, nbytes, out.data(), cap, &n));
-        std::vector<std::vector<int16_t>> res(rows);
-        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + 2 * r * cap, out.begin() + 2 * (r * cap + n));
-        return res;
+        return cut_rows(out, rows, cap, n, 2);
     }
-    uint64_t outputs() const
-    {
-        uint64_t n = 0;
-        check(fmd_channelizer_outputs(h_, &n));
-        return n;
-    }
+    uint64_t outputs() const { return value_of<uint64_t>(fmd_channelizer_outputs, h_); }
     void reset() { check(fmd_channelizer_reset(h_)); }
     uint32_t n_stations() const { return n_stations_; }
 
 private:
     uint32_t decim_, n_streams_, n_stations_;
-    fmd_channelizer* h_ = nullptr;
+    Owned<fmd_channelizer, fmd_channelizer_free> h_;
 };
 
 // Audio taps of a StereoBank, as the Python stereo_taps(): a Hamming-windowed sinc low-pass at cutoff_hz convolved with the
@@ -276,7 +307,6 @@ private:
 inline std::vector<int16_t> stereo_taps(double mpx_rate, uint32_t n_taps, double cutoff_hz = 15000, double tau_us = 75)
 {
     if (n_taps < 1 || n_taps > 256) throw Error(FMD_ERR_INVALID_ARG);
-    const double pi = 3.14159265358979323846;
     std::vector<double> d(1, 1.0);
     if (tau_us > 0) {
         const uint32_t nd = std::max<uint32_t>(1, n_taps / 2);
@@ -287,11 +317,7 @@ inline std::vector<int16_t> stereo_taps(double mpx_rate, uint32_t n_taps, double
     const uint32_t nl = n_taps - (uint32_t)d.size() + 1;
     std::vector<double> lp(nl), g(n_taps, 0.0);
     const double fc = 2 * cutoff_hz / mpx_rate;
-    for (uint32_t i = 0; i < nl; ++i) {
-        const double t = i - (nl - 1) / 2.0, x = pi * fc * t;
-        const double w = nl > 1 ? 0.54 - 0.46 * std::cos(2 * pi * i / (nl - 1)) : 1.0;
-        lp[i] = fc * (t == 0 ? 1.0 : std::sin(x) / x) * w;
-    }
+    for (uint32_t i = 0; i < nl; ++i) lp[i] = fc * detail::sinc(detail::pi * fc * (i - (nl - 1) / 2.0)) * detail::hamming(i, nl);
     for (uint32_t i = 0; i < nl; ++i)
         for (size_t j = 0; j < d.size(); ++j) g[i + j] += lp[i] * d[j];
     double sum = 0;
@@ -299,6 +325,25 @@ inline std::vector<int16_t> stereo_taps(double mpx_rate, uint32_t n_taps, double
     std::vector<int16_t> out(n_taps);
     for (uint32_t i = 0; i < n_taps; ++i) out[i] = (int16_t)std::floor(g[i] / sum * (16383.0 - n_taps) + 0.5);
     return out;
+}
+
+// As the Python stereo.default_pilot_min(): a quarter of a nominal 6.75 kHz pilot at f_m = capture_rate / decim, in discriminator
+// units (32768 f / f_m).
+inline uint32_t default_pilot_min(uint32_t capture_rate, uint32_t decim)
+{
+    return (uint32_t)((32768ull * 6750 * decim) / (4ull * capture_rate));
+}
+
+// As the Python stereo.default_audio_shift(): the smallest shift (<= 16) at which mono at full deviation (75 kHz) stays inside
+// int16, sum(g) 32768 75 kHz / f_m >> (shift + 1).
+inline uint32_t default_audio_shift(const std::vector<int16_t>& audio_taps, uint32_t capture_rate, uint32_t decim)
+{
+    int64_t sum = 0;
+    for (int16_t v : audio_taps) sum += v;
+    const uint64_t peak = (uint64_t)(sum < 0 ? -sum : sum) * 32768ull * 75000ull * decim / capture_rate;
+    uint32_t shift = 0;
+    while (shift < 16 && (peak >> (shift + 1)) > 32767) ++shift;
+    return shift;
 }
 
 // Stereo station bank (fmd_stereo_*): run() takes [n_streams][nbytes] and returns interleaved (L, R) audio
@@ -312,44 +357,28 @@ public:
     {
         fmd_device_config dev{n_streams, device_id, 0};
         check(fmd_stereo_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, audio_taps.data(),
-                             (uint32_t)audio_taps.size(), &cfg, &dev, &h_));
+                             (uint32_t)audio_taps.size(), &cfg, &dev, h_.out()));
     }
-    ~StereoBank() { fmd_stereo_free(h_); }
-    StereoBank(const StereoBank&) = delete;
-    StereoBank& operator=(const StereoBank&) = delete;
 
     // FMD_ERR_TOO_SHORT (a call that completes no audio sample) returns empty rows and changes nothing.
-    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    Rows run(const uint8_t* iq, size_t nbytes)
     {
         const size_t cap = std::max<size_t>(1, fmd_stereo_out_cap(decim_, audio_decim_, nbytes));
         const size_t rows = (size_t)n_streams_ * n_stations_;
         std::vector<int16_t> out(2 * cap * rows);
         size_t n = 0;
         const int rc = fmd_stereo_run_batch(h_, iq, nbytes, out.data(), cap, &n);
-        if (rc == FMD_ERR_TOO_SHORT) return std::vector<std::vector<int16_t>>(rows);
+        if (rc == FMD_ERR_TOO_SHORT) return Rows(rows);
         check(rc);
-        std::vector<std::vector<int16_t>> res(rows);
-        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + 2 * r * cap, out.begin() + 2 * (r * cap + n));
-        return res;
+        return cut_rows(out, rows, cap, n, 2);
     }
-    std::pair<bool, uint32_t> pilot(uint32_t stream, uint32_t station)
-    {
-        int present = 0;
-        uint32_t level = 0;
-        check(fmd_stereo_pilot(h_, stream, station, &present, &level));
-        return {present != 0, level};
-    }
-    uint64_t outputs() const
-    {
-        uint64_t n = 0;
-        check(fmd_stereo_outputs(h_, &n));
-        return n;
-    }
+    std::pair<bool, uint32_t> pilot(uint32_t stream, uint32_t station) { return flag_and_level(fmd_stereo_pilot, h_, stream, station); }
+    uint64_t outputs() const { return value_of<uint64_t>(fmd_stereo_outputs, h_); }
     void reset() { check(fmd_stereo_reset(h_)); }
 
 private:
     uint32_t decim_, audio_decim_, n_streams_, n_stations_;
-    fmd_stereo* h_ = nullptr;
+    Owned<fmd_stereo, fmd_stereo_free> h_;
 };
 
 // Taps of an RdsBank, as the Python rds_taps(): a Hamming-windowed sinc low-pass at +-cutoff_hz around the subcarrier, scaled to
@@ -357,13 +386,11 @@ private:
 inline std::pair<std::vector<int16_t>, uint32_t> rds_taps(double mpx_rate, uint32_t n_taps, double cutoff_hz = 2400)
 {
     if (n_taps < 1 || n_taps > 256) throw Error(FMD_ERR_INVALID_ARG);
-    const double pi = 3.14159265358979323846, fc = 2 * cutoff_hz / mpx_rate;
+    const double fc = 2 * cutoff_hz / mpx_rate;
     std::vector<double> g(n_taps);
     double sum = 0;
     for (uint32_t i = 0; i < n_taps; ++i) {
-        const double t = i - (n_taps - 1) / 2.0, x = pi * fc * t;
-        const double w = n_taps > 1 ? 0.54 - 0.46 * std::cos(2 * pi * i / (n_taps - 1)) : 1.0;
-        g[i] = fc * (t == 0 ? 1.0 : std::sin(x) / x) * w;
+        g[i] = fc * detail::sinc(detail::pi * fc * (i - (n_taps - 1) / 2.0)) * detail::hamming(i, n_taps);
         sum += std::fabs(g[i]);
     }
     std::vector<int16_t> out(n_taps);
@@ -377,6 +404,24 @@ inline std::pair<std::vector<int16_t>, uint32_t> rds_taps(double mpx_rate, uint3
     return {out, shift};
 }
 
+// A front-end prototype for an RdsBank where the boxcar would cut the 57 kHz subcarrier: a 64-tap Hamming-windowed sinc of +-62 kHz
+// with peak 2047, and the front-end shift that keeps every |y| component <= 256 (where the reference's discriminator cannot wrap)
+// with sum(|Wr| + |Wi|) <= 2 sum |h| + 2 n_taps (rounding).
+inline std::pair<std::vector<int16_t>, uint32_t> rds_front_taps(uint32_t capture_rate)
+{
+    const double fc = 2.0 * 62000.0 / capture_rate;
+    const double peak = detail::sinc(detail::pi * fc * 0.5) * detail::hamming(31, 64);
+    std::vector<int16_t> h(64);
+    uint64_t sum = 0;
+    for (int i = 0; i < 64; ++i) {
+        h[i] = (int16_t)std::lround(detail::sinc(detail::pi * fc * (i - 31.5)) * detail::hamming(i, 64) / peak * 2047.0);
+        sum += (uint64_t)std::abs((int)h[i]);
+    }
+    uint32_t shift = 0;
+    while ((256ull * (2 * sum + 128) + (1ull << shift) - 1) >> shift > 256ull) ++shift;
+    return {h, shift};
+}
+
 // RDS bank (fmd_rds_*): run() takes [n_streams][nbytes] and returns interleaved (ur, ui) baseband
 // [n_streams * n_stations] (row stream * n_stations + station) at capture_rate / (decim out_decim).
 class RdsBank {
@@ -388,54 +433,35 @@ public:
     {
         fmd_device_config dev{n_streams, device_id, 0};
         check(fmd_rds_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, rds_taps.data(),
-                          (uint32_t)rds_taps.size(), &cfg, &dev, &h_));
+                          (uint32_t)rds_taps.size(), &cfg, &dev, h_.out()));
     }
-    ~RdsBank() { fmd_rds_free(h_); }
-    RdsBank(const RdsBank&) = delete;
-    RdsBank& operator=(const RdsBank&) = delete;
 
     // FMD_ERR_TOO_SHORT (a call that completes no output) returns empty rows and changes nothing.
-    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    Rows run(const uint8_t* iq, size_t nbytes)
     {
         const size_t cap = std::max<size_t>(1, fmd_rds_out_cap(decim_, out_decim_, nbytes));
         const size_t rows = (size_t)n_streams_ * n_stations_;
         std::vector<int16_t> out(2 * cap * rows);
         size_t n = 0;
         const int rc = fmd_rds_run_batch(h_, iq, nbytes, out.data(), cap, &n);
-        if (rc == FMD_ERR_TOO_SHORT) return std::vector<std::vector<int16_t>>(rows);
+        if (rc == FMD_ERR_TOO_SHORT) return Rows(rows);
         check(rc);
-        std::vector<std::vector<int16_t>> res(rows);
-        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + 2 * r * cap, out.begin() + 2 * (r * cap + n));
-        return res;
+        return cut_rows(out, rows, cap, n, 2);
     }
-    std::pair<bool, uint32_t> pilot(uint32_t stream, uint32_t station)
-    {
-        int present = 0;
-        uint32_t level = 0;
-        check(fmd_rds_pilot(h_, stream, station, &present, &level));
-        return {present != 0, level};
-    }
-    uint64_t outputs() const
-    {
-        uint64_t n = 0;
-        check(fmd_rds_outputs(h_, &n));
-        return n;
-    }
+    std::pair<bool, uint32_t> pilot(uint32_t stream, uint32_t station) { return flag_and_level(fmd_rds_pilot, h_, stream, station); }
+    uint64_t outputs() const { return value_of<uint64_t>(fmd_rds_outputs, h_); }
     void reset() { check(fmd_rds_reset(h_)); }
 
 private:
     uint32_t decim_, out_decim_, n_streams_, n_stations_;
-    fmd_rds* h_ = nullptr;
+    Owned<fmd_rds, fmd_rds_free> h_;
 };
 
 // RDS decoder of one (stream, station) (fmd_rds_decoder_*, host only): push() takes interleaved (ur, ui) pairs at rate_num / rate_den
 // Hz and returns the groups completed since.
 class RdsDecoder {
 public:
-    RdsDecoder(uint32_t rate_num, uint32_t rate_den) { check(fmd_rds_decoder_new(rate_num, rate_den, &h_)); }
-    ~RdsDecoder() { fmd_rds_decoder_free(h_); }
-    RdsDecoder(const RdsDecoder&) = delete;
-    RdsDecoder& operator=(const RdsDecoder&) = delete;
+    RdsDecoder(uint32_t rate_num, uint32_t rate_den) { check(fmd_rds_decoder_new(rate_num, rate_den, h_.out())); }
 
     std::vector<fmd_rds_group> push(const std::vector<int16_t>& iq)
     {
@@ -449,16 +475,11 @@ public:
             check(fmd_rds_decoder_push(h_, nullptr, 0, buf, 64, &n));
         }
     }
-    fmd_rds_info info() const
-    {
-        fmd_rds_info i;
-        check(fmd_rds_decoder_info(h_, &i));
-        return i;
-    }
+    fmd_rds_info info() const { return value_of<fmd_rds_info>(fmd_rds_decoder_info, h_); }
     void reset() { check(fmd_rds_decoder_reset(h_)); }
 
 private:
-    fmd_rds_decoder* h_ = nullptr;
+    Owned<fmd_rds_decoder, fmd_rds_decoder_free> h_;
 };
 
 // Channel taps of a NarrowBank, as the Python narrow_taps(): a Hamming-windowed complex band-pass from lo_hz to hi_hz at the
@@ -467,7 +488,7 @@ private:
 inline std::pair<std::vector<int16_t>, std::vector<int16_t>> narrow_taps(double rate, uint32_t n_taps, double lo_hz, double hi_hz)
 {
     if (n_taps < 1 || n_taps > 256 || !(hi_hz > lo_hz)) throw Error(FMD_ERR_INVALID_ARG);
-    const double pi = 3.14159265358979323846;
+    const double pi = detail::pi;
     const uint32_t n = n_taps;
     const double bw = (hi_hz - lo_hz) / rate, fc = (hi_hz + lo_hz) / (2 * rate);
     const bool real = lo_hz == -hi_hz;
@@ -476,7 +497,7 @@ inline std::pair<std::vector<int16_t>, std::vector<int16_t>> narrow_taps(double 
     for (uint32_t i = 0; i < n; ++i) {
         const double t = i - (n - 1) / 2.0, x = pi * (bw * t);
         const double w = n > 1 ? 0.54 + 0.46 * std::cos(pi * (2.0 * i + 1.0 - n) / (n - 1.0)) : 1.0;
-        const double lp = bw * (t == 0 ? 1.0 : std::sin(x) / x) * w;
+        const double lp = bw * detail::sinc(x) * w;
         if (real) re[i] = lp;
         else {
             const double ph = 2 * pi * fc * t;          // the correlation sum_t g[t] y[R n + t] passes +fc with g = lp exp(-j ph)
@@ -495,6 +516,20 @@ inline std::pair<std::vector<int16_t>, std::vector<int16_t>> narrow_taps(double 
     return {gr, gi};
 }
 
+// As the Python narrow_auto_shift(): the smallest chan_shift (<= 30) that keeps every |u| component <= limit -- 256 in FM mode
+// (where the reference's discriminator cannot wrap), 16384 otherwise -- for a front end whose |y| components stay within y_bound.
+inline uint32_t narrow_chan_shift(uint64_t y_bound, const std::vector<int16_t>& chan_taps_re, const std::vector<int16_t>& chan_taps_im,
+                                  uint64_t limit)
+{
+    uint64_t sum = 0;
+    for (int16_t v : chan_taps_re) sum += (uint64_t)std::abs((int)v);
+    for (int16_t v : chan_taps_im) sum += (uint64_t)std::abs((int)v);
+    const uint64_t peak = y_bound * sum;
+    uint32_t shift = 0;
+    while (shift < 30 && ((peak + (1ull << shift) - 1) >> shift) > limit) ++shift;
+    return shift;
+}
+
 // Narrow-band bank (fmd_narrow_*): run() takes [n_streams][nbytes] and returns [n_streams * n_stations] rows (row stream *
 // n_stations + station) of int16 audio -- interleaved (re, im) in IQ mode -- at capture_rate / (decim chan_decim).
 class NarrowBank {
@@ -508,44 +543,28 @@ public:
         if (!chan_taps_im.empty() && chan_taps_im.size() != chan_taps_re.size()) throw Error(FMD_ERR_INVALID_ARG);
         fmd_device_config dev{n_streams, device_id, 0};
         check(fmd_narrow_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, chan_taps_re.data(),
-                             chan_taps_im.empty() ? nullptr : chan_taps_im.data(), (uint32_t)chan_taps_re.size(), &cfg, &dev, &h_));
+                             chan_taps_im.empty() ? nullptr : chan_taps_im.data(), (uint32_t)chan_taps_re.size(), &cfg, &dev, h_.out()));
     }
-    ~NarrowBank() { fmd_narrow_free(h_); }
-    NarrowBank(const NarrowBank&) = delete;
-    NarrowBank& operator=(const NarrowBank&) = delete;
 
     // FMD_ERR_TOO_SHORT (a call that completes no audio sample) returns empty rows and changes nothing.
-    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    Rows run(const uint8_t* iq, size_t nbytes)
     {
         const size_t cap = std::max<size_t>(1, fmd_narrow_out_cap(decim_, chan_decim_, nbytes));
         const size_t rows = (size_t)n_streams_ * n_stations_;
         std::vector<int16_t> out(width_ * cap * rows);
         size_t n = 0;
         const int rc = fmd_narrow_run_batch(h_, iq, nbytes, out.data(), cap, &n);
-        if (rc == FMD_ERR_TOO_SHORT) return std::vector<std::vector<int16_t>>(rows);
+        if (rc == FMD_ERR_TOO_SHORT) return Rows(rows);
         check(rc);
-        std::vector<std::vector<int16_t>> res(rows);
-        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + width_ * r * cap, out.begin() + width_ * (r * cap + n));
-        return res;
+        return cut_rows(out, rows, cap, n, width_);
     }
-    std::pair<bool, uint32_t> level(uint32_t stream, uint32_t station)
-    {
-        int open = 0;
-        uint32_t rms = 0;
-        check(fmd_narrow_level(h_, stream, station, &open, &rms));
-        return {open != 0, rms};
-    }
-    uint64_t outputs() const
-    {
-        uint64_t n = 0;
-        check(fmd_narrow_outputs(h_, &n));
-        return n;
-    }
+    std::pair<bool, uint32_t> level(uint32_t stream, uint32_t station) { return flag_and_level(fmd_narrow_level, h_, stream, station); }
+    uint64_t outputs() const { return value_of<uint64_t>(fmd_narrow_outputs, h_); }
     void reset() { check(fmd_narrow_reset(h_)); }
 
 private:
     uint32_t decim_, chan_decim_, width_, n_streams_, n_stations_;
-    fmd_narrow* h_ = nullptr;
+    Owned<fmd_narrow, fmd_narrow_free> h_;
 };
 
 // Power spectrum (fmd_spectrum_*): power() takes [n_streams][nbytes] and returns u64 [n_streams][n_bins] in natural DFT order.
@@ -562,11 +581,8 @@ public:
         : n_bins_((uint32_t)window.size()), n_streams_(n_streams)
     {
         fmd_device_config dev{n_streams, device_id, 0};
-        check(fmd_spectrum_new(window.data(), n_bins_, hop, shift, &dev, &h_));
+        check(fmd_spectrum_new(window.data(), n_bins_, hop, shift, &dev, h_.out()));
     }
-    ~Spectrum() { fmd_spectrum_free(h_); }
-    Spectrum(const Spectrum&) = delete;
-    Spectrum& operator=(const Spectrum&) = delete;
 
     std::vector<uint64_t> power(const uint8_t* iq, size_t nbytes)
     {
@@ -574,12 +590,7 @@ public:
         check(fmd_spectrum_power_batch(h_, iq, nbytes, p.data()));
         return p;
     }
-    uint32_t bin_inc(uint32_t bin) const
-    {
-        uint32_t inc = 0;
-        check(fmd_spectrum_bin_inc(bin, n_bins_, &inc));
-        return inc;
-    }
+    uint32_t bin_inc(uint32_t bin) const { return value_of<uint32_t>(fmd_spectrum_bin_inc, bin, n_bins_); }
     // offset of bin k from the capture's centre, in Hz
     double bin_offset_hz(uint32_t k, double capture_rate) const
     {
@@ -589,7 +600,7 @@ public:
 
 private:
     uint32_t n_bins_, n_streams_;
-    fmd_spectrum* h_ = nullptr;
+    Owned<fmd_spectrum, fmd_spectrum_free> h_;
 };
 
 // Uniform channelizer (fmd_uniform_*).  The prototype, as the Python uniform_taps(): h[t] = floor(amplitude s[t] / max|s| + 1/2),
@@ -597,13 +608,10 @@ private:
 inline std::vector<int16_t> uniform_taps(uint32_t n_channels, uint32_t taps_per_channel, uint32_t amplitude = 2047)
 {
     const size_t T = (size_t)n_channels * taps_per_channel;
-    const double pi = 3.14159265358979323846;
     std::vector<double> s(T);
     double peak = 0;
     for (size_t t = 0; t < T; ++t) {
-        const double x = pi * (((double)t - ((double)T - 1) / 2.0) / n_channels);
-        const double w = T > 1 ? 0.54 - 0.46 * std::cos(2.0 * pi * (double)t / ((double)T - 1)) : 1.0;
-        s[t] = (x == 0.0 ? 1.0 : std::sin(x) / x) * w;
+        s[t] = detail::sinc(detail::pi * (((double)t - ((double)T - 1) / 2.0) / n_channels)) * detail::hamming(t, T);
         peak = std::max(peak, std::fabs(s[t]));
     }
     std::vector<int16_t> h(T);
@@ -613,9 +621,7 @@ inline std::vector<int16_t> uniform_taps(uint32_t n_channels, uint32_t taps_per_
 
 inline uint32_t uniform_channel_inc(uint32_t channel, uint32_t n_channels)
 {
-    uint32_t inc = 0;
-    check(fmd_uniform_channel_inc(channel, n_channels, &inc));
-    return inc;
+    return value_of<uint32_t>(fmd_uniform_channel_inc, channel, n_channels);
 }
 
 // The smallest shift with ceil(256 G / 2^shift) <= 16384, G = max over `channels` (empty: all) of sum_t |Wr| + |Wi|.
@@ -650,36 +656,26 @@ public:
     {
         fmd_device_config dev{n_streams, device_id, 0};
         check(fmd_uniform_new(taps.data(), (uint32_t)taps.size(), n_channels, hop, shift, channels.empty() ? nullptr : channels.data(),
-                              n_selected_, &dev, &h_));
+                              n_selected_, &dev, h_.out()));
     }
-    ~UniformChannelizer() { fmd_uniform_free(h_); }
-    UniformChannelizer(const UniformChannelizer&) = delete;
-    UniformChannelizer& operator=(const UniformChannelizer&) = delete;
 
-    std::vector<std::vector<int16_t>> run(const uint8_t* iq, size_t nbytes)
+    Rows run(const uint8_t* iq, size_t nbytes)
     {
         const size_t cap = std::max<size_t>(1, fmd_uniform_out_cap(hop_, nbytes));
         const size_t rows = (size_t)n_streams_ * n_selected_;
         std::vector<int16_t> out(2 * cap * rows);
         size_t n = 0;
         check(fmd_uniform_run_batch(h_, iq, nbytes, out.data(), cap, &n));
-        std::vector<std::vector<int16_t>> res(rows);
-        for (size_t r = 0; r < rows; ++r) res[r].assign(out.begin() + 2 * r * cap, out.begin() + 2 * (r * cap + n));
-        return res;
+        return cut_rows(out, rows, cap, n, 2);
     }
-    uint64_t outputs() const
-    {
-        uint64_t n = 0;
-        check(fmd_uniform_outputs(h_, &n));
-        return n;
-    }
+    uint64_t outputs() const { return value_of<uint64_t>(fmd_uniform_outputs, h_); }
     void reset() { check(fmd_uniform_reset(h_)); }
     int tap_digits() const { return fmd_uniform_tap_digits(h_); }
     uint32_t n_selected() const { return n_selected_; }
 
 private:
     uint32_t hop_, n_streams_, n_selected_;
-    fmd_uniform* h_ = nullptr;
+    Owned<fmd_uniform, fmd_uniform_free> h_;
 };
 
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DeviceConfig, CheckedHandle, check, lib, stream_phase_incs
+from ._ffi import DeviceConfig, DownConverter, check, lib, stream_phase_incs
 from .stations import _max_gain, stations_auto_shift
 from .stereo import FRONT_END_LIMIT
 
@@ -67,11 +67,12 @@ def narrow_auto_shift(taps, phase_incs, shift, gr, gi=None, mode=NARROW_IQ, limi
     return s
 
 
-class NarrowBank(CheckedHandle):
+class NarrowBank(DownConverter):
     """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream).  `chan_taps` is gr or the
     pair (gr, gi) (narrow_taps).  `shift=None` takes the smallest front-end shift with every |y| component <= 16384;
     `chan_shift=None` narrow_auto_shift.  `gain` is Q8."""
     _prefix = "narrow"
+    _passes = 2                                              # 0: front end; 1: channel FIR, detector, squelch
 
     def __init__(self, taps, decim, phase_incs, chan_taps, chan_decim, mode=NARROW_FM, n_streams=1, block=256, squelch=0, gain=256,
                  chan_shift=None, shift=None, device_id=-1):
@@ -102,23 +103,8 @@ class NarrowBank(CheckedHandle):
                                    self.gr.ctypes.data_as(p16), None if self.gi is None else self.gi.ctypes.data_as(p16),
                                    self.gr.size, C.byref(cfg), C.byref(dev), C.byref(self._h)))
 
-    def kernel_name(self, which=0):
-        """Pass 0 (front end) or 1 (channel FIR, detector, squelch), as rocprofv3 --kernel-trace prints it."""
-        buf = C.create_string_buffer(128)
-        check(lib().fmd_narrow_kernel_name(self._h, int(which), buf, len(buf)))
-        return buf.value.decode()
-
-    def reset(self):
-        check(lib().fmd_narrow_reset(self._h))
-
     def out_cap(self, nbytes):
         return int(lib().fmd_narrow_out_cap(self.decim, self.chan_decim, nbytes))
-
-    def outputs(self):
-        """Audio samples per (stream, station) produced since creation or reset."""
-        n = C.c_uint64(0)
-        check(lib().fmd_narrow_outputs(self._h, C.byref(n)))
-        return n.value
 
     def level(self, stream=0, station=0):
         """(open, rms) of the last completed block: the squelch state and the channel's RMS amplitude in units of u."""
@@ -128,19 +114,5 @@ class NarrowBank(CheckedHandle):
 
     def run_batch(self, iq):
         """iq uint8 [n_streams, nbytes] -> int16 [n_streams, n_stations, n] ([..., 2] of (re, im) in IQ mode)."""
-        iq = np.ascontiguousarray(iq, dtype=np.uint8)
-        if iq.ndim != 2 or iq.shape[0] != self.n_streams:
-            raise ValueError("iq must be [n_streams, nbytes]")
-        cap = max(1, self.out_cap(iq.shape[1]))
-        out = np.empty((self.n_streams, self.n_stations, cap, self.width), dtype=np.int16)
-        n = C.c_size_t(0)
-        check(lib().fmd_narrow_run_batch(self._h, iq.ctypes.data, iq.shape[1], out.ctypes.data, cap, C.byref(n)))
-        out = out[:, :, :n.value]
-        return out.copy() if self.mode == NARROW_IQ else out[..., 0].copy()
-
-    def run_device(self, d_iq, nbytes, d_out, out_cap, stream=None):
-        """Enqueue on device pointers (d_out [n_streams][n_stations][out_cap][width] int16); returns the audio samples per (stream,
-        station).  `stream` must stay alive until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
-        n = C.c_size_t(0)
-        check(lib().fmd_narrow_run_device(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
-        return n.value
+        out = super().run_batch(iq)
+        return out if self.mode == NARROW_IQ else out[..., 0].copy()

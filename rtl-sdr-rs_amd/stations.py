@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DemodState, DeviceConfig, CheckedHandle, check, lib, stream_phase_incs
+from ._ffi import DemodState, BankHandle, DeviceConfig, check, lib, stream_phase_incs
 
 
 def phase_inc(offset_hz, rate):
@@ -43,7 +43,7 @@ def stations_auto_shift(taps, phase_incs, limit=2048):
     return s
 
 
-class StationBank(CheckedHandle):
+class StationBank(BankHandle):
     """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream)."""
     _prefix = "stations"
 
@@ -59,9 +59,6 @@ class StationBank(CheckedHandle):
         check(lib().fmd_stations_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim, self.shift,
                                      self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations, self.rate_out,
                                      self.rate_resample, C.byref(dev), C.byref(self._h)))
-
-    def reset(self):
-        check(lib().fmd_stations_reset(self._h))
 
     def out_cap(self, nbytes):
         return int(lib().fmd_stations_out_cap(self.decim, self.rate_out, self.rate_resample, nbytes))

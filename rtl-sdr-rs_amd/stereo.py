@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DeviceConfig, CheckedHandle, check, lib, stream_phase_incs
+from ._ffi import DeviceConfig, DownConverter, check, lib, stream_phase_incs
 from .stations import stations_auto_shift
 
 
@@ -62,11 +62,12 @@ def pilot_inc(capture_rate, decim):
     return inc.value
 
 
-class StereoBank(CheckedHandle):
+class StereoBank(DownConverter):
     """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream).  `shift=None` takes the smallest
     front-end shift with every |y| component <= 256 (FRONT_END_LIMIT); `pilot_min=None` a quarter of a nominal pilot;
-    `audio_shift=None` default_audio_shift."""
+    `audio_shift=None` default_audio_shift.  run_batch returns [n_streams, n_stations, n_audio, 2] of (L, R)."""
     _prefix = "stereo"
+    _passes = 2                                              # 0: front end, discriminator, pilot sums; 1: carrier, FIRs, matrix
 
     def __init__(self, taps, decim, phase_incs, capture_rate, audio_taps, audio_decim, n_streams=1, block=4096, pilot_min=None,
                  audio_shift=None, shift=None, device_id=-1):
@@ -89,44 +90,11 @@ class StereoBank(CheckedHandle):
                                    self.audio_taps.ctypes.data_as(C.POINTER(C.c_int16)), self.audio_taps.size, C.byref(cfg),
                                    C.byref(dev), C.byref(self._h)))
 
-    def kernel_name(self, which=0):
-        """Pass 0 (front end, discriminator, pilot sums) or 1 (carrier, FIRs, matrix), as rocprofv3 --kernel-trace prints it."""
-        buf = C.create_string_buffer(128)
-        check(lib().fmd_stereo_kernel_name(self._h, int(which), buf, len(buf)))
-        return buf.value.decode()
-
-    def reset(self):
-        check(lib().fmd_stereo_reset(self._h))
-
     def out_cap(self, nbytes):
         return int(lib().fmd_stereo_out_cap(self.decim, self.audio_decim, nbytes))
-
-    def outputs(self):
-        """Audio samples per (stream, station) produced since creation or reset."""
-        n = C.c_uint64(0)
-        check(lib().fmd_stereo_outputs(self._h, C.byref(n)))
-        return n.value
 
     def pilot(self, stream=0, station=0):
         """(present, level) of the last completed block: the stereo indicator and the pilot amplitude in discriminator units."""
         p, lv = C.c_int(0), C.c_uint32(0)
         check(lib().fmd_stereo_pilot(self._h, int(stream), int(station), C.byref(p), C.byref(lv)))
         return bool(p.value), lv.value
-
-    def run_batch(self, iq):
-        """iq uint8 [n_streams, nbytes] -> int16 array [n_streams, n_stations, n_audio, 2] of (L, R)."""
-        iq = np.ascontiguousarray(iq, dtype=np.uint8)
-        if iq.ndim != 2 or iq.shape[0] != self.n_streams:
-            raise ValueError("iq must be [n_streams, nbytes]")
-        cap = max(1, self.out_cap(iq.shape[1]))
-        out = np.empty((self.n_streams, self.n_stations, cap, 2), dtype=np.int16)
-        n = C.c_size_t(0)
-        check(lib().fmd_stereo_run_batch(self._h, iq.ctypes.data, iq.shape[1], out.ctypes.data, cap, C.byref(n)))
-        return out[:, :, :n.value].copy()
-
-    def run_device(self, d_iq, nbytes, d_out, out_cap, stream=None):
-        """Enqueue on device pointers (d_out [n_streams][n_stations][out_cap][2] int16); returns the audio samples per (stream,
-        station).  `stream` must stay alive until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
-        n = C.c_size_t(0)
-        check(lib().fmd_stereo_run_device(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
-        return n.value

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DeviceConfig, CheckedHandle, check, lib
+from ._ffi import DeviceConfig, DownConverter, check, lib
 from .stations import stations_auto_shift
 
 
@@ -40,10 +40,11 @@ def uniform_auto_shift(taps, n_channels, channels=None):
     return stations_auto_shift(taps, incs, limit=16384)
 
 
-class UniformChannelizer(CheckedHandle):
+class UniformChannelizer(DownConverter):
     """All `n_channels` channels (or the strictly increasing selection `channels`) of every stream, one output per `hop` input
     samples.  `shift=None` takes the smallest normalisation shift with |y| <= 16384."""
     _prefix = "uniform"
+    _rows = "n_selected"                                     # run_batch: [n_streams, n_selected, n_out, 2] of (yr, yi)
 
     def __init__(self, taps, n_channels, hop, channels=None, n_streams=1, shift=None, device_id=-1):
         self.taps = np.ascontiguousarray(taps, dtype=np.int16)
@@ -58,36 +59,9 @@ class UniformChannelizer(CheckedHandle):
         check(lib().fmd_uniform_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.n_channels, self.hop,
                                     self.shift, sel, self.n_selected, C.byref(dev), C.byref(self._h)))
 
-    def reset(self):
-        check(lib().fmd_uniform_reset(self._h))
-
     def out_cap(self, nbytes):
         return int(lib().fmd_uniform_out_cap(self.hop, nbytes))
-
-    def outputs(self):
-        """Outputs per (stream, channel) produced since creation or reset: the index m of the next one."""
-        n = C.c_uint64(0)
-        check(lib().fmd_uniform_outputs(self._h, C.byref(n)))
-        return n.value
 
     def tap_digits(self):
         """1 or 2: the i8 digits per tap on the matrix cores."""
         return int(lib().fmd_uniform_tap_digits(self._h))
-
-    def run_batch(self, iq):
-        """iq uint8 [n_streams, nbytes] -> int16 array [n_streams, n_selected, n_out, 2] of (yr, yi)."""
-        iq = np.ascontiguousarray(iq, dtype=np.uint8)
-        if iq.ndim != 2 or iq.shape[0] != self.n_streams:
-            raise ValueError("iq must be [n_streams, nbytes]")
-        cap = max(1, self.out_cap(iq.shape[1]))
-        out = np.empty((self.n_streams, self.n_selected, cap, 2), dtype=np.int16)
-        n = C.c_size_t(0)
-        check(lib().fmd_uniform_run_batch(self._h, iq.ctypes.data, iq.shape[1], out.ctypes.data, cap, C.byref(n)))
-        return out[:, :, :n.value].copy()
-
-    def run_device(self, d_iq, nbytes, d_out, out_cap, stream=None):
-        """Enqueue on device pointers (d_out [n_streams][n_selected][out_cap][2] int16); returns the outputs per (stream, channel).
-        `stream` must stay alive until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
-        n = C.c_size_t(0)
-        check(lib().fmd_uniform_run_device(self._h, d_iq, nbytes, d_out, out_cap, C.byref(n), stream))
-        return n.value

@@ -4,59 +4,22 @@ at 240 kHz.  Per K (--k 1,4,8,16): ms per call (HIP events), input and output by
 test-side definition (tests/channelizer_ref.py) on a seeded sample of streams, and two baselines timed in the same process: the
 station bank at the same K (which computes the same y and then demodulates), and what a user writes today in torch (u8 -> float,
 a complex mix per station, conv1d with stride D).  Writes every line to --out (profiles/channelizer_bench.json)."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-import rtl_sdr_rs_amd as fmd
+import bench_common as bc
+from bench_common import fmd, time_calls
 
 FS, D, T, FAST, SLOW = 2400000, 10, 64, 240000, 32000
-
-
-def lowpass(T, cutoff):
-    n = np.arange(T) - (T - 1) / 2
-    h = np.sinc(2 * cutoff * n) * np.hamming(T)
-    h = h / np.abs(h).max()
-    return np.round(h * 2047).astype(np.int16)
-
-
-def time_calls(launch, iters, reps=3):
-    for _ in range(3):
-        launch(0)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(iters):
-            launch(i)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / iters)
-    return sorted(ts)[len(ts) // 2], ts
 
 
 def run(K, S, n, iters, parity_streams):
     import channelizer_ref as cr
     import stations_ref as sr
-    h = lowpass(T, 100000 / FS)
-    rng = np.random.default_rng(K)
-    offs = np.linspace(-1000000, 1000000, K) if K > 1 else np.array([300000.0])
-    incs = np.array([[fmd.phase_inc(int(o) + int(rng.integers(-5000, 5000)), FS) for o in offs] for _ in range(S)], np.uint32)
+    h = bc.lowpass(T, 100000 / FS)
+    incs = bc.station_incs(K, S, FS)
     ch = fmd.Channelizer(h, D, incs, n_streams=S, device_id=0)
-    stream = torch.cuda.current_stream().cuda_stream
-    bufs = []
-    for b in range(2):
-        t = torch.empty((S, n), dtype=torch.uint8, device="cuda")
-        fmd.synth.fill_device(t.data_ptr(), S, n, sample_offset=b * (n // 2), stream=stream)
-        bufs.append(t)
+    bufs, stream = bc.device_buffers(S, n)
     cap = ch.out_cap(n)
     out = torch.empty((S, K, cap, 2), dtype=torch.int16, device="cuda")
     got = {}
@@ -99,7 +62,7 @@ def run(K, S, n, iters, parity_streams):
     torch.cuda.empty_cache()
     # parity: a fresh channelizer, two calls, sampled streams against the definition
     pc = fmd.Channelizer(h, D, incs, n_streams=S, device_id=0)
-    sample = sorted(np.random.default_rng(7).choice(S, min(parity_streams, S), replace=False).tolist())
+    sample = bc.parity_sample(S, parity_streams)
     refs = {s: cr.ChannelizerRef(h, D, incs[s], pc.shift, z=sr.z_corr) for s in sample}
     ok = True
     for b in range(2):
@@ -121,23 +84,16 @@ def run(K, S, n, iters, parity_streams):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = bc.parser()
     ap.add_argument("--k", default="1,4,8,16")
-    ap.add_argument("--streams", type=int, default=512)
-    ap.add_argument("--nbytes", type=int, default=fmd.DEFAULT_BUF_LENGTH)
-    ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--parity-streams", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "channelizer_bench.json"))
+    bc.add_out(ap, "channelizer_bench.json")
     a = ap.parse_args()
     rows = []
     for K in [int(x) for x in a.k.split(",")]:
         rows.append(run(K, a.streams, a.nbytes, a.iters, a.parity_streams))
-        print(json.dumps(rows[-1]), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
-            f.write("\n")
+        bc.emit(rows[-1])
+    bc.write_rows(a.out, rows=rows)
 
 
 if __name__ == "__main__":

@@ -5,37 +5,14 @@ ms per call (HIP events, both passes), a parity bit against the test-side defini
 streams, and two baselines timed in the same process: the channelizer at the same K and shift (pass 1 alone: the floor), and the
 same chain in float torch (u8 -> mix -> conv1d stride D -> complex conv1d stride R -> abs / angle / real).  Writes every line to
 --out (profiles/narrow_bench.json)."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-import rtl_sdr_rs_amd as fmd
+import bench_common as bc
+from bench_common import fmd, time_calls
 
 FS, D, T, R, TA, P = 2400000, 10, 64, 20, 256, 256
 BANDS = {"iq": (-5000, 5000), "fm": (-6000, 6000), "am": (-4000, 4000), "usb": (300, 3000)}
-
-
-def time_calls(launch, iters, reps=3):
-    for _ in range(3):
-        launch(0)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(iters):
-            launch(i)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / iters)
-    return sorted(ts)[len(ts) // 2], ts
 
 
 def torch_chain(bufs, incs, h, gr, gi, mode, S, K, n, chunk):
@@ -77,17 +54,9 @@ def torch_chain(bufs, incs, h, gr, gi, mode, S, K, n, chunk):
 def run(K, S, n, iters, parity_streams, modes):
     import narrow_ref as nr
     import stations_ref as sr
-    import stereo_ref as st
-    h = st.lowpass(T, 100000 / FS)
-    rng = np.random.default_rng(K)
-    offs = np.linspace(-1000000, 1000000, K) if K > 1 else np.array([300000.0])
-    incs = np.array([[fmd.phase_inc(int(o) + int(rng.integers(-5000, 5000)), FS) for o in offs] for _ in range(S)], np.uint32)
-    stream = torch.cuda.current_stream().cuda_stream
-    bufs = []
-    for b in range(2):
-        t = torch.empty((S, n), dtype=torch.uint8, device="cuda")
-        fmd.synth.fill_device(t.data_ptr(), S, n, sample_offset=b * (n // 2), stream=stream)
-        bufs.append(t)
+    h = bc.lowpass(T, 100000 / FS)
+    incs = bc.station_incs(K, S, FS)
+    bufs, stream = bc.device_buffers(S, n)
     shift = fmd.stations_auto_shift(h, incs, limit=16384)
     # the floor: the channelizer at the same K and shift (pass 1 alone)
     ch = fmd.Channelizer(h, D, incs, n_streams=S, shift=shift, device_id=0)
@@ -117,7 +86,7 @@ def run(K, S, n, iters, parity_streams, modes):
         torch.cuda.empty_cache()
         # parity: a fresh bank, two calls, sampled streams against the definition
         pb = mk()
-        sample = sorted(np.random.default_rng(7).choice(S, min(parity_streams, S), replace=False).tolist())
+        sample = bc.parity_sample(S, parity_streams)
         refs = {s: nr.NarrowRef(h, D, incs[s], pb.shift, pb.gr, pb.gi, pb.mode, R, pb.chan_shift, P, pb.squelch, pb.gain, z=sr.z_corr)
                 for s in sample}
         ok = True
@@ -138,29 +107,22 @@ def run(K, S, n, iters, parity_streams, modes):
                      "torch_ms": None if ms_torch is None else round(ms_torch, 3), "torch_ms_all": [round(t, 3) for t in ts_torch],
                      "speedup_vs_torch": None if ms_torch is None else round(ms_torch / ms, 1),
                      "parity": bool(ok), "parity_streams": sample})
-        print(json.dumps(rows[-1]), flush=True)
+        bc.emit(rows[-1])
         del nb, pb, out
     return rows
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = bc.parser()
     ap.add_argument("--k", default="1,4,8,16,32")
     ap.add_argument("--modes", default="iq,fm,am,usb")
-    ap.add_argument("--streams", type=int, default=512)
-    ap.add_argument("--nbytes", type=int, default=fmd.DEFAULT_BUF_LENGTH)
-    ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--parity-streams", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "narrow_bench.json"))
+    bc.add_out(ap, "narrow_bench.json")
     a = ap.parse_args()
     rows = []
     for K in [int(x) for x in a.k.split(",")]:
         rows += run(K, a.streams, a.nbytes, a.iters, a.parity_streams, a.modes.split(","))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
-            f.write("\n")
+    bc.write_rows(a.out, rows=rows)
 
 
 if __name__ == "__main__":

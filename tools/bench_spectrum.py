@@ -4,34 +4,11 @@ windows of amplitude 127 and 2047), against the same power computed the way a us
 torch.fft.fft, |.|^2, sum over frames).  One JSON line per (N, digits) and all of them in --out: ms per call (HIP events), input
 TB/s, i8 MACs per second (S F x 2 N digits rows x 2 N bytes), and a parity bit against the test-side definition
 (tests/spectrum_ref.py) on a seeded sample of streams."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-import rtl_sdr_rs_amd as fmd
-
-
-def time_calls(launch, iters, reps=3):
-    for _ in range(3):
-        launch(0)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(iters):
-            launch(i)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / iters)
-    return sorted(ts)[len(ts) // 2], ts
+import bench_common as bc
+from bench_common import fmd, time_calls
 
 
 def run(N, digits, S, n, iters, parity_streams, bufs):
@@ -63,7 +40,7 @@ def run(N, digits, S, n, iters, parity_streams, bufs):
     torch.cuda.synchronize()
     got = power.cpu().numpy().view(np.uint64)
     host = bufs[(iters - 1) % 2].cpu().numpy()
-    sample = sorted(np.random.default_rng(7).choice(S, min(parity_streams, S), replace=False).tolist())
+    sample = bc.parity_sample(S, parity_streams)
     ok = all(np.array_equal(got[s], spr.power(w, N, shift, host[s:s + 1])[0]) for s in sample)
     F = sp.frames(n)
     macs = S * F * (2 * N * digits) * (2 * N)
@@ -75,31 +52,19 @@ def run(N, digits, S, n, iters, parity_streams, bufs):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = bc.parser()
     ap.add_argument("--bins", default="64,256")
-    ap.add_argument("--streams", type=int, default=512)
-    ap.add_argument("--nbytes", type=int, default=fmd.DEFAULT_BUF_LENGTH)
-    ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--parity-streams", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spectrum_bench.json"))
+    bc.add_out(ap, "spectrum_bench.json")
     a = ap.parse_args()
-    stream = torch.cuda.current_stream().cuda_stream
-    bufs = []
-    for b in range(2):
-        t = torch.empty((a.streams, a.nbytes), dtype=torch.uint8, device="cuda")
-        fmd.synth.fill_device(t.data_ptr(), a.streams, a.nbytes, sample_offset=b * (a.nbytes // 2), stream=stream)
-        bufs.append(t)
+    bufs, _ = bc.device_buffers(a.streams, a.nbytes)
     rows = []
     for N in [int(x) for x in a.bins.split(",")]:
         for d in (1, 2):
             r = run(N, d, a.streams, a.nbytes, a.iters, a.parity_streams, bufs)
-            print(json.dumps(r), flush=True)
+            bc.emit(r)
             rows.append(r)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
-            f.write("\n")
+    bc.write_rows(a.out, rows=rows)
 
 
 if __name__ == "__main__":

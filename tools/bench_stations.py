@@ -3,59 +3,22 @@
 against the same S streams through K fmd_firdemod launches (what a user can do today, without even the mixing).  One JSON
 line per K (--k 1,4,8,16): ms per call (HIP events), input TB/s, station-outputs/s, and a parity bit against the test-side
 definition (tests/stations_ref.py) on a seeded sample of streams."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-import rtl_sdr_rs_amd as fmd
+import bench_common as bc
+from bench_common import fmd, time_calls
 
 FS, D, T, FAST, SLOW = 2400000, 10, 64, 240000, 32000
-
-
-def lowpass(T, cutoff):
-    n = np.arange(T) - (T - 1) / 2
-    h = np.sinc(2 * cutoff * n) * np.hamming(T)
-    h = h / np.abs(h).max()
-    return np.round(h * 2047).astype(np.int16)
-
-
-def time_calls(launch, iters, reps=3):
-    for _ in range(5):
-        launch(0)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(iters):
-            launch(i)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / iters)
-    return sorted(ts)[len(ts) // 2], ts
 
 
 def run(K, S, n, iters, parity_streams):
     import oracle_lib
     import stations_ref as sr
-    h = lowpass(T, 100000 / FS)
-    rng = np.random.default_rng(K)
-    offs = np.linspace(-1000000, 1000000, K) if K > 1 else np.array([300000.0])
-    incs = np.array([[fmd.phase_inc(int(o) + int(rng.integers(-5000, 5000)), FS) for o in offs] for _ in range(S)], np.uint32)
+    h = bc.lowpass(T, 100000 / FS)
+    incs = bc.station_incs(K, S, FS)
     bank = fmd.StationBank(h, D, incs, FAST, SLOW, n_streams=S, device_id=0)
-    stream = torch.cuda.current_stream().cuda_stream
-    bufs = []
-    for b in range(2):
-        t = torch.empty((S, n), dtype=torch.uint8, device="cuda")
-        fmd.synth.fill_device(t.data_ptr(), S, n, sample_offset=b * (n // 2), stream=stream)
-        bufs.append(t)
+    bufs, stream = bc.device_buffers(S, n)
     cap = bank.out_cap(n)
     out = torch.zeros((S, K, cap), dtype=torch.int16, device="cuda")
     got = {}
@@ -63,7 +26,7 @@ def run(K, S, n, iters, parity_streams):
     def launch(i):
         got["n"] = bank.demodulate_device(bufs[i % 2].data_ptr(), n, out.data_ptr(), cap, stream)
 
-    ms, ts = time_calls(launch, iters)
+    ms, ts = time_calls(launch, iters, warmup=5)
     bank.check()
     # K fmd_firdemod launches over the same streams (real taps, no mixing)
     fd = fmd.FirDemodBank(h, D, FAST, SLOW, S, device_id=0)
@@ -74,11 +37,11 @@ def run(K, S, n, iters, parity_streams):
         for _ in range(K):
             fd.demodulate_device(bufs[i % 2].data_ptr(), n, fout.data_ptr(), fcap, stream)
 
-    ms_fd, ts_fd = time_calls(launch_fd, max(2, iters // max(1, K // 2)))
+    ms_fd, ts_fd = time_calls(launch_fd, max(2, iters // max(1, K // 2)), warmup=5)
     fd.check()
     # parity: a fresh bank, two calls, sampled streams against the definition
     pb = fmd.StationBank(h, D, incs, FAST, SLOW, n_streams=S, device_id=0)
-    sample = sorted(np.random.default_rng(7).choice(S, min(parity_streams, S), replace=False).tolist())
+    sample = bc.parity_sample(S, parity_streams)
     o = oracle_lib.load()
     refs = {s: sr.StationsRef(o, h, D, incs[s], FAST, SLOW, pb.shift) for s in sample}
     ok = True
@@ -98,15 +61,12 @@ def run(K, S, n, iters, parity_streams):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = bc.parser()
     ap.add_argument("--k", default="1,4,8,16")
-    ap.add_argument("--streams", type=int, default=512)
-    ap.add_argument("--nbytes", type=int, default=fmd.DEFAULT_BUF_LENGTH)
-    ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--parity-streams", type=int, default=2)
     a = ap.parse_args()
     for K in [int(x) for x in a.k.split(",")]:
-        print(json.dumps(run(K, a.streams, a.nbytes, a.iters, a.parity_streams)), flush=True)
+        bc.emit(run(K, a.streams, a.nbytes, a.iters, a.parity_streams))
 
 
 if __name__ == "__main__":

@@ -5,53 +5,23 @@ both passes and the block-sum reset), a parity bit against the test-side definit
 streams, and three baselines timed in the same process: the channelizer and the station bank at the same K, and the same chain in
 float torch (u8 -> mix -> conv1d -> angle -> block pilot correlation -> carrier -> conv1d with stride R).  Writes every line to --out
 (profiles/stereo_bench.json)."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-import rtl_sdr_rs_amd as fmd
+import bench_common as bc
+from bench_common import fmd, time_calls
 
 FS, D, T, R, TA, P = 2400000, 10, 64, 5, 127, 4096
-
-
-def time_calls(launch, iters, reps=3):
-    for _ in range(3):
-        launch(0)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(iters):
-            launch(i)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / iters)
-    return sorted(ts)[len(ts) // 2], ts
 
 
 def run(K, S, n, iters, parity_streams):
     import stations_ref as sr
     import stereo_ref as st
-    h = st.lowpass(T, 130000 / FS)
+    h = bc.lowpass(T, 130000 / FS)
     g = fmd.stereo_taps(FS // D, R, TA)
-    rng = np.random.default_rng(K)
-    offs = np.linspace(-1000000, 1000000, K) if K > 1 else np.array([300000.0])
-    incs = np.array([[fmd.phase_inc(int(o) + int(rng.integers(-5000, 5000)), FS) for o in offs] for _ in range(S)], np.uint32)
+    incs = bc.station_incs(K, S, FS)
     sb = fmd.StereoBank(h, D, incs, FS, g, R, n_streams=S, block=P, device_id=0)
-    stream = torch.cuda.current_stream().cuda_stream
-    bufs = []
-    for b in range(2):
-        t = torch.empty((S, n), dtype=torch.uint8, device="cuda")
-        fmd.synth.fill_device(t.data_ptr(), S, n, sample_offset=b * (n // 2), stream=stream)
-        bufs.append(t)
+    bufs, stream = bc.device_buffers(S, n)
     cap = sb.out_cap(n)
     out = torch.empty((S, K, cap, 2), dtype=torch.int16, device="cuda")
     got = {}
@@ -112,7 +82,7 @@ def run(K, S, n, iters, parity_streams):
     torch.cuda.empty_cache()
     # parity: a fresh bank, two calls, sampled streams against the definition
     pb = fmd.StereoBank(h, D, incs, FS, g, R, n_streams=S, block=P, device_id=0)
-    sample = sorted(np.random.default_rng(7).choice(S, min(parity_streams, S), replace=False).tolist())
+    sample = bc.parity_sample(S, parity_streams)
     refs = {s: st.StereoRef(h, D, incs[s], pb.shift, FS, g, R, P, pb.pilot_min, pb.audio_shift, z=sr.z_corr) for s in sample}
     ok = True
     for b in range(2):
@@ -138,23 +108,16 @@ def run(K, S, n, iters, parity_streams):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = bc.parser()
     ap.add_argument("--k", default="1,4,8,16")
-    ap.add_argument("--streams", type=int, default=512)
-    ap.add_argument("--nbytes", type=int, default=fmd.DEFAULT_BUF_LENGTH)
-    ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--parity-streams", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stereo_bench.json"))
+    bc.add_out(ap, "stereo_bench.json")
     a = ap.parse_args()
     rows = []
     for K in [int(x) for x in a.k.split(",")]:
         rows.append(run(K, a.streams, a.nbytes, a.iters, a.parity_streams))
-        print(json.dumps(rows[-1]), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
-            f.write("\n")
+        bc.emit(rows[-1])
+    bc.write_rows(a.out, rows=rows)
 
 
 if __name__ == "__main__":

@@ -7,38 +7,15 @@ stream and a few channels over two calls, and two baselines timed in the same pr
     to its central 256 taps (a shorter, worse filter: the channelizer admits no more) -- only where hop <= 64;
   - what a torch user writes: u8 -> complex64, frames by unfold, window, fold to N, torch.fft.fft.
 Writes every line to --out (profiles/uniform_bench.json)."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-import rtl_sdr_rs_amd as fmd
+import bench_common as bc
+from bench_common import fmd, time_calls
 
 FS = 2400000
 ROWS = [(16, 8, 128, None), (128, 64, 1024, None), (256, 128, 2048, None), (128, 64, 1024, 32)]
 PEAK_MACS = 256 * 4 * (16 * 16 * 64 / 16.0) * 2.4e9        # 256 CUs x 4 SIMDs x one 16x16x64 MFMA per 16 cycles at 2.4 GHz
-
-
-def time_calls(launch, iters, reps=3):
-    for _ in range(3):
-        launch(0)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(iters):
-            launch(i)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / iters)
-    return sorted(ts)[len(ts) // 2], ts
 
 
 def torch_chain(bufs, h, N, hop, S, n, chunk):
@@ -61,12 +38,7 @@ def run(N, hop, T, nsel, S, n, iters):
     import uniform_ref as ur
     h = fmd.uniform_taps(N, T // N)
     sel = None if nsel is None else [int(k) for k in np.linspace(0, N - 1, nsel).astype(int)]
-    stream = torch.cuda.current_stream().cuda_stream
-    bufs = []
-    for b in range(2):
-        t = torch.empty((S, n), dtype=torch.uint8, device="cuda")
-        fmd.synth.fill_device(t.data_ptr(), S, n, sample_offset=b * (n // 2), stream=stream)
-        bufs.append(t)
+    bufs, stream = bc.device_buffers(S, n)
     mk = lambda: fmd.UniformChannelizer(h, N, hop, channels=sel, n_streams=S, device_id=0)
     u = mk()
     K = u.n_selected
@@ -132,24 +104,17 @@ def run(N, hop, T, nsel, S, n, iters):
         a = out[s, :, :m].cpu().numpy()[pick]
         ok &= bool(np.array_equal(a, ref.feed(host)))
     row.update({"parity": bool(ok), "parity_stream": s, "parity_rows": pick})
-    print(json.dumps(row), flush=True)
+    bc.emit(row)
     return row
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = bc.parser()
     ap.add_argument("--rows", default="0,1,2,3")
-    ap.add_argument("--streams", type=int, default=512)
-    ap.add_argument("--nbytes", type=int, default=fmd.DEFAULT_BUF_LENGTH)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "uniform_bench.json"))
+    bc.add_out(ap, "uniform_bench.json")
     a = ap.parse_args()
     rows = [run(*ROWS[int(i)], a.streams, a.nbytes, a.iters) for i in a.rows.split(",")]
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "peak_macs_per_s": PEAK_MACS, "rows": rows}, f, indent=1)
-            f.write("\n")
+    bc.write_rows(a.out, peak_macs_per_s=PEAK_MACS, rows=rows)
 
 
 if __name__ == "__main__":
