@@ -682,6 +682,49 @@ int fmd_uniform_tap_digits(const fmd_uniform *u);
 /* Name of the kernel this handle launches, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_uniform_kernel_name(const fmd_uniform *u, char *name, size_t cap);
 
+/* ---- band-plan bank: audio and squelch for every channel of a plan ---------------------------------------------- */
+/* NEW SURFACE (the reference has none).  The uniform channelizer's y of every selected channel of a band plan, fed to the
+ * narrow-band bank's second stage: a complex decimating FIR, one of four detectors and a block-wise squelch per channel, plus an
+ * activity map of the whole plan.  Definition (integers only; tests/bandplan_ref.py), per stream and selected channel k -- the
+ * composition of two definitions above, with no new arithmetic:
+ *   y[k][m]   exactly the uniform channelizer's: the same prototype h, n_channels, hop, shift, `channels` selection, history and
+ *             call rules
+ *   v, u, a, E_j, A_j, open_j, dc_j, w, out   exactly the narrow-band bank's over that y: taps (gr + j gi) at stride R, chan_shift,
+ *             blocks of P audio samples using the previous block's estimates, the modes FMD_NARROW_IQ / FM / AM / SSB, the Q8 gain,
+ *             sat16, the squelch; cfg is the narrow-band bank's fmd_narrow_config, one for all channels
+ * out is [n_streams][n_selected][out_cap][width] int16, width = fmd_narrow_out_width(mode), at capture_rate / (hop R).
+ * Domain (else FMD_ERR_UNSUPPORTED, decided before a device is queried): the uniform channelizer's for stage one, whose bound is
+ * B_y = ceil(256 G / 2^shift) <= 16384 over the selected channels; the narrow-band bank's for stage two with 1 <= R <= 8,
+ * 1 <= Ta <= 64 and ceil(B_y sum(|gr| + |gi|) / 2^chan_shift) <= 16384.
+ * Calls are whole hops: nbytes % (2 hop) != 0 -> FMD_ERR_BAD_LENGTH.  A call that completes no audio sample -> FMD_ERR_TOO_SHORT and
+ * changes NOTHING -- neither the carried stage-one history nor any output count -- even when it would have completed stage-one
+ * outputs.  The output does not depend on how the stream is cut into calls.  Stream lifetime and completion points: as
+ * fmd_channelizer_* (fmd_bandplan_check). */
+typedef struct fmd_bandplan fmd_bandplan;
+int fmd_bandplan_new(const int16_t *taps, uint32_t n_taps, uint32_t n_channels, uint32_t hop, uint32_t shift,
+                     const uint32_t *channels, uint32_t n_selected, const int16_t *chan_taps_re, const int16_t *chan_taps_im,
+                     uint32_t n_chan_taps, const fmd_narrow_config *cfg, const fmd_device_config *dev, fmd_bandplan **out);
+void fmd_bandplan_free(fmd_bandplan *b);
+int fmd_bandplan_reset(fmd_bandplan *b);
+/* ceil(nbytes / (2 hop R)): audio samples one call of nbytes can complete per (stream, channel), whatever the history; 0 for hop 0
+ * or R 0. */
+size_t fmd_bandplan_out_cap(uint32_t hop, uint32_t chan_decim, size_t nbytes);
+/* HOST buffers; *out_len = audio samples per (stream, channel) (the same for all). */
+int fmd_bandplan_run_batch(fmd_bandplan *b, const uint8_t *iq, size_t nbytes, int16_t *out, size_t out_cap, size_t *out_len);
+/* DEVICE buffers (d_iq 4-byte aligned, d_out 4-byte aligned in IQ mode and 2-byte otherwise, any out_cap), enqueued on `stream`
+ * without synchronising; *out_len as above. */
+int fmd_bandplan_run_device(fmd_bandplan *b, const void *d_iq, size_t nbytes, void *d_out, size_t out_cap, size_t *out_len,
+                            void *stream);
+int fmd_bandplan_check(fmd_bandplan *b);
+/* Audio samples per (stream, channel) produced since creation or the last reset. */
+int fmd_bandplan_outputs(const fmd_bandplan *b, uint64_t *outputs);
+/* The activity map, HOST arrays [n_streams][n_selected], every row in one copy: open = open_j and rms = isqrt(E_j >> log2 P) of the
+ * last completed block (zeros before the first block completes).  Synchronises first. */
+int fmd_bandplan_levels(fmd_bandplan *b, uint8_t *open, uint32_t *rms);
+/* Name of pass 0 (the uniform channelizer's kernel) or 1 (channel FIR, detector, squelch), as `rocprofv3 --kernel-trace` prints
+ * it. */
+int fmd_bandplan_kernel_name(const fmd_bandplan *b, uint32_t pass, char *name, size_t cap);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

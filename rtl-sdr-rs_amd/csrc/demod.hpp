@@ -678,6 +678,77 @@ private:
     Owned<fmd_uniform, fmd_uniform_free> h_;
 };
 
+// B_y of the uniform channelizer at `shift`: ceil(256 G / 2^shift), G = max over `channels` (empty: all) of sum_t |Wr| + |Wi|.
+inline uint64_t uniform_y_bound(const std::vector<int16_t>& taps, uint32_t n_channels, uint32_t shift, const std::vector<uint32_t>& channels = {})
+{
+    int16_t tab[1024];
+    check(fmd_stations_nco_table(tab));
+    uint64_t gain = 0;
+    const size_t rows = channels.empty() ? n_channels : channels.size();
+    for (size_t i = 0; i < rows; ++i) {
+        const uint32_t inc = uniform_channel_inc(channels.empty() ? (uint32_t)i : channels[i], n_channels);
+        uint64_t g = 0;
+        for (size_t t = 0; t < taps.size(); ++t) {
+            const uint32_t ix = ((uint32_t)t * inc) >> 22;
+            const int32_t wr = (taps[t] * tab[ix] + 8192) >> 14, wi = (-taps[t] * tab[(ix - 256u) & 1023u] + 8192) >> 14;
+            g += (uint64_t)std::abs(wr) + (uint64_t)std::abs(wi);
+        }
+        gain = std::max(gain, g);
+    }
+    return (256 * gain + ((1ull << shift) - 1)) >> shift;
+}
+
+// Band-plan bank (fmd_bandplan_*): run() takes [n_streams][nbytes] (whole hops) and returns [n_streams * n_selected] rows (row
+// stream * n_selected + selected channel) of int16 audio -- interleaved (re, im) in IQ mode -- at capture_rate / (hop chan_decim);
+// levels() is the activity map of the last completed block, one (open, rms) per row.
+class BandPlanBank {
+public:
+    // `channels` empty: all n_channels
+    BandPlanBank(const std::vector<int16_t>& taps, uint32_t n_channels, uint32_t hop, uint32_t shift, const std::vector<uint32_t>& channels,
+                 uint32_t n_streams, const std::vector<int16_t>& chan_taps_re, const std::vector<int16_t>& chan_taps_im,
+                 const fmd_narrow_config& cfg, int32_t device_id = -1)
+        : hop_(hop), chan_decim_(cfg.chan_decim), width_(fmd_narrow_out_width(cfg.mode)), n_streams_(n_streams),
+          n_selected_(channels.empty() ? n_channels : (uint32_t)channels.size())
+    {
+        if (!chan_taps_im.empty() && chan_taps_im.size() != chan_taps_re.size()) throw Error(FMD_ERR_INVALID_ARG);
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_bandplan_new(taps.data(), (uint32_t)taps.size(), n_channels, hop, shift, channels.empty() ? nullptr : channels.data(),
+                               n_selected_, chan_taps_re.data(), chan_taps_im.empty() ? nullptr : chan_taps_im.data(),
+                               (uint32_t)chan_taps_re.size(), &cfg, &dev, h_.out()));
+    }
+
+    // FMD_ERR_TOO_SHORT (a call that completes no audio sample) returns empty rows and changes nothing.
+    Rows run(const uint8_t* iq, size_t nbytes)
+    {
+        const size_t cap = std::max<size_t>(1, fmd_bandplan_out_cap(hop_, chan_decim_, nbytes));
+        const size_t rows = (size_t)n_streams_ * n_selected_;
+        std::vector<int16_t> out(width_ * cap * rows);
+        size_t n = 0;
+        const int rc = fmd_bandplan_run_batch(h_, iq, nbytes, out.data(), cap, &n);
+        if (rc == FMD_ERR_TOO_SHORT) return Rows(rows);
+        check(rc);
+        return cut_rows(out, rows, cap, n, width_);
+    }
+    std::vector<std::pair<bool, uint32_t>> levels()
+    {
+        const size_t rows = (size_t)n_streams_ * n_selected_;
+        std::vector<uint8_t> open(rows);
+        std::vector<uint32_t> rms(rows);
+        check(fmd_bandplan_levels(h_, open.data(), rms.data()));
+        std::vector<std::pair<bool, uint32_t>> res(rows);
+        for (size_t r = 0; r < rows; ++r) res[r] = {open[r] != 0, rms[r]};
+        return res;
+    }
+    uint64_t outputs() const { return value_of<uint64_t>(fmd_bandplan_outputs, h_); }
+    void reset() { check(fmd_bandplan_reset(h_)); }
+    uint32_t n_selected() const { return n_selected_; }
+    uint32_t width() const { return width_; }
+
+private:
+    uint32_t hop_, chan_decim_, width_, n_streams_, n_selected_;
+    Owned<fmd_bandplan, fmd_bandplan_free> h_;
+};
+
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.
 inline void output(const std::vector<int16_t>& buf, FILE* f = stdout)
 {

@@ -176,6 +176,11 @@ pub struct fmd_uniform {
 }
 
 #[repr(C)]
+pub struct fmd_bandplan {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
 }
@@ -319,6 +324,17 @@ extern "C" {
     pub fn fmd_uniform_outputs(u: *const fmd_uniform, outputs: *mut u64) -> c_int;
     pub fn fmd_uniform_tap_digits(u: *const fmd_uniform) -> c_int;
     pub fn fmd_uniform_kernel_name(u: *const fmd_uniform, name: *mut c_char, cap: usize) -> c_int;
+    // band-plan bank: the declarations only (no safe wrapper yet)
+    pub fn fmd_bandplan_new(taps: *const i16, n_taps: u32, n_channels: u32, hop: u32, shift: u32, channels: *const u32, n_selected: u32, chan_taps_re: *const i16, chan_taps_im: *const i16, n_chan_taps: u32, cfg: *const fmd_narrow_config, dev: *const DeviceConfig, out: *mut *mut fmd_bandplan) -> c_int;
+    pub fn fmd_bandplan_free(b: *mut fmd_bandplan);
+    pub fn fmd_bandplan_reset(b: *mut fmd_bandplan) -> c_int;
+    pub fn fmd_bandplan_out_cap(hop: u32, chan_decim: u32, nbytes: usize) -> usize;
+    pub fn fmd_bandplan_run_batch(b: *mut fmd_bandplan, iq: *const u8, nbytes: usize, out: *mut i16, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn fmd_bandplan_run_device(b: *mut fmd_bandplan, d_iq: *const c_void, nbytes: usize, d_out: *mut c_void, out_cap: usize, out_len: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_bandplan_check(b: *mut fmd_bandplan) -> c_int;
+    pub fn fmd_bandplan_outputs(b: *const fmd_bandplan, outputs: *mut u64) -> c_int;
+    pub fn fmd_bandplan_levels(b: *mut fmd_bandplan, open: *mut u8, rms: *mut u32) -> c_int;
+    pub fn fmd_bandplan_kernel_name(b: *const fmd_bandplan, pass: u32, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;

@@ -1,4 +1,4 @@
-"""What the down-converter bench tools (bench_{stations,channelizer,stereo,narrow,rds,spectrum,uniform}.py) share: the repository
+"""What the down-converter bench tools (bench_{stations,channelizer,stereo,narrow,rds,spectrum,uniform,bandplan}.py) share: the repository
 and tests/ on sys.path, the front-end prototype, the stations' phase increments, the two synthetic device buffers, HIP-event timing,
 the common arguments, and the tail that prints every row and writes them to --out."""
 import argparse
