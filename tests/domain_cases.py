@@ -1,6 +1,7 @@
-"""Case generators of the *_domain GPU tests of the stereo bank, the RDS bank, the narrow-band bank and the channelizer: shapes,
-tap sets and call-size sequences, in plain numpy, with the host-side plan arithmetic (tile sizes) copied from DESIGN.md so that a
-case can say which kernel path it reaches.  tests/test_domain_cases.py runs these against the references alone and asserts what each case
+"""Case generators of the *_domain GPU tests of the stereo bank, the RDS bank, the narrow-band bank, the channelizer, the uniform
+channelizer and the band-plan bank: shapes, tap sets and call-size sequences, in plain numpy, with the host-side plan arithmetic
+(tile sizes, the uniform kernel's instantiation, the band-plan pass's tap chunks) copied from DESIGN.md so that a case can say
+which kernel path it reaches.  tests/test_domain_cases.py runs these against the references alone and asserts what each case
 claims; the GPU files feed the same cases to the handles."""
 import os
 from types import SimpleNamespace as NS
@@ -8,6 +9,7 @@ from types import SimpleNamespace as NS
 import numpy as np
 
 import stations_ref as sr
+import uniform_ref as ur
 
 DECIMS = (2, 4, 6, 30, 62, 64)
 TAPS = (1, 2, 26, 27, 58, 59, 250, 256)
@@ -619,6 +621,318 @@ def channelizer_sweep():
         c.tiles = tiles
         c.seed = int(rng.integers(0, 1 << 31))
         yield c
+
+
+# ---- uniform channelizer -------------------------------------------------------------------------------------------------------
+
+UV_TABLE_BYTES = 2048                                              # the NCO table beside the staged bytes
+UV_HOPS = tuple(range(8, 257, 8))
+UV_CELLS = tuple((R, G) for G in (8, 4) for R in (1, 2, 4))
+UV_K_EDGES = [(k, 2) for k in (16, 17, 32, 33)] + [(k, 1) for k in (32, 33, 64, 65)]
+UV_G_EDGES = ((240, 1248), (240, 1249), (248, 224), (248, 225))    # hop, T: G = 8 | 4 on the two sides of each pair
+UV_LIMITS = (16384, 2048, 256)
+
+
+def uniform_plan(K, digits, hop, T):
+    """(R, G, nrt, nkc, lds_bytes) of a uniform channelizer with K selected channels: row tiles of 4 channels with
+    two-digit taps and of 8 with one-digit taps; R = 1, 2, 4 row tiles per batch for up to 4, up to 8, more row tiles; K chunks of
+    64 bytes over the frame's 2 T; G = 8 column groups where the staged bytes of 16 G frames -- 2 hop (16 G - 1) + 64 nkc, in whole
+    256-byte rows -- and the NCO table fit 64 KiB, else 4."""
+    nrt = -(-K // (4 if digits == 2 else 8))
+    nkc = -(-2 * T // 64)
+    R = 4 if nrt > 8 else (2 if nrt > 4 else 1)
+    raw = lambda G: (2 * hop * (16 * G - 1) + 64 * nkc + 255) & ~255
+    G = 8 if raw(8) + UV_TABLE_BYTES <= 65536 else 4
+    return R, G, nrt, nkc, raw(G) + UV_TABLE_BYTES
+
+
+def uniform_taps(rng, T, digits):
+    """Prototype taps of the wanted digit form for ANY selection: |h| <= 127 keeps every |W| <= 127; one tap at +-2047 puts the
+    larger of |Wr|, |Wi| of every channel at 1447 or more."""
+    if digits == 1:
+        return rng.integers(-127, 128, T).astype(np.int16)
+    h = rng.integers(-2047, 2048, T).astype(np.int16)
+    h[int(rng.integers(0, T))] = 2047 * int(rng.choice([-1, 1]))
+    return h
+
+
+def uniform_handle(c, fmd):
+    """The handle of a uniform case; the smallest admissible shift is left to the handle to find."""
+    return fmd.UniformChannelizer(c.h, c.N, c.hop, channels=c.sel, n_streams=c.S, shift=None if c.limit == 16384 else c.shift, device_id=0)
+
+
+def uniform_refs(c, ur, check=None):
+    return {s: ur.UniformRef(c.h, c.N, c.hop, c.shift, channels=c.sel, z=c.z) for s in (range(c.S) if check is None else check)}
+
+
+def uniform_outputs(c):
+    """(m before, m after) of every accepted call of a uniform case, by the arithmetic of include/fmd.h alone; a call that
+    completes no output is refused and changes nothing."""
+    out_of = lambda p: (p - c.T) // c.hop + 1 if p >= c.T else 0
+    pos, acc = 0, []
+    for n in c.sizes:
+        if out_of(pos + n // 2) - out_of(pos) < 1:
+            continue
+        acc.append((out_of(pos), out_of(pos + n // 2)))
+        pos += n // 2
+    return acc
+
+
+# hop: N, K, digits, T.  Every hop once; the rows marked G = 4 are the only ones where eight column groups do not fit.
+UV_SHAPES = (
+    (8, 256, 256, 2, 33),       # nrt = 64: the most row tiles
+    (16, 64, 16, 2, 32),
+    (24, 40, 17, 2, 24),        # T = hop; nrt = 5: R = 2 with a last batch of one
+    (32, 64, 32, 2, 33),        # T = hop + 1
+    (40, 96, 33, 2, 120),       # T = 3 hop; nrt = 9: R = 4 with a last batch of one
+    (48, 64, 32, 1, 37),        # T < hop: no history
+    (56, 100, 33, 1, 2047),
+    (64, 128, 64, 1, 65),
+    (72, 130, 65, 1, 72),
+    (80, 256, 70, 2, 100),      # nrt = 18: five batches, wave 0 takes two, the last one holds two row tiles
+    (88, 200, 85, 1, 300),      # nrt = 11: a last batch of three
+    (96, 12, 12, 2, 2048),
+    (104, 48, 21, 2, 416),
+    (112, 96, 47, 1, 111),
+    (120, 256, 130, 1, 121),    # nrt = 17: five batches, the last one holds one row tile
+    (128, 2, 2, 2, 1),
+    (136, 77, 18, 2, 700),
+    (144, 150, 37, 2, 433),
+    (152, 33, 33, 1, 152),
+    (160, 256, 3, 1, 2048),
+    (168, 90, 34, 2, 169),
+    (176, 64, 40, 1, 1000),
+    (184, 256, 66, 1, 185),
+    (192, 20, 20, 2, 64),
+    (200, 180, 35, 2, 400),
+    (208, 97, 9, 1, 2047),
+    (216, 50, 29, 2, 217),
+    (224, 120, 45, 2, 96),
+    (232, 255, 5, 2, 2048),     # the largest hop whose G is 8 at every T
+    (240, 40, 17, 2, 1249),     # G = 4
+    (240, 100, 33, 1, 1248),    # G = 8 with exactly 64 KiB of LDS
+    (248, 60, 43, 2, 224),      # G = 8 with exactly 64 KiB of LDS; nrt = 11
+    (248, 256, 65, 1, 225),     # G = 4
+    (256, 80, 33, 2, 2048),     # G = 4 from here on
+    (256, 64, 33, 1, 2047),
+    (256, 32, 16, 2, 255),
+    (256, 48, 32, 1, 257),
+    (256, 7, 5, 2, 256),
+)
+
+
+def uniform_sweep():
+    """One case per row of UV_SHAPES: all 32 hops, the six (R, G) cells in both digit forms, the K edges of both forms, partial
+    last batches, the four shapes at the G edge, T at the chunk edges and around hop.  The shift is alternately the smallest
+    admissible one (limit 16384) and a larger one (limits 2048, 256).  Calls: one shorter than T (refused; it exists only where
+    T > hop, since a call is whole hops), one of three tiles and a part of a fourth, one of a single hop, one of a tile and a
+    part.  Every second case, at least one of every cell among them, goes through the device path."""
+    _, rng = fuzz(len(UV_SHAPES), 5101)
+    for i, (hop, N, K, digits, T) in enumerate(UV_SHAPES):
+        sel = None if K == N else np.sort(rng.choice(N, K, replace=False)).astype(np.uint32)
+        h = uniform_taps(rng, T, digits)
+        R, G, nrt, nkc, lds = uniform_plan(K, digits, hop, T)
+        limit = UV_LIMITS[i % 3]
+        tile, first = 16 * G, -(-T // hop)                         # hops of the stream's first output
+        hops = ([first - 1] if T > hop else []) + [first - 1 + 3 * tile + int(rng.integers(1, tile)), 1, tile + int(rng.integers(1, tile))]
+        yield NS(kind="uniform", i=i, N=N, hop=hop, T=T, K=K, sel=sel, digits=digits, h=h, S=3 if i % 5 == 0 and K <= 33 else 2,
+                 limit=limit, shift=shift_for(h, ur.channel_incs(N, sel), limit), R=R, G=G, nrt=nrt, nkc=nkc, lds_bytes=lds, dev=i % 2 == 1,
+                 refuses=T > hop, sizes=[2 * hop * n for n in hops], seed=int(rng.integers(0, 1 << 31)),
+                 z=sr.z_direct)                                    # a few hundred outputs: the gather matrices are the quicker form
+
+
+# ---- band-plan bank ------------------------------------------------------------------------------------------------------------
+
+BP_BLOCKS = tuple(16 << i for i in range(9))                       # 16 ... 4096
+BP_TILE = 256                                                      # audio samples per second-pass tile
+BP_Q_EDGES = {True: (4, 5, 8, 9), False: (8, 9, 16, 17)}           # ceil(Ta / R) around the tap chunks: 4 complex or 8 real taps
+# the stage-one shapes under the bank, one per instantiation: N, K, digits, hop, T (T > hop: a call of one hop is refused)
+BP_STAGE1 = ((16, 3, 1, 8, 40), (40, 17, 2, 24, 50), (96, 33, 2, 48, 100), (8, 2, 1, 256, 257), (64, 17, 2, 256, 260), (80, 33, 2, 256, 257))
+
+
+def bp_cpr(Ta, R, cplx):
+    """Eight-dword tap chunks per polyphase row of the second pass: a row holds ceil(Ta / R) taps, a chunk four
+    complex taps or eight real ones."""
+    tpc = 4 if cplx else 8
+    return -(-(-(-Ta // R)) // tpc)
+
+
+def bp_pitch(Ta, R, cplx):
+    """LDS row pitch in dwords: the tile's 256 cells and the padded taps' reach, odd."""
+    return (BP_TILE + bp_cpr(Ta, R, cplx) * (4 if cplx else 8)) | 1
+
+
+def bp_q_targets(R, cplx):
+    """The ceil(Ta / R) a band-plan sweep takes at chan_decim R: the chunk edges, or the largest there is (Ta = 64) in place of
+    those that Ta <= 64 cannot reach."""
+    qmax = -(-64 // R)
+    return sorted({min(q, qmax) for q in BP_Q_EDGES[cplx]})
+
+
+def edge_taps(rng, Ta, cplx):
+    """Taps at the edges of the rule: one component at +-16383 and sum |gr| + |gi| = 65535 exactly (every component at +-16383
+    where fewer than five of them cannot reach that sum)."""
+    cells = Ta * (2 if cplx else 1)
+    if cells * 16383 <= 65535:
+        mag = np.full(cells, 16383, np.int64)
+    else:
+        mag = rng.multinomial(65535 - 16383, np.ones(cells - 1) / (cells - 1)).astype(np.int64)
+        mag = np.concatenate([[16383], np.minimum(mag, 16383)])
+        while mag.sum() < 65535:                             # what the clip took goes to the smallest components
+            i = int(np.argmin(mag))
+            mag[i] += min(16383 - mag[i], 65535 - mag.sum())
+        assert mag.sum() == 65535 and mag.max() == 16383
+    g = (mag * rng.choice([-1, 1], cells))[rng.permutation(cells)]
+    return g[:Ta].astype(np.int16), (g[Ta:].astype(np.int16) if cplx else None)
+
+
+def bandplan_handle(c, fmd, squelch=None, S=None):
+    """The bank of a band-plan case; a shift that the case claims to be the smallest legal one is left to the handle to find."""
+    return fmd.BandPlanBank(c.h, c.N, c.hop, c.gr if c.gi is None else (c.gr, c.gi), c.R, mode=c.mode, channels=c.sel,
+                            n_streams=c.S if S is None else S, block=c.P, squelch=c.squelch if squelch is None else squelch,
+                            gain=c.gain, chan_shift=None if getattr(c, "auto_chan_shift", False) else c.chan_shift,
+                            shift=None if getattr(c, "auto_shift", False) else c.shift, device_id=0)
+
+
+def bandplan_refs(c, br, check=None, squelch=None, sel=None, mode=None, gain=None):
+    return {s: br.BandPlanRef(c.h, c.N, c.hop, c.shift, c.gr, c.gi, c.mode if mode is None else mode, c.R, c.chan_shift, c.P,
+                              c.squelch if squelch is None else squelch, c.gain if gain is None else gain,
+                              channels=c.sel if sel is None else sel, z=getattr(c, "z", sr.z_corr))
+            for s in (range(c.S) if check is None else check)}
+
+
+def bandplan_probe_squelch(c, br, data):
+    """A squelch between the loud and the quiet block RMS of the first selected channel over `data` (one stream); with fewer than
+    two complete blocks, the RMS of all its samples."""
+    first = [int(c.sel[0])] if c.sel is not None else [0]
+    p = bandplan_refs(c, br, check=[0], squelch=0, sel=first, mode=br.IQ, gain=256)[0]
+    u = p.feed(data)[0].astype(np.float64)
+    e = (u ** 2).sum(axis=1)
+    nblk = e.size // c.P
+    if nblk < 2:
+        return max(1, min(23170, int(np.sqrt(e.mean()))))
+    rms = np.sqrt(e[:nblk * c.P].reshape(nblk, c.P).mean(axis=1))
+    return max(1, min(23170, int(np.sqrt(max(1.0, rms.min()) * rms.max()))))
+
+
+def bp_sizes(c, ms):
+    """Byte counts of consecutive calls after which stage one has produced ms[0], ms[1], ... outputs in all (T > hop or ms[0] >= 1:
+    output m completes with hop ceil(T / hop) + m hops)."""
+    first = -(-c.T // c.hop)
+    hops = [first - 1 + m for m in ms]
+    assert hops[0] >= 1 and all(b > a for a, b in zip(hops[:-1], hops[1:]))
+    return [2 * c.hop * (b - a) for a, b in zip([0] + hops[:-1], hops)]
+
+
+def bandplan_sweep():
+    """For every chan_decim R in 1 ... 8: complex and real tap counts with ceil(Ta / R) on both sides of the tap-chunk edges
+    (bp_q_targets), one Ta below R (1 at R = 1) and Ta = 64; taps alternately filling the rule and at its edges; the four modes
+    against both tap kinds; P walking 16 ... 4096; a random gain; chan_shift at the limits 256, 4096, 16384 (FM: 256 in every
+    second FM case at least); the stage-one shift above its minimum in every third case; stage one cycling through the six
+    instantiations of the uniform kernel.  Calls: a refused one (one hop, or -- every second case with Ta >= 2 -- Ta - 1 stage-one
+    outputs, which complete no audio sample), the first that completes audio, one of more than three tiles of 256 audio samples,
+    one of one or two stage-one outputs that completes an audio sample (fewer than Ta - 1 where Ta >= 4: the y history is rebuilt
+    from old history plus new samples), one more."""
+    _, rng = fuzz(80, 6101)
+    i = 0
+    for R in range(1, 9):
+        specs = [(True, q) for q in bp_q_targets(R, True)] + [(False, q) for q in bp_q_targets(R, False)]
+        specs += [(R % 2 == 1, "below"), (R % 2 == 0, 64)]
+        for j, (cplx, q) in enumerate(specs):
+            if q == "below":
+                Ta = max(1, R - 1) if R < 4 else int(rng.integers(1, R))
+            elif q == 64:
+                Ta = 64
+            else:
+                Ta = int(rng.integers((q - 1) * R + 1, min(64, q * R) + 1))
+            N, K, digits, hop, T = BP_STAGE1[i % 6]
+            sel = np.sort(rng.choice(N, K, replace=False)).astype(np.uint32)
+            h = uniform_taps(rng, T, digits)
+            mode = (j + R) % 4
+            rule = (j + j // 4 + R) % 2 == 0
+            gr, gi = chan_taps(rng, Ta, cplx) if rule else edge_taps(rng, Ta, cplx)
+            incs = ur.channel_incs(N, sel)
+            raised = i % 3 == 1
+            shift = shift_for(h, incs, int(rng.choice([256, 2048])) if raised else 16384)
+            fm_keeps = mode == 1 and (i // 4) % 2 == 0
+            cs_limit = 256 if fm_keeps else (256, 4096, 16384)[(i + i // 3) % 3]
+            c = NS(kind="bandplan", i=i, j=j, R=R, Ta=Ta, cplx=cplx, q=-(-Ta // R), mode=mode, rule=rule, N=N, K=K, sel=sel, digits=digits,
+                   hop=hop, T=T, h=h, gr=gr, gi=gi, S=2, P=BP_BLOCKS[i % 9], gain=int(rng.integers(1, 65536)), shift=shift,
+                   shift_min=shift_for(h, incs, 16384), cs_limit=cs_limit, chan_shift=chan_shift_for(h, incs, shift, gr, gi, cs_limit),
+                   uv=uniform_plan(K, digits, hop, T), cpr=bp_cpr(Ta, R, cplx), pitch=bp_pitch(Ta, R, cplx), squelch=0,
+                   use_squelch=(i + i // 9) % 3 != 2, z=sr.z_direct, auto_shift=not raised,
+                   auto_chan_shift=cs_limit == (256 if mode == 1 else 16384))
+            e = 1 if R >= 2 and Ta >= 4 and i % 2 == 0 else 0      # the short call has 1 + e stage-one outputs
+            m1 = Ta + R * int(rng.integers(0, 6)) + int(rng.integers(0, R))
+            n2 = (m1 - Ta) // R + 1 + 3 * BP_TILE + int(rng.integers(1, BP_TILE))
+            m2 = Ta + R * (n2 - 1) + R - 1 - e
+            m3 = m2 + 1 + e
+            m4 = m3 + R * int(rng.integers(5, 80)) + int(rng.integers(0, R))
+            c.ms = [m1, m2, m3, m4]
+            c.refused_outputs = Ta - 1 if Ta >= 2 and i % 2 == 1 else 0
+            c.sizes = [2 * hop * (-(-T // hop) - 1 + c.refused_outputs)] + bp_sizes(c, c.ms)
+            c.seed = int(rng.integers(0, 1 << 31))
+            i += 1
+            yield c
+
+
+def bp_plan(c):
+    """(mS, mE, nS, nE) of every accepted call of a band-plan case, as plan() gives them for the narrow-band bank."""
+    return plan(NS(T=c.T, D=c.hop, Ta=c.Ta, R=c.R, sizes=c.sizes))
+
+
+def bandplan_edges(P, mode, off=0):
+    """Audio ends on j P - 1, j P and j P + 1, around a squelch between the loud and the quiet stretches of the bytes.  P = 16:
+    calls of several tiles that start inside a block (17 blocks in a tile).  P = 256, the tile's length: with off = 0 the first
+    calls end on block edges, so block and tile coincide; with off = 1 the first call ends one sample later, so every tile of the
+    later calls holds the last sample of one block and 255 of the next.  P = 4096: one block open across many calls."""
+    rng = np.random.default_rng(6202 + P + mode + 7 * off)
+    N, hop, T, Ta, R = 16, 8, 27, 9, 2
+    sel = np.array([0, 5, 11], np.uint32)
+    h = uniform_taps(rng, T, 2)
+    if P == 16:
+        ends = [P - 1, P, P + 1, 3 * P - 1, 3 * P + 5 + 3 * 256, 3 * P + 5 + 3 * 256 + 11, 64 * P, 64 * P + 1, 70 * P - 1, 70 * P + 600, 112 * P]
+    elif P == 256:
+        ends = [P + off, 4 * P + off, 6 * P + off, 7 * P - 1, 7 * P, 7 * P + 1, 10 * P + 1, 12 * P]
+    else:
+        ends = [300, 1000, 2000, 3000, P - 1, P, P + 1, P + 500, P + 2500, 2 * P - 1, 2 * P + 1, 3 * P, 3 * P + 700]
+    gr, gi = chan_taps(rng, Ta, mode != 2)
+    incs = ur.channel_incs(N, sel)
+    shift = shift_for(h, incs, 16384)
+    c = NS(kind="bandplan", R=R, K=3, N=N, hop=hop, T=T, Ta=Ta, S=2, h=h, sel=sel, P=P, mode=mode, gr=gr, gi=gi, shift=shift,
+           chan_shift=chan_shift_for(h, incs, shift, gr, gi, 16384), gain=300, ends=ends, off=off, squelch=0)
+    c.sizes = bp_sizes(c, [y_for_audio(Ta, R, n) for n in ends])
+    c.data = loud_quiet(rng, 2, sum(c.sizes), 2 * hop * R * {16: 40, 256: 300, 4096: 3000}[P])
+    c.data[1] = c.data[1][::-1]
+    return c
+
+
+def bandplan_threshold(mode):
+    """narrow_threshold on the band-plan bank: N = 2, hop 8, T = 1, h = [1], shift 0, one channel tap 1, chan_shift 0, so u is the
+    centred first byte pair of every hop in both channels (inc 0 and 2^31: hop inc is a whole turn); the other 14 bytes of a hop
+    are never read.  Blocks of 16 samples with E = 400 = 5^2 * 16, 399 and 401 against squelch 5."""
+    t = narrow_threshold(mode)
+    rng = np.random.default_rng(6404 + mode)
+    pairs = t.data[0].reshape(-1, 4)[:, :2]
+    b = rng.integers(0, 256, (pairs.shape[0], 16), dtype=np.uint8)
+    b[:, :2] = pairs
+    P = t.P
+    return NS(kind="bandplan", R=1, K=2, N=2, hop=8, T=1, Ta=1, S=1, h=np.ones(1, np.int16), sel=None, P=P, mode=mode,
+              gr=np.ones(1, np.int16), gi=None, shift=0, chan_shift=0, gain=4000, squelch=5, data=b.reshape(1, -1), kinds=t.kinds,
+              want_open=t.want_open, sizes=[16 * (2 * P + 2), 16 * (3 * P - 2), 16 * (4 * P + 4), 16 * (3 * P - 4)])
+
+
+def bandplan_extreme(mode):
+    """narrow_extreme's front end and bytes (T = 16, every tap 2047, the smallest shifts, four channel taps of 16383, gain 65535,
+    bytes at the rails) with hop 8 in place of decim 2, N = 2, channel 0 alone.  A byte lies within 128 of the centre and the
+    shifts are sized for 256, so a component of y and of u reaches half of its bound of 16384: |ur|, |ui| <= 8188, and
+    a = isqrt(ur^2 + ui^2) reaches sqrt 2 times that, not 23170.  FM at that |u|: the discriminator's i32 products wrap and the
+    output takes both rails."""
+    e = narrow_extreme(mode)
+    sel = np.array([0], np.uint32)
+    n = e.data.shape[1] // 16 * 16
+    return NS(kind="bandplan", R=1, K=1, N=2, hop=8, T=e.T, Ta=4, S=1, h=e.h, sel=sel, P=16, mode=mode, gr=e.gr, gi=None, shift=e.shift,
+              chan_shift=e.chan_shift, gain=65535, squelch=0, data=e.data[:, :n], sizes=[n // 2, n // 2])
 
 
 # ---- what a case reaches -------------------------------------------------------------------------------------------------------

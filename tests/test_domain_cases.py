@@ -3,6 +3,10 @@ reaches what it claims.  The first-pass tile is 64 G outputs (64 G - 1 in the st
 raw + 2048 + 256 K G <= 40960 bytes of LDS, raw = max(12 + 6 D + 8 D (16 G - 1) + 64 nkc, 12 + 2 D (64 G - 1) + 2 T + 15) rounded
 up to 16 and nkc = ceil((12 + 2 T) / 64) (st_lds, nb_lds, ch_lds): dc.groups is the test-side copy.
 
+For the uniform channelizer and the band-plan bank dc.uniform_plan, dc.bp_cpr and dc.bp_pitch are the test-side copies of the host
+plans, checked here at the points worked out by hand; the GPU files hold every case to the kernel name its
+plan claims.
+
 For the RDS bank the file also shows, still without a GPU, that the cases can tell a wrong kernel from a right one: each of five
 deliberately wrong variants of the definition (small subclasses of rds_ref.RdsRef below) gives, on the family of cases built for
 it, a result that differs from the definition's."""
@@ -372,3 +376,250 @@ def test_rds_extremes(g, rds_shift):
         assert set(np.unique(u).tolist()) == {-1, 0}               # |v| < 2^24: the sign of v is all that is left
         _, bad = _rds_run(c, cls=ShiftTruncates)
         assert _differs(good, bad, "output")
+
+
+# ---- uniform channelizer and band-plan bank -----------------------------------------------------------------------------------------
+
+def test_uniform_plan_copy():
+    """The test-side plan (dc.uniform_plan, dc.bp_cpr, dc.bp_pitch) at the points worked out by hand."""
+    Ts = range(1, 2049)
+    for hop, T in dc.UV_G_EDGES:                                   # the two G edges, 64 KiB exactly on their G = 8 side
+        _, G, _, _, lds = dc.uniform_plan(1, 2, hop, T)
+        assert (G, lds == 65536) == ((8, True) if T in (1248, 224) else (4, False)), (hop, T)
+    assert [min(T for T in Ts if dc.uniform_plan(1, 2, hop, T)[1] == 4) for hop in (240, 248)] == [1249, 225]
+    assert all(dc.uniform_plan(1, 2, hop, T)[1] == (4 if T >= e else 8) for hop, e in ((240, 1249), (248, 225)) for T in Ts)
+    assert all(dc.uniform_plan(1, 2, 256, T)[1] == 4 for T in Ts)
+    assert all(dc.uniform_plan(1, 2, hop, T)[1] == 8 for hop in dc.UV_HOPS if hop <= 232 for T in Ts)
+    assert all(dc.uniform_plan(K, d, hop, T)[4] <= 65536 for K in (1, 256) for d in (1, 2) for hop in dc.UV_HOPS for T in Ts)
+    # R by the row tiles: 4 channels a tile with two-digit taps, 8 with one-digit taps
+    assert [dc.uniform_plan(K, 2, 8, 8)[:3:2] for K in (1, 16, 17, 32, 33, 256)] == [(1, 1), (1, 4), (2, 5), (2, 8), (4, 9), (4, 64)]
+    assert [dc.uniform_plan(K, 1, 8, 8)[:3:2] for K in (1, 32, 33, 64, 65, 256)] == [(1, 1), (1, 4), (2, 5), (2, 8), (4, 9), (4, 32)]
+    assert [dc.uniform_plan(1, 2, 8, T)[3] for T in (1, 32, 33, 2047, 2048)] == [1, 1, 2, 64, 64]
+    # pass 2: R rows of `pitch` dwords fit the 2176 staged dwords, and a row holds the tile's cells plus the padded taps' reach
+    for R in range(1, 9):
+        for Ta in range(1, 65):
+            for cplx in (False, True):
+                cpr, pitch = dc.bp_cpr(Ta, R, cplx), dc.bp_pitch(Ta, R, cplx)
+                tpc = 4 if cplx else 8
+                assert (cpr - 1) * tpc < -(-Ta // R) <= cpr * tpc and pitch % 2 == 1 and pitch >= dc.BP_TILE + cpr * tpc
+                assert pitch * R <= 2176, (R, Ta, cplx)
+    assert dc.bp_pitch(64, 8, False) * 8 == 2120 and dc.bp_pitch(64, 1, True) == 321
+
+
+def _uniform_cases():
+    if not hasattr(_uniform_cases, "cases"):
+        _uniform_cases.cases = list(dc.uniform_sweep())
+    return _uniform_cases.cases
+
+
+def _bandplan_cases():
+    if not hasattr(_bandplan_cases, "cases"):
+        _bandplan_cases.cases = list(dc.bandplan_sweep())
+    return _bandplan_cases.cases
+
+
+def test_uniform_sweep_claims():
+    import uniform_ref as ur
+    for c in _uniform_cases():
+        incs = ur.channel_incs(c.N, c.sel)
+        assert len(incs) == c.K and (c.sel is None) == (c.K == c.N)
+        assert ur.digits(c.h, incs) == c.digits, c.i
+        assert dc.y_bound(c.h, incs, c.shift) <= c.limit and c.shift <= 24, c.i
+        assert c.shift == 0 or dc.y_bound(c.h, incs, c.shift - 1) > c.limit, c.i
+        assert c.shift >= ur.min_shift(c.h, incs) and (c.shift == ur.min_shift(c.h, incs)) == (c.limit == 16384), c.i
+        assert (c.R, c.G, c.nrt, c.nkc, c.lds_bytes) == dc.uniform_plan(c.K, c.digits, c.hop, c.T), c.i
+    shifts = [c.limit for c in _uniform_cases()]
+    assert set(shifts) == {256, 2048, 16384} and all(a != b for a, b in zip(shifts[:-1], shifts[1:]))
+
+
+def test_uniform_sweep_covers_the_kernel():
+    cases = _uniform_cases()
+    cell = lambda c: (c.R, c.G)
+    assert {(cell(c), c.digits) for c in cases} == {(x, d) for x in dc.UV_CELLS for d in (1, 2)}
+    assert {(c.K, c.digits) for c in cases} >= set(dc.UV_K_EDGES)
+    # batching: a partial last batch of 1 and of 3 row tiles at R = 4, of 1 at R = 2; K that does not fill its last row tile
+    assert {c.nrt % 4 for c in cases if c.R == 4} >= {1, 3} and {c.nrt % 2 for c in cases if c.R == 2} >= {1}
+    assert any(c.R > 1 and c.digits == 2 and c.K % 4 for c in cases) and any(c.R > 1 and c.digits == 1 and c.K % 2 for c in cases)
+    assert any(-(-c.nrt // c.R) > 4 and c.nrt % c.R for c in cases)                      # a wave takes a second batch, the last is partial
+    assert any(c.nrt == 64 and c.N == 256 and c.digits == 2 for c in cases)
+    # the G edge, at R = 2 or 4
+    at = {(c.hop, c.T): c for c in cases}
+    assert set(dc.UV_G_EDGES) <= set(at) and all(at[e].R in (2, 4) for e in dc.UV_G_EDGES)
+    assert [(at[e].G, at[e].lds_bytes == 65536) for e in dc.UV_G_EDGES] == [(8, True), (4, False), (8, True), (4, False)]
+    assert {at[e].R for e in dc.UV_G_EDGES if at[e].G == 4} == {2, 4}                     # G = 4 no longer with R = 1 alone
+    # hops: all 32, and those that are no power of two in every R
+    assert {c.hop for c in cases} == set(dc.UV_HOPS) and len(dc.UV_HOPS) == 32
+    assert {c.R for c in cases if c.hop & (c.hop - 1)} == {1, 2, 4}
+    # taps: the K-chunk edges, no history, exactly one hop, one more, whole hops
+    assert {c.T for c in cases} >= {32, 33, 2047, 2048, 1}
+    assert any(c.T < c.hop for c in cases) and any(c.T == c.hop for c in cases) and any(c.T == c.hop + 1 for c in cases)
+    assert any(c.T % c.hop == 0 and c.T > c.hop for c in cases)
+    # the device path: half of the cases, every cell
+    dev = [c for c in cases if c.dev]
+    assert 2 * len(dev) == len(cases) and {cell(c) for c in dev} == set(dc.UV_CELLS)
+    assert max(c.S for c in cases) == 3 and min(c.S for c in cases) == 2
+
+
+def test_uniform_sweep_calls():
+    """By the definition's own counting: the first call is refused wherever a refusal exists (T > hop: a call is at least one hop,
+    and one hop completes an output when T <= hop), three calls are accepted, the first of them spans more than three tiles and
+    ends inside one, a single hop follows, then more than a tile."""
+    import uniform_ref as ur
+    for c in _uniform_cases():
+        ref = ur.UniformRef(np.ones(c.T, np.int64), c.N, c.hop, 0, channels=[0])
+        fed, spans = [], []
+        for n in c.sizes:
+            m = ref.outputs_after(n // 2) - ref.m_next
+            fed.append(m >= 1)
+            if m >= 1:
+                spans.append(m)
+                ref.m_next += m
+                ref.pos += n // 2
+        tile = 16 * c.G
+        assert c.refuses == (c.T > c.hop) and fed == ([False] if c.refuses else []) + [True] * 3, c.i
+        assert spans[0] > 3 * tile and spans[0] % tile and spans[1] == 1 and tile < spans[2] < 2 * tile, (c.i, spans)
+        assert [b - a for a, b in dc.uniform_outputs(c)] == spans
+        assert c.sizes[-2] == 2 * c.hop and all(n % (2 * c.hop) == 0 and n > 0 for n in c.sizes)
+        assert sum(spans) <= 800                                   # a few hundred outputs per channel, not a workload
+    assert sum(c.refuses for c in _uniform_cases()) >= 25
+
+
+def test_bandplan_sweep_covers_the_second_pass():
+    cases = _bandplan_cases()
+    for R in range(1, 9):
+        mine = [c for c in cases if c.R == R]
+        qmax = -(-64 // R)
+        for cplx in (True, False):
+            want = {min(q, qmax) for q in dc.BP_Q_EDGES[cplx]}
+            assert {c.q for c in mine if c.cplx == cplx} >= want, (R, cplx)
+            assert want == set(dc.BP_Q_EDGES[cplx]) or qmax in want      # what Ta <= 64 cannot reach: the nearest edge there is
+        assert any(c.Ta < R for c in mine) or R == 1
+        assert any(c.Ta == 64 for c in mine) and {c.uv[:2] for c in mine} == set(dc.UV_CELLS), R
+    assert {c.R for c in cases} == set(range(1, 9))
+    # the chunk edges as the kernel sees them: 1 | 2 and 2 | 3 chunks a row in both tap kinds
+    assert {(c.cplx, c.cpr) for c in cases} >= {(x, n) for x in (True, False) for n in (1, 2, 3)}
+    for c in cases:
+        assert 1 <= c.Ta <= 64 and c.q == -(-c.Ta // c.R) and c.cpr == dc.bp_cpr(c.Ta, c.R, c.cplx) and c.pitch * c.R <= 2176
+        assert c.cplx == (c.gi is not None and bool(np.any(c.gi))), c.i
+        total = int(np.abs(c.gr.astype(np.int64)).sum() + (0 if c.gi is None else np.abs(c.gi.astype(np.int64)).sum()))
+        peak = max(int(np.abs(c.gr).max()), 0 if c.gi is None else int(np.abs(c.gi).max()))
+        assert total <= 65535 and peak <= 16383
+        if not c.rule:                                             # the edge taps
+            assert peak == 16383 and (total == 65535 or c.Ta * (2 if c.cplx else 1) < 5), c.i
+    assert {(c.rule, c.cplx) for c in cases} == {(a, b) for a in (True, False) for b in (True, False)}
+    assert {(c.mode, c.cplx) for c in cases} == {(m, x) for m in range(4) for x in (False, True)}
+    assert {c.P for c in cases} == set(dc.BP_BLOCKS) and len(dc.BP_BLOCKS) == 9 and dc.BP_BLOCKS[0] == 16 and dc.BP_BLOCKS[-1] == 4096
+    assert 3 * sum(c.use_squelch for c in cases) == 2 * len(cases)
+    assert {c.P for c in cases if c.use_squelch} == set(dc.BP_BLOCKS) == {c.P for c in cases if not c.use_squelch}
+    assert len({c.gain for c in cases}) > len(cases) // 2 and all(1 <= c.gain <= 65535 for c in cases)
+    assert min(c.gain for c in cases) < 8192 and max(c.gain for c in cases) > 57344
+
+
+def test_bandplan_sweep_shifts_and_stage_one():
+    import bandplan_ref as br
+    import uniform_ref as ur
+    cases = _bandplan_cases()
+    for c in cases:
+        incs = ur.channel_incs(c.N, c.sel)
+        assert ur.digits(c.h, incs) == c.digits and c.uv == dc.uniform_plan(c.K, c.digits, c.hop, c.T), c.i
+        assert c.shift_min == ur.min_shift(c.h, incs) <= c.shift <= 24 and (c.shift == c.shift_min) == c.auto_shift, c.i
+        assert c.chan_shift == br.min_chan_shift(c.h, c.N, c.shift, c.gr, c.gi, c.sel, limit=c.cs_limit) <= 30, c.i
+        assert c.auto_chan_shift == (c.cs_limit == (256 if c.mode == br.FM else 16384))
+    assert {c.cs_limit for c in cases} == {256, 4096, 16384}
+    assert {c.cs_limit for c in cases if c.mode != br.FM} == {256, 4096, 16384}
+    fm = [c for c in cases if c.mode == br.FM]
+    assert 2 * sum(c.cs_limit == 256 for c in fm) >= len(fm) and any(c.cs_limit > 256 for c in fm)
+    assert 3 * sum(not c.auto_shift for c in cases) == len(cases)
+    assert {c.uv[:2] for c in cases} == set(dc.UV_CELLS) and all(c.K <= 33 for c in cases)
+
+
+def test_bandplan_sweep_calls():
+    """By the definition's own counting (completes): the first call is refused -- in some cases although it completes stage-one
+    outputs -- and the other four are accepted: the first audio, more than three tiles of 256, a call of one or two stage-one
+    outputs (fewer than Ta - 1 wherever Ta >= 4) that completes an audio sample, one more."""
+    import bandplan_ref as br
+    kinds = set()
+    for c in _bandplan_cases():
+        ref = br.BandPlanRef(np.ones(c.T, np.int64), c.N, c.hop, 0, c.gr, c.gi, c.mode, c.R, 0, c.P, 0, 256, channels=[0])
+        done, ys = [], []
+        for n in c.sizes:
+            a = ref.completes(n)
+            m = ref.ch.outputs_after(n // 2) - ref.ch.m_next
+            if not done and not ys and a < 1:
+                kinds.add(m > 0)
+                ys.append(m)
+                continue
+            done.append(a)
+            ys.append(m)
+            ref.n_next += a
+            ref.ch.m_next += m
+            ref.ch.pos += n // 2
+        assert len(c.sizes) == 5 and len(done) == 4 and min(done) >= 1, (c.i, done)
+        assert ys[0] == c.refused_outputs < c.Ta and done[1] > 3 * dc.BP_TILE and done[1] % dc.BP_TILE and done[2] == 1, (c.i, ys, done)
+        assert ys[3] in (1, 2) and (ys[3] < c.Ta - 1 or c.Ta < 4), (c.i, ys)
+        assert [(mE - mS, nE - nS) for mS, mE, nS, nE in dc.bp_plan(c)] == list(zip(ys[1:], done)), c.i
+        assert ref.ch.m_next == c.ms[-1] and all(n % (2 * c.hop) == 0 for n in c.sizes)
+    assert kinds == {False, True}
+    assert sum(c.Ta >= 4 for c in _bandplan_cases()) >= 50
+
+
+@pytest.mark.parametrize("P,mode,off", [(16, nr.AM, 0), (16, nr.FM, 0), (256, nr.AM, 0), (256, nr.FM, 1), (256, nr.IQ, 1), (4096, nr.AM, 0),
+                                        (4096, nr.SSB, 0)])
+def test_bandplan_block_edges(P, mode, off):
+    import bandplan_ref as br
+    c = dc.bandplan_edges(P, mode, off)
+    p = dc.bp_plan(c)
+    assert [nE for _, _, _, nE in p] == c.ends and len(p) == len(c.sizes)          # no call is refused
+    f = dc.edge_facts([(nS, nE) for _, _, nS, nE in p], P)
+    assert f.rel == {-1, 0, 1}
+    if P == 16:
+        assert f.starts_on_edge and any(nS % P and nE - nS >= 256 for _, _, nS, nE in p)              # 17 blocks in a tile
+    elif P == 256:
+        tiles = [(nS + t, min(nS + t + 256, nE)) for _, _, nS, nE in p for t in range(0, nE - nS, 256)]
+        whole = [a % P == 0 and b - a == P for a, b in tiles]
+        split = [a % P == 1 and b - a == P for a, b in tiles]      # the last sample of a block and 255 of the next
+        assert (sum(whole) >= 6 and not any(split[:3])) if off == 0 else (sum(split) >= 5 and sum(whole) <= 1), (whole, split)
+    else:
+        assert f.open_calls >= 4
+    c.squelch = dc.bandplan_probe_squelch(c, br, c.data[0])
+    assert c.squelch > 0
+    ref = dc.bandplan_refs(c, br, check=[0])[0]
+    for d in dc.calls(c):
+        ref.feed(d[0])
+    opens = [ref.estimate(0, j)[0] for j in range(ref.n_next // P)]
+    assert {o for o in opens} == {True, False}
+
+
+@pytest.mark.parametrize("mode", [nr.IQ, nr.FM, nr.AM, nr.SSB])
+def test_bandplan_threshold_is_exact_equality(mode):
+    import bandplan_ref as br
+    import uniform_ref as ur
+    c = dc.bandplan_threshold(mode)
+    assert ur.channel_incs(2) == [0, 1 << 31] and (c.N, c.hop, c.T, c.Ta, c.P, c.squelch, c.shift, c.chan_shift) == (2, 8, 1, 1, 16, 5, 0, 0)
+    t = dc.narrow_threshold(mode)
+    assert np.array_equal(c.data.reshape(-1, 16)[:, :2], t.data.reshape(-1, 4)[:, :2]) and c.kinds == t.kinds
+    ref = dc.bandplan_refs(c, br)[0]
+    out = np.concatenate([ref.feed(d[0]) for d in dc.calls(c)], axis=1)
+    E = [ref.block(0, j)[0] for j in range(len(c.kinds))]
+    assert E == [400 + kd for kd in c.kinds] and 400 == c.squelch ** 2 * c.P
+    assert [ref.block(1, j)[0] for j in range(len(c.kinds))] == E    # the half-turn channel: the same energies
+    assert [ref.estimate(0, j)[0] for j in range(len(c.kinds))] == c.want_open == [e >= 400 for e in E]
+    if mode != nr.AM:                                              # (AM: a - dc is 5 - 5 in most open blocks)
+        for k in (0, 1):
+            loud = [bool(out[k, j * c.P:(j + 1) * c.P].any()) for j in range(len(c.kinds))]
+            assert loud == [False] + c.want_open[:-1], (k, loud)    # a block sounds exactly when the block before had E >= 400
+
+
+def test_bandplan_extremes():
+    """What bytes can reach: a component of y, and of u, half of its bound of 16384 (8187 after the two floors), so
+    a = isqrt(ur^2 + ui^2) stops at 11578 = floor(sqrt 2 * 8187), not at 23170, as in the narrow-band bank's case."""
+    import bandplan_ref as br
+    for mode in (nr.FM, nr.AM):
+        c, e = dc.bandplan_extreme(mode), dc.narrow_extreme(mode)
+        assert (c.N, c.hop, c.T, c.Ta, c.gain) == (2, 8, 16, 4, 65535) and (c.h == 2047).all() and (c.gr == 16383).all()
+        assert np.array_equal(c.data, e.data) and (c.shift, c.chan_shift) == (e.shift, e.chan_shift)
+        assert c.shift == br.ur.min_shift(c.h, [0]) and c.chan_shift == br.min_chan_shift(c.h, 2, c.shift, c.gr, None, [0])
+        ref = dc.bandplan_refs(c, br)[0]
+        out = np.concatenate([ref.feed(d[0]) for d in dc.calls(c)], axis=1)
+        assert out.min() == -32768 and out.max() == 32767 and ref.v_max > (1 << 28)
+        assert int(np.abs(ref.u[0]).max()) == 8187 and (mode == nr.FM or ref.a_max == 11578)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import bandplan_ref as br
+import domain_cases as dc
 import uniform_ref as ur
 
 pytestmark = pytest.mark.gpu
@@ -25,21 +26,7 @@ def _bytes(rng, S, n, quiet=True):
     return b
 
 
-def _edge_taps(rng, Ta, cplx):
-    """Taps at the edges of the rule: one component at +-16383 and sum |gr| + |gi| = 65535 exactly (every component at +-16383
-    where fewer than five of them cannot reach that sum)."""
-    cells = Ta * (2 if cplx else 1)
-    if cells * 16383 <= 65535:
-        mag = np.full(cells, 16383, np.int64)
-    else:
-        mag = rng.multinomial(65535 - 16383, np.ones(cells - 1) / (cells - 1)).astype(np.int64)
-        mag = np.concatenate([[16383], np.minimum(mag, 16383)])
-        while mag.sum() < 65535:                             # what the clip took goes to the smallest components
-            i = int(np.argmin(mag))
-            mag[i] += min(16383 - mag[i], 65535 - mag.sum())
-        assert mag.sum() == 65535 and mag.max() == 16383
-    g = (mag * rng.choice([-1, 1], cells))[rng.permutation(cells)]
-    return g[:Ta].astype(np.int16), (g[Ta:].astype(np.int16) if cplx else None)
+_edge_taps = dc.edge_taps                                   # shared with the band-plan domain cases
 
 
 class Run:
