@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from ._ffi import DeviceConfig, DownConverter, check, lib
-from .narrow import MODES, NARROW_FM, NARROW_IQ, Y_LIMIT, NarrowConfig, narrow_auto_shift
+from .narrow import NARROW_FM, NARROW_IQ, Y_LIMIT, ChanStage, narrow_auto_shift
 from .stereo import FRONT_END_LIMIT
 from .uniform import uniform_auto_shift, uniform_channel_inc
 
@@ -21,7 +21,7 @@ def bandplan_auto_shifts(taps, n_channels, channels, gr, gi=None, mode=NARROW_IQ
     return s, narrow_auto_shift(taps, incs, s, gr, gi, mode, limit=limit)
 
 
-class BandPlanBank(DownConverter):
+class BandPlanBank(ChanStage, DownConverter):
     """All `n_channels` channels (or the strictly increasing selection `channels`) of every stream through one second stage:
     `chan_taps` is gr or the pair (gr, gi) (narrow_taps at capture_rate / hop), `chan_decim` R in 1 ... 8, at most 64 taps.
     `shift=None` and `chan_shift=None` take the smallest legal shifts (bandplan_auto_shifts).  `gain` is Q8."""
@@ -32,33 +32,19 @@ class BandPlanBank(DownConverter):
     def __init__(self, taps, n_channels, hop, chan_taps, chan_decim, mode=NARROW_FM, channels=None, n_streams=1, block=256,
                  squelch=0, gain=256, chan_shift=None, shift=None, device_id=-1):
         self.taps = np.ascontiguousarray(taps, dtype=np.int16)
-        if isinstance(chan_taps, tuple):
-            gr, gi = chan_taps
-        else:
-            gr, gi = chan_taps, None
-        self.gr = np.ascontiguousarray(gr, dtype=np.int16)
-        self.gi = None if gi is None else np.ascontiguousarray(gi, dtype=np.int16)
-        if self.gi is not None and self.gi.size != self.gr.size:
-            raise ValueError("gr and gi differ in length")
-        self.mode = MODES[mode] if isinstance(mode, str) else int(mode)
+        self._chan_setup(chan_taps, mode, chan_decim, block, squelch, gain)
         self.n_channels, self.hop, self.n_streams = int(n_channels), int(hop), int(n_streams)
-        self.chan_decim, self.block, self.squelch, self.gain = int(chan_decim), int(block), int(squelch), int(gain)
         self.channels = (np.arange(self.n_channels, dtype=np.uint32) if channels is None
                          else np.ascontiguousarray(channels, dtype=np.uint32).ravel())
         self.n_selected = int(self.channels.size)
         auto = bandplan_auto_shifts(self.taps, self.n_channels, self.channels, self.gr, self.gi, self.mode, shift)
         self.shift = auto[0]
         self.chan_shift = auto[1] if chan_shift is None else int(chan_shift)
-        self.width = 2 if self.mode == NARROW_IQ else 1
-        cfg = NarrowConfig(self.mode, self.chan_decim, self.chan_shift, self.block, self.squelch, self.gain)
         self._h = C.c_void_p()
         dev = DeviceConfig(self.n_streams, device_id, 0)
-        p16 = C.POINTER(C.c_int16)
         sel = None if channels is None else self.channels.ctypes.data_as(C.POINTER(C.c_uint32))
-        check(lib().fmd_bandplan_new(self.taps.ctypes.data_as(p16), self.taps.size, self.n_channels, self.hop, self.shift, sel,
-                                     self.n_selected, self.gr.ctypes.data_as(p16),
-                                     None if self.gi is None else self.gi.ctypes.data_as(p16), self.gr.size, C.byref(cfg),
-                                     C.byref(dev), C.byref(self._h)))
+        check(lib().fmd_bandplan_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.n_channels, self.hop, self.shift,
+                                     sel, self.n_selected, *self._chan_args(), C.byref(dev), C.byref(self._h)))
 
     def out_cap(self, nbytes):
         return int(lib().fmd_bandplan_out_cap(self.hop, self.chan_decim, nbytes))
@@ -70,8 +56,3 @@ class BandPlanBank(DownConverter):
         r = np.zeros((self.n_streams, self.n_selected), dtype=np.uint32)
         check(lib().fmd_bandplan_levels(self._h, o.ctypes.data_as(C.POINTER(C.c_uint8)), r.ctypes.data_as(C.POINTER(C.c_uint32))))
         return o.astype(bool), r
-
-    def run_batch(self, iq):
-        """iq uint8 [n_streams, nbytes] -> int16 [n_streams, n_selected, n] ([..., 2] of (re, im) in IQ mode)."""
-        out = super().run_batch(iq)
-        return out if self.mode == NARROW_IQ else out[..., 0].copy()

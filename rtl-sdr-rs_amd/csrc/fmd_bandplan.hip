@@ -27,6 +27,10 @@
 //      parity of their global address and leave as dwords; only a row's odd first or last sample is a 2-byte store.
 //   After the last tile: the next call's y history and the row's carry (partial sums, last block's estimates, u[n - 1]), both
 //   double-buffered through FmdDdcCore.
+//
+// Host side: the second stage's checks, state, call plan, launch fields and level report are fmd_chan_stage.h's, shared with the
+// narrow-band bank; stage one's domain and gain bound are decided by the uniform channelizer's own constructor steps
+// (fmd_ddc.h).  This file keeps the kernel, its tap layout and the order of the two.
 #include "../../include/fmd.h"
 
 #include <hip/hip_runtime.h>
@@ -34,18 +38,22 @@
 #include <new>
 #include <vector>
 
+#include "fmd_chan_stage.h"
 #include "fmd_ddc.h"
 #include "fmd_device.h"
 #include "fmd_internal.h"
 
 namespace fmd_bp {
 
+using fmd_chan::kCarry;                                   // u64 per row: E part, A part, E last, u[n - 1], dc, open
+using fmd_chan::isqrt29;
+using fmd_chan::wave_sum64;
+
 constexpr uint32_t kWave = 64;                            // threads of a workgroup: one wave, one row
 constexpr uint32_t kPer = 4;                              // audio samples per lane and tile
 constexpr uint32_t kTile = kWave * kPer;                  // audio samples per tile (at most)
 constexpr uint32_t kMaxR = 8, kMaxTa = 64;
-constexpr uint32_t kYCap = 2176;                          // y dwords a tile stages: R pitch <= kYCap (bp_pitch)
-constexpr uint32_t kCarry = 6;                            // u64 per row: E part, A part, E last, u[n - 1], dc, open
+constexpr uint32_t kYCap = 2176;                          // y dwords a tile stages: R pitch <= kYCap (fmd_bandplan_new)
 
 struct ChanLaunch {
     const uint32_t* y;         // [S K][ystride]: the call's y
@@ -66,22 +74,6 @@ struct ChanLaunch {
     int16_t* out;              // [S K][out_cap][width]
     uint64_t out_cap;
 };
-
-// floor(sqrt(x)), x <= 2^29: the f32 estimate is within 1 of it
-__device__ __forceinline__ uint32_t isqrt29(uint32_t x)
-{
-    uint32_t r = (uint32_t)__builtin_amdgcn_sqrtf((float)x);
-    r -= (r * r > x) ? 1u : 0u;
-    r += ((r + 1u) * (r + 1u) <= x) ? 1u : 0u;
-    return r;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 typedef short s2 __attribute__((ext_vector_type(2)));
 
@@ -139,7 +131,7 @@ __global__ void __launch_bounds__(kWave) fmd_bandplan_chan_kernel(const ChanLaun
         const uint32_t na0 = t * kTile;                      // first audio sample (of this call) of the tile
         const uint32_t cnt = L.NA - na0 < kTile ? L.NA - na0 : kTile;
         const int rel0 = L.yoff0 + (int)(L.R * na0);         // the tile's first y, relative to the call's first
-        const uint32_t nsamp = L.R * (cnt - 1u) + L.Ta;      // <= R pitch: bp_pitch
+        const uint32_t nsamp = L.R * (cnt - 1u) + L.Ta;      // <= R pitch: host plan
 
         // ---- 1. y into LDS, polyphase -------------------------------------------------------------------------------------------
 #pragma unroll 4
@@ -264,73 +256,34 @@ __global__ void __launch_bounds__(kWave) fmd_bandplan_chan_kernel(const ChanLaun
 struct fmd_bandplan {
     FmdDdcBank bank;                                      // T, D = hop, K = selected channels, S; the core holds pass 2's state
     fmd_uniform* uv = nullptr;                            // pass 1
-    uint32_t Ta = 0, R = 0, cpr = 0, P = 0, pshift = 0, chan_shift = 0, mode = 0, squelch = 0, gain = 0, width = 1;
-    uint32_t HX = 0, HXS = 0, pitch = 0, rinv = 0;
-    bool cplx = false;
-    void* d_g = nullptr;                                  // [R][cpr][8] tap operands
-    FmdDdcPair yh;                                        // [S K][HXS] y history (packed dwords)
-    FmdDdcPair carry;                                     // [S K][kCarry] (u64)
-    void* d_y = nullptr; size_t d_y_cap = 0;              // the call's y
+    fmd_chan::ChanStage cs;                               // d_g: [R][cpr][8] tap operands
+    uint32_t cpr = 0;                                     // eight-dword tap chunks per polyphase row
 };
 
 namespace {
 
-// audio samples completed once `samples` samples per stream have arrived
-uint64_t bp_audio(const fmd_bandplan* h, uint64_t samples)
-{
-    return fmd_ddc_fir_outputs(h->Ta, h->R, fmd_ddc_outputs(h->bank.T, h->bank.D, samples));
-}
-
-uint32_t bp_isqrt_u64(uint64_t v)
-{
-    uint64_t r = (uint64_t)std::sqrt((double)v);
-    while (r * r > v) --r;
-    while ((r + 1) * (r + 1) <= v) ++r;
-    return (uint32_t)r;
-}
-
-// LDS row pitch: a tile's kTile cells and the padded taps' reach, odd (the staging writes of consecutive samples go to R rows)
-uint32_t bp_pitch(uint32_t qp) { return (fmd_bp::kTile + qp) | 1u; }
-
 int bp_enqueue(fmd_bandplan* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
 {
-    const FmdDdcBank& b = h->bank;
+    FmdDdcBank& b = h->bank;
     FmdDdcCore& c = h->bank.core;
     if (nbytes % (2ull * b.D) != 0) { fmd_internal_set_err("nbytes % (2 hop) != 0"); return FMD_ERR_BAD_LENGTH; }
-    if (const int rc = fmd_ddc_check_call(nbytes, d_iq, d_out, 2u * h->width)) return rc;
-    const uint64_t ns = nbytes / 2;
-    const uint64_t mS = fmd_ddc_outputs(b.T, b.D, c.pos), M = fmd_ddc_outputs(b.T, b.D, c.pos + ns) - mS;
-    const uint64_t nS = bp_audio(h, c.pos), NA = bp_audio(h, c.pos + ns) - nS;
-    if (NA < 1) { fmd_internal_set_err("the call completes no audio sample"); return FMD_ERR_TOO_SHORT; }   // (pass 1 not enqueued)
-    if (NA > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
-    const uint64_t SK = (uint64_t)b.S * b.K;
-    const uint64_t ystride = (M + 3) & ~3ull;
-    FMD_DDC_TRY(fmd_ddc_grow(h->d_y, h->d_y_cap, (size_t)(SK * ystride * 4)));
+    fmd_chan::ChanCall q;
+    if (const int rc = fmd_chan::chan_plan_call(b, h->cs, nbytes, d_iq, d_out, out_cap, q)) return rc;   // (pass 1 not enqueued)
 
     fmd_bp::ChanLaunch B{};
-    B.y = static_cast<const uint32_t*>(h->d_y); B.ystride = (uint32_t)ystride; B.M = (uint32_t)M;
-    B.yh_in = h->yh.in<uint32_t>(c.cur); B.yh_out = h->yh.out<uint32_t>(c.cur);
-    B.HX = h->HX; B.HXS = h->HXS;
-    B.carry_in = h->carry.in<unsigned long long>(c.cur); B.carry_out = h->carry.out<unsigned long long>(c.cur);
-    B.SK = (uint32_t)SK;
-    B.yoff0 = (int32_t)((int64_t)(h->R * nS) - (int64_t)mS);
-    B.nS = nS; B.NA = (uint32_t)NA; B.ntiles = (uint32_t)((NA + fmd_bp::kTile - 1) / fmd_bp::kTile);
-    B.R = h->R; B.cpr = h->cpr; B.rinv = h->rinv; B.pitch = h->pitch; B.Ta = h->Ta;
-    B.chan_shift = h->chan_shift; B.pshift = h->pshift; B.mode = h->mode; B.gain = h->gain;
-    B.thr = (uint64_t)h->squelch * h->squelch * h->P;
-    B.g = static_cast<const uint32_t*>(h->d_g);
-    B.out = static_cast<int16_t*>(d_out); B.out_cap = out_cap;   // samples per row: int16 each, a dword each in IQ mode
+    fmd_chan::chan_fill(B, b, h->cs, q, d_out, out_cap);
+    B.ntiles = (uint32_t)((q.NA + fmd_bp::kTile - 1) / fmd_bp::kTile); B.cpr = h->cpr;
 
     FMD_DDC_TRY(c.order.before(stream));
     // pass 1 counts the same samples as this handle, so it completes exactly M outputs; a refusal leaves both handles as they were
     size_t m1 = 0;
-    if (const int rc = fmd_uniform_run_device(h->uv, d_iq, nbytes, h->d_y, (size_t)ystride, &m1, stream)) return rc;
-    if (m1 != M) { fmd_internal_set_err("the two passes disagree on the call's outputs"); return FMD_ERR_BAD_STATE; }
-    if (h->cplx) hipLaunchKernelGGL(fmd_bp::fmd_bandplan_chan_kernel<true>, dim3((uint32_t)SK), dim3(fmd_bp::kWave), 0, stream, B);
-    else hipLaunchKernelGGL(fmd_bp::fmd_bandplan_chan_kernel<false>, dim3((uint32_t)SK), dim3(fmd_bp::kWave), 0, stream, B);
+    if (const int rc = fmd_uniform_run_device(h->uv, d_iq, nbytes, h->cs.d_y, (size_t)q.ystride, &m1, stream)) return rc;
+    if (m1 != q.M) { fmd_internal_set_err("the two passes disagree on the call's outputs"); return FMD_ERR_BAD_STATE; }
+    if (h->cs.cplx) hipLaunchKernelGGL(fmd_bp::fmd_bandplan_chan_kernel<true>, dim3(B.SK), dim3(fmd_bp::kWave), 0, stream, B);
+    else hipLaunchKernelGGL(fmd_bp::fmd_bandplan_chan_kernel<false>, dim3(B.SK), dim3(fmd_bp::kWave), 0, stream, B);
     FMD_DDC_TRY(hipGetLastError());
-    fmd_ddc_commit(c, stream, ns);
-    if (out_len) *out_len = (size_t)NA;
+    fmd_ddc_commit(c, stream, q.ns);
+    if (out_len) *out_len = (size_t)q.NA;
     return FMD_OK;
 }
 
@@ -338,12 +291,7 @@ int bp_enqueue(fmd_bandplan* h, const void* d_iq, size_t nbytes, void* d_out, si
 
 extern "C" {
 
-size_t fmd_bandplan_out_cap(uint32_t hop, uint32_t chan_decim, size_t nbytes)
-{
-    if (!hop || !chan_decim) return 0;
-    const uint64_t d = 2ull * hop * chan_decim;
-    return (size_t)((nbytes + d - 1) / d);
-}
+size_t fmd_bandplan_out_cap(uint32_t hop, uint32_t chan_decim, size_t nbytes) { return fmd_chan::chan_out_cap(hop, chan_decim, nbytes); }
 
 int fmd_bandplan_new(const int16_t* taps, uint32_t n_taps, uint32_t n_channels, uint32_t hop, uint32_t shift, const uint32_t* channels,
                      uint32_t n_selected, const int16_t* chan_taps_re, const int16_t* chan_taps_im, uint32_t n_chan_taps,
@@ -353,84 +301,28 @@ int fmd_bandplan_new(const int16_t* taps, uint32_t n_taps, uint32_t n_channels, 
         fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG;
     }
     *out = nullptr;
-    // stage one: the uniform channelizer's domain (fmd_uniform_new decides it again, with the same result)
-    if (n_channels < 2 || n_channels > 256 || hop < 8 || hop > 256 || hop % 8 != 0 || n_taps == 0 || n_taps > 2048 || shift > 24 ||
-        dev->n_channels > 65535u) {
-        fmd_internal_set_err("need 2 <= n_channels <= 256, hop a multiple of 8 in 8 ... 256, 1 <= n_taps <= 2048, shift <= 24, n_streams <= 65535");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    for (uint32_t t = 0; t < n_taps; ++t)
-        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
-    if (!channels) n_selected = n_channels;
-    if (n_selected == 0 || n_selected > n_channels) { fmd_internal_set_err("need 1 <= n_selected <= n_channels"); return FMD_ERR_UNSUPPORTED; }
-    for (uint32_t i = 0; i < n_selected; ++i) {
-        const uint32_t k = channels ? channels[i] : i;
-        if (k >= n_channels || (channels && i > 0 && k <= channels[i - 1])) {
-            fmd_internal_set_err("channels must be strictly increasing and < n_channels");
-            return FMD_ERR_UNSUPPORTED;
-        }
-    }
-    // stage two: the narrow-band bank's domain with 1 <= R <= 8 and 1 <= Ta <= 64
-    const uint32_t R = cfg->chan_decim, P = cfg->block, Ta = n_chan_taps;
-    if (cfg->mode > FMD_NARROW_SSB || R < 1u || R > fmd_bp::kMaxR || Ta < 1u || Ta > fmd_bp::kMaxTa || cfg->chan_shift > 30u ||
-        cfg->squelch > 23170u || cfg->gain < 1u || cfg->gain > 65535u) {
-        fmd_internal_set_err("need mode <= 3, 1 <= chan_decim <= 8, 1 <= n_chan_taps <= 64, chan_shift <= 30, squelch <= 23170, 1 <= gain <= 65535");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    if (P < 16u || P > 4096u || (P & (P - 1u)) != 0) { fmd_internal_set_err("block must be a power of two in [16, 4096]"); return FMD_ERR_UNSUPPORTED; }
-    uint64_t gsum = 0;
+    // the refusals in this order, all before a device is queried: stage one's domain, stage two's, stage one's gain, stage two's
+    if (const int rc = fmd_uniform_args(taps, n_taps, n_channels, hop, shift, channels, n_selected, dev)) return rc;
+    const uint32_t R = cfg->chan_decim, Ta = n_chan_taps;
+    uint64_t gsum = 0, bound = 0;
     bool cplx = false;
-    for (uint32_t t = 0; t < Ta; ++t) {
-        const int gr = chan_taps_re[t], gi = chan_taps_im ? chan_taps_im[t] : 0;
-        if (gr > 16383 || gr < -16383 || gi > 16383 || gi < -16383) { fmd_internal_set_err("|chan tap| > 16383"); return FMD_ERR_UNSUPPORTED; }
-        gsum += (uint64_t)(gr < 0 ? -gr : gr) + (uint64_t)(gi < 0 ? -gi : gi);
-        if (gi) cplx = true;
-    }
-    if (gsum > 65535u) { fmd_internal_set_err("sum |gr| + |gi| > 65535"); return FMD_ERR_UNSUPPORTED; }
-    // B_y over the selected channels, from the complex taps themselves
-    uint64_t max_gain = 0;
-    {
-        int16_t tab[1024];
-        fmd_st_nco_table(tab);
-        std::vector<int32_t> wr(n_taps), wi(n_taps);
-        for (uint32_t i = 0; i < n_selected; ++i) {
-            uint32_t inc = 0;
-            (void)fmd_uniform_channel_inc(channels ? channels[i] : i, n_channels, &inc);
-            fmd_st_complex_taps(taps, n_taps, inc, tab, wr.data(), wi.data());
-            uint64_t gk = 0;
-            for (uint32_t t = 0; t < n_taps; ++t) gk += (uint64_t)(wr[t] < 0 ? -wr[t] : wr[t]) + (uint64_t)(wi[t] < 0 ? -wi[t] : wi[t]);
-            if (gk > max_gain) max_gain = gk;
-        }
-    }
-    const uint64_t bound = (256ull * max_gain + ((1ull << shift) - 1ull)) >> shift;
-    if (bound > 16384ull) {
-        fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    if (((bound * gsum + ((1ull << cfg->chan_shift) - 1ull)) >> cfg->chan_shift) > 16384ull) {
-        fmd_internal_set_err("channel filter gain too large: need ceil(B_y * sum(|gr| + |gi|) / 2^chan_shift) <= 16384");
-        return FMD_ERR_UNSUPPORTED;
-    }
-
+    if (const int rc = fmd_chan::chan_args(cfg, chan_taps_re, chan_taps_im, Ta, fmd_bp::kMaxR, fmd_bp::kMaxTa, &gsum, &cplx)) return rc;
     fmd_bandplan* h = new (std::nothrow) fmd_bandplan();
     if (!h) return FMD_ERR_NOMEM;
-    if (const int rc = fmd_uniform_new(taps, n_taps, n_channels, hop, shift, channels, n_selected, dev, &h->uv)) { delete h; return rc; }
-    FmdDdcBank& b = h->bank;
-    b.T = n_taps; b.D = hop; b.K = n_selected; b.S = dev->n_channels; b.shift = shift; b.HB = 0;
-    b.plan.amat.assign(4, 0u);                            // (the core's front-end buffers are pass 1's: the uniform handle holds them)
-    b.plan.kconst.assign(2, 0);
+    if (const int rc = fmd_uniform_host(taps, n_taps, n_channels, hop, shift, channels, n_selected, dev, &h->uv, &bound)) { delete h; return rc; }
+    const auto refuse = [&](int rc) { fmd_uniform_discard(h->uv); delete h; return rc; };
+    if (const int rc = fmd_chan::chan_gain_ok(bound, gsum, cfg->chan_shift)) return refuse(rc);
+
+    FmdDdcBank& b = h->bank;                              // (its plan stays empty: the front end is pass 1's, in the uniform handle)
+    b.T = n_taps; b.D = hop; b.K = channels ? n_selected : n_channels; b.S = dev->n_channels; b.shift = shift; b.HB = 0;
+    fmd_chan::chan_init(b, h->cs, cfg, Ta, cplx);
     const uint32_t tpc = cplx ? 4u : 8u;                  // taps per eight-dword chunk
-    h->Ta = Ta; h->R = R; h->cpr = ((Ta + R - 1u) / R + tpc - 1u) / tpc; h->P = P; h->chan_shift = cfg->chan_shift; h->mode = cfg->mode;
-    h->squelch = cfg->squelch; h->gain = cfg->gain; h->width = cfg->mode == FMD_NARROW_IQ ? 2u : 1u; h->cplx = cplx;
-    while ((1u << h->pshift) < P) ++h->pshift;
-    h->HX = Ta - 1u; h->HXS = h->HX ? h->HX : 1u;
-    h->rinv = R >= 2u ? (uint32_t)(((1ull << 32) + R - 1u) / R) : 0u;
-    const uint32_t qp = h->cpr * tpc;
-    h->pitch = bp_pitch(qp);
+    h->cpr = ((Ta + R - 1u) / R + tpc - 1u) / tpc;
+    // LDS row pitch: a tile's kTile cells and the padded taps' reach, odd (the staging writes of consecutive samples go to R rows)
+    h->cs.pitch = (fmd_bp::kTile + h->cpr * tpc) | 1u;
     static_assert((fmd_bp::kMaxR * ((fmd_bp::kTile + 8u + 7u) | 1u)) <= fmd_bp::kYCap, "R = 8 with its 8 (padded: up to 15) taps per row");
-    if ((uint64_t)R * h->pitch > fmd_bp::kYCap) {         // (R qp <= Ta + 8 R - 1 < 128: cannot happen inside the domain)
-        fmd_uniform_free(h->uv); delete h;
-        fmd_internal_set_err("second stage does not fit the tile"); return FMD_ERR_UNSUPPORTED;
+    if ((uint64_t)R * h->cs.pitch > fmd_bp::kYCap) {      // (R qp <= Ta + 8 R - 1 < 128: cannot happen inside the domain)
+        fmd_internal_set_err("second stage does not fit the tile"); return refuse(FMD_ERR_UNSUPPORTED);
     }
 
     // [R][cpr][8]: complex taps as the operand pairs A = (gr, -gi), B = (gi, gr); real taps as A = (g, 0) alone
@@ -447,11 +339,8 @@ int fmd_bandplan_new(const int16_t* taps, uint32_t n_taps, uint32_t n_channels, 
             gp[((size_t)r * h->cpr + q / 8u) * 8u + q % 8u] = gr;
         }
     }
-    const size_t SK = (size_t)b.S * b.K;
-    fmd_ddc_add_pair(b.core, h->yh, SK * h->HXS * 4);
-    fmd_ddc_add_pair(b.core, h->carry, SK * fmd_bp::kCarry * 8);
-    fmd_ddc_add_owned(b.core, h->d_g, gp.data(), gp.size() * sizeof(uint32_t));
-    fmd_ddc_add_owned(b.core, h->d_y);
+    fmd_ddc_add_owned(b.core, h->cs.d_g, gp.data(), gp.size() * sizeof(uint32_t));
+    if (const int rc = fmd_uniform_device(h->uv, dev)) { delete h; return rc; }
     const char* what;
     if (const int rc = fmd_ddc_bank_device(b, dev, &what)) {
         if (!what) { fmd_uniform_free(h->uv); delete h; return rc; }
@@ -492,40 +381,28 @@ int fmd_bandplan_run_batch(fmd_bandplan* h, const uint8_t* iq, size_t nbytes, in
 {
     if (!h || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
     if (nbytes % (2ull * h->bank.D) != 0) { fmd_internal_set_err("nbytes % (2 hop) != 0"); return FMD_ERR_BAD_LENGTH; }
-    const size_t out_bytes = out_cap * h->bank.S * h->bank.K * h->width * sizeof(int16_t);
+    const size_t out_bytes = out_cap * h->bank.S * h->bank.K * h->cs.width * sizeof(int16_t);
     return fmd_ddc_run_batch(h->bank, iq, nbytes, out, out_bytes, out_cap, out_len, [h](auto... a) { return bp_enqueue(h, a...); });
 }
 
 int fmd_bandplan_outputs(const fmd_bandplan* h, uint64_t* outputs)
 {
     if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *outputs = bp_audio(h, h->bank.core.pos);
+    *outputs = fmd_chan::chan_audio(h->bank, h->cs, h->bank.core.pos);
     return FMD_OK;
 }
 
 int fmd_bandplan_levels(fmd_bandplan* h, uint8_t* open, uint32_t* rms)
 {
     if (!h || !open || !rms) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->bank.core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    const size_t SK = (size_t)h->bank.S * h->bank.K;
-    memset(open, 0, SK);
-    memset(rms, 0, SK * sizeof(uint32_t));
-    if ((bp_audio(h, h->bank.core.pos) >> h->pshift) == 0) return FMD_OK;   // no block has completed
-    std::vector<unsigned long long> c(SK * fmd_bp::kCarry);
-    FMD_DDC_TRY(hipMemcpy(c.data(), h->carry.in<unsigned long long>(h->bank.core.cur), c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    for (size_t r = 0; r < SK; ++r) {
-        open[r] = (h->squelch == 0u || c[r * fmd_bp::kCarry + 5]) ? 1 : 0;
-        rms[r] = bp_isqrt_u64(c[r * fmd_bp::kCarry + 2] >> h->pshift);
-    }
-    return FMD_OK;
+    return fmd_chan::chan_levels(h->bank, h->cs, 0, (size_t)h->bank.S * h->bank.K, open, rms);
 }
 
 int fmd_bandplan_kernel_name(const fmd_bandplan* h, uint32_t pass, char* name, size_t cap)
 {
     if (!h || !name || cap == 0 || pass > 1) return FMD_ERR_INVALID_ARG;
     if (pass == 0) return fmd_uniform_kernel_name(h->uv, name, cap);
-    return fmd_ddc_name_rc(snprintf(name, cap, h->cplx ? "fmd_bp::fmd_bandplan_chan_kernel<true>" : "fmd_bp::fmd_bandplan_chan_kernel<false>"), cap);
+    return fmd_ddc_name_rc(snprintf(name, cap, h->cs.cplx ? "fmd_bp::fmd_bandplan_chan_kernel<true>" : "fmd_bp::fmd_bandplan_chan_kernel<false>"), cap);
 }
 
 }  // extern "C"

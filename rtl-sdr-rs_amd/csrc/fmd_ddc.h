@@ -372,13 +372,14 @@ inline int fmd_ddc_open(FmdDdcCore& c, const fmd_device_config* dev)
     return FMD_OK;
 }
 
-// On c.device: the plan's buffers (the NCO table with the phase steps), a zeroed history of `hist_bytes` twice when non-zero,
-// the stream, the registered pairs zeroed and the registered constants.  nullptr, or what failed.
+// On c.device: the plan's buffers that are not empty (the NCO table with the phase steps; a handle whose front end is another
+// handle's leaves its plan empty), a zeroed history of `hist_bytes` twice when non-zero, the stream, the registered pairs zeroed
+// and the registered constants.  nullptr, or what failed.
 inline const char* fmd_ddc_upload(FmdDdcCore& c, const FmdDdcPlan& P, size_t hist_bytes)
 {
-    if (hipMalloc(&c.d_amat, P.amat.size() * 4) != hipSuccess || hipMemcpy(c.d_amat, P.amat.data(), P.amat.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    if (!P.amat.empty() && (hipMalloc(&c.d_amat, P.amat.size() * 4) != hipSuccess || hipMemcpy(c.d_amat, P.amat.data(), P.amat.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
         return "hipMalloc(tap matrix)";
-    if (hipMalloc(&c.d_kconst, P.kconst.size() * 4) != hipSuccess || hipMemcpy(c.d_kconst, P.kconst.data(), P.kconst.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    if (!P.kconst.empty() && (hipMalloc(&c.d_kconst, P.kconst.size() * 4) != hipSuccess || hipMemcpy(c.d_kconst, P.kconst.data(), P.kconst.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
         return "hipMalloc(constants)";
     if (!P.dinc.empty()) {
         if (hipMalloc(&c.d_dinc, P.dinc.size() * 4) != hipSuccess || hipMemcpy(c.d_dinc, P.dinc.data(), P.dinc.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
@@ -649,3 +650,13 @@ inline void fmd_ddc_free(FmdDdcCore& c)
     FmdDeviceGuard guard(c.device);
     fmd_ddc_release(c);
 }
+
+// fmd_uniform_new in steps (fmd_uniform.hip), for the band-plan bank, which decides its own second stage between them: the domain
+// of the arguments (pointers non-null, `channels` aside); that check again, the handle, its plan and *bound = B_y <= 16384; the
+// device step, whose failure frees the handle.  Only the device step queries a device; discard drops a handle that has not run it.
+int fmd_uniform_args(const int16_t* taps, uint32_t n_taps, uint32_t n_channels, uint32_t hop, uint32_t shift, const uint32_t* channels,
+                     uint32_t n_selected, const fmd_device_config* dev);
+int fmd_uniform_host(const int16_t* taps, uint32_t n_taps, uint32_t n_channels, uint32_t hop, uint32_t shift, const uint32_t* channels,
+                     uint32_t n_selected, const fmd_device_config* dev, fmd_uniform** out, uint64_t* bound);
+void fmd_uniform_discard(fmd_uniform* h);
+int fmd_uniform_device(fmd_uniform* h, const fmd_device_config* dev);

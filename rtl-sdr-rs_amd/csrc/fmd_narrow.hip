@@ -30,6 +30,7 @@
 #include <new>
 #include <vector>
 
+#include "fmd_chan_stage.h"
 #include "fmd_ddc.h"
 #include "fmd_device.h"
 #include "fmd_internal.h"
@@ -38,11 +39,13 @@ namespace fmd_nb {
 
 using fmd_ddc::kThreads;
 using fmd_ddc::kTableBytes;
+using fmd_chan::kCarry;                                   // u64 per row: E part, A part, E last, u[n - 1], dc, open
+using fmd_chan::isqrt29;
+using fmd_chan::wave_sum64;
 
 constexpr uint32_t kTile = 256;                           // audio samples per pass-2 tile (at most)
 constexpr uint32_t kYCap = 6144;                          // (yr, yi) cells a pass-2 tile stages: R pitch <= kYCap
 constexpr uint32_t kMaxBlk = kTile / 16 + 2;              // blocks one tile touches (<= 17: P >= 16)
-constexpr uint32_t kCarry = 6;                            // u64 per row: E part, A part, E last, u[n - 1], dc, open
 
 struct DdcLaunch {
     const uint8_t* iq;         // [S][nbytes]
@@ -116,22 +119,6 @@ struct ChanLaunch {
     int16_t* out;              // [S K][out_cap][width]
     uint64_t out_cap;
 };
-
-// floor(sqrt(x)), x <= 2^29: the f32 estimate is within 1 of it
-__device__ __forceinline__ uint32_t isqrt29(uint32_t x)
-{
-    uint32_t r = (uint32_t)__builtin_amdgcn_sqrtf((float)x);
-    r -= (r * r > x) ? 1u : 0u;
-    r += ((r + 1u) * (r + 1u) <= x) ? 1u : 0u;
-    return r;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // acc + g y with 24-bit operands; the tap g is wave-uniform (an SGPR)
 __device__ __forceinline__ int mad24(int g, int y, int acc)
@@ -296,75 +283,40 @@ __global__ void __launch_bounds__(kThreads) fmd_narrow_chan_kernel(const ChanLau
 struct fmd_narrow {
     FmdDdcBank bank;
     FmdDdcTiling tl;
-    uint32_t Ta = 0, R = 0, Q = 0, P = 0, pshift = 0, chan_shift = 0, mode = 0, squelch = 0, gain = 0, width = 1;
-    uint32_t HX = 0, HXS = 0, na = 0, pitch = 0, rinv = 0;
-    bool cplx = false;
-    void* d_g = nullptr;                                  // [R][Q] polyphase taps (int2)
-    FmdDdcPair yh;                                        // [S K][HXS] y history (packed dwords)
-    FmdDdcPair carry;                                     // [S K][kCarry] (u64)
-    void* d_y = nullptr; size_t d_y_cap = 0;              // the call's y
+    fmd_chan::ChanStage cs;                               // d_g: [R][Q] polyphase taps (int2)
+    uint32_t Q = 0, na = 0;                               // taps per polyphase row (a multiple of 4), audio samples per pass-2 tile
 };
 
 namespace {
 
-// audio samples completed once `samples` samples per stream have arrived
-uint64_t nb_audio(const fmd_narrow* h, uint64_t samples)
-{
-    return fmd_ddc_fir_outputs(h->Ta, h->R, fmd_ddc_outputs(h->bank.T, h->bank.D, samples));
-}
-
-uint32_t isqrt_u64(uint64_t v)
-{
-    uint64_t r = (uint64_t)std::sqrt((double)v);
-    while (r * r > v) --r;
-    while ((r + 1) * (r + 1) <= v) ++r;
-    return (uint32_t)r;
-}
-
 int nb_enqueue(fmd_narrow* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
 {
-    if (const int rc = fmd_ddc_check_call(nbytes, d_iq, d_out, 2u * h->width)) return rc;
-    const FmdDdcBank& b = h->bank;
+    FmdDdcBank& b = h->bank;
     FmdDdcCore& c = h->bank.core;
-    const uint64_t ns = nbytes / 2;
-    const uint64_t mS = fmd_ddc_outputs(b.T, b.D, c.pos), M = fmd_ddc_outputs(b.T, b.D, c.pos + ns) - mS;
-    const uint64_t nS = nb_audio(h, c.pos), NA = nb_audio(h, c.pos + ns) - nS;
-    if (NA < 1) { fmd_internal_set_err("the call completes no audio sample"); return FMD_ERR_TOO_SHORT; }
-    if (NA > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
-    const uint64_t SK = (uint64_t)b.S * b.K;
-    const uint64_t nt1 = (M + h->tl.tile - 1) / h->tl.tile, nt2 = (NA + h->na - 1) / h->na;
+    fmd_chan::ChanCall q;
+    if (const int rc = fmd_chan::chan_plan_call(b, h->cs, nbytes, d_iq, d_out, out_cap, q)) return rc;
+    const uint64_t nt1 = (q.M + h->tl.tile - 1) / h->tl.tile, nt2 = (q.NA + h->na - 1) / h->na;
+    // (cannot happen: the constructor refuses S > 65535 and the call checks bound M)
     if (nt1 > (1u << 30) || b.S > 65535u) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
-    const uint64_t ystride = (M + 3) & ~3ull;
-    FMD_DDC_TRY(fmd_ddc_grow(h->d_y, h->d_y_cap, (size_t)(SK * ystride * 4)));
 
     fmd_nb::DdcLaunch A{};
-    fmd_ddc_fill_front(A, b, d_iq, nbytes, mS);
-    A.m0_lo = (uint32_t)mS; A.M = (uint32_t)M;
+    fmd_ddc_fill_front(A, b, d_iq, nbytes, q.mS);
+    A.m0_lo = (uint32_t)q.mS; A.M = (uint32_t)q.M;
     A.tile = h->tl.tile; A.ntiles = (uint32_t)nt1; A.raw_bytes = h->tl.raw_bytes;
-    A.y = static_cast<uint32_t*>(h->d_y); A.ystride = (uint32_t)ystride;
+    A.y = static_cast<uint32_t*>(h->cs.d_y); A.ystride = (uint32_t)q.ystride;
 
     fmd_nb::ChanLaunch B{};
-    B.y = A.y; B.ystride = A.ystride; B.M = (uint32_t)M;
-    B.yh_in = h->yh.in<uint32_t>(c.cur); B.yh_out = h->yh.out<uint32_t>(c.cur);
-    B.HX = h->HX; B.HXS = h->HXS;
-    B.carry_in = h->carry.in<unsigned long long>(c.cur); B.carry_out = h->carry.out<unsigned long long>(c.cur);
-    B.SK = (uint32_t)SK;
-    B.yoff0 = (int32_t)((int64_t)(h->R * nS) - (int64_t)mS);
-    B.nS = nS; B.NA = (uint32_t)NA; B.na = h->na; B.ntiles = (uint32_t)nt2;
-    B.R = h->R; B.Q = h->Q; B.rinv = h->rinv; B.pitch = h->pitch; B.Ta = h->Ta;
-    B.chan_shift = h->chan_shift; B.pshift = h->pshift; B.mode = h->mode; B.gain = h->gain;
-    B.thr = (uint64_t)h->squelch * h->squelch * h->P;
-    B.g = static_cast<const int2*>(h->d_g);
-    B.out = static_cast<int16_t*>(d_out); B.out_cap = out_cap;   // samples per row: int16 each, a dword each in IQ mode
+    fmd_chan::chan_fill(B, b, h->cs, q, d_out, out_cap);
+    B.na = h->na; B.ntiles = (uint32_t)nt2; B.Q = h->Q;
 
     FMD_DDC_TRY(c.order.before(stream));
     hipLaunchKernelGGL(fmd_nb::fmd_narrow_ddc_kernel, dim3(A.ntiles, b.S), dim3(fmd_nb::kThreads), h->tl.lds, stream, A);
     FMD_DDC_TRY(hipGetLastError());
-    if (h->cplx) hipLaunchKernelGGL(fmd_nb::fmd_narrow_chan_kernel<true>, dim3((uint32_t)SK), dim3(fmd_nb::kThreads), 0, stream, B);
-    else hipLaunchKernelGGL(fmd_nb::fmd_narrow_chan_kernel<false>, dim3((uint32_t)SK), dim3(fmd_nb::kThreads), 0, stream, B);
+    if (h->cs.cplx) hipLaunchKernelGGL(fmd_nb::fmd_narrow_chan_kernel<true>, dim3(B.SK), dim3(fmd_nb::kThreads), 0, stream, B);
+    else hipLaunchKernelGGL(fmd_nb::fmd_narrow_chan_kernel<false>, dim3(B.SK), dim3(fmd_nb::kThreads), 0, stream, B);
     FMD_DDC_TRY(hipGetLastError());
-    fmd_ddc_commit(c, stream, ns);
-    if (out_len) *out_len = (size_t)NA;
+    fmd_ddc_commit(c, stream, q.ns);
+    if (out_len) *out_len = (size_t)q.NA;
     return FMD_OK;
 }
 
@@ -372,12 +324,7 @@ int nb_enqueue(fmd_narrow* h, const void* d_iq, size_t nbytes, void* d_out, size
 
 extern "C" {
 
-size_t fmd_narrow_out_cap(uint32_t decim, uint32_t chan_decim, size_t nbytes)
-{
-    if (!decim || !chan_decim) return 0;
-    const uint64_t d = 2ull * decim * chan_decim;
-    return (size_t)((nbytes + d - 1) / d);
-}
+size_t fmd_narrow_out_cap(uint32_t decim, uint32_t chan_decim, size_t nbytes) { return fmd_chan::chan_out_cap(decim, chan_decim, nbytes); }
 
 uint32_t fmd_narrow_out_width(uint32_t mode) { return mode == FMD_NARROW_IQ ? 2u : 1u; }
 
@@ -390,49 +337,26 @@ int fmd_narrow_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
     }
     *out = nullptr;
     if (const int rc = fmd_ddc_front_args(taps, n_taps, decim, shift, n_stations, dev)) return rc;
-    const uint32_t R = cfg->chan_decim, P = cfg->block, Ta = n_chan_taps;
-    if (cfg->mode > FMD_NARROW_SSB || R < 1u || R > 32u || Ta < 1u || Ta > 256u || cfg->chan_shift > 30u || cfg->squelch > 23170u ||
-        cfg->gain < 1u || cfg->gain > 65535u) {
-        fmd_internal_set_err("need mode <= 3, 1 <= chan_decim <= 32, 1 <= n_chan_taps <= 256, chan_shift <= 30, squelch <= 23170, 1 <= gain <= 65535");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    if (P < 16u || P > 4096u || (P & (P - 1u)) != 0) { fmd_internal_set_err("block must be a power of two in [16, 4096]"); return FMD_ERR_UNSUPPORTED; }
+    const uint32_t R = cfg->chan_decim, Ta = n_chan_taps;
     uint64_t gsum = 0;
     bool cplx = false;
-    for (uint32_t t = 0; t < Ta; ++t) {
-        const int gr = chan_taps_re[t], gi = chan_taps_im ? chan_taps_im[t] : 0;
-        if (gr > 16383 || gr < -16383 || gi > 16383 || gi < -16383) { fmd_internal_set_err("|chan tap| > 16383"); return FMD_ERR_UNSUPPORTED; }
-        gsum += (uint64_t)(gr < 0 ? -gr : gr) + (uint64_t)(gi < 0 ? -gi : gi);
-        if (gi) cplx = true;
-    }
-    if (gsum > 65535u) { fmd_internal_set_err("sum |gr| + |gi| > 65535"); return FMD_ERR_UNSUPPORTED; }
+    if (const int rc = fmd_chan::chan_args(cfg, chan_taps_re, chan_taps_im, Ta, 32u, 256u, &gsum, &cplx)) return rc;
     fmd_narrow* h = new (std::nothrow) fmd_narrow();
     if (!h) return FMD_ERR_NOMEM;
     uint64_t bound;
     if (const int rc = fmd_ddc_bank_front(h->bank, taps, n_taps, decim, shift, phase_inc, n_stations, dev, &bound)) { delete h; return rc; }
-    if (((bound * gsum + ((1ull << cfg->chan_shift) - 1ull)) >> cfg->chan_shift) > 16384ull) {
-        delete h;
-        fmd_internal_set_err("channel filter gain too large: need ceil(B_y * sum(|gr| + |gi|) / 2^chan_shift) <= 16384");
-        return FMD_ERR_UNSUPPORTED;
-    }
+    if (const int rc = fmd_chan::chan_gain_ok(bound, gsum, cfg->chan_shift)) { delete h; return rc; }
     h->tl = fmd_ddc_tiling(decim, h->bank.plan.nkc, n_taps, n_stations);
-    h->Ta = Ta; h->R = R; h->Q = ((Ta + R - 1u) / R + 3u) & ~3u; h->P = P; h->chan_shift = cfg->chan_shift; h->mode = cfg->mode;
-    h->squelch = cfg->squelch; h->gain = cfg->gain; h->width = fmd_narrow_out_width(cfg->mode); h->cplx = cplx;
-    while ((1u << h->pshift) < P) ++h->pshift;
-    h->HX = Ta - 1u; h->HXS = h->HX ? h->HX : 1u;
-    h->rinv = R >= 2u ? (uint32_t)(((1ull << 32) + R - 1u) / R) : 0u;
+    fmd_chan::chan_init(h->bank, h->cs, cfg, Ta, cplx);
+    h->Q = ((Ta + R - 1u) / R + 3u) & ~3u;
     const uint32_t pmax = (fmd_nb::kYCap / R - 1u) | 1u;  // the largest odd pitch with R pitch <= kYCap (>= 191)
     const uint32_t na = pmax - h->Q;                      // >= 183
     h->na = na < fmd_nb::kTile ? na : fmd_nb::kTile;
-    h->pitch = (h->na + h->Q) | 1u;                       // <= pmax
+    h->cs.pitch = (h->na + h->Q) | 1u;                    // <= pmax
 
     std::vector<int2> gp((size_t)R * h->Q, int2{0, 0});
     for (uint32_t t = 0; t < Ta; ++t) gp[(size_t)(t % R) * h->Q + t / R] = int2{chan_taps_re[t], chan_taps_im ? chan_taps_im[t] : 0};
-    const size_t SK = (size_t)h->bank.S * h->bank.K;
-    fmd_ddc_add_pair(h->bank.core, h->yh, SK * h->HXS * 4);
-    fmd_ddc_add_pair(h->bank.core, h->carry, SK * fmd_nb::kCarry * 8);
-    fmd_ddc_add_owned(h->bank.core, h->d_g, gp.data(), gp.size() * sizeof(int2));
-    fmd_ddc_add_owned(h->bank.core, h->d_y);
+    fmd_ddc_add_owned(h->bank.core, h->cs.d_g, gp.data(), gp.size() * sizeof(int2));
     const char* what;
     if (const int rc = fmd_ddc_bank_device(h->bank, dev, &what)) {
         if (!what) { delete h; return rc; }
@@ -470,14 +394,14 @@ int fmd_narrow_check(fmd_narrow* h)
 int fmd_narrow_run_batch(fmd_narrow* h, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap, size_t* out_len)
 {
     if (!h || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    const size_t out_bytes = out_cap * h->bank.S * h->bank.K * h->width * sizeof(int16_t);
+    const size_t out_bytes = out_cap * h->bank.S * h->bank.K * h->cs.width * sizeof(int16_t);
     return fmd_ddc_run_batch(h->bank, iq, nbytes, out, out_bytes, out_cap, out_len, [h](auto... a) { return nb_enqueue(h, a...); });
 }
 
 int fmd_narrow_outputs(const fmd_narrow* h, uint64_t* outputs)
 {
     if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *outputs = nb_audio(h, h->bank.core.pos);
+    *outputs = fmd_chan::chan_audio(h->bank, h->cs, h->bank.core.pos);
     return FMD_OK;
 }
 
@@ -485,22 +409,14 @@ int fmd_narrow_level(fmd_narrow* h, uint32_t stream, uint32_t station, int* open
 {
     if (!h || !open || !rms) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
     if (stream >= h->bank.S || station >= h->bank.K) { fmd_internal_set_err("stream or station out of range"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->bank.core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    *open = 0; *rms = 0;
-    if ((nb_audio(h, h->bank.core.pos) >> h->pshift) == 0) return FMD_OK;   // no block has completed
-    unsigned long long c[fmd_nb::kCarry];
-    FMD_DDC_TRY(hipMemcpy(c, h->carry.in<unsigned long long>(h->bank.core.cur) + (size_t)fmd_nb::kCarry * ((size_t)stream * h->bank.K + station), sizeof c, hipMemcpyDeviceToHost));
-    *open = (h->squelch == 0u || c[5]) ? 1 : 0;
-    *rms = isqrt_u64(c[2] >> h->pshift);
-    return FMD_OK;
+    return fmd_chan::chan_levels(h->bank, h->cs, (size_t)stream * h->bank.K + station, 1, open, rms);
 }
 
 int fmd_narrow_kernel_name(const fmd_narrow* h, uint32_t pass, char* name, size_t cap)
 {
     if (!h || !name || cap == 0 || pass > 1) return FMD_ERR_INVALID_ARG;
     return fmd_ddc_name_rc(snprintf(name, cap, pass == 0 ? "fmd_nb::fmd_narrow_ddc_kernel" :
-                                    (h->cplx ? "fmd_nb::fmd_narrow_chan_kernel<true>" : "fmd_nb::fmd_narrow_chan_kernel<false>")), cap);
+                                    (h->cs.cplx ? "fmd_nb::fmd_narrow_chan_kernel<true>" : "fmd_nb::fmd_narrow_chan_kernel<false>")), cap);
 }
 
 }  // extern "C"

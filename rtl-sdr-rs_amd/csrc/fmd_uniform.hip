@@ -52,7 +52,7 @@ struct UvLaunch {
     uint32_t vb_first;         // virtual byte (history ++ call) of the frame of the call's first output: a multiple of 16
     uint32_t m0_lo;            // global index of the call's first output, mod 2^32
     uint32_t M;                // outputs of this call per (stream, channel)
-    uint32_t hop, T, K, S, shift;   // K: selected channels (tap rows)
+    uint32_t D, T, K, S, shift;     // D: the hop; K: selected channels (tap rows)
     uint32_t nrt, nkc, digits;
     uint32_t ntiles, raw_bytes;
     const uint32_t* amat;      // [nrt][nkc][64][4]
@@ -78,8 +78,8 @@ __global__ void __launch_bounds__(kThreads) fmd_uniform_kernel(const UvLaunch L)
 
     const uint32_t o0 = t * kTile;                           // first output (of this call) of the tile
     const uint32_t no = L.M - o0 < kTile ? L.M - o0 : kTile;
-    const uint32_t vb = L.vb_first + 2u * L.hop * o0;        // virtual byte of output o0's frame (16-byte aligned)
-    const uint32_t nq = (2u * L.hop * (no - 1u) + 2u * L.T + 15u) >> 4;
+    const uint32_t vb = L.vb_first + 2u * L.D * o0;          // virtual byte of output o0's frame (16-byte aligned)
+    const uint32_t nq = (2u * L.D * (no - 1u) + 2u * L.T + 15u) >> 4;
     const uint32_t nq16 = (nq + 15u) & ~15u;                 // whole 256-byte rows (<= raw_bytes / 16: host plan)
     int16_t* const tab = reinterpret_cast<int16_t*>(lds + (L.raw_bytes >> 2));
 
@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(kThreads) fmd_uniform_kernel(const UvLaunch L)
     // ---- 2. contraction: batches of R row tiles x all G column groups, looping over the K chunks --------------------------------
     const uint8_t* const lb = reinterpret_cast<const uint8_t*>(lds);
     const uint32_t j = lane & 15u, q = lane >> 4;
-    const uint32_t hc = L.hop >> 3;                          // 16-byte chunks per hop
+    const uint32_t hc = L.D >> 3;                            // 16-byte chunks per hop
     typedef const FMD_DDC_GLOBAL i4* gq;
     const gq amat = (gq)(uintptr_t)L.amat + lane;
     const uint32_t sh = 14u + L.shift;
@@ -233,17 +233,9 @@ int uv_enqueue(fmd_uniform* h, const void* d_iq, size_t nbytes, void* d_out, siz
     const uint32_t tile = 16u * h->G;
     const uint64_t ntiles = (M + tile - 1) / tile;
     fmd_uv::UvLaunch L{};
-    L.iq = static_cast<const uint8_t*>(d_iq);
-    L.nbytes = nbytes;
-    L.hist_in = c.d_hist[c.cur]; L.hist_out = c.d_hist[c.cur ^ 1];
-    L.HB = b.HB;
-    L.vb_first = (uint32_t)(2ull * (b.D * m0 + b.HB / 2 - c.pos));   // >= 0: that frame starts at most HB / 2 samples back
-    L.m0_lo = (uint32_t)m0;
-    L.M = (uint32_t)M;
-    L.hop = b.D; L.T = b.T; L.K = b.K; L.S = b.S; L.shift = b.shift;
-    L.nrt = b.plan.nrt; L.nkc = b.plan.nkc; L.digits = b.plan.digits;
+    fmd_ddc_fill_front(L, b, d_iq, nbytes, m0);              // (every frame of the call starts at most HB / 2 samples back)
+    L.m0_lo = (uint32_t)m0; L.M = (uint32_t)M;
     L.ntiles = (uint32_t)ntiles; L.raw_bytes = h->raw_bytes;
-    L.amat = c.d_amat; L.kconst = c.d_kconst; L.dinc = c.d_dinc; L.tab = c.d_tab;
     L.out = static_cast<uint32_t*>(d_out); L.out_stride = out_cap;
     FMD_DDC_TRY(c.order.before(stream));
     if (h->G == 8) uv_launch_g<8>(h->R, L, h->lds, stream);
@@ -255,6 +247,76 @@ int uv_enqueue(fmd_uniform* h, const void* d_iq, size_t nbytes, void* d_out, siz
 }
 
 }  // namespace
+
+// ---- the constructor's steps (fmd_ddc.h): fmd_uniform_new is fmd_uniform_host, then fmd_uniform_device ------------------------
+
+int fmd_uniform_args(const int16_t* taps, uint32_t n_taps, uint32_t n_channels, uint32_t hop, uint32_t shift, const uint32_t* channels,
+                     uint32_t n_selected, const fmd_device_config* dev)
+{
+    if (n_channels < 2 || n_channels > 256 || hop < 8 || hop > 256 || hop % 8 != 0 || n_taps == 0 || n_taps > 2048 || shift > 24 ||
+        dev->n_channels > 65535u) {
+        fmd_internal_set_err("need 2 <= n_channels <= 256, hop a multiple of 8 in 8 ... 256, 1 <= n_taps <= 2048, shift <= 24, n_streams <= 65535");
+        return FMD_ERR_UNSUPPORTED;
+    }
+    for (uint32_t t = 0; t < n_taps; ++t)
+        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
+    if (!channels) n_selected = n_channels;
+    if (n_selected == 0 || n_selected > n_channels) { fmd_internal_set_err("need 1 <= n_selected <= n_channels"); return FMD_ERR_UNSUPPORTED; }
+    for (uint32_t i = 0; i < n_selected; ++i) {
+        const uint32_t k = channels ? channels[i] : i;
+        if (k >= n_channels || (channels && i > 0 && k <= channels[i - 1])) {
+            fmd_internal_set_err("channels must be strictly increasing and < n_channels");
+            return FMD_ERR_UNSUPPORTED;
+        }
+    }
+    return FMD_OK;
+}
+
+int fmd_uniform_host(const int16_t* taps, uint32_t n_taps, uint32_t n_channels, uint32_t hop, uint32_t shift, const uint32_t* channels,
+                     uint32_t n_selected, const fmd_device_config* dev, fmd_uniform** out, uint64_t* bound)
+{
+    if (const int rc = fmd_uniform_args(taps, n_taps, n_channels, hop, shift, channels, n_selected, dev)) return rc;
+    if (!channels) n_selected = n_channels;
+    std::vector<uint32_t> inc(n_selected), dinc(n_selected);
+    for (uint32_t i = 0; i < n_selected; ++i) {
+        uv_inc(channels ? channels[i] : i, n_channels, &inc[i]);
+        dinc[i] = hop * inc[i];
+    }
+    fmd_uniform* h = new (std::nothrow) fmd_uniform();
+    if (!h) return FMD_ERR_NOMEM;
+    FmdDdcBank& b = h->bank;
+    h->N = n_channels;
+    b.T = n_taps; b.D = hop; b.K = n_selected; b.S = dev->n_channels; b.shift = shift;
+    b.HB = 2u * hop * ((n_taps + hop - 1u) / hop - 1u);
+    // one plan for all streams: every frame starts 16-byte aligned (one delta, no slack in K)
+    fmd_ddc_build_plan(taps, n_taps, inc.data(), 1u, n_selected, 1u, (2u * n_taps + 63u) / 64u, b.plan);
+    b.plan.dinc = dinc;
+    *bound = (256ull * b.plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
+    if (*bound > 16384ull) {
+        fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
+        delete h;
+        return FMD_ERR_UNSUPPORTED;
+    }
+    h->R = b.plan.nrt > 8u ? 4u : (b.plan.nrt > 4u ? 2u : 1u);
+    h->G = (size_t)uv_raw_bytes(hop, b.plan.nkc, 8u) + fmd_uv::kTableBytes <= 65536u ? 8u : 4u;
+    h->raw_bytes = uv_raw_bytes(hop, b.plan.nkc, h->G);
+    h->lds = (size_t)h->raw_bytes + fmd_uv::kTableBytes;
+    *out = h;
+    return FMD_OK;
+}
+
+void fmd_uniform_discard(fmd_uniform* h) { delete h; }
+
+int fmd_uniform_device(fmd_uniform* h, const fmd_device_config* dev)
+{
+    const char* what;
+    if (const int rc = fmd_ddc_bank_device(h->bank, dev, &what)) {
+        if (!what) { delete h; return rc; }
+        fmd_internal_set_err(what); fmd_uniform_free(h); return rc;
+    }
+    std::vector<uint32_t>().swap(h->bank.plan.amat);      // (up to 4 MiB; the device holds it now)
+    return FMD_OK;
+}
 
 extern "C" {
 
@@ -276,52 +338,9 @@ int fmd_uniform_new(const int16_t* taps, uint32_t n_taps, uint32_t n_channels, u
 {
     if (!taps || !dev || !out || dev->n_channels == 0) { fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG; }
     *out = nullptr;
-    if (n_channels < 2 || n_channels > 256 || hop < 8 || hop > 256 || hop % 8 != 0 || n_taps == 0 || n_taps > 2048 || shift > 24 ||
-        dev->n_channels > 65535u) {
-        fmd_internal_set_err("need 2 <= n_channels <= 256, hop a multiple of 8 in 8 ... 256, 1 <= n_taps <= 2048, shift <= 24, n_streams <= 65535");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    for (uint32_t t = 0; t < n_taps; ++t)
-        if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
-    if (!channels) n_selected = n_channels;
-    if (n_selected == 0 || n_selected > n_channels) { fmd_internal_set_err("need 1 <= n_selected <= n_channels"); return FMD_ERR_UNSUPPORTED; }
-    std::vector<uint32_t> inc(n_selected), dinc(n_selected);
-    for (uint32_t i = 0; i < n_selected; ++i) {
-        const uint32_t k = channels ? channels[i] : i;
-        if (k >= n_channels || (channels && i > 0 && k <= channels[i - 1])) {
-            fmd_internal_set_err("channels must be strictly increasing and < n_channels");
-            return FMD_ERR_UNSUPPORTED;
-        }
-        uv_inc(k, n_channels, &inc[i]);
-        dinc[i] = hop * inc[i];
-    }
-    fmd_uniform* h = new (std::nothrow) fmd_uniform();
-    if (!h) return FMD_ERR_NOMEM;
-    FmdDdcBank& b = h->bank;
-    h->N = n_channels;
-    b.T = n_taps; b.D = hop; b.K = n_selected; b.S = dev->n_channels; b.shift = shift;
-    b.HB = 2u * hop * ((n_taps + hop - 1u) / hop - 1u);
-    // one plan for all streams: every frame starts 16-byte aligned (one delta, no slack in K)
-    fmd_ddc_build_plan(taps, n_taps, inc.data(), 1u, n_selected, 1u, (2u * n_taps + 63u) / 64u, b.plan);
-    b.plan.dinc = dinc;
-    const uint64_t bound = (256ull * b.plan.max_gain + ((1ull << shift) - 1ull)) >> shift;
-    if (bound > 16384ull) {
-        fmd_internal_set_err("filter gain too large: need ceil(256 * max sum(|Wr| + |Wi|) / 2^shift) <= 16384");
-        delete h;
-        return FMD_ERR_UNSUPPORTED;
-    }
-    h->R = b.plan.nrt > 8u ? 4u : (b.plan.nrt > 4u ? 2u : 1u);
-    h->G = (size_t)uv_raw_bytes(hop, b.plan.nkc, 8u) + fmd_uv::kTableBytes <= 65536u ? 8u : 4u;
-    h->raw_bytes = uv_raw_bytes(hop, b.plan.nkc, h->G);
-    h->lds = (size_t)h->raw_bytes + fmd_uv::kTableBytes;
-
-    const char* what;
-    if (const int rc = fmd_ddc_bank_device(b, dev, &what)) {
-        if (!what) { delete h; return rc; }
-        fmd_internal_set_err(what); fmd_uniform_free(h); return rc;
-    }
-    std::vector<uint32_t>().swap(b.plan.amat);            // (up to 4 MiB; the device holds it now)
-    *out = h;
+    uint64_t bound;
+    if (const int rc = fmd_uniform_host(taps, n_taps, n_channels, hop, shift, channels, n_selected, dev, out, &bound)) return rc;
+    if (const int rc = fmd_uniform_device(*out, dev)) { *out = nullptr; return rc; }
     return FMD_OK;
 }
 

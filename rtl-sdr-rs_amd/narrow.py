@@ -67,7 +67,33 @@ def narrow_auto_shift(taps, phase_incs, shift, gr, gi=None, mode=NARROW_IQ, limi
     return s
 
 
-class NarrowBank(DownConverter):
+class ChanStage:
+    """The second stage's side of a wrapper -- the channel taps, the mode, the config -- for the two handles that have it:
+    NarrowBank and bandplan.BandPlanBank.  A mixin in front of DownConverter."""
+
+    def _chan_setup(self, chan_taps, mode, chan_decim, block, squelch, gain):
+        gr, gi = chan_taps if isinstance(chan_taps, tuple) else (chan_taps, None)
+        self.gr = np.ascontiguousarray(gr, dtype=np.int16)
+        self.gi = None if gi is None else np.ascontiguousarray(gi, dtype=np.int16)
+        if self.gi is not None and self.gi.size != self.gr.size:
+            raise ValueError("gr and gi differ in length")
+        self.mode = MODES[mode] if isinstance(mode, str) else int(mode)
+        self.chan_decim, self.block, self.squelch, self.gain = int(chan_decim), int(block), int(squelch), int(gain)
+        self.width = 2 if self.mode == NARROW_IQ else 1
+
+    def _chan_args(self):
+        """chan_taps_re, chan_taps_im, n_chan_taps, cfg of a *_new (once self.chan_shift is set)"""
+        p16 = C.POINTER(C.c_int16)
+        cfg = NarrowConfig(self.mode, self.chan_decim, self.chan_shift, self.block, self.squelch, self.gain)
+        return (self.gr.ctypes.data_as(p16), None if self.gi is None else self.gi.ctypes.data_as(p16), self.gr.size, C.byref(cfg))
+
+    def run_batch(self, iq):
+        """iq uint8 [n_streams, nbytes] -> int16 [n_streams, rows, n] ([..., 2] of (re, im) in IQ mode)."""
+        out = super().run_batch(iq)
+        return out if self.mode == NARROW_IQ else out[..., 0].copy()
+
+
+class NarrowBank(ChanStage, DownConverter):
     """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream).  `chan_taps` is gr or the
     pair (gr, gi) (narrow_taps).  `shift=None` takes the smallest front-end shift with every |y| component <= 16384;
     `chan_shift=None` narrow_auto_shift.  `gain` is Q8."""
@@ -77,31 +103,18 @@ class NarrowBank(DownConverter):
     def __init__(self, taps, decim, phase_incs, chan_taps, chan_decim, mode=NARROW_FM, n_streams=1, block=256, squelch=0, gain=256,
                  chan_shift=None, shift=None, device_id=-1):
         self.taps = np.ascontiguousarray(taps, dtype=np.int16)
-        if isinstance(chan_taps, tuple):
-            gr, gi = chan_taps
-        else:
-            gr, gi = chan_taps, None
-        self.gr = np.ascontiguousarray(gr, dtype=np.int16)
-        self.gi = None if gi is None else np.ascontiguousarray(gi, dtype=np.int16)
-        if self.gi is not None and self.gi.size != self.gr.size:
-            raise ValueError("gr and gi differ in length")
-        self.mode = MODES[mode] if isinstance(mode, str) else int(mode)
-        self.decim, self.n_streams, self.chan_decim, self.block = int(decim), int(n_streams), int(chan_decim), int(block)
-        self.squelch, self.gain = int(squelch), int(gain)
+        self._chan_setup(chan_taps, mode, chan_decim, block, squelch, gain)
+        self.decim, self.n_streams = int(decim), int(n_streams)
         self.phase_incs = stream_phase_incs(phase_incs, self.n_streams)
         self.n_stations = self.phase_incs.shape[1]
         self.shift = stations_auto_shift(self.taps, self.phase_incs, limit=Y_LIMIT) if shift is None else int(shift)
         self.chan_shift = (narrow_auto_shift(self.taps, self.phase_incs, self.shift, self.gr, self.gi, self.mode)
                            if chan_shift is None else int(chan_shift))
-        self.width = 2 if self.mode == NARROW_IQ else 1
-        cfg = NarrowConfig(self.mode, self.chan_decim, self.chan_shift, self.block, self.squelch, self.gain)
         self._h = C.c_void_p()
         dev = DeviceConfig(self.n_streams, device_id, 0)
-        p16 = C.POINTER(C.c_int16)
-        check(lib().fmd_narrow_new(self.taps.ctypes.data_as(p16), self.taps.size, self.decim, self.shift,
-                                   self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations,
-                                   self.gr.ctypes.data_as(p16), None if self.gi is None else self.gi.ctypes.data_as(p16),
-                                   self.gr.size, C.byref(cfg), C.byref(dev), C.byref(self._h)))
+        check(lib().fmd_narrow_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim, self.shift,
+                                   self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations, *self._chan_args(),
+                                   C.byref(dev), C.byref(self._h)))
 
     def out_cap(self, nbytes):
         return int(lib().fmd_narrow_out_cap(self.decim, self.chan_decim, nbytes))
@@ -111,8 +124,3 @@ class NarrowBank(DownConverter):
         o, r = C.c_int(0), C.c_uint32(0)
         check(lib().fmd_narrow_level(self._h, int(stream), int(station), C.byref(o), C.byref(r)))
         return bool(o.value), r.value
-
-    def run_batch(self, iq):
-        """iq uint8 [n_streams, nbytes] -> int16 [n_streams, n_stations, n] ([..., 2] of (re, im) in IQ mode)."""
-        out = super().run_batch(iq)
-        return out if self.mode == NARROW_IQ else out[..., 0].copy()

@@ -142,6 +142,9 @@ def test_stage_two_domain_edges_both_sides():
     _, lib = _lib()
     for R, ok in ((0, False), (1, True), (8, True), (9, False), (32, False)):
         _edge(lib, ok, R=R)
+    _edge(lib, False, R=9)
+    msg = lib.fmd_last_error().decode()                          # this bank's own limits, not the narrow-band bank's
+    assert "chan_decim <= 8" in msg and "n_chan_taps <= 64" in msg, msg
     for Ta, ok in ((1, True), (64, True), (65, False), (256, False)):
         _edge(lib, ok, gr=np.full(Ta, 10, np.int16))
     _edge(lib, False, n_chan=0)

@@ -1,14 +1,17 @@
 """The five down-converter handles (station bank, channelizer, stereo, narrow-band and RDS bank) alive at once on the MI355X: they
 share one host layer (csrc/fmd_ddc.h), so each is checked bit for bit against its own definition while the others run, are reset,
-refuse a call and are freed around it."""
+refuse a call and are freed around it.  Likewise the narrow-band bank, the uniform channelizer and the band-plan bank: the two banks
+share their second stage's host side (csrc/fmd_chan_stage.h), and the band-plan bank drives a uniform channelizer of its own."""
 import numpy as np
 import pytest
 
+import bandplan_ref as br
 import channelizer_ref as cr
 import narrow_ref as nr
 import rds_ref as rr
 import stations_ref as sr
 import stereo_ref as st
+import uniform_ref as ur
 
 pytestmark = pytest.mark.gpu
 
@@ -100,3 +103,83 @@ def test_five_handles_interleaved_reset_refusal_and_free(fmd, oracle):
     ref2 = [cr.ChannelizerRef(h, D, incs[s], ch2.shift, z=sr.z_corr) for s in range(S)]
     assert _same(ch2.run_batch(cuts[0]), [ref2[s].feed(cuts[0][s]) for s in range(S)])
     ch2.close()
+
+
+N, HOP, SEL = 8, 8, [1, 4, 6]                                # the plan of the uniform channelizer and the band-plan bank: K channels
+CUTS_HOPS = (16 * 301, 16 * 257, 16 * 195)                   # whole hops; blocks of 16 audio samples and windows end inside calls
+
+
+def test_narrow_uniform_and_bandplan_interleaved_reset_refusal_and_free(fmd):
+    rng = np.random.default_rng(616)
+    h = rng.integers(-900, 901, T).astype(np.int16)          # the two-digit tap form
+    incs = np.array([[int(x) for x in rng.integers(0, 1 << 32, K)] for _ in range(S)], np.uint32)
+    assert max(np.abs(w).max() for i in ur.channel_incs(N, SEL) for w in sr.complex_taps(h, int(i))) > 127
+    gr = rng.integers(-1500, 1501, TA).astype(np.int16)      # real taps for the narrow-band bank, complex ones for the band-plan
+    gi = rng.integers(-1500, 1501, TA).astype(np.int16)      # bank: both variants of the second pass run
+    data = rng.integers(0, 256, (S, sum(CUTS_HOPS)), dtype=np.uint8)
+    cuts = np.split(data, np.cumsum(CUTS_HOPS)[:-1], axis=1)
+
+    nb = fmd.NarrowBank(h, D, incs, gr, R, mode="fm", n_streams=S, block=16, squelch=0, device_id=0)
+    uv = fmd.UniformChannelizer(h, N, HOP, channels=SEL, n_streams=S, device_id=0)
+    mk_bp = lambda: fmd.BandPlanBank(h, N, HOP, (gr, gi), R, mode="am", channels=SEL, n_streams=S, block=16, squelch=0, device_id=0)
+    bp = mk_bp()
+    assert nb.kernel_name(1).endswith("<false>") and bp.kernel_name(1).endswith("<true>")
+
+    def refs(kind):
+        if kind == "nb":
+            return [nr.NarrowRef(h, D, incs[s], nb.shift, nb.gr, nb.gi, nb.mode, R, nb.chan_shift, 16, 0, nb.gain, z=sr.z_corr)
+                    for s in range(S)]
+        if kind == "uv":
+            return [ur.UniformRef(h, N, HOP, uv.shift, channels=SEL) for _ in range(S)]
+        return [br.BandPlanRef(h, N, HOP, bp.shift, bp.gr, bp.gi, bp.mode, R, bp.chan_shift, 16, 0, bp.gain, channels=SEL) for _ in range(S)]
+
+    ref = {kind: refs(kind) for kind in ("nb", "uv", "bp")}
+    run = {"nb": nb.run_batch, "uv": uv.run_batch, "bp": lambda cut: bp.run_batch(cut)}
+
+    def levels_agree():
+        opn, rms = bp.levels()
+        want = [[ref["bp"][s].level(k) for k in range(K)] for s in range(S)]
+        return opn.tolist() == [[o for o, _ in row] for row in want] and rms.tolist() == [[r for _, r in row] for row in want]
+
+    def step(kind, cut):
+        """one call of one handle, against its definition; every call completes at least one output"""
+        exp = [ref[kind][s].feed(cut[s]) for s in range(S)]
+        got = run[kind](cut)
+        assert got.shape[2] == len(exp[0][0]) >= 1 and _same(got, exp), kind
+        assert kind != "bp" or levels_agree()
+        return got
+
+    # cut 1, the handles interleaved call by call
+    first = {kind: step(kind, cuts[0]) for kind in ("nb", "uv", "bp")}
+    assert first["bp"].any()
+
+    # the band-plan bank back to the start: it reproduces its first output, the other two continue unbroken
+    bp.reset()
+    assert bp.outputs() == 0 and not bp.levels()[0].any() and not bp.levels()[1].any()
+    ref["bp"] = refs("bp")
+    step("nb", cuts[1])
+    assert np.array_equal(step("bp", cuts[0]), first["bp"])
+    step("uv", cuts[1])
+    # a refused call on it between good calls on the others: nothing changes, its inner uniform channelizer included.  16 bytes
+    # are one hop, one y; after cut 1 (297 of them, 145 audio samples) the stride-2 second filter needs two more
+    before, lv = bp.outputs(), bp.levels()
+    assert ref["bp"][0].completes(16) < 1
+    with pytest.raises(fmd.FmdError) as e:
+        bp.run_batch(data[:, :16])
+    assert e.value.status == TOO_SHORT and bp.outputs() == before
+    assert np.array_equal(bp.levels()[0], lv[0]) and np.array_equal(bp.levels()[1], lv[1])
+    step("bp", cuts[1])                                      # (had the refused call advanced pass 1, this y would be one hop off)
+
+    step("uv", cuts[2])
+    step("bp", cuts[2])
+    step("nb", cuts[2])
+    assert uv.outputs() == ref["uv"][0].m_next and nb.outputs() == ref["nb"][0].n_next and bp.outputs() == ref["bp"][0].n_next
+    assert all(nb.level(s, k) == ref["nb"][s].level(k) for s in range(S) for k in range(K))
+
+    # freed in another order than created; a band-plan bank created afterwards starts clean
+    for hd in (uv, bp, nb):
+        hd.close()
+    bp = mk_bp()
+    ref["bp"] = refs("bp")
+    step("bp", cuts[0])
+    bp.close()

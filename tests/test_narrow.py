@@ -282,6 +282,8 @@ def test_domain_refusals_need_no_gpu():
     assert _new(lib, incs=np.zeros(33)) == U
     assert _new(lib, taps=np.full(64, 2047, np.int16), shift=0) == U          # B_y > 16384
     assert _new(lib, R=0) == U and _new(lib, R=33) == U
+    msg = lib.fmd_last_error().decode()                      # this bank's own limits, not the band-plan bank's
+    assert "chan_decim <= 32" in msg and "n_chan_taps <= 256" in msg, msg
     assert _new(lib, gr=np.ones(257, np.int16)) == U
     assert _new(lib, gr=[16384], cs=30) == U and _new(lib, gr=[1], gi=[-16384], cs=30) == U          # |tap| > 16383
     assert _new(lib, gr=[16383] * 4 + [4], cs=30) == U                       # G = 65536
