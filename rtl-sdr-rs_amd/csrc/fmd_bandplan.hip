@@ -291,7 +291,7 @@ int bp_enqueue(fmd_bandplan* h, const void* d_iq, size_t nbytes, void* d_out, si
 
 extern "C" {
 
-size_t fmd_bandplan_out_cap(uint32_t hop, uint32_t chan_decim, size_t nbytes) { return fmd_chan::chan_out_cap(hop, chan_decim, nbytes); }
+size_t fmd_bandplan_out_cap(uint32_t hop, uint32_t chan_decim, size_t nbytes) { return fmd_ddc_fir_out_cap(hop, chan_decim, nbytes); }
 
 int fmd_bandplan_new(const int16_t* taps, uint32_t n_taps, uint32_t n_channels, uint32_t hop, uint32_t shift, const uint32_t* channels,
                      uint32_t n_selected, const int16_t* chan_taps_re, const int16_t* chan_taps_im, uint32_t n_chan_taps,

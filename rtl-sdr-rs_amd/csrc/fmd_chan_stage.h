@@ -104,14 +104,6 @@ inline uint64_t chan_audio(const FmdDdcBank& b, const ChanStage& c, uint64_t sam
     return fmd_ddc_fir_outputs(c.Ta, c.R, fmd_ddc_outputs(b.T, b.D, samples));
 }
 
-// fmd_*_out_cap: audio samples per row that a call of nbytes can complete at most, at D samples per y and R y per audio sample
-inline size_t chan_out_cap(uint32_t D, uint32_t R, size_t nbytes)
-{
-    if (!D || !R) return 0;
-    const uint64_t d = 2ull * D * R;
-    return (size_t)((nbytes + d - 1) / d);
-}
-
 // The counts of one call: samples per stream; y before the call, of the call; audio samples before the call, of the call; rows;
 // dwords of a row of the call's y (a multiple of 4).
 struct ChanCall { uint64_t ns, mS, M, nS, NA, SK, ystride; };

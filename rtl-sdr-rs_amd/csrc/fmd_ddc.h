@@ -559,6 +559,14 @@ inline FmdDdcTiling fmd_ddc_tiling(uint32_t D, uint32_t nkc, uint32_t T, uint32_
 inline uint64_t fmd_ddc_outputs(uint32_t T, uint32_t D, uint64_t samples) { return samples >= T ? (samples - T) / D + 1 : 0; }
 // outputs of a second filter of Ta taps at stride R over m inputs
 inline uint64_t fmd_ddc_fir_outputs(uint32_t Ta, uint32_t R, uint64_t m) { return fmd_ddc_outputs(Ta, R, m); }
+// a second stage's `_out_cap` entry point: its outputs per row that a call of nbytes can complete at most, at D samples per
+// front-end output and R of those per output of the second filter
+inline size_t fmd_ddc_fir_out_cap(uint32_t D, uint32_t R, size_t nbytes)
+{
+    if (!D || !R) return 0;
+    const uint64_t d = 2ull * D * R;
+    return (size_t)((nbytes + d - 1) / d);
+}
 
 // The checks every enqueue starts with; d_out must be aligned to `out_align` (a power of two) bytes.
 inline int fmd_ddc_check_call(size_t nbytes, const void* d_iq, const void* d_out, uint32_t out_align)

@@ -324,7 +324,7 @@ int nb_enqueue(fmd_narrow* h, const void* d_iq, size_t nbytes, void* d_out, size
 
 extern "C" {
 
-size_t fmd_narrow_out_cap(uint32_t decim, uint32_t chan_decim, size_t nbytes) { return fmd_chan::chan_out_cap(decim, chan_decim, nbytes); }
+size_t fmd_narrow_out_cap(uint32_t decim, uint32_t chan_decim, size_t nbytes) { return fmd_ddc_fir_out_cap(decim, chan_decim, nbytes); }
 
 uint32_t fmd_narrow_out_width(uint32_t mode) { return mode == FMD_NARROW_IQ ? 2u : 1u; }
 

@@ -12,19 +12,17 @@
 //   4. one wave per station row: the integer discriminator (fmd_device.h disc_nosel), the pilot products x cosq(theta),
 //      x sinq(theta) summed per block (a tile touches at most two: P >= 1024), reduced across the wave and added into the call's
 //      block sums with 64-bit integer atomics (exact in any order); x stored as i16.
-// Pass 2 (fmd_stereo_audio_kernel): one workgroup = one (stream, station) row and one tile of up to 256 audio samples:
-//   1. the estimate (present, c2, s2) of each block the tile's inputs need, one lane per block (i64 / 128-bit arithmetic);
-//   2. (x, s) of every MPX sample the tile's FIR reads into LDS: the carried Ta - 1 samples of the previous call from the history,
-//      the call's own with s = (x kc) >> 14, kc from the NCO table in LDS;
-//   3. one lane per audio sample: both FIRs with v_mad_i32_i24 (|g| <= 16383, |x| <= 32768, |s| <= 65540 fit 24-bit operands), the
-//      matrix step, saturation, one dword store of the (L, R) pair.
-// The last tile of a row writes the next call's (x, s) history; tile 0 the next call's block carry (the sums of the last
-// complete block, the partial sums of a block that straddles calls).
+// Pass 2 (fmd_stereo_audio_kernel) is the second-pass tile that this bank and the RDS bank share (fmd_stereo_mpx.h, stage_tile: one
+// workgroup = one (stream, station) row and one tile of up to 256 audio samples, the pairs of every MPX sample the tile's FIR reads
+// in LDS, the last Ta - 1 of them carried from call to call, one lane per audio sample) with this bank's side (AudioPass):
+//   - before the staging, the estimate (present, c2, s2) of each block the tile's inputs need, one lane per block;
+//   - the pair (x, s), s = (x kc) >> 14 with kc from the NCO table in LDS;
+//   - from the two FIR sums (|g| <= 16383, |x| <= 32768, |s| <= 65540 fit v_mad_i32_i24's 24-bit operands) the matrix step, the
+//     saturation, one dword store of the (L, R) pair.
+// The host side of the second stage -- handle, constructor, launch fields, enqueue -- is that header's as well.
 #include "../../include/fmd.h"
 
 #include <hip/hip_runtime.h>
-
-#include <new>
 
 #include "fmd_ddc.h"
 #include "fmd_device.h"
@@ -36,8 +34,7 @@ namespace fmd_sto {
 using fmd_ddc::kThreads;
 using fmd_ddc::kTableBytes;
 
-constexpr uint32_t kAudioTile = 256;                      // audio samples per pass-2 tile (at most)
-constexpr uint32_t kXCap = 2048;                          // (x, s) pairs a pass-2 tile stages: R tile + 2 Ta <= kXCap
+constexpr uint32_t kXCap = 2048;                          // (x, s) pairs a pass-2 tile has room for: R tile + 2 Ta <= kXCap
 constexpr uint32_t kMaxBlocks = 4;                        // blocks one pass-2 tile touches (<= 3: kXCap / 1024 + 1)
 
 __device__ __forceinline__ long long wave_sum(long long v)
@@ -116,26 +113,9 @@ hipError_t launch_mpx(const MpxLaunch& A, size_t lds, hipStream_t stream)
     return hipGetLastError();
 }
 
-struct AudioLaunch {
-    const int16_t* x;          // [S K][M]
-    uint32_t M;
-    const int32_t* xh_in;      // [S K][HXS][2]: (x, s) of the HX samples before the call
-    int32_t* xh_out;
-    uint32_t HX, HXS;          // Ta - 1, row stride (>= 1)
-    const long long* sums;     // [nbc][S K][2]
-    const long long* carry_in; // [S K][4]: I, Q of block jfirst - 1; partial I, Q of block jfirst from earlier calls
-    long long* carry_out;
-    uint32_t SK;
-    uint64_t mS, mE, jfirst;   // MPX samples before / after the call, block of mS
-    uint64_t nS;               // audio samples before the call
-    uint32_t NA, na, ntiles;   // audio samples of the call, per tile, tiles per row
-    uint32_t R, Ta, audio_shift;
-    uint32_t pshift, inc_p;
+struct AudioLaunch : StageLaunch {                          // x: the multiplex, pairs (x, s), shift: audio_shift, out: (L, R)
+    uint32_t inc_p;
     uint64_t thr;              // pilot_min P 8192 (0: every block absent)
-    const int16_t* g;
-    const uint32_t* tab;
-    uint32_t* out;             // [S K][out_stride] (L, R) pairs
-    uint64_t out_stride;
 };
 
 // a^2 + b^2 >= thr^2 in 128 bits (|a|, |b| <= 2^43, thr <= 2^41)
@@ -149,151 +129,88 @@ __device__ __forceinline__ bool pilot_present(long long I, long long Q, uint64_t
     return hi > thi || (hi == thi && lo >= tlo);
 }
 
-__global__ void __launch_bounds__(kThreads) fmd_stereo_audio_kernel(const AudioLaunch L)
-{
-    __shared__ __attribute__((aligned(16))) int2 xs[kXCap];
-    __shared__ int32_t gl[256];
-    __shared__ int16_t tab[1024];
-    __shared__ int32_t est[kMaxBlocks][3];                   // present, c2, s2 of block jA - 1 + i
-    const uint32_t tid = threadIdx.x;
-    const uint32_t row = blockIdx.x / L.ntiles, t = blockIdx.x - row * L.ntiles;
-    if (row >= L.SK) return;
+// The audio pass's side of a second-pass tile (fmd_stereo_mpx.h, stage_tile).
+struct AudioPass {
+    static constexpr uint32_t kSlots = kXCap;
+    int32_t (*est)[3];                                       // LDS: present, c2, s2 of block jA - 1 + i
+    uint64_t jA;                                             // block of the first of the call's own samples the tile stages
 
-    const uint32_t na0 = t * L.na;                           // first audio sample (of this call) of the tile
-    const uint32_t cnt = L.NA - na0 < L.na ? L.NA - na0 : L.na;
-    const bool last = t == L.ntiles - 1u;
-    // virtual index v: MPX sample mS - HX + v (v < HX: the carried history)
-    const uint32_t vfir = (uint32_t)(L.R * (L.nS + na0) + L.HX - L.mS);      // the tile's first FIR window
-    const uint32_t vtot = L.HX + L.M;
-    uint32_t vlo = vfir, vhi = vfir + L.R * (cnt - 1u) + L.Ta;
-    if (last) { vlo = vlo < L.M ? vlo : L.M; vhi = vtot; }   // the last tile also forms the next call's history
-    const uint32_t span = vhi - vlo;                         // <= kXCap: host plan
-    const uint32_t va = vlo > L.HX ? vlo : L.HX;             // first virtual index of the call's own samples
-    const uint64_t jA = (L.mS + (va - L.HX)) >> L.pshift;
+    static __device__ __forceinline__ uint32_t slot(uint32_t i) { return i; }
 
-    // ---- 1. block estimates, the NCO table, the taps ------------------------------------------------------------------------
-    if (va < vhi && tid < kMaxBlocks) {
+    // the estimate of each block the tile's own samples need, one lane per block (i64 / 128-bit arithmetic)
+    __device__ __forceinline__ void before(const AudioLaunch& L, uint32_t row, uint32_t tid, uint32_t vlo, uint32_t vhi)
+    {
+        const uint32_t va = vlo > L.HX ? vlo : L.HX;         // first virtual index of the call's own samples
+        jA = (L.mS + (va - L.HX)) >> L.pshift;
+        if (va >= vhi || tid >= kMaxBlocks) return;
         const uint64_t jB = (L.mS + (vhi - 1u - L.HX)) >> L.pshift;
-        if (jA + tid <= jB) {
-            long long I, Q;
-            block_iq(L, row, (int64_t)(jA + tid) - 1, I, Q);
-            int present = pilot_present(I, Q, L.thr) ? 1 : 0, c2 = 0, s2 = 0;
-            if (present) {
-                const uint64_t mx = (uint64_t)(I < 0 ? -I : I) | (uint64_t)(Q < 0 ? -Q : Q);   // same bit length as the max
-                const int bl = 64 - __builtin_clzll(mx);
-                const int e = bl > 23 ? bl - 23 : 0;
-                const long long a = I >> e, b = Q >> e;
-                const long long E = a * a + b * b;
-                c2 = (int)((b * b - a * a) * 16384 / E);
-                s2 = (int)((2 * a * b) * 16384 / E);
-            }
-            est[tid][0] = present; est[tid][1] = c2; est[tid][2] = s2;
+        if (jA + tid > jB) return;
+        long long I, Q;
+        block_iq(L, row, (int64_t)(jA + tid) - 1, I, Q);
+        int present = pilot_present(I, Q, L.thr) ? 1 : 0, c2 = 0, s2 = 0;
+        if (present) {
+            const uint64_t mx = (uint64_t)(I < 0 ? -I : I) | (uint64_t)(Q < 0 ? -Q : Q);   // same bit length as the max
+            const int bl = 64 - __builtin_clzll(mx);
+            const int e = bl > 23 ? bl - 23 : 0;
+            const long long a = I >> e, b = Q >> e;
+            const long long E = a * a + b * b;
+            c2 = (int)((b * b - a * a) * 16384 / E);
+            s2 = (int)((2 * a * b) * 16384 / E);
         }
+        est[tid][0] = present; est[tid][1] = c2; est[tid][2] = s2;
     }
-    for (uint32_t i = tid; i < 512u; i += kThreads) reinterpret_cast<uint32_t*>(tab)[i] = L.tab[i];
-    for (uint32_t i = tid; i < L.Ta; i += kThreads) gl[i] = L.g[i];
-    __syncthreads();
 
-    // ---- 2. (x, s) of the tile's samples ------------------------------------------------------------------------------------
-    const int16_t* const xr = L.x + (uint64_t)row * L.M;
-    const int32_t* const hin = L.xh_in + (uint64_t)row * L.HXS * 2u;
-    for (uint32_t i = tid; i < span; i += kThreads) {
-        const uint32_t v = vlo + i;
-        int2 p;
-        if (v < L.HX) {
-            p = int2{hin[2u * v], hin[2u * v + 1u]};
-        } else {
-            const uint64_t m = L.mS + (v - L.HX);
-            const int xv = xr[v - L.HX];
-            const uint32_t jj = (uint32_t)((m >> L.pshift) - jA);
-            int sv = 0;
-            if (est[jj][0]) {
-                const uint32_t ix = (((uint32_t)m * L.inc_p) << 1) >> 22;                  // 2 theta
-                const int kc = (tab[(ix - 256u) & 1023u] * est[jj][1] + tab[ix] * est[jj][2]) >> 13;
-                sv = (xv * kc) >> 14;
-            }
-            p = int2{xv, sv};
+    // (x, s): s = (x kc) >> 14 with kc from 2 theta and the block's estimate, 0 while the pilot is absent
+    __device__ __forceinline__ int2 pair(const AudioLaunch& L, const int16_t* tab, uint64_t m, int xv) const
+    {
+        const uint32_t jj = (uint32_t)((m >> L.pshift) - jA);
+        int sv = 0;
+        if (est[jj][0]) {
+            const uint32_t ix = (((uint32_t)m * L.inc_p) << 1) >> 22;                      // 2 theta
+            const int kc = (tab[(ix - 256u) & 1023u] * est[jj][1] + tab[ix] * est[jj][2]) >> 13;
+            sv = (xv * kc) >> 14;
         }
-        xs[i] = p;
+        return int2{xv, sv};
     }
-    __syncthreads();
-    if (last) {                                              // the next call's history: virtual indices M ... M + HX - 1
-        int32_t* const hout = L.xh_out + (uint64_t)row * L.HXS * 2u;
-        for (uint32_t i = tid; i < L.HX; i += kThreads) {
-            const int2 p = xs[L.M + i - vlo];
-            hout[2u * i] = p.x; hout[2u * i + 1u] = p.y;
-        }
-    }
-    if (t == 0u && tid == 0u) write_block_carry(L, row);     // the next call's block carry
 
-    // ---- 3. FIRs, matrix, saturation ------------------------------------------------------------------------------------------
-    uint32_t* const out = L.out + (uint64_t)row * L.out_stride + na0;
-    const uint32_t sh = L.audio_shift + 1u;
-    for (uint32_t i = tid; i < cnt; i += kThreads) {
-        const int2* w = xs + (vfir - vlo) + L.R * i;
-        int m = 0, sd = 0;
-        for (uint32_t k = 0; k < L.Ta; ++k) {
-            const int2 p = w[k];
-            const int gk = gl[k];
-            m = __mul24(gk, p.x) + m;
-            sd = __mul24(gk, p.y) + sd;
-        }
-        int l = (m + sd) >> sh, r = (m - sd) >> sh;
+    // the matrix step and the saturation: a = sum g x, b = sum g s
+    static __device__ __forceinline__ uint32_t output(int a, int b, uint32_t shift)
+    {
+        int l = (a + b) >> (shift + 1u), r = (a - b) >> (shift + 1u);
         l = l > 32767 ? 32767 : (l < -32768 ? -32768 : l);
         r = r > 32767 ? 32767 : (r < -32768 ? -32768 : r);
-        out[i] = ((uint32_t)l & 0xFFFFu) | ((uint32_t)r << 16);
+        return ((uint32_t)l & 0xFFFFu) | ((uint32_t)r << 16);
     }
+};
+
+__global__ void __launch_bounds__(kThreads) fmd_stereo_audio_kernel(const AudioLaunch L)
+{
+    __shared__ int32_t est[kMaxBlocks][3];
+    stage_tile(L, AudioPass{est, 0});
 }
 
 }  // namespace fmd_sto
 
-struct fmd_stereo {
-    FmdDdcBank bank;
-    fmd_sto::MpxState mpx;
-    uint32_t Ta = 0, R = 0, audio_shift = 0;
-    uint32_t HX = 0, HXS = 0, na = 0;
-    void* d_g = nullptr;                                  // int16 audio taps
-    FmdDdcPair xh;                                        // [S K][HXS][2] (x, s) history (int32)
-};
+struct fmd_stereo : fmd_sto::MpxHandle {};
 
 namespace {
 
+constexpr fmd_sto::StageLimits kLimits{106000u, "audio_decim", "audio_taps", "audio_shift", 16u};
+
 int st_enqueue(fmd_stereo* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
 {
-    FmdDdcCore& c = h->bank.core;
-    fmd_sto::MpxCall q;
-    fmd_sto::MpxLaunch A{};
-    if (const int rc = fmd_sto::mpx_plan_call(h->bank, h->mpx, h->Ta, h->R, h->na, d_iq, nbytes, d_out, out_cap, q, A)) return rc;
-
-    fmd_sto::AudioLaunch B{};
-    fmd_sto::mpx_fill_blocks(B, h->bank, h->mpx, q);
-    B.xh_in = h->xh.in<int32_t>(c.cur); B.xh_out = h->xh.out<int32_t>(c.cur);
-    B.HX = h->HX; B.HXS = h->HXS;
-    B.na = h->na;
-    B.R = h->R; B.Ta = h->Ta; B.audio_shift = h->audio_shift;
-    B.inc_p = h->mpx.inc_p;
-    B.thr = (uint64_t)h->mpx.pilot_min * h->mpx.P * 8192u;
-    B.g = static_cast<const int16_t*>(h->d_g);
-    B.out = static_cast<uint32_t*>(d_out); B.out_stride = out_cap;
-
-    if (const int rc = fmd_sto::mpx_enqueue(h->bank, h->mpx, q, A, stream)) return rc;
-    hipLaunchKernelGGL(fmd_sto::fmd_stereo_audio_kernel, dim3((uint32_t)(q.nt2 * q.SK)), dim3(fmd_sto::kThreads), 0, stream, B);
-    FMD_DDC_TRY(hipGetLastError());
-    fmd_ddc_commit(c, stream, q.ns);
-    if (out_len) *out_len = (size_t)q.NA;
-    return FMD_OK;
+    return fmd_sto::stage_enqueue<fmd_sto::AudioLaunch>(*h, d_iq, nbytes, d_out, out_cap, out_len, stream, [&](fmd_sto::AudioLaunch& B, uint32_t grid) {
+        B.inc_p = h->mpx.inc_p;
+        B.thr = (uint64_t)h->mpx.pilot_min * h->mpx.P * 8192u;
+        hipLaunchKernelGGL(fmd_sto::fmd_stereo_audio_kernel, dim3(grid), dim3(fmd_sto::kThreads), 0, stream, B);
+    });
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t fmd_stereo_out_cap(uint32_t decim, uint32_t audio_decim, size_t nbytes)
-{
-    if (!decim || !audio_decim) return 0;
-    const uint64_t d = 2ull * decim * audio_decim;
-    return (size_t)((nbytes + d - 1) / d);
-}
+size_t fmd_stereo_out_cap(uint32_t decim, uint32_t audio_decim, size_t nbytes) { return fmd_ddc_fir_out_cap(decim, audio_decim, nbytes); }
 
 int fmd_stereo_pilot_inc(uint32_t capture_rate, uint32_t decim, uint32_t* inc)
 {
@@ -307,41 +224,12 @@ int fmd_stereo_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
                    uint32_t n_stations, const int16_t* audio_taps, uint32_t n_audio_taps, const fmd_stereo_config* cfg,
                    const fmd_device_config* dev, fmd_stereo** out)
 {
-    if (!taps || !phase_inc || !audio_taps || !cfg || !dev || !out || dev->n_channels == 0) {
-        fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG;
-    }
-    *out = nullptr;
-    if (const int rc = fmd_ddc_front_args(taps, n_taps, decim, shift, n_stations, dev)) return rc;
-    if ((uint64_t)cfg->capture_rate < 106000ull * decim) { fmd_internal_set_err("need capture_rate >= 106000 * decim"); return FMD_ERR_UNSUPPORTED; }
-    const uint32_t P = cfg->block;
-    if (P < 1024u || P > 16384u || (P & (P - 1u)) != 0) { fmd_internal_set_err("block must be a power of two in [1024, 16384]"); return FMD_ERR_UNSUPPORTED; }
-    if (cfg->audio_decim < 1u || cfg->audio_decim > 32u || n_audio_taps < 1u || n_audio_taps > 256u || cfg->audio_shift > 16u ||
-        cfg->pilot_min > 16384u) {
-        fmd_internal_set_err("need 1 <= audio_decim <= 32, 1 <= n_audio_taps <= 256, audio_shift <= 16, pilot_min <= 16384");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    uint64_t gsum = 0;
-    for (uint32_t t = 0; t < n_audio_taps; ++t) gsum += (uint64_t)(audio_taps[t] < 0 ? -(int)audio_taps[t] : audio_taps[t]);
-    if (gsum > 16383u) { fmd_internal_set_err("sum |audio_taps| > 16383"); return FMD_ERR_UNSUPPORTED; }
-    fmd_stereo* h = new (std::nothrow) fmd_stereo();
-    if (!h) return FMD_ERR_NOMEM;
-    uint64_t bound;
-    if (const int rc = fmd_ddc_bank_front(h->bank, taps, n_taps, decim, shift, phase_inc, n_stations, dev, &bound)) { delete h; return rc; }
-    fmd_sto::mpx_init(h->bank, h->mpx, P, cfg->pilot_min, cfg->capture_rate);
-    h->Ta = n_audio_taps; h->R = cfg->audio_decim; h->audio_shift = cfg->audio_shift;
-    h->HX = n_audio_taps - 1u; h->HXS = h->HX ? h->HX : 1u;
-    const uint32_t na = (fmd_sto::kXCap - 2u * h->Ta) / h->R;   // >= 48: R tile + 2 Ta <= kXCap
-    h->na = na < fmd_sto::kAudioTile ? na : fmd_sto::kAudioTile;
-    fmd_ddc_add_pair(h->bank.core, h->xh, (size_t)h->bank.S * h->bank.K * h->HXS * 8);
-    fmd_ddc_add_owned(h->bank.core, h->d_g, audio_taps, 2u * n_audio_taps);
-
-    const char* what;
-    if (const int rc = fmd_ddc_bank_device(h->bank, dev, &what)) {
-        if (!what) { delete h; return rc; }
-        fmd_internal_set_err(what); fmd_stereo_free(h); return rc;
-    }
-    *out = h;
-    return FMD_OK;
+    if (!cfg) { fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG; }
+    const fmd_sto::StageConfig c{cfg->capture_rate, cfg->block, cfg->audio_decim, cfg->audio_shift, cfg->pilot_min};
+    uint64_t gsum;
+    if (const int rc = fmd_sto::stage_args(kLimits, taps, n_taps, decim, shift, phase_inc, n_stations, audio_taps, n_audio_taps, c, dev, out, &gsum)) return rc;
+    const uint32_t room = fmd_sto::kXCap - 2u * n_audio_taps;   // na >= 48: R na + 2 Ta <= kXCap
+    return fmd_sto::stage_new(taps, n_taps, decim, shift, phase_inc, n_stations, audio_taps, n_audio_taps, c, room, dev, fmd_stereo_free, out);
 }
 
 void fmd_stereo_free(fmd_stereo* h)
@@ -376,17 +264,11 @@ int fmd_stereo_run_batch(fmd_stereo* h, const uint8_t* iq, size_t nbytes, int16_
     return fmd_ddc_run_batch(h->bank, iq, nbytes, out, out_bytes, out_cap, out_len, [h](auto... a) { return st_enqueue(h, a...); });
 }
 
-int fmd_stereo_outputs(const fmd_stereo* h, uint64_t* outputs)
-{
-    if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *outputs = fmd_ddc_fir_outputs(h->Ta, h->R, fmd_ddc_outputs(h->bank.T, h->bank.D, h->bank.core.pos));
-    return FMD_OK;
-}
+int fmd_stereo_outputs(const fmd_stereo* h, uint64_t* outputs) { return fmd_sto::stage_outputs(h, outputs); }
 
 int fmd_stereo_pilot(fmd_stereo* h, uint32_t stream, uint32_t station, int* present, uint32_t* level)
 {
-    if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    return fmd_sto::mpx_pilot(h->bank, h->mpx, stream, station, present, level);
+    return fmd_sto::stage_pilot(h, stream, station, present, level);
 }
 
 int fmd_stereo_kernel_name(const fmd_stereo* h, uint32_t pass, char* name, size_t cap)

@@ -1,7 +1,13 @@
-// fmd_stereo_mpx.h -- the multiplex pass (fmd_sto::fmd_stereo_mpx_kernel, fmd_stereo.hip) as the handles that start from the
-// multiplex use it: the stereo station bank (fmd_stereo.hip) and the RDS bank (fmd_rds.hip).  The kernel is compiled once, in
-// fmd_stereo.hip; this header holds its launch struct, its tiling plan, the launch itself, the host state and call plan of the
-// multiplex stage, the pilot report, and the device side of the block sums that both second passes continue.
+// fmd_stereo_mpx.h -- the multiplex stage and the second stage over it, as the handles that start from the multiplex use them: the
+// stereo station bank (fmd_stereo.hip) and the RDS bank (fmd_rds.hip).
+//
+// The multiplex pass (fmd_sto::fmd_stereo_mpx_kernel) is compiled once, in fmd_stereo.hip; this header holds its launch struct, its
+// tiling plan, the launch itself, the host state and call plan of the multiplex stage and the pilot report.
+//
+// The second stage is a real FIR at stride R over pairs that a bank forms from the multiplex sample x[m] and the NCO table, with the
+// last Ta - 1 pairs carried from call to call.  The two banks keep their own pass kernels and launch structs; this header holds what
+// is the same around and inside them: the constructor's checks and steps, the host state, the launch fields both kernels read, the
+// enqueue, the entry points' one-liners, and the device skeleton of a second-pass tile (stage_tile) with the block sums it continues.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +15,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <new>
 
 #include "fmd_ddc.h"
 
@@ -144,39 +151,166 @@ inline int mpx_enqueue(FmdDdcBank& b, MpxState& m, const MpxCall& q, const MpxLa
     return FMD_OK;
 }
 
-// The fields of a second pass's launch struct that continue the pilot's block sums (same names in both).
-template <class Launch>
-inline void mpx_fill_blocks(Launch& B, const FmdDdcBank& b, const MpxState& m, const MpxCall& q)
+// ---- the second stage over the multiplex: host ------------------------------------------------------------------------------------
+
+constexpr uint32_t kStageTile = 256;                      // outputs per second-pass tile (at most)
+
+// What a handle holds for its second stage, and the handle itself: fmd_stereo and fmd_rds are one each.
+struct MpxStage {
+    uint32_t Ta = 0, R = 0, shift = 0;                    // taps, stride, the output's shift
+    uint32_t HX = 0, HXS = 0, na = 0;                     // Ta - 1, its row stride (>= 1), outputs per tile
+    void* d_g = nullptr;                                  // int16 taps
+    FmdDdcPair ph;                                        // [S K][HXS][2] pair history (int32)
+};
+struct MpxHandle {
+    FmdDdcBank bank;
+    MpxState mpx;
+    MpxStage st;
+};
+
+// A bank's config as plain values, and the bank's own names and limits in the refusal texts.
+struct StageConfig { uint32_t capture_rate, block, R, shift, pilot_min; };
+struct StageLimits { uint32_t rate_floor; const char* decim; const char* taps; const char* shift; uint32_t max_shift; };
+
+// The checks of a *_new whose `cfg` is not null, in the order they refuse.  *gsum = sum |g|.
+template <class H>
+inline int stage_args(const StageLimits& lim, const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t* phase_inc,
+                      uint32_t n_stations, const int16_t* g, uint32_t Ta, const StageConfig& c, const fmd_device_config* dev, H** out,
+                      uint64_t* gsum)
 {
-    B.x = static_cast<const int16_t*>(m.d_x); B.M = (uint32_t)q.M;
-    B.sums = static_cast<const long long*>(m.d_sums);
-    B.carry_in = m.carry.in<long long>(b.core.cur); B.carry_out = m.carry.out<long long>(b.core.cur);
+    if (!taps || !phase_inc || !g || !dev || !out || dev->n_channels == 0) { fmd_internal_set_err("null / empty argument"); return FMD_ERR_INVALID_ARG; }
+    *out = nullptr;
+    if (const int rc = fmd_ddc_front_args(taps, n_taps, decim, shift, n_stations, dev)) return rc;
+    char m[160];
+    const auto refuse = [](const char* text) { fmd_internal_set_err(text); return FMD_ERR_UNSUPPORTED; };
+    snprintf(m, sizeof m, "need capture_rate >= %u * decim", lim.rate_floor);
+    if ((uint64_t)c.capture_rate < (uint64_t)lim.rate_floor * decim) return refuse(m);
+    if (c.block < 1024u || c.block > 16384u || (c.block & (c.block - 1u)) != 0) return refuse("block must be a power of two in [1024, 16384]");
+    snprintf(m, sizeof m, "need 1 <= %s <= 32, 1 <= n_%s <= 256, %s <= %u, pilot_min <= 16384", lim.decim, lim.taps, lim.shift, lim.max_shift);
+    if (c.R < 1u || c.R > 32u || Ta < 1u || Ta > 256u || c.shift > lim.max_shift || c.pilot_min > 16384u) return refuse(m);
+    *gsum = 0;
+    for (uint32_t t = 0; t < Ta; ++t) *gsum += (uint64_t)(g[t] < 0 ? -(int)g[t] : g[t]);
+    snprintf(m, sizeof m, "sum |%s| > 16383", lim.taps);
+    if (*gsum > 16383u) return refuse(m);                 // both FIR sums fit 24-bit operands and 32-bit accumulators
+    return FMD_OK;
+}
+
+// In a *_new, after the bank's front step and before its device step: the multiplex stage, the derived fields, the history pair
+// and the taps.  `room` is the pairs a tile may stage beyond the Ta (or 2 Ta) that the bank's kernel sets aside: R na <= room.
+inline void stage_init(MpxHandle& h, const StageConfig& c, const int16_t* g, uint32_t Ta, uint32_t room)
+{
+    mpx_init(h.bank, h.mpx, c.block, c.pilot_min, c.capture_rate);
+    MpxStage& s = h.st;
+    s.Ta = Ta; s.R = c.R; s.shift = c.shift;
+    s.HX = Ta - 1u; s.HXS = s.HX ? s.HX : 1u;
+    s.na = room / c.R < kStageTile ? room / c.R : kStageTile;
+    fmd_ddc_add_pair(h.bank.core, s.ph, (size_t)h.bank.S * h.bank.K * s.HXS * 8);
+    fmd_ddc_add_owned(h.bank.core, s.d_g, g, 2u * Ta);
+}
+
+// A *_new from the handle on: the bank's front step, stage_init, the device step.  A device that refuses has allocated nothing and
+// the handle is deleted; a failed upload goes through the bank's own *_free.
+template <class H>
+inline int stage_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t* phase_inc, uint32_t n_stations,
+                     const int16_t* g, uint32_t Ta, const StageConfig& c, uint32_t room, const fmd_device_config* dev, void (*free_h)(H*), H** out)
+{
+    H* h = new (std::nothrow) H();
+    if (!h) return FMD_ERR_NOMEM;
+    uint64_t bound;
+    if (const int rc = fmd_ddc_bank_front(h->bank, taps, n_taps, decim, shift, phase_inc, n_stations, dev, &bound)) { delete h; return rc; }
+    stage_init(*h, c, g, Ta, room);
+    const char* what;
+    if (const int rc = fmd_ddc_bank_device(h->bank, dev, &what)) {
+        if (!what) { delete h; return rc; }
+        fmd_internal_set_err(what); free_h(h); return rc;
+    }
+    *out = h;
+    return FMD_OK;
+}
+
+// What both second passes read: a bank's launch struct is this and the fields of its carrier.
+struct StageLaunch {
+    const int16_t* x;          // [S K][M]
+    uint32_t M;
+    const int32_t* ph_in;      // [S K][HXS][2]: the pairs of the HX samples before the call
+    int32_t* ph_out;
+    uint32_t HX, HXS;          // Ta - 1, row stride (>= 1)
+    const long long* sums;     // [nbc][S K][2]
+    const long long* carry_in; // [S K][4]: I, Q of block jfirst - 1; partial I, Q of block jfirst from earlier calls
+    long long* carry_out;
+    uint32_t SK;
+    uint64_t mS, mE, jfirst;   // MPX samples before / after the call, block of mS
+    uint64_t nS;               // outputs before the call
+    uint32_t NA, na, ntiles;   // outputs of the call, per tile, tiles per row
+    uint32_t R, Ta, shift, pshift;
+    const int16_t* g;
+    const uint32_t* tab;
+    uint32_t* out;             // [S K][out_stride] packed pairs of int16
+    uint64_t out_stride;
+};
+
+inline void stage_fill(StageLaunch& B, const MpxHandle& h, const MpxCall& q, void* d_out, size_t out_cap)
+{
+    const int cur = h.bank.core.cur;
+    B.x = static_cast<const int16_t*>(h.mpx.d_x); B.M = (uint32_t)q.M;
+    B.ph_in = h.st.ph.in<int32_t>(cur); B.ph_out = h.st.ph.out<int32_t>(cur);
+    B.HX = h.st.HX; B.HXS = h.st.HXS;
+    B.sums = static_cast<const long long*>(h.mpx.d_sums);
+    B.carry_in = h.mpx.carry.in<long long>(cur); B.carry_out = h.mpx.carry.out<long long>(cur);
     B.SK = (uint32_t)q.SK;
     B.mS = q.mS; B.mE = q.mE; B.jfirst = q.jfirst; B.nS = q.nS;
-    B.NA = (uint32_t)q.NA; B.ntiles = (uint32_t)q.nt2;
-    B.pshift = m.pshift;
-    B.tab = b.core.d_tab;
+    B.NA = (uint32_t)q.NA; B.na = h.st.na; B.ntiles = (uint32_t)q.nt2;
+    B.R = h.st.R; B.Ta = h.st.Ta; B.shift = h.st.shift; B.pshift = h.mpx.pshift;
+    B.g = static_cast<const int16_t*>(h.st.d_g);
+    B.tab = h.bank.core.d_tab;
+    B.out = static_cast<uint32_t*>(d_out); B.out_stride = out_cap;
+}
+
+// An enqueue: the call's plan, both launch structs, the multiplex pass, then launch(B, grid) -- the bank sets its carrier fields
+// and launches its second pass on `grid` workgroups of kThreads -- and the commit.
+template <class Launch, class Fn>
+inline int stage_enqueue(MpxHandle& h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream,
+                         Fn launch)
+{
+    MpxCall q;
+    MpxLaunch A{};
+    if (const int rc = mpx_plan_call(h.bank, h.mpx, h.st.Ta, h.st.R, h.st.na, d_iq, nbytes, d_out, out_cap, q, A)) return rc;
+    Launch B{};
+    stage_fill(B, h, q, d_out, out_cap);
+    if (const int rc = mpx_enqueue(h.bank, h.mpx, q, A, stream)) return rc;
+    launch(B, (uint32_t)(q.nt2 * q.SK));
+    FMD_DDC_TRY(hipGetLastError());
+    fmd_ddc_commit(h.bank.core, stream, q.ns);
+    if (out_len) *out_len = (size_t)q.NA;
+    return FMD_OK;
+}
+
+// fmd_stereo_outputs / fmd_rds_outputs
+inline int stage_outputs(const MpxHandle* h, uint64_t* outputs)
+{
+    if (!h || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    *outputs = fmd_ddc_fir_outputs(h->st.Ta, h->st.R, fmd_ddc_outputs(h->bank.T, h->bank.D, h->bank.core.pos));
+    return FMD_OK;
 }
 
 // fmd_stereo_pilot / fmd_rds_pilot: the last complete block of (stream, station)
-inline int mpx_pilot(const FmdDdcBank& b, const MpxState& m, uint32_t stream, uint32_t station, int* present, uint32_t* level)
+inline int stage_pilot(const MpxHandle* h, uint32_t stream, uint32_t station, int* present, uint32_t* level)
 {
-    if (!present || !level) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    if (!h || !present || !level) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    const FmdDdcBank& b = h->bank;
     if (stream >= b.S || station >= b.K) { fmd_internal_set_err("stream or station out of range"); return FMD_ERR_INVALID_ARG; }
     FMD_DDC_ON_DEVICE(b.core.device);
     FMD_DDC_TRY(hipDeviceSynchronize());
     long long c[4];
-    FMD_DDC_TRY(hipMemcpy(c, m.carry.in<long long>(b.core.cur) + 4ull * ((size_t)stream * b.K + station), sizeof c, hipMemcpyDeviceToHost));
-    pilot_report(c[0], c[1], m.pilot_min, m.P, present, level);
+    FMD_DDC_TRY(hipMemcpy(c, h->mpx.carry.in<long long>(b.core.cur) + 4ull * ((size_t)stream * b.K + station), sizeof c, hipMemcpyDeviceToHost));
+    pilot_report(c[0], c[1], h->mpx.pilot_min, h->mpx.P, present, level);
     return FMD_OK;
 }
 
-// ---- device: the block sums as a second pass reads them ------------------------------------------------------------------------
-// `Launch` is the second pass's launch struct; sums, carry_in, carry_out, SK, jfirst, mE and pshift have the same names in both.
+// ---- the second stage over the multiplex: device ----------------------------------------------------------------------------------
 
 // I, Q of block j (>= jfirst - 1, every sample of it already in the sums)
-template <class Launch>
-__device__ __forceinline__ void block_iq(const Launch& L, uint32_t row, int64_t j, long long& I, long long& Q)
+__device__ __forceinline__ void block_iq(const StageLaunch& L, uint32_t row, int64_t j, long long& I, long long& Q)
 {
     const int64_t jf = (int64_t)L.jfirst;
     if (j < 0) { I = 0; Q = 0; return; }
@@ -187,8 +321,7 @@ __device__ __forceinline__ void block_iq(const Launch& L, uint32_t row, int64_t 
 }
 
 // the next call's block carry of `row`: the sums of the last complete block, the partial sums of a block that straddles calls
-template <class Launch>
-__device__ __forceinline__ void write_block_carry(const Launch& L, uint32_t row)
+__device__ __forceinline__ void write_block_carry(const StageLaunch& L, uint32_t row)
 {
     const int64_t jn = (int64_t)(L.mE >> L.pshift);
     long long I = 0, Q = 0, Ip = 0, Qp = 0;
@@ -196,6 +329,78 @@ __device__ __forceinline__ void write_block_carry(const Launch& L, uint32_t row)
     if (L.mE & ((1ull << L.pshift) - 1u)) block_iq(L, row, jn, Ip, Qp);
     long long* const c = L.carry_out + 4u * row;
     c[0] = I; c[1] = Q; c[2] = Ip; c[3] = Qp;
+}
+
+// One tile of a second pass: one workgroup = one (stream, station) row and up to L.na consecutive outputs of it.  `Launch` is the
+// bank's launch struct (a StageLaunch), `Pass` the bank's side:
+//   kSlots                    LDS slots for the pairs; the host keeps a tile's span within what they hold
+//   slot(i)                   the slot of the tile's pair i
+//   before(L, row, tid, vlo, vhi)   a step of its own before the staging (followed by a barrier)
+//   pair(L, tab, m, x)        the pair of multiplex sample m (global index), x = x[m]
+//   output(a, b, shift)       the packed output dword from the two FIR sums
+//
+// Virtual index v of a row: multiplex sample mS - HX + v, so v < HX is the carried history and HX <= v < HX + M the call's own.
+// Output n reads the Ta pairs from R n on, hence the tile's first window starts at vlo = R (nS + na0) + HX - mS; the call completes
+// that output, so vlo + Ta <= HX + M, i.e. vlo <= M - 1.  A tile stages [vlo, vhi): up to the end of its last window, and in the
+// row's last tile up to HX + M, which is further -- the output after the call's last is incomplete, so HX + M < vlo + R cnt + Ta --
+// and holds the next call's history, the virtual indices M ... M + HX - 1, all of them >= vlo.  That span is the one the host's
+// capacity rule bounds: R na + Ta pairs.
+template <class Launch, class Pass>
+__device__ __forceinline__ void stage_tile(const Launch& L, Pass pass)
+{
+    __shared__ __attribute__((aligned(16))) int2 ps[Pass::kSlots];
+    __shared__ int32_t gl[256];
+    __shared__ int16_t tab[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row = blockIdx.x / L.ntiles, t = blockIdx.x - row * L.ntiles;
+    if (row >= L.SK) return;
+
+    const uint32_t na0 = t * L.na;                           // first output (of this call) of the tile
+    const uint32_t cnt = L.NA - na0 < L.na ? L.NA - na0 : L.na;
+    const bool last = t == L.ntiles - 1u;
+    const uint32_t vlo = (uint32_t)(L.R * (L.nS + na0) + L.HX - L.mS);
+    const uint32_t vhi = last ? L.HX + L.M : vlo + L.R * (cnt - 1u) + L.Ta;
+    const uint32_t span = vhi - vlo;
+
+    // ---- 1. the bank's own step, the NCO table, the taps ----------------------------------------------------------------------
+    pass.before(L, row, tid, vlo, vhi);
+    for (uint32_t i = tid; i < 512u; i += fmd_ddc::kThreads) reinterpret_cast<uint32_t*>(tab)[i] = L.tab[i];
+    for (uint32_t i = tid; i < L.Ta; i += fmd_ddc::kThreads) gl[i] = L.g[i];
+    __syncthreads();
+
+    // ---- 2. the pairs of the tile's samples -------------------------------------------------------------------------------------
+    const int16_t* const xr = L.x + (uint64_t)row * L.M;
+    const int32_t* const hin = L.ph_in + (uint64_t)row * L.HXS * 2u;
+    for (uint32_t i = tid; i < span; i += fmd_ddc::kThreads) {
+        const uint32_t v = vlo + i;
+        int2 p;
+        if (v < L.HX) p = int2{hin[2u * v], hin[2u * v + 1u]};
+        else p = pass.pair(L, tab, L.mS + (v - L.HX), (int)xr[v - L.HX]);
+        ps[Pass::slot(i)] = p;
+    }
+    __syncthreads();
+    if (last) {                                              // the next call's history
+        int32_t* const hout = L.ph_out + (uint64_t)row * L.HXS * 2u;
+        for (uint32_t i = tid; i < L.HX; i += fmd_ddc::kThreads) {
+            const int2 p = ps[Pass::slot(L.M + i - vlo)];
+            hout[2u * i] = p.x; hout[2u * i + 1u] = p.y;
+        }
+    }
+    if (t == 0u && tid == 0u) write_block_carry(L, row);     // the next call's block carry
+
+    // ---- 3. one lane per output: both FIR sums with v_mad_i32_i24 (|g| <= 16383 and the pairs fit 24-bit operands) ------------
+    uint32_t* const out = L.out + (uint64_t)row * L.out_stride + na0;
+    for (uint32_t i = tid; i < cnt; i += fmd_ddc::kThreads) {
+        const uint32_t p0 = L.R * i;
+        int a = 0, b = 0;
+        for (uint32_t k = 0; k < L.Ta; ++k) {
+            const int2 p = ps[Pass::slot(p0 + k)];
+            const int gk = gl[k];
+            a = __mul24(gk, p.x) + a;
+            b = __mul24(gk, p.y) + b;
+        }
+        out[i] = Pass::output(a, b, L.shift);
+    }
 }
 
 }  // namespace fmd_sto

@@ -5,10 +5,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._ffi import DeviceConfig, DownConverter, check, lib, stream_phase_incs
+from ._ffi import DownConverter, check, lib
 from .channelizer import as_complex
-from .stations import stations_auto_shift
-from .stereo import FRONT_END_LIMIT, default_pilot_min
+from .stereo import MpxStage
 
 
 class RdsConfig(C.Structure):
@@ -48,7 +47,7 @@ def rds_shift_for(g):
     return s
 
 
-class RdsBank(DownConverter):
+class RdsBank(MpxStage, DownConverter):
     """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream).  `shift=None` takes the smallest
     front-end shift with every |y| component <= 256 (stereo.FRONT_END_LIMIT); `pilot_min=None` a quarter of a nominal pilot;
     `rds_shift=None` the smallest exact one.  run_batch returns [n_streams, n_stations, n, 2] of (ur, ui)."""
@@ -57,33 +56,16 @@ class RdsBank(DownConverter):
 
     def __init__(self, taps, decim, phase_incs, capture_rate, rds_taps, out_decim, n_streams=1, block=4096, pilot_min=None,
                  rds_shift=None, shift=None, device_id=-1):
-        self.taps = np.ascontiguousarray(taps, dtype=np.int16)
+        self._mpx_setup(taps, decim, phase_incs, capture_rate, n_streams, block, pilot_min, shift)
         self.rds_taps = np.ascontiguousarray(rds_taps, dtype=np.int16)
-        self.decim, self.n_streams, self.capture_rate = int(decim), int(n_streams), int(capture_rate)
-        self.out_decim, self.block = int(out_decim), int(block)
-        self.phase_incs = stream_phase_incs(phase_incs, self.n_streams)
-        self.n_stations = self.phase_incs.shape[1]
-        self.shift = stations_auto_shift(self.taps, self.phase_incs, limit=FRONT_END_LIMIT) if shift is None else int(shift)
-        self.pilot_min = default_pilot_min(self.capture_rate, self.decim) if pilot_min is None else int(pilot_min)
+        self.out_decim = int(out_decim)
         self.rds_shift = rds_shift_for(self.rds_taps) if rds_shift is None else int(rds_shift)
         self.rate_num, self.rate_den = self.capture_rate, self.decim * self.out_decim
         self.out_rate = self.rate_num / self.rate_den
-        cfg = RdsConfig(self.capture_rate, self.block, self.out_decim, self.rds_shift, self.pilot_min)
-        self._h = C.c_void_p()
-        dev = DeviceConfig(self.n_streams, device_id, 0)
-        check(lib().fmd_rds_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim, self.shift,
-                                self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations,
-                                self.rds_taps.ctypes.data_as(C.POINTER(C.c_int16)), self.rds_taps.size, C.byref(cfg),
-                                C.byref(dev), C.byref(self._h)))
+        self._mpx_new(self.rds_taps, RdsConfig(self.capture_rate, self.block, self.out_decim, self.rds_shift, self.pilot_min), device_id)
 
     def out_cap(self, nbytes):
         return int(lib().fmd_rds_out_cap(self.decim, self.out_decim, nbytes))
-
-    def pilot(self, stream=0, station=0):
-        """(present, level) of the last completed block, as StereoBank.pilot."""
-        p, lv = C.c_int(0), C.c_uint32(0)
-        check(lib().fmd_rds_pilot(self._h, int(stream), int(station), C.byref(p), C.byref(lv)))
-        return bool(p.value), lv.value
 
     def run_complex(self, iq):
         """run_batch as complex64 [n_streams, n_stations, n]."""

@@ -62,7 +62,35 @@ def pilot_inc(capture_rate, decim):
     return inc.value
 
 
-class StereoBank(DownConverter):
+class MpxStage:
+    """The common side of the two wrappers whose handle runs a second stage over the multiplex -- the front end's arguments, the
+    rates, the pilot -- for StereoBank and rds.RdsBank.  A mixin in front of DownConverter."""
+
+    def _mpx_setup(self, taps, decim, phase_incs, capture_rate, n_streams, block, pilot_min, shift):
+        self.taps = np.ascontiguousarray(taps, dtype=np.int16)
+        self.decim, self.n_streams, self.capture_rate, self.block = int(decim), int(n_streams), int(capture_rate), int(block)
+        self.phase_incs = stream_phase_incs(phase_incs, self.n_streams)
+        self.n_stations = self.phase_incs.shape[1]
+        self.shift = stations_auto_shift(self.taps, self.phase_incs, limit=FRONT_END_LIMIT) if shift is None else int(shift)
+        self.pilot_min = default_pilot_min(self.capture_rate, self.decim) if pilot_min is None else int(pilot_min)
+
+    def _mpx_new(self, g, cfg, device_id):
+        """fmd_<_prefix>_new with the second stage's taps `g` and the bank's config"""
+        p16 = C.POINTER(C.c_int16)
+        self._h = C.c_void_p()
+        dev = DeviceConfig(self.n_streams, device_id, 0)
+        check(self._fn("new")(self.taps.ctypes.data_as(p16), self.taps.size, self.decim, self.shift,
+                              self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations, g.ctypes.data_as(p16), g.size,
+                              C.byref(cfg), C.byref(dev), C.byref(self._h)))
+
+    def pilot(self, stream=0, station=0):
+        """(present, level) of the last completed block: the stereo indicator and the pilot amplitude in discriminator units."""
+        p, lv = C.c_int(0), C.c_uint32(0)
+        check(self._fn("pilot")(self._h, int(stream), int(station), C.byref(p), C.byref(lv)))
+        return bool(p.value), lv.value
+
+
+class StereoBank(MpxStage, DownConverter):
     """`phase_incs` is [n_streams][n_stations] (a flat list of n_stations is taken for every stream).  `shift=None` takes the smallest
     front-end shift with every |y| component <= 256 (FRONT_END_LIMIT); `pilot_min=None` a quarter of a nominal pilot;
     `audio_shift=None` default_audio_shift.  run_batch returns [n_streams, n_stations, n_audio, 2] of (L, R)."""
@@ -71,30 +99,14 @@ class StereoBank(DownConverter):
 
     def __init__(self, taps, decim, phase_incs, capture_rate, audio_taps, audio_decim, n_streams=1, block=4096, pilot_min=None,
                  audio_shift=None, shift=None, device_id=-1):
-        self.taps = np.ascontiguousarray(taps, dtype=np.int16)
+        self._mpx_setup(taps, decim, phase_incs, capture_rate, n_streams, block, pilot_min, shift)
         self.audio_taps = np.ascontiguousarray(audio_taps, dtype=np.int16)
-        self.decim, self.n_streams, self.capture_rate = int(decim), int(n_streams), int(capture_rate)
-        self.audio_decim, self.block = int(audio_decim), int(block)
-        self.phase_incs = stream_phase_incs(phase_incs, self.n_streams)
-        self.n_stations = self.phase_incs.shape[1]
-        self.shift = stations_auto_shift(self.taps, self.phase_incs, limit=FRONT_END_LIMIT) if shift is None else int(shift)
-        self.pilot_min = default_pilot_min(self.capture_rate, self.decim) if pilot_min is None else int(pilot_min)
+        self.audio_decim = int(audio_decim)
         self.audio_shift = (default_audio_shift(self.audio_taps, self.capture_rate, self.decim) if audio_shift is None
                             else int(audio_shift))
         self.audio_rate = self.capture_rate / (self.decim * self.audio_decim)
-        cfg = StereoConfig(self.capture_rate, self.block, self.audio_decim, self.audio_shift, self.pilot_min)
-        self._h = C.c_void_p()
-        dev = DeviceConfig(self.n_streams, device_id, 0)
-        check(lib().fmd_stereo_new(self.taps.ctypes.data_as(C.POINTER(C.c_int16)), self.taps.size, self.decim, self.shift,
-                                   self.phase_incs.ctypes.data_as(C.POINTER(C.c_uint32)), self.n_stations,
-                                   self.audio_taps.ctypes.data_as(C.POINTER(C.c_int16)), self.audio_taps.size, C.byref(cfg),
-                                   C.byref(dev), C.byref(self._h)))
+        self._mpx_new(self.audio_taps, StereoConfig(self.capture_rate, self.block, self.audio_decim, self.audio_shift, self.pilot_min),
+                      device_id)
 
     def out_cap(self, nbytes):
         return int(lib().fmd_stereo_out_cap(self.decim, self.audio_decim, nbytes))
-
-    def pilot(self, stream=0, station=0):
-        """(present, level) of the last completed block: the stereo indicator and the pilot amplitude in discriminator units."""
-        p, lv = C.c_int(0), C.c_uint32(0)
-        check(lib().fmd_stereo_pilot(self._h, int(stream), int(station), C.byref(p), C.byref(lv)))
-        return bool(p.value), lv.value

@@ -1,6 +1,7 @@
 """The five down-converter handles (station bank, channelizer, stereo, narrow-band and RDS bank) alive at once on the MI355X: they
 share one host layer (csrc/fmd_ddc.h), so each is checked bit for bit against its own definition while the others run, are reset,
-refuse a call and are freed around it.  Likewise the narrow-band bank, the uniform channelizer and the band-plan bank: the two banks
+refuse a call and are freed around it.  The stereo and the RDS bank, which share their second stage over the multiplex
+(csrc/fmd_stereo_mpx.h), also run on the same bytes.  Likewise the narrow-band bank, the uniform channelizer and the band-plan bank: the two banks
 share their second stage's host side (csrc/fmd_chan_stage.h), and the band-plan bank drives a uniform channelizer of its own."""
 import numpy as np
 import pytest
@@ -103,6 +104,66 @@ def test_five_handles_interleaved_reset_refusal_and_free(fmd, oracle):
     ref2 = [cr.ChannelizerRef(h, D, incs[s], ch2.shift, z=sr.z_corr) for s in range(S)]
     assert _same(ch2.run_batch(cuts[0]), [ref2[s].feed(cuts[0][s]) for s in range(S)])
     ch2.close()
+
+
+def test_stereo_and_rds_banks_on_the_same_bytes(fmd):
+    """The two banks share their second stage (csrc/fmd_stereo_mpx.h) and differ in what they stage, where in LDS, and what they
+    store.  One front end, the same bytes call by call, at the smallest shape where the shared tile can go wrong in one bank only:
+    40 second-stage taps (HX = 39), stride 5 against 32, D = 2 and T = 3, so that the first 4 n bytes are n - 1 multiplex samples."""
+    S2, K2, D2, TA2 = 2, 2, 2, 40
+    rng = np.random.default_rng(717)
+    h = rng.integers(-900, 901, 3).astype(np.int16)
+    incs = np.array([[int(x) for x in rng.integers(0, 1 << 32, K2)] for _ in range(S2)], np.uint32)
+    g = rng.integers(-400, 401, TA2).astype(np.int16)        # sum |g| <= 16000
+    data = rng.integers(0, 256, (S2, 64 + 8400 + 136 + 8400), dtype=np.uint8)
+    short, a, b, c = np.split(data, np.cumsum((64, 8400, 136)), axis=1)
+
+    sb = fmd.StereoBank(h, D2, incs, RATE, g, 5, n_streams=S2, block=1024, pilot_min=1, device_id=0)
+    rb = fmd.RdsBank(h, D2, incs, RATE, g, 32, n_streams=S2, block=1024, pilot_min=1, device_id=0)
+    sref = [st.StereoRef(h, D2, incs[s], sb.shift, RATE, g, 5, 1024, 1, sb.audio_shift, z=sr.z_corr) for s in range(S2)]
+    rref = [rr.RdsRef(h, D2, incs[s], rb.shift, RATE, g, 32, rb.rds_shift, 1024, 1, z=sr.z_corr) for s in range(S2)]
+    assert sb.shift == rb.shift
+
+    def pilots_agree():
+        want = [sref[s].pilot(k) for s in range(S2) for k in range(K2)]
+        assert want == [rref[s].pilot(k) for s in range(S2) for k in range(K2)]
+        return all([bank.pilot(s, k) for s in range(S2) for k in range(K2)] == want for bank in (sb, rb))
+
+    def step(cut, n_stereo, n_rds):
+        """one call of both banks against their definitions: `cut` completes n_stereo and n_rds outputs per row"""
+        got = []
+        for bank, ref, n in ((sb, sref, n_stereo), (rb, rref, n_rds)):
+            exp = np.stack([ref[s].feed(cut[s]) for s in range(S2)])
+            got.append(bank.run_batch(cut))
+            assert got[-1].shape == (S2, K2, n, 2) and np.array_equal(got[-1], exp), bank._prefix
+            assert bank.outputs() == ref[0].n_next
+        assert pilots_agree()
+        return got
+
+    # 64 bytes are 15 multiplex samples, fewer than the 40 taps: both refuse, nothing changes
+    for bank, ref in ((sb, sref), (rb, rref)):
+        assert ref[0].completes(64) < 1
+        with pytest.raises(fmd.FmdError) as e:
+            bank.run_batch(short)
+        assert e.value.status == TOO_SHORT and bank.outputs() == 0
+    assert pilots_agree()
+    # 2099 multiplex samples: two tiles per row in both second passes (256 + 156 audio samples, 60 + 5 RDS outputs), two pilot
+    # blocks, and the RDS staging beyond slot 32 at stride 32
+    first = step(a, 412, 65)
+    assert any(sref[s].pilot(k)[0] for s in range(S2) for k in range(K2))
+    # 34 multiplex samples, fewer than HX: the next history is the old history's tail and the call; one RDS output exactly
+    step(b, 7, 1)
+    step(c, 420, 66)
+    # back to the start
+    for hd in (sb, rb):
+        hd.reset()
+    for ref in sref + rref:
+        ref.reset()
+    assert sb.outputs() == 0 and rb.outputs() == 0 and pilots_agree()
+    again = step(a, 412, 65)
+    assert np.array_equal(again[0], first[0]) and np.array_equal(again[1], first[1])
+    sb.close()
+    rb.close()
 
 
 N, HOP, SEL = 8, 8, [1, 4, 6]                                # the plan of the uniform channelizer and the band-plan bank: K channels

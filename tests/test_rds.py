@@ -117,9 +117,12 @@ def test_domain_refusals_need_no_gpu():
     assert _new(lib, incs=np.zeros(33)) == U
     assert _new(lib, taps=np.full(64, 2047, np.int16), shift=0) == U          # |y| bound
     assert _new(lib, rate=120000 * 10 - 1) == U                              # capture_rate < 120000 decim
+    assert "120000" in lib.fmd_last_error().decode()
     for P in (512, 1000, 3000, 32768):
         assert _new(lib, block=P) == U, P
     assert _new(lib, R=0) == U and _new(lib, R=33) == U
+    msg = lib.fmd_last_error().decode()                      # this bank's own names and limits, not the stereo bank's
+    assert "out_decim <= 32" in msg and "rds_shift <= 24" in msg, msg
     assert _new(lib, g=np.ones(257, np.int16), rshift=14) == U
     assert _new(lib, g=np.array([16383, 1], np.int16), rshift=24) == U       # sum |g| > 16383
     assert _new(lib, g=np.array([-8192, 8192], np.int16), rshift=24) == U

@@ -184,15 +184,19 @@ def test_domain_refusals_need_no_gpu():
     assert _new(lib, incs=np.zeros(33)) == U
     assert _new(lib, taps=np.full(64, 2047, np.int16), shift=0) == U          # |y| bound
     assert _new(lib, rate=106000 * 10 - 1) == U                              # capture_rate < 106000 decim
+    assert "106000" in lib.fmd_last_error().decode()
     for P in (512, 1000, 3000, 32768):
         assert _new(lib, block=P) == U, P
     assert _new(lib, adec=0) == U and _new(lib, adec=33) == U
+    msg = lib.fmd_last_error().decode()                      # this bank's own names and limits, not the RDS bank's
+    assert "audio_decim <= 32" in msg and "audio_shift <= 16" in msg and "rds" not in msg, msg
     assert _new(lib, g=np.ones(257, np.int16)) == U
     assert _new(lib, g=np.array([16383, 1], np.int16)) == U                  # sum |g| > 16383
     assert _new(lib, g=np.array([-8192, 8192], np.int16)) == U
     assert _new(lib, ash=17) == U and _new(lib, pmin=16385) == U
     assert _new(lib, n_streams=65536) == U
     assert _new(lib, n_streams=0) == -1
+    assert _new(lib, g=np.array([16383], np.int16), ash=0) != U              # the RDS bank's exact-store rule is not this bank's
     for kw in (dict(), dict(decim=64, rate=106000 * 64, block=16384, adec=32, g=np.full(256, 63, np.int16), ash=16, pmin=16384),
                dict(decim=2, rate=212000, block=1024, adec=1, g=np.array([16383], np.int16), pmin=0),
                dict(g=np.array([-8191, 8192], np.int16))):
