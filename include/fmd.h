@@ -529,6 +529,49 @@ int fmd_rds_decoder_reset(fmd_rds_decoder *d);
 int fmd_rds_decoder_push(fmd_rds_decoder *d, const int16_t *iq, size_t n, fmd_rds_group *groups, size_t cap, size_t *n_groups);
 int fmd_rds_decoder_info(const fmd_rds_decoder *d, fmd_rds_info *info);
 
+/* ---- FM receiver bank: stereo audio and the RDS baseband out of one multiplex pass ---------------------------- */
+/* NEW SURFACE (the reference has none).  A stereo station bank and an RDS bank over the same stations in one handle: the multiplex
+ * pass (front end, discriminator, pilot block sums) runs once per call and both second stages read its x[m].  No new arithmetic.
+ * Per (stream, station): `audio` is bit for bit fmd_stereo_*'s for the same front-end arguments, capture_rate, block, pilot_min,
+ * audio_taps, audio_decim and audio_shift; `rds` is bit for bit fmd_rds_*'s for the same front-end arguments and rds_taps,
+ * rds_decim (its out_decim), rds_shift; the pilot report is theirs.  Neither output depends on how the stream is cut into calls.
+ * Domain (else FMD_ERR_UNSUPPORTED, decided before a device is queried): the intersection of the two banks' -- capture_rate >=
+ * 120000 decim (the RDS bank's floor), each stage's own limits on its stride, taps, sum |g| and shift (the exact-store rule on
+ * rds_shift included), one block and one pilot_min.  nbytes % 8 != 0 -> FMD_ERR_BAD_LENGTH.  A call is accepted only if it completes
+ * at least one output of EACH stage; otherwise FMD_ERR_TOO_SHORT, and nothing changes (send the bytes again with the next ones).
+ * Stream lifetime and completion points: as fmd_channelizer_* (fmd_receiver_check). */
+typedef struct fmd_receiver fmd_receiver;
+typedef struct fmd_receiver_config {
+    uint32_t capture_rate;   /* Hz: sets the pilot step inc_p                                         */
+    uint32_t block;          /* P: pilot block length in MPX samples                                  */
+    uint32_t pilot_min;      /* presence threshold, in discriminator units                            */
+    uint32_t audio_decim;    /* the audio stage's R                                                   */
+    uint32_t audio_shift;
+    uint32_t rds_decim;      /* the RDS stage's R                                                     */
+    uint32_t rds_shift;
+} fmd_receiver_config;
+int fmd_receiver_new(const int16_t *taps, uint32_t n_taps, uint32_t decim, uint32_t shift, const uint32_t *phase_inc,
+                     uint32_t n_stations, const int16_t *audio_taps, uint32_t n_audio_taps, const int16_t *rds_taps,
+                     uint32_t n_rds_taps, const fmd_receiver_config *cfg, const fmd_device_config *dev, fmd_receiver **out);
+void fmd_receiver_free(fmd_receiver *s);
+int fmd_receiver_reset(fmd_receiver *s);
+/* HOST buffers: audio [n_streams][n_stations][audio_cap][2] (L, R), rds [n_streams][n_stations][rds_cap][2] (ur, ui); the
+ * capacities are fmd_stereo_out_cap(decim, audio_decim, nbytes) and fmd_rds_out_cap(decim, rds_decim, nbytes) at least.
+ * *n_audio, *n_rds = outputs per (stream, station) of each (the same for all). */
+int fmd_receiver_run_batch(fmd_receiver *s, const uint8_t *iq, size_t nbytes, int16_t *audio, size_t audio_cap, size_t *n_audio,
+                           int16_t *rds, size_t rds_cap, size_t *n_rds);
+/* DEVICE buffers (d_iq, d_audio and d_rds 4-byte aligned), enqueued on `stream` without synchronising; counts as above. */
+int fmd_receiver_run_device(fmd_receiver *s, const void *d_iq, size_t nbytes, void *d_audio, size_t audio_cap, size_t *n_audio,
+                            void *d_rds, size_t rds_cap, size_t *n_rds, void *stream);
+int fmd_receiver_check(fmd_receiver *s);
+/* Audio samples and RDS baseband samples per (stream, station) produced since creation or the last reset. */
+int fmd_receiver_outputs(const fmd_receiver *s, uint64_t *audio, uint64_t *rds);
+/* The last completed block's pilot, with the semantics of fmd_stereo_pilot.  Synchronises first. */
+int fmd_receiver_pilot(fmd_receiver *s, uint32_t stream, uint32_t station, int *present, uint32_t *level);
+/* Name of pass 0 (the stereo bank's multiplex pass) or 1 (both second stages in one launch), as `rocprofv3 --kernel-trace` prints
+ * it. */
+int fmd_receiver_kernel_name(const fmd_receiver *s, uint32_t pass, char *name, size_t cap);
+
 /* ---- narrow-band bank: AM, NFM, SSB and IQ channels with squelch --------------------------------------------- */
 /* NEW SURFACE (rtl_fm's -M fm / am / usb / lsb / raw with a squelch, in the rtl-sdr ecosystem; the reference has none).  This is
  * the project's own operator, not the reference's chain: the channelizer's y, a second, COMPLEX decimating FIR that reaches

@@ -166,6 +166,16 @@ PROTOTYPES = {
     "fmd_rds_decoder_reset": (C.c_int, [_vp]),
     "fmd_rds_decoder_push": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
     "fmd_rds_decoder_info": (C.c_int, [_vp, _vp]),
+    "fmd_receiver_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, _i16p, C.c_uint32, _i16p,
+                                   C.c_uint32, _vp, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_receiver_free": (None, [_vp]),
+    "fmd_receiver_reset": (C.c_int, [_vp]),
+    "fmd_receiver_run_batch": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp, _vp, _sz, _szp]),
+    "fmd_receiver_run_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp, _vp, _sz, _szp, _vp]),
+    "fmd_receiver_check": (C.c_int, [_vp]),
+    "fmd_receiver_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fmd_receiver_pilot": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "fmd_receiver_kernel_name": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_size_t]),
     "fmd_narrow_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, _i16p, _i16p, C.c_uint32,
                                  _vp, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
     "fmd_narrow_free": (None, [_vp]),

@@ -482,6 +482,50 @@ private:
     Owned<fmd_rds_decoder, fmd_rds_decoder_free> h_;
 };
 
+// FM receiver bank (fmd_receiver_*): a StereoBank and an RdsBank over the same stations out of one multiplex pass.  run() takes
+// [n_streams][nbytes] and returns (audio, rds): the interleaved (L, R) audio and the interleaved (ur, ui) baseband, each
+// [n_streams * n_stations] (row stream * n_stations + station), bit for bit what the two banks return.
+class ReceiverBank {
+public:
+    ReceiverBank(const std::vector<int16_t>& taps, uint32_t decim, uint32_t shift, const std::vector<uint32_t>& phase_incs,
+                 uint32_t n_streams, const std::vector<int16_t>& audio_taps, const std::vector<int16_t>& rds_taps,
+                 const fmd_receiver_config& cfg, int32_t device_id = -1)
+        : decim_(decim), audio_decim_(cfg.audio_decim), rds_decim_(cfg.rds_decim), n_streams_(n_streams),
+          n_stations_(n_streams ? (uint32_t)(phase_incs.size() / n_streams) : 0u)
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_receiver_new(taps.data(), (uint32_t)taps.size(), decim, shift, phase_incs.data(), n_stations_, audio_taps.data(),
+                               (uint32_t)audio_taps.size(), rds_taps.data(), (uint32_t)rds_taps.size(), &cfg, &dev, h_.out()));
+    }
+
+    // FMD_ERR_TOO_SHORT (a call that does not complete an output of each stage) returns empty rows and changes nothing.
+    std::pair<Rows, Rows> run(const uint8_t* iq, size_t nbytes)
+    {
+        const size_t ca = std::max<size_t>(1, fmd_stereo_out_cap(decim_, audio_decim_, nbytes));
+        const size_t cr = std::max<size_t>(1, fmd_rds_out_cap(decim_, rds_decim_, nbytes));
+        const size_t rows = (size_t)n_streams_ * n_stations_;
+        std::vector<int16_t> audio(2 * ca * rows), rds(2 * cr * rows);
+        size_t na = 0, nr = 0;
+        const int rc = fmd_receiver_run_batch(h_, iq, nbytes, audio.data(), ca, &na, rds.data(), cr, &nr);
+        if (rc == FMD_ERR_TOO_SHORT) return {Rows(rows), Rows(rows)};
+        check(rc);
+        return {cut_rows(audio, rows, ca, na, 2), cut_rows(rds, rows, cr, nr, 2)};
+    }
+    std::pair<bool, uint32_t> pilot(uint32_t stream, uint32_t station) { return flag_and_level(fmd_receiver_pilot, h_, stream, station); }
+    // (audio samples, baseband samples) per row since creation or reset
+    std::pair<uint64_t, uint64_t> outputs() const
+    {
+        uint64_t a = 0, r = 0;
+        check(fmd_receiver_outputs(h_, &a, &r));
+        return {a, r};
+    }
+    void reset() { check(fmd_receiver_reset(h_)); }
+
+private:
+    uint32_t decim_, audio_decim_, rds_decim_, n_streams_, n_stations_;
+    Owned<fmd_receiver, fmd_receiver_free> h_;
+};
+
 // Channel taps of a NarrowBank, as the Python narrow_taps(): a Hamming-windowed complex band-pass from lo_hz to hi_hz at the
 // channelizer's output rate, scaled to sum |gr| + |gi| <= 65535 with every tap within 16383.  The second vector is empty (real
 // taps) when lo_hz == -hi_hz.  USB is e.g. (300, 3000), LSB (-3000, -300).

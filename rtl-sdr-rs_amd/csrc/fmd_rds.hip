@@ -15,52 +15,26 @@
 //   - from the two FIR sums (|g| <= 16383, |q| <= 32768 fit v_mad_i32_i24's 24-bit operands; |v| < 2^29) the shift and one dword
 //     store of the (ur, ui) pair.
 // The host side of the second stage -- handle, constructor, launch fields, enqueue -- is that header's as well; the exact-store check
-// on rds_shift is this bank's own.
+// on rds_shift is this bank's own.  BasebandPass and its launch struct are in fmd_mpx_passes.h, where the receiver bank finds them too.
 #include "../../include/fmd.h"
 
 #include <hip/hip_runtime.h>
 
 #include "fmd_ddc.h"
 #include "fmd_internal.h"
+#include "fmd_mpx_passes.h"
 #include "fmd_stereo_mpx.h"
 
 namespace fmd_rdsk {
 
 using fmd_ddc::kThreads;
 
-constexpr uint32_t kQCap = 1984;                          // pairs a tile stages: R tile + Ta <= kQCap
-constexpr uint32_t kQSlots = 2048;                        // LDS slots: kQCap + kQCap / 32 = 2046 padded positions (16 KiB, the stereo pass's xs)
-
-struct BasebandLaunch : fmd_sto::StageLaunch {            // pairs (qr, qi), shift: rds_shift, out: (ur, ui)
-    uint32_t inc3;             // carrier step 3 inc_p mod 2^32
-};
-
-// The baseband pass's side of a second-pass tile (fmd_stereo_mpx.h, stage_tile).
-struct BasebandPass {
-    static constexpr uint32_t kSlots = kQSlots;
-
-    // lanes read at stride R, and without the padding an even R puts them on few banks (R = 32: all 64 lanes on one pair of banks)
-    static __device__ __forceinline__ uint32_t slot(uint32_t i) { return i + (i >> 5); }
-
-    __device__ __forceinline__ void before(const BasebandLaunch&, uint32_t, uint32_t, uint32_t, uint32_t) {}
-
-    // q[m] = (x cosq(phi), -x sinq(phi)) >> 14, phi = 3 m inc_p mod 2^32 (|x tab| <= 2^29)
-    __device__ __forceinline__ int2 pair(const BasebandLaunch& L, const int16_t* tab, uint64_t m, int xv) const
-    {
-        const uint32_t ix = ((uint32_t)m * L.inc3) >> 22;
-        return int2{(xv * (int)tab[ix]) >> 14, (-xv * (int)tab[(ix - 256u) & 1023u]) >> 14};
-    }
-
-    // the normalising shift; the host's store check makes the wrap to 16 bits exact (|v| < 2^29)
-    static __device__ __forceinline__ uint32_t output(int a, int b, uint32_t shift)
-    {
-        return ((uint32_t)(a >> shift) & 0xFFFFu) | ((uint32_t)(b >> shift) << 16);
-    }
-};
-
 __global__ void __launch_bounds__(kThreads) fmd_rds_baseband_kernel(const BasebandLaunch L)
 {
-    fmd_sto::stage_tile(L, BasebandPass{});
+    __shared__ __attribute__((aligned(16))) int2 ps[fmd_sto::kStageSlots];
+    __shared__ int32_t gl[256];
+    __shared__ int16_t tab[1024];
+    fmd_sto::stage_tile(L, BasebandPass{}, blockIdx.x, ps, gl, tab);
 }
 
 }  // namespace fmd_rdsk
@@ -69,7 +43,7 @@ struct fmd_rds : fmd_sto::MpxHandle {};
 
 namespace {
 
-constexpr fmd_sto::StageLimits kLimits{120000u, "out_decim", "rds_taps", "rds_shift", 24u};
+constexpr fmd_sto::StageLimits kLimits = fmd_rdsk::kBasebandLimits;
 
 int rd_enqueue(fmd_rds* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
 {
@@ -92,12 +66,9 @@ int fmd_rds_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_t s
     const fmd_sto::StageConfig c{cfg->capture_rate, cfg->block, cfg->out_decim, cfg->rds_shift, cfg->pilot_min};
     uint64_t gsum;
     if (const int rc = fmd_sto::stage_args(kLimits, taps, n_taps, decim, shift, phase_inc, n_stations, rds_taps, n_rds_taps, c, dev, out, &gsum)) return rc;
-    if (((32768ull * gsum + ((1ull << c.shift) - 1ull)) >> c.shift) > 32767ull) {
-        fmd_internal_set_err("rds_shift too small: need ceil(32768 * sum |rds_taps| / 2^rds_shift) <= 32767");
-        return FMD_ERR_UNSUPPORTED;
-    }
-    const uint32_t room = fmd_rdsk::kQCap - n_rds_taps;      // na >= 54: R na + Ta <= kQCap
-    return fmd_sto::stage_new(taps, n_taps, decim, shift, phase_inc, n_stations, rds_taps, n_rds_taps, c, room, dev, fmd_rds_free, out);
+    if (const int rc = fmd_rdsk::store_check(gsum, c.shift)) return rc;
+    return fmd_sto::stage_new(taps, n_taps, decim, shift, phase_inc, n_stations, rds_taps, n_rds_taps, c, fmd_rdsk::baseband_room(n_rds_taps), dev,
+                              fmd_rds_free, out);
 }
 
 void fmd_rds_free(fmd_rds* h)

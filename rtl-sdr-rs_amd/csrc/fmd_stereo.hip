@@ -19,6 +19,7 @@
 //   - the pair (x, s), s = (x kc) >> 14 with kc from the NCO table in LDS;
 //   - from the two FIR sums (|g| <= 16383, |x| <= 32768, |s| <= 65540 fit v_mad_i32_i24's 24-bit operands) the matrix step, the
 //     saturation, one dword store of the (L, R) pair.
+// AudioPass and its launch struct are in fmd_mpx_passes.h, where the receiver bank finds them too.
 // The host side of the second stage -- handle, constructor, launch fields, enqueue -- is that header's as well.
 #include "../../include/fmd.h"
 
@@ -27,15 +28,13 @@
 #include "fmd_ddc.h"
 #include "fmd_device.h"
 #include "fmd_internal.h"
+#include "fmd_mpx_passes.h"
 #include "fmd_stereo_mpx.h"
 
 namespace fmd_sto {
 
 using fmd_ddc::kThreads;
 using fmd_ddc::kTableBytes;
-
-constexpr uint32_t kXCap = 2048;                          // (x, s) pairs a pass-2 tile has room for: R tile + 2 Ta <= kXCap
-constexpr uint32_t kMaxBlocks = 4;                        // blocks one pass-2 tile touches (<= 3: kXCap / 1024 + 1)
 
 __device__ __forceinline__ long long wave_sum(long long v)
 {
@@ -113,80 +112,13 @@ hipError_t launch_mpx(const MpxLaunch& A, size_t lds, hipStream_t stream)
     return hipGetLastError();
 }
 
-struct AudioLaunch : StageLaunch {                          // x: the multiplex, pairs (x, s), shift: audio_shift, out: (L, R)
-    uint32_t inc_p;
-    uint64_t thr;              // pilot_min P 8192 (0: every block absent)
-};
-
-// a^2 + b^2 >= thr^2 in 128 bits (|a|, |b| <= 2^43, thr <= 2^41)
-__device__ __forceinline__ bool pilot_present(long long I, long long Q, uint64_t thr)
-{
-    if (thr == 0u) return false;
-    const uint64_t ua = (uint64_t)(I < 0 ? -I : I), ub = (uint64_t)(Q < 0 ? -Q : Q);
-    const uint64_t alo = ua * ua, ahi = __umul64hi(ua, ua), blo = ub * ub, bhi = __umul64hi(ub, ub);
-    const uint64_t lo = alo + blo, hi = ahi + bhi + (lo < alo ? 1u : 0u);
-    const uint64_t tlo = thr * thr, thi = __umul64hi(thr, thr);
-    return hi > thi || (hi == thi && lo >= tlo);
-}
-
-// The audio pass's side of a second-pass tile (fmd_stereo_mpx.h, stage_tile).
-struct AudioPass {
-    static constexpr uint32_t kSlots = kXCap;
-    int32_t (*est)[3];                                       // LDS: present, c2, s2 of block jA - 1 + i
-    uint64_t jA;                                             // block of the first of the call's own samples the tile stages
-
-    static __device__ __forceinline__ uint32_t slot(uint32_t i) { return i; }
-
-    // the estimate of each block the tile's own samples need, one lane per block (i64 / 128-bit arithmetic)
-    __device__ __forceinline__ void before(const AudioLaunch& L, uint32_t row, uint32_t tid, uint32_t vlo, uint32_t vhi)
-    {
-        const uint32_t va = vlo > L.HX ? vlo : L.HX;         // first virtual index of the call's own samples
-        jA = (L.mS + (va - L.HX)) >> L.pshift;
-        if (va >= vhi || tid >= kMaxBlocks) return;
-        const uint64_t jB = (L.mS + (vhi - 1u - L.HX)) >> L.pshift;
-        if (jA + tid > jB) return;
-        long long I, Q;
-        block_iq(L, row, (int64_t)(jA + tid) - 1, I, Q);
-        int present = pilot_present(I, Q, L.thr) ? 1 : 0, c2 = 0, s2 = 0;
-        if (present) {
-            const uint64_t mx = (uint64_t)(I < 0 ? -I : I) | (uint64_t)(Q < 0 ? -Q : Q);   // same bit length as the max
-            const int bl = 64 - __builtin_clzll(mx);
-            const int e = bl > 23 ? bl - 23 : 0;
-            const long long a = I >> e, b = Q >> e;
-            const long long E = a * a + b * b;
-            c2 = (int)((b * b - a * a) * 16384 / E);
-            s2 = (int)((2 * a * b) * 16384 / E);
-        }
-        est[tid][0] = present; est[tid][1] = c2; est[tid][2] = s2;
-    }
-
-    // (x, s): s = (x kc) >> 14 with kc from 2 theta and the block's estimate, 0 while the pilot is absent
-    __device__ __forceinline__ int2 pair(const AudioLaunch& L, const int16_t* tab, uint64_t m, int xv) const
-    {
-        const uint32_t jj = (uint32_t)((m >> L.pshift) - jA);
-        int sv = 0;
-        if (est[jj][0]) {
-            const uint32_t ix = (((uint32_t)m * L.inc_p) << 1) >> 22;                      // 2 theta
-            const int kc = (tab[(ix - 256u) & 1023u] * est[jj][1] + tab[ix] * est[jj][2]) >> 13;
-            sv = (xv * kc) >> 14;
-        }
-        return int2{xv, sv};
-    }
-
-    // the matrix step and the saturation: a = sum g x, b = sum g s
-    static __device__ __forceinline__ uint32_t output(int a, int b, uint32_t shift)
-    {
-        int l = (a + b) >> (shift + 1u), r = (a - b) >> (shift + 1u);
-        l = l > 32767 ? 32767 : (l < -32768 ? -32768 : l);
-        r = r > 32767 ? 32767 : (r < -32768 ? -32768 : r);
-        return ((uint32_t)l & 0xFFFFu) | ((uint32_t)r << 16);
-    }
-};
-
 __global__ void __launch_bounds__(kThreads) fmd_stereo_audio_kernel(const AudioLaunch L)
 {
+    __shared__ __attribute__((aligned(16))) int2 ps[kStageSlots];
+    __shared__ int32_t gl[256];
+    __shared__ int16_t tab[1024];
     __shared__ int32_t est[kMaxBlocks][3];
-    stage_tile(L, AudioPass{est, 0});
+    stage_tile(L, AudioPass{est, 0}, blockIdx.x, ps, gl, tab);
 }
 
 }  // namespace fmd_sto
@@ -195,7 +127,7 @@ struct fmd_stereo : fmd_sto::MpxHandle {};
 
 namespace {
 
-constexpr fmd_sto::StageLimits kLimits{106000u, "audio_decim", "audio_taps", "audio_shift", 16u};
+constexpr fmd_sto::StageLimits kLimits = fmd_sto::kAudioLimits;
 
 int st_enqueue(fmd_stereo* h, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len, hipStream_t stream)
 {
@@ -228,8 +160,8 @@ int fmd_stereo_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint32_
     const fmd_sto::StageConfig c{cfg->capture_rate, cfg->block, cfg->audio_decim, cfg->audio_shift, cfg->pilot_min};
     uint64_t gsum;
     if (const int rc = fmd_sto::stage_args(kLimits, taps, n_taps, decim, shift, phase_inc, n_stations, audio_taps, n_audio_taps, c, dev, out, &gsum)) return rc;
-    const uint32_t room = fmd_sto::kXCap - 2u * n_audio_taps;   // na >= 48: R na + 2 Ta <= kXCap
-    return fmd_sto::stage_new(taps, n_taps, decim, shift, phase_inc, n_stations, audio_taps, n_audio_taps, c, room, dev, fmd_stereo_free, out);
+    return fmd_sto::stage_new(taps, n_taps, decim, shift, phase_inc, n_stations, audio_taps, n_audio_taps, c, fmd_sto::audio_room(n_audio_taps), dev,
+                              fmd_stereo_free, out);
 }
 
 void fmd_stereo_free(fmd_stereo* h)

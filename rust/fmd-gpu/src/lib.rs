@@ -118,6 +118,24 @@ pub struct fmd_rds_config {
 }
 
 #[repr(C)]
+pub struct fmd_receiver {
+    _private: [u8; 0],
+}
+
+/// `fmd_receiver_config` of include/fmd.h (FM receiver bank).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_receiver_config {
+    pub capture_rate: u32,
+    pub block: u32,
+    pub pilot_min: u32,
+    pub audio_decim: u32,
+    pub audio_shift: u32,
+    pub rds_decim: u32,
+    pub rds_shift: u32,
+}
+
+#[repr(C)]
 pub struct fmd_rds_decoder {
     _private: [u8; 0],
 }
@@ -286,6 +304,15 @@ extern "C" {
     pub fn fmd_rds_outputs(s: *const fmd_rds, outputs: *mut u64) -> c_int;
     pub fn fmd_rds_pilot(s: *mut fmd_rds, stream: u32, station: u32, present: *mut c_int, level: *mut u32) -> c_int;
     pub fn fmd_rds_kernel_name(s: *const fmd_rds, pass: u32, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_receiver_new(taps: *const i16, n_taps: u32, decim: u32, shift: u32, phase_inc: *const u32, n_stations: u32, audio_taps: *const i16, n_audio_taps: u32, rds_taps: *const i16, n_rds_taps: u32, cfg: *const fmd_receiver_config, dev: *const DeviceConfig, out: *mut *mut fmd_receiver) -> c_int;
+    pub fn fmd_receiver_free(s: *mut fmd_receiver);
+    pub fn fmd_receiver_reset(s: *mut fmd_receiver) -> c_int;
+    pub fn fmd_receiver_run_batch(s: *mut fmd_receiver, iq: *const u8, nbytes: usize, audio: *mut i16, audio_cap: usize, n_audio: *mut usize, rds: *mut i16, rds_cap: usize, n_rds: *mut usize) -> c_int;
+    pub fn fmd_receiver_run_device(s: *mut fmd_receiver, d_iq: *const c_void, nbytes: usize, d_audio: *mut c_void, audio_cap: usize, n_audio: *mut usize, d_rds: *mut c_void, rds_cap: usize, n_rds: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_receiver_check(s: *mut fmd_receiver) -> c_int;
+    pub fn fmd_receiver_outputs(s: *const fmd_receiver, audio: *mut u64, rds: *mut u64) -> c_int;
+    pub fn fmd_receiver_pilot(s: *mut fmd_receiver, stream: u32, station: u32, present: *mut c_int, level: *mut u32) -> c_int;
+    pub fn fmd_receiver_kernel_name(s: *const fmd_receiver, pass: u32, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_rds_decoder_new(rate_num: u32, rate_den: u32, out: *mut *mut fmd_rds_decoder) -> c_int;
     pub fn fmd_rds_decoder_free(d: *mut fmd_rds_decoder);
     pub fn fmd_rds_decoder_reset(d: *mut fmd_rds_decoder) -> c_int;
