@@ -9,13 +9,18 @@ plan claims.
 
 For the RDS bank the file also shows, still without a GPU, that the cases can tell a wrong kernel from a right one: each of five
 deliberately wrong variants of the definition (small subclasses of rds_ref.RdsRef below) gives, on the family of cases built for
-it, a result that differs from the definition's."""
+it, a result that differs from the definition's.
+
+For the receiver bank dc.receiver_plan counts both second stages of every call and says which calls are refused and what they
+would have completed; the tile counts of the two sides of its one second-pass grid follow from dc.stereo_na and
+dc.rds_na."""
 import numpy as np
 import pytest
 
 import domain_cases as dc
 import narrow_ref as nr
 import rds_ref as rr
+import receiver_ref as rxr
 import stereo_ref as st
 
 
@@ -376,6 +381,176 @@ def test_rds_extremes(g, rds_shift):
         assert set(np.unique(u).tolist()) == {-1, 0}               # |v| < 2^24: the sign of v is all that is left
         _, bad = _rds_run(c, cls=ShiftTruncates)
         assert _differs(good, bad, "output")
+
+
+# ---- receiver bank -------------------------------------------------------------------------------------------------------------
+
+def _rx_run(c, stream=0, pilot_min=None):
+    """The definition of one stream over the case's calls: (ref, [(audio, rds, [pilot(k) for every k]) per accepted call])."""
+    ref = dc.receiver_refs(c, rxr, check=[stream], pilot_min=pilot_min)[stream]
+    out = []
+    for d in dc.calls(c):
+        if min(ref.completes(d.shape[1])) < 1:
+            continue
+        a, u = ref.feed(d[stream])
+        out.append((a, u, [ref.pilot(k) for k in range(ref.K)]))
+    return ref, out
+
+
+def test_receiver_sweep_covers_the_shapes():
+    cases = list(dc.receiver_sweep())
+    assert len(cases) >= 32
+    assert {c.Ra for c in cases} == set(range(1, 33)) == {c.Rr for c in cases} and all(c.Ra != c.Rr for c in cases)
+    _edges_both_forms(cases)
+    assert {c.Ta_a for c in cases} >= set(dc.ST_TA) and {c.Ta_r for c in cases} >= set(dc.RX_TA_R)
+    assert any(c.Ta_a < c.Ra for c in cases) and any(c.Ta_r < c.Rr for c in cases)
+    assert {c.P for c in cases} == set(dc.ST_BLOCKS)
+    assert {c.pilot_min for c in cases} >= {0, 1, 16384} and any(1 < c.pilot_min < 16384 for c in cases)
+    assert any(c.na_a < 256 for c in cases) and any(c.na_r < 256 for c in cases)
+    assert any(c.na_a == 48 for c in cases) and any(c.na_r == 54 for c in cases)
+    small = [c for c in cases if c.rds_shift == c.rds_shift_min]
+    assert len(small) >= 8 and len(cases) - len(small) >= 8 and max(c.rds_shift for c in cases) >= 20
+    assert {c.long_tiles for c in small} == {False, True} == {c.long_tiles for c in cases if c.rds_shift > c.rds_shift_min}
+    tiles, kinds, uneven_odd_rows = set(), set(), 0
+    for c in cases:
+        refused = []
+        p = dc.receiver_plan(c, refused)
+        kinds |= {k for _, k in refused}
+        assert c.rate >= 120000 * c.D and 0 <= c.audio_shift <= 16 and dc.rds_shift_for(c.gr) == c.rds_shift_min <= c.rds_shift <= 24
+        assert c.na_a == dc.stereo_na(c.Ta_a, c.Ra) and c.Ra * c.na_a + 2 * c.Ta_a <= 2048
+        assert c.na_r == dc.rds_na(c.Ta_r, c.Rr) and c.Rr * c.na_r + c.Ta_r <= 1984
+        for g in (c.ga, c.gr):
+            assert max(g.size, 8000) <= int(np.abs(g.astype(np.int64)).sum()) <= 16383
+        assert p and len(p) + len(refused) == len(c.sizes) == 7 and c.sizes[2] == 8 and max(c.Ra, c.Rr) >= 4
+        # the 8-byte call after the first that completes both stages is refused in every case; a call refused although it completes
+        # a stage is the receiver's own rule at work
+        assert 2 in [i for i, _ in refused] and 1 not in [i for i, _ in refused] and 5 not in [i for i, _ in refused], (c.i, refused)
+        assert max(mE - mS for mS, mE, _, _ in p) > c.P and any(mE // c.P > mS // c.P for mS, mE, _, _ in p), c.i
+        nts = [dc.receiver_tiles(c, call) for call in p]
+        tiles |= {(a > 1, r > 1) for a, r in nts}
+        spans = sorted((c.Ra * c.na_a, c.Rr * c.na_r))
+        if c.long_tiles:                                           # more than three tiles of the side with the smaller tile
+            assert any(mE - mS > 3 * spans[0] for mS, mE, _, _ in p), c.i
+        uneven_odd_rows += (c.S * c.K) % 2 == 1 and any(a > 1 and r > 1 and a != r for a, r in nts)
+    assert tiles == {(False, False), (False, True), (True, False), (True, True)}
+    assert uneven_odd_rows >= 4
+    assert sum(c.long_tiles for c in cases) >= len(cases) // 4
+    assert kinds == {"audio", "rds", "neither"}
+
+
+def test_receiver_full_tiles():
+    c = dc.receiver_full_tiles()
+    assert (c.Ta_a, c.Ra, c.na_a) == (256, 6, 256) and c.Ra * c.na_a + 2 * c.Ta_a == 2048
+    assert (c.Ta_r, c.Rr, c.na_r) == (256, 8, 216) and c.Rr * c.na_r + c.Ta_r == 1984
+    p = dc.receiver_plan(c)
+    assert [mE for _, mE, _, _ in p] == c.ends == [14079, 27903, 27975]
+    assert [dc.receiver_tiles(c, call) for call in p] == [(9, 8), (9, 8), (1, 1)]
+    three = 0
+    for mS, mE, (aS, aE), (rS, rE) in p[:2]:
+        assert (aE - aS, rE - rS) == (9 * c.na_a, 8 * c.na_r) and (mE - 256) % 24 == 23
+        # the last tile of either side: from its first window to the call's end, the largest span there is
+        assert mE - c.Ra * (aS + 8 * c.na_a) == c.Ra * c.na_a + c.Ta_a - 1 == 1791
+        assert mE - c.Rr * (rS + 7 * c.na_r) == c.Rr * c.na_r + c.Ta_r - 1 == 1983
+        for t in range(9):                                         # the call's own samples that audio tile t stages
+            lo = max(c.Ra * (aS + t * c.na_a), mS)
+            hi = mE if t == 8 else c.Ra * (aS + (t + 1) * c.na_a - 1) + c.Ta_a
+            three += (hi - 1) // c.P - lo // c.P + 1 == 3
+    assert three >= 1
+    mS, _, (aS, _), (rS, _) = p[1]                                 # the second call's first windows start Ta - 1 samples back
+    assert mS - c.Ra * aS == c.Ta_a - 1 and mS - c.Rr * rS == c.Ta_r - 1
+    assert 1982 + (1982 >> 5) == 2043
+
+
+@pytest.mark.parametrize("Ra,Rr", dc.RX_SHORT)
+def test_receiver_short_calls(Ra, Rr):
+    c = dc.receiver_short(Ra, Rr)
+    refused = []
+    p = dc.receiver_plan(c, refused)
+    assert refused == c.refused and len(p) + len(refused) == len(c.spans)
+    # the byte ranges are what the bank's position makes of them: an accepted call starts where the last accepted one ended, and a
+    # refused call's bytes are the head of the next call, which is accepted
+    pos, ref_idx = 0, {i for i, _ in refused}
+    for i, (a, b) in enumerate(c.spans):
+        assert a == pos and b > a
+        if i in ref_idx:
+            assert i + 1 not in ref_idx and c.spans[i + 1][0] == a and c.spans[i + 1][1] > b
+        else:
+            pos = b
+    assert pos == c.data.shape[1]
+    Ms = [mE - mS for mS, mE, _, _ in p]
+    assert set(Ms) >= {1, 2, c.Ta_r - 2, c.Ta_r - 1, c.Ta_r, c.Ta_a - 2, c.Ta_a - 1, c.Ta_a} and Ms[-1] == 3000
+    assert all(aE > aS and rE > rS for _, _, (aS, aE), (rS, rE) in p)
+    # the kinds of refusal the strides allow: a side at stride 1 completes an output with every sample
+    allowed = {"audio", "rds", "neither"} - ({"audio", "neither"} if Rr == 1 else set()) - ({"rds", "neither"} if Ra == 1 else set())
+    assert {k for _, k in refused} == allowed and ((Ra, Rr) != (3, 5) or len(allowed) == 3)
+    # a refusal comes before accepted calls of 2 and of Ta - 2 ... Ta samples
+    after = {c.sizes[i + 1] // 8 for i, _ in refused}               # D = 4: 8 bytes a multiplex sample
+    assert after >= {2, 254, 255, 256}
+    # call-cut invariance of the definition: the uncut bytes give the concatenation of the accepted calls
+    _, cut = _rx_run(c)
+    whole = dc.receiver_refs(c, rxr, check=[0])[0]
+    a, u = whole.feed(c.data[0])
+    assert np.array_equal(a, np.concatenate([x[0] for x in cut], axis=1)) and np.array_equal(u, np.concatenate([x[1] for x in cut], axis=1))
+    assert [whole.pilot(k) for k in range(c.K)] == cut[-1][2]
+
+
+@pytest.mark.parametrize("P", [1024, 4096])
+def test_receiver_block_edges(P):
+    c = dc.receiver_edges(P)
+    e = dc.rds_edges(P)
+    assert c.ends == dc.stereo_edges(P).ends and np.array_equal(c.data, e.data) and np.array_equal(c.incs, e.incs)
+    assert (c.Ta_a, c.Ra, c.Ta_r, c.Rr) == (9, 1, 9, 1) and c.pilot_min == dc.default_pilot_min(c.rate, c.D) > 0
+    p = dc.receiver_plan(c)
+    assert [mE for _, mE, _, _ in p] == c.ends                     # no call is refused
+    f = dc.edge_facts([(mS, mE) for mS, mE, _, _ in p], P)
+    assert f.rel == {-1, 0, 1} and f.open_calls >= 4 and f.whole >= 4 and f.starts_on_edge
+    for s in (0, 1):
+        ref, got = _rx_run(c, stream=s)
+        for k in (0, 1) if s == 0 else (1, 2):                     # the two stations that are there: a pilot appears or vanishes
+            reports = [pl[k] for _, _, pl in got]
+            assert len(set(reports)) >= 3 and {pr for pr, _ in reports} == {False, True}, (s, k, reports)
+        assert ref.stereo.kc_max > 0                               # the audio was stereo somewhere
+
+
+def test_receiver_threshold_is_exact_equality():
+    c, t = dc.receiver_threshold(), dc.stereo_threshold()
+    assert np.array_equal(c.data, t.data) and c.sizes == t.sizes and c.rate == t.rate >= 120000 * c.D
+    assert st.pilot_inc(c.rate, c.D) == 1 << 29
+    audio, base = {}, {}
+    for pm in (7, 8, 9):
+        ref, got = _rx_run(c, pilot_min=pm)
+        assert len(got) == len(c.sizes)
+        I, Q = ref.stereo.block_iq(0, 0)
+        assert (I, Q) == (1 << 26, 0) and I * I + Q * Q == (8 * c.P * 8192) ** 2
+        audio[pm] = np.concatenate([a for a, _, _ in got], axis=1)[0, :2 * c.P - c.Ta_a + 1]
+        base[pm] = np.concatenate([u for _, u, _ in got], axis=1)
+    assert np.array_equal(audio[7], audio[8]) and not np.array_equal(audio[8], audio[9])
+    assert np.array_equal(audio[9][:, 0], audio[9][:, 1]) and not np.array_equal(audio[8][:, 0], audio[8][:, 1])
+    assert np.array_equal(base[7], base[8]) and np.array_equal(base[8], base[9]) and base[8].any()
+
+
+@pytest.mark.parametrize("which", dc.RX_EXTREMES)
+def test_receiver_extremes(which):
+    c = dc.receiver_extreme(which)
+    ref, got = _rx_run(c)
+    assert len(got) == len(c.sizes)
+    a = np.concatenate([x[0] for x in got], axis=1)
+    u = np.concatenate([x[1] for x in got], axis=1)
+    for ch in (0, 1):                                              # the audio at both rails in both channels
+        assert a[..., ch].min() == -32768 and a[..., ch].max() == 32767
+    assert int(np.abs(c.gr.astype(np.int64)).sum()) == 16383 and dc.rds_shift_for(c.gr) == 14 and c.audio_shift == 0
+    if which == "stereo":
+        e = dc.stereo_extreme(16384, 1)
+        assert np.array_equal(c.data, e.data) and np.array_equal(c.ga, e.g) and c.shift == e.shift and c.rds_shift == 14
+        assert ref.stereo.kc_max >= 32000 and ref.stereo.corr_max > (1 << 23) and ref.rds.v_max > (1 << 24)
+    else:
+        e = dc.rds_extreme(*{"rds-plus": ("plus", 14), "rds-256": ("256", 24)}[which])
+        assert np.array_equal(c.data, e.data) and np.array_equal(c.gr, e.g) and (c.shift, c.rds_shift) == (e.shift, e.rds_shift)
+        assert c.ga.tolist() == [16383]
+        if c.Ta_r == 1:                                            # what tests/test_gpu_rds_domain.py asserts of the RDS bank's output
+            assert ref.rds.v_max == 16384 * 16383 and u.min() == -16383 and u.max() == 16383
+        if c.rds_shift == 24:
+            assert set(np.unique(u).tolist()) == {-1, 0}
 
 
 # ---- uniform channelizer and band-plan bank -----------------------------------------------------------------------------------------
