@@ -768,6 +768,49 @@ int fmd_bandplan_levels(fmd_bandplan *b, uint8_t *open, uint32_t *rms);
  * it. */
 int fmd_bandplan_kernel_name(const fmd_bandplan *b, uint32_t pass, char *name, size_t cap);
 
+/* ---- rational resampler: any bank's int16 output at a fixed rate ------------------------------------------------ */
+/* NEW SURFACE (the reference has only the fractional boxcar of low_pass_real).  A polyphase L / M filter over the int16 rows a bank
+ * leaves on the device; a row is one (stream, station) or (stream, channel), `width` int16 per sample: 1 for mono audio, 2 for
+ * interleaved (L, R) or (I, Q).  Definition (integers only; tests/resample_ref.py), per row and component c < width:
+ *   x[i][c]   int16 input, i >= 0 counted from creation or reset
+ *   g[p][t]   int16 polyphase taps, p < L phases of T taps each, phase-major: taps[p T + t]
+ *   q_n = n M,  i_n = floor(q_n / L),  p_n = q_n mod L                                        (u64)
+ *   v[n][c]   = sum_{t < T} g[p_n][t] x[i_n + t][c]         (exact in i32: every phase has sum_t |g[p][t]| <= 32767)
+ *   out[n][c] = sat16(v[n][c] >> shift)                     (arithmetic shift: floor)
+ * Output n comes with the call in which x[i_n + T - 1] arrives: after N inputs per row, N >= T ? ceil((N - T + 1) L / M) : 0
+ * outputs exist, the same for every row, and a call returns the new ones.  The handle carries max(0, N - i_next) <= T - 1 samples,
+ * i_next = floor(outputs M / L); where M / L > T, i_next may lie beyond N and the next call skips inputs.  The output does not
+ * depend on how the stream is cut into calls that each complete an output.  L = M = 1 is a plain FIR (g = [1]: the identity), L = 1
+ * the banks' own rule for a FIR at stride M.
+ * Domain (else FMD_ERR_UNSUPPORTED, decided before a device is queried): width 1 or 2; 1 <= L <= 1024 and 1 <= M <= 1024;
+ * M <= 32 L; L <= 8 M; 1 <= T <= 256; L T <= 16384; shift <= 24; n_rows = dev->n_channels >= 1; every phase's sum |g| <= 32767.
+ * n_in > in_cap or an out_cap below the call's outputs -> FMD_ERR_CAPACITY (nothing is written); a call that completes no output ->
+ * FMD_ERR_TOO_SHORT and changes nothing (its samples are not taken).  Stream lifetime and completion points: as fmd_channelizer_*
+ * (fmd_resample_check). */
+typedef struct fmd_resample fmd_resample;
+/* L / M = rate_out rate_in_den / rate_in_num (the input rate is rate_in_num / rate_in_den Hz), reduced by the gcd in u64.  Zero
+ * rates, rate_in_den or rate_out of 2^32 and more, or a reduced ratio outside the domain -> FMD_ERR_UNSUPPORTED. */
+int fmd_resample_ratio(uint64_t rate_in_num, uint64_t rate_in_den, uint64_t rate_out, uint32_t *L, uint32_t *M);
+int fmd_resample_new(const int16_t *taps, uint32_t L, uint32_t M, uint32_t T, uint32_t shift, uint32_t width,
+                     const fmd_device_config *dev, fmd_resample **out);
+void fmd_resample_free(fmd_resample *r);
+int fmd_resample_reset(fmd_resample *r);
+/* ceil(n_in L / M) + 1: outputs per row one call of n_in samples can complete at most, whatever the history; 0 for L 0 or M 0. */
+size_t fmd_resample_out_cap(uint32_t L, uint32_t M, size_t n_in);
+/* HOST buffers: in [n_rows][in_cap][width], the first n_in samples of each row valid; out [n_rows][out_cap][width]; *n_out =
+ * outputs per row (the same for all). */
+int fmd_resample_run_batch(fmd_resample *r, const int16_t *in, size_t n_in, size_t in_cap, int16_t *out, size_t out_cap,
+                           size_t *n_out);
+/* DEVICE buffers, enqueued on `stream` without synchronising: d_in is a bank's d_out as it stands, with the bank's out_cap as
+ * in_cap; pointers 4-byte aligned at width 2 and 2-byte aligned at width 1, any in_cap and out_cap. */
+int fmd_resample_run_device(fmd_resample *r, const void *d_in, size_t n_in, size_t in_cap, void *d_out, size_t out_cap,
+                            size_t *n_out, void *stream);
+int fmd_resample_check(fmd_resample *r);
+/* Samples taken and outputs produced per row since creation or the last reset. */
+int fmd_resample_outputs(const fmd_resample *r, uint64_t *inputs, uint64_t *outputs);
+/* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_resample_kernel_name(const fmd_resample *r, char *name, size_t cap);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

@@ -793,6 +793,92 @@ private:
     Owned<fmd_bandplan, fmd_bandplan_free> h_;
 };
 
+// As the Python resample_ratio(): (L, M) with L / M = rate_out rate_in_den / rate_in_num in lowest terms.
+inline std::pair<uint32_t, uint32_t> resample_ratio(uint64_t rate_in_num, uint64_t rate_in_den, uint64_t rate_out)
+{
+    uint32_t L = 0, M = 0;
+    check(fmd_resample_ratio(rate_in_num, rate_in_den, rate_out, &L, &M));
+    return {L, M};
+}
+
+// Polyphase taps of a Resampler, tap for tap the Python resample_taps(): a Hamming-windowed sinc of L T points at cutoff / max(L, M)
+// cycles per upsampled sample; g[p][t] takes prototype point L (T - 1 - t) + p; every phase is scaled to the sum 2^shift, rounded to
+// nearest, and the rounding's remainder goes to the first of its largest taps; shift is the largest value <= 14 at which every
+// phase has sum |g| <= 32767.  Phase-major [L][T].
+inline std::pair<std::vector<int16_t>, uint32_t> resample_taps(uint32_t L, uint32_t M, uint32_t T, double cutoff = 0.45)
+{
+    if (L < 1 || M < 1 || T < 1) throw Error(FMD_ERR_INVALID_ARG);
+    const size_t n = (size_t)L * T;
+    const double fc = cutoff / (double)std::max(L, M);
+    std::vector<double> h(n);
+    for (size_t i = 0; i < n; ++i) {
+        const double x = 2 * detail::pi * fc * ((double)i - (double)(n - 1) / 2.0);
+        h[i] = detail::sinc(x) * detail::hamming(i, n);
+    }
+    std::vector<int16_t> g(n);
+    std::vector<int64_t> row(T);
+    for (int shift = 14; shift >= 0; --shift) {
+        bool ok = true;
+        for (uint32_t p = 0; p < L && ok; ++p) {
+            double s = 0;
+            for (uint32_t t = 0; t < T; ++t) s += h[(size_t)L * (T - 1 - t) + p];
+            if (!(s > 0)) throw Error(FMD_ERR_INVALID_ARG);
+            const double scale = std::ldexp(1.0, shift) / s;
+            int64_t sum = 0;
+            uint32_t big = 0;
+            for (uint32_t t = 0; t < T; ++t) {
+                row[t] = (int64_t)std::floor(h[(size_t)L * (T - 1 - t) + p] * scale + 0.5);
+                sum += row[t];
+                if (row[t] > row[big]) big = t;
+            }
+            row[big] += ((int64_t)1 << shift) - sum;
+            int64_t mag = 0;
+            for (uint32_t t = 0; t < T; ++t) mag += row[t] < 0 ? -row[t] : row[t];
+            if (mag > 32767) { ok = false; break; }
+            for (uint32_t t = 0; t < T; ++t) g[(size_t)p * T + t] = (int16_t)row[t];
+        }
+        if (ok) return {g, (uint32_t)shift};
+    }
+    throw Error(FMD_ERR_UNSUPPORTED);
+}
+
+// Rational resampler (fmd_resample_*): `taps` is [L][T] phase-major; run() takes [n_rows][n_in][width] int16 and returns the
+// call's outputs per row, interleaved by `width`.
+class Resampler {
+public:
+    Resampler(const std::vector<int16_t>& taps, uint32_t L, uint32_t M, uint32_t shift, uint32_t n_rows = 1, uint32_t width = 1,
+              int32_t device_id = -1)
+        : L_(L), M_(M), n_rows_(n_rows), width_(width)
+    {
+        fmd_device_config dev{n_rows, device_id, 0};
+        check(fmd_resample_new(taps.data(), L, M, L ? (uint32_t)(taps.size() / L) : 0u, shift, width, &dev, h_.out()));
+    }
+
+    // FMD_ERR_TOO_SHORT (a call that completes no output) returns empty rows and changes nothing: the samples are not taken.
+    Rows run(const int16_t* x, size_t n_in)
+    {
+        const size_t cap = std::max<size_t>(1, fmd_resample_out_cap(L_, M_, n_in));
+        std::vector<int16_t> out(width_ * cap * n_rows_);
+        size_t n = 0;
+        const int rc = fmd_resample_run_batch(h_, x, n_in, n_in, out.data(), cap, &n);
+        if (rc == FMD_ERR_TOO_SHORT) return Rows(n_rows_);
+        check(rc);
+        return cut_rows(out, n_rows_, cap, n, width_);
+    }
+    // (inputs, outputs) per row since creation or reset
+    std::pair<uint64_t, uint64_t> counts() const
+    {
+        uint64_t i = 0, o = 0;
+        check(fmd_resample_outputs(h_, &i, &o));
+        return {i, o};
+    }
+    void reset() { check(fmd_resample_reset(h_)); }
+
+private:
+    uint32_t L_, M_, n_rows_, width_;
+    Owned<fmd_resample, fmd_resample_free> h_;
+};
+
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.
 inline void output(const std::vector<int16_t>& buf, FILE* f = stdout)
 {

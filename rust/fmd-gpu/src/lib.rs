@@ -199,6 +199,11 @@ pub struct fmd_bandplan {
 }
 
 #[repr(C)]
+pub struct fmd_resample {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
 }
@@ -362,6 +367,16 @@ extern "C" {
     pub fn fmd_bandplan_outputs(b: *const fmd_bandplan, outputs: *mut u64) -> c_int;
     pub fn fmd_bandplan_levels(b: *mut fmd_bandplan, open: *mut u8, rms: *mut u32) -> c_int;
     pub fn fmd_bandplan_kernel_name(b: *const fmd_bandplan, pass: u32, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_resample_ratio(rate_in_num: u64, rate_in_den: u64, rate_out: u64, l: *mut u32, m: *mut u32) -> c_int;
+    pub fn fmd_resample_new(taps: *const i16, l: u32, m: u32, t: u32, shift: u32, width: u32, dev: *const DeviceConfig, out: *mut *mut fmd_resample) -> c_int;
+    pub fn fmd_resample_free(r: *mut fmd_resample);
+    pub fn fmd_resample_reset(r: *mut fmd_resample) -> c_int;
+    pub fn fmd_resample_out_cap(l: u32, m: u32, n_in: usize) -> usize;
+    pub fn fmd_resample_run_batch(r: *mut fmd_resample, input: *const i16, n_in: usize, in_cap: usize, out: *mut i16, out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn fmd_resample_run_device(r: *mut fmd_resample, d_in: *const c_void, n_in: usize, in_cap: usize, d_out: *mut c_void, out_cap: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_resample_check(r: *mut fmd_resample) -> c_int;
+    pub fn fmd_resample_outputs(r: *const fmd_resample, inputs: *mut u64, outputs: *mut u64) -> c_int;
+    pub fn fmd_resample_kernel_name(r: *const fmd_resample, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
