@@ -811,6 +811,66 @@ int fmd_resample_outputs(const fmd_resample *r, uint64_t *inputs, uint64_t *outp
 /* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_resample_kernel_name(const fmd_resample *r, char *name, size_t cap);
 
+/* ---- automatic gain control: any bank's int16 output at a steady level, without clipping ------------------------ */
+/* NEW SURFACE (the reference has no AGC).  A block-peak AGC with one block of look-ahead over the int16 rows a bank leaves on the
+ * device -- the other half of the output chain bank -> AGC -> resampler; a row is one (stream, station) or (stream, channel),
+ * `width` int16 per sample: 1 for mono audio, 2 for interleaved (L, R) or (I, Q) under one common gain.  With gain = 256 the narrow
+ * and band-plan banks' w fits int16 in every mode, so their rows carry the detector's full precision.  Definition (integers only;
+ * tests/agc_ref.py), per row, with P = block:
+ *   x[i][c]    int16 input, i >= 0 counted from creation or reset, c < width
+ *   m[i]       = max_c |x[i][c]|                                  0 ... 32768
+ *   block j    = the samples i with floor(i / P) = j;   p_j = max m[i] over block j
+ *   e_j        = max(p_j, p_{j+1})                                one block of look-ahead
+ *   d_j        = min(gain_max, floor(target 1024 / e_j))          Q10, for e_j > 0
+ *   state (G, h), starting at G = gain_max, h = 0; per block j in order:
+ *       e_j == 0      : G, h unchanged          (a muted or silent block holds the gain)
+ *       d_j <= G      : G = d_j,  h = hang      (attack: complete one block BEFORE the loud block, thanks to the look-ahead)
+ *       h > 0         : h = h - 1               (hang)
+ *       otherwise     : G = min(d_j, G + max(1, ((d_j - G) decay) >> 8))        (release)
+ *   G_j        = G after block j;   G_{-1} := G_0
+ *   g[i]       = G_{j-1} + (((G_j - G_{j-1}) (r + 1)) >> log2 P),   j = floor(i / P), r = i mod P    (arithmetic shift: floor)
+ *   out[i][c]  = (x[i][c] g[i]) >> 10                             (arithmetic shift)
+ * Bounds: |G_j - G_{j-1}| (r + 1) <= 2^18 2^12 = 2^30.  For e_j > 0, G_j <= d_j (attack sets it, hang keeps a smaller G, release
+ * takes the minimum), so G_j <= target 1024 / p_j and, as e_{j-1} >= p_j, G_{j-1} <= target 1024 / p_j too (where e_j or e_{j-1}
+ * is 0, p_j is 0 and block j is all zeros).  g[i] lies between the two ends of the ramp, hence |x g| <= 1024 target < 2^25 and
+ * |out| <= target: the AGC never clips and needs no sat16, and everything is exact in i32.
+ * Calls: output block j needs p_{j+1}.  After N inputs per row P max(0, floor(N / P) - 1) outputs exist, the same for every row,
+ * and a call returns the new ones.  The handle carries the N - outputs samples not yet emitted (at most 2 P - 1) and (G, h) per
+ * row.  A call that completes no block is accepted: FMD_OK, *n_out = 0, and its samples go into the history.  n_in == 0 is FMD_OK,
+ * launches nothing and changes nothing.  n_in > in_cap or an out_cap below the call's outputs -> FMD_ERR_CAPACITY (nothing is
+ * written or taken).  The output does not depend on how the stream is cut into calls.  The last P ... 2 P - 1 samples of a stream
+ * never come out on their own: a caller who wants them appends 2 P zero samples.
+ * Domain (else FMD_ERR_UNSUPPORTED, decided before a device is queried): width 1 or 2; block a power of two in [16, 4096];
+ * 1 <= target <= 32767; 1 <= gain_max <= 262144 (256 x in Q10); hang <= 65535; 1 <= decay <= 256; n_rows = dev->n_channels >= 1.
+ * Stream lifetime and completion points: as fmd_channelizer_* (fmd_agc_check). */
+typedef struct fmd_agc fmd_agc;
+typedef struct fmd_agc_config {
+    uint32_t block;     /* P: samples per block                                        */
+    uint32_t target;    /* the largest |out|                                           */
+    uint32_t gain_max;  /* Q10: the gain of a quiet row                                */
+    uint32_t hang;      /* blocks the gain is held after an attack                     */
+    uint32_t decay;     /* release: the fraction decay / 256 of the gap, per block     */
+} fmd_agc_config;
+int fmd_agc_new(const fmd_agc_config *cfg, uint32_t width, const fmd_device_config *dev, fmd_agc **out);
+void fmd_agc_free(fmd_agc *a);
+int fmd_agc_reset(fmd_agc *a);
+/* block ceil(n_in / block): outputs per row one call of n_in samples can complete at most, whatever the history; 0 for block 0. */
+size_t fmd_agc_out_cap(uint32_t block, size_t n_in);
+/* HOST buffers: in [n_rows][in_cap][width], the first n_in samples of each row valid; out [n_rows][out_cap][width]; *n_out =
+ * outputs per row (the same for all). */
+int fmd_agc_run_batch(fmd_agc *a, const int16_t *in, size_t n_in, size_t in_cap, int16_t *out, size_t out_cap, size_t *n_out);
+/* DEVICE buffers, enqueued on `stream` without synchronising: d_in is a bank's d_out as it stands, with the bank's out_cap as
+ * in_cap; pointers 4-byte aligned at width 2 and 2-byte aligned at width 1, any in_cap and out_cap. */
+int fmd_agc_run_device(fmd_agc *a, const void *d_in, size_t n_in, size_t in_cap, void *d_out, size_t out_cap, size_t *n_out,
+                       void *stream);
+int fmd_agc_check(fmd_agc *a);
+/* Samples taken and outputs produced per row since creation or the last reset. */
+int fmd_agc_outputs(const fmd_agc *a, uint64_t *inputs, uint64_t *outputs);
+/* (G, h) of `row` after the last emitted block; gain_max, 0 before any block.  Synchronises first. */
+int fmd_agc_gain(fmd_agc *a, uint32_t row, uint32_t *gain, uint32_t *hang);
+/* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_agc_kernel_name(const fmd_agc *a, char *name, size_t cap);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

@@ -20,8 +20,9 @@ from .spectrum import Spectrum, find_stations, hann_window
 from .uniform import UniformChannelizer, uniform_auto_shift, uniform_channel_inc, uniform_channel_offsets, uniform_taps
 from .bandplan import BandPlanBank, bandplan_auto_shifts
 from .resample import Resampler, bank_rate, fixed_rate, resample_ratio, resample_taps
+from .agc import Agc, leveled
 from . import shard, synth
 
-__all__ = ["DEFAULT_BUF_LENGTH", "Demod", "DemodBank", "PinnedBuffer", "FirBank", "Sink", "pump", "FirDemodBank", "auto_shift", "StationBank", "phase_inc", "stations_auto_shift", "Channelizer", "as_complex", "StereoBank", "stereo_taps", "RdsBank", "RdsDecoder", "decode_stations", "rds_taps", "ReceiverBank", "receive_stations", "NarrowBank", "narrow_taps", "narrow_auto_shift", "Spectrum", "find_stations", "hann_window", "UniformChannelizer", "uniform_auto_shift", "uniform_channel_inc", "uniform_channel_offsets", "uniform_taps", "BandPlanBank", "bandplan_auto_shifts", "Resampler", "bank_rate", "fixed_rate", "resample_ratio", "resample_taps", "DemodConfig", "DemodState", "DeviceConfig", "FmdError",
+__all__ = ["DEFAULT_BUF_LENGTH", "Demod", "DemodBank", "PinnedBuffer", "FirBank", "Sink", "pump", "FirDemodBank", "auto_shift", "StationBank", "phase_inc", "stations_auto_shift", "Channelizer", "as_complex", "StereoBank", "stereo_taps", "RdsBank", "RdsDecoder", "decode_stations", "rds_taps", "ReceiverBank", "receive_stations", "NarrowBank", "narrow_taps", "narrow_auto_shift", "Spectrum", "find_stations", "hann_window", "UniformChannelizer", "uniform_auto_shift", "uniform_channel_inc", "uniform_channel_offsets", "uniform_taps", "BandPlanBank", "bandplan_auto_shifts", "Resampler", "bank_rate", "fixed_rate", "resample_ratio", "resample_taps", "Agc", "leveled", "DemodConfig", "DemodState", "DeviceConfig", "FmdError",
            "RadioConfig", "SynthParams", "build", "check", "lib", "device_count", "optimal_settings", "out_cap",
            "shard", "synth"]

@@ -231,6 +231,16 @@ PROTOTYPES = {
     "fmd_resample_check": (C.c_int, [_vp]),
     "fmd_resample_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fmd_resample_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_agc_new": (C.c_int, [_vp, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_agc_free": (None, [_vp]),
+    "fmd_agc_reset": (C.c_int, [_vp]),
+    "fmd_agc_out_cap": (_sz, [C.c_uint32, _sz]),
+    "fmd_agc_run_batch": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp]),
+    "fmd_agc_run_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_agc_check": (C.c_int, [_vp]),
+    "fmd_agc_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fmd_agc_gain": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "fmd_agc_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

@@ -879,6 +879,48 @@ private:
     Owned<fmd_resample, fmd_resample_free> h_;
 };
 
+// Automatic gain control (fmd_agc_*): run() takes [n_rows][n_in][width] int16 and returns the call's outputs per row, interleaved
+// by `width`: block j comes with the call that completes block j + 1, so a call may return empty rows (its samples are taken), and
+// the last block ... 2 block - 1 samples of a stream come out only behind 2 block further (zero) samples.
+class Agc {
+public:
+    explicit Agc(const fmd_agc_config& cfg, uint32_t n_rows = 1, uint32_t width = 1, int32_t device_id = -1)
+        : block_(cfg.block), n_rows_(n_rows), width_(width)
+    {
+        fmd_device_config dev{n_rows, device_id, 0};
+        check(fmd_agc_new(&cfg, width, &dev, h_.out()));
+    }
+
+    Rows run(const int16_t* x, size_t n_in)
+    {
+        const size_t cap = std::max<size_t>(1, fmd_agc_out_cap(block_, n_in));
+        std::vector<int16_t> out(width_ * cap * n_rows_);
+        size_t n = 0;
+        check(fmd_agc_run_batch(h_, x, n_in, n_in, out.data(), cap, &n));
+        return cut_rows(out, n_rows_, cap, n, width_);
+    }
+    // (inputs, outputs) per row since creation or reset
+    std::pair<uint64_t, uint64_t> counts() const
+    {
+        uint64_t i = 0, o = 0;
+        check(fmd_agc_outputs(h_, &i, &o));
+        return {i, o};
+    }
+    // (G, h) of `row` after the last emitted block: the Q10 gain and the hang blocks left
+    std::pair<uint32_t, uint32_t> gain(uint32_t row = 0)
+    {
+        uint32_t g = 0, h = 0;
+        check(fmd_agc_gain(h_, row, &g, &h));
+        return {g, h};
+    }
+    void reset() { check(fmd_agc_reset(h_)); }
+    uint32_t block() const { return block_; }
+
+private:
+    uint32_t block_, n_rows_, width_;
+    Owned<fmd_agc, fmd_agc_free> h_;
+};
+
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.
 inline void output(const std::vector<int16_t>& buf, FILE* f = stdout)
 {

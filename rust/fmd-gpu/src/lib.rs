@@ -204,6 +204,22 @@ pub struct fmd_resample {
 }
 
 #[repr(C)]
+pub struct fmd_agc {
+    _private: [u8; 0],
+}
+
+/// `fmd_agc_config` of include/fmd.h (automatic gain control).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_agc_config {
+    pub block: u32,
+    pub target: u32,
+    pub gain_max: u32,
+    pub hang: u32,
+    pub decay: u32,
+}
+
+#[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
 }
@@ -377,6 +393,17 @@ extern "C" {
     pub fn fmd_resample_check(r: *mut fmd_resample) -> c_int;
     pub fn fmd_resample_outputs(r: *const fmd_resample, inputs: *mut u64, outputs: *mut u64) -> c_int;
     pub fn fmd_resample_kernel_name(r: *const fmd_resample, name: *mut c_char, cap: usize) -> c_int;
+    // automatic gain control: the declarations only (no safe wrapper yet)
+    pub fn fmd_agc_new(cfg: *const fmd_agc_config, width: u32, dev: *const DeviceConfig, out: *mut *mut fmd_agc) -> c_int;
+    pub fn fmd_agc_free(a: *mut fmd_agc);
+    pub fn fmd_agc_reset(a: *mut fmd_agc) -> c_int;
+    pub fn fmd_agc_out_cap(block: u32, n_in: usize) -> usize;
+    pub fn fmd_agc_run_batch(a: *mut fmd_agc, input: *const i16, n_in: usize, in_cap: usize, out: *mut i16, out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn fmd_agc_run_device(a: *mut fmd_agc, d_in: *const c_void, n_in: usize, in_cap: usize, d_out: *mut c_void, out_cap: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_agc_check(a: *mut fmd_agc) -> c_int;
+    pub fn fmd_agc_outputs(a: *const fmd_agc, inputs: *mut u64, outputs: *mut u64) -> c_int;
+    pub fn fmd_agc_gain(a: *mut fmd_agc, row: u32, gain: *mut u32, hang: *mut u32) -> c_int;
+    pub fn fmd_agc_kernel_name(a: *const fmd_agc, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
