@@ -394,6 +394,49 @@ class DownConverter(BankHandle):
         return n.value
 
 
+class RowProcessor(BankHandle):
+    """Base of the handles that post-process the int16 rows a bank leaves on the device, through fmd_<_prefix>_run_*: `n_rows` rows
+    of `width` 1 or 2 int16 per sample.  A subclass gives out_cap(n_in)."""
+
+    def counts(self):
+        """(inputs, outputs) per row since creation or reset."""
+        i, o = C.c_uint64(0), C.c_uint64(0)
+        check(self._fn("outputs")(self._h, C.byref(i), C.byref(o)))
+        return i.value, o.value
+
+    def outputs(self):
+        return self.counts()[1]
+
+    def run_batch(self, x):
+        """x int16 [n_rows, n_in, width] ([n_rows, n_in] at width 1) -> int16 of the same form with n_out outputs per row (none
+        when the handle takes a call that completes nothing, as the Agc does with a call that completes no block)."""
+        x = np.ascontiguousarray(x, dtype=np.int16)
+        flat = x.ndim == 2 and self.width == 1
+        if flat:
+            x = x[:, :, None]
+        if x.ndim != 3 or x.shape[0] != self.n_rows or x.shape[2] != self.width:
+            raise ValueError("x must be [n_rows, n_in, width]")
+        cap = max(1, self.out_cap(x.shape[1]))
+        out = np.empty((self.n_rows, cap, self.width), dtype=np.int16)
+        n = C.c_size_t(0)
+        check(self._fn("run_batch")(self._h, x.ctypes.data, x.shape[1], x.shape[1], out.ctypes.data, cap, C.byref(n)))
+        out = out[:, :n.value].copy()
+        return out[:, :, 0] if flat else out
+
+    def run_device(self, d_in, n_in, in_cap, d_out, out_cap, stream=None):
+        """Enqueue on device pointers (d_in [n_rows][in_cap][width], the first n_in samples of each row valid; d_out
+        [n_rows][out_cap][width]); returns the outputs per row (0 when the Agc's call completes no block).  `stream` must stay
+        alive until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
+        n = C.c_size_t(0)
+        check(self._fn("run_device")(self._h, d_in, n_in, in_cap, d_out, out_cap, C.byref(n), stream))
+        return n.value
+
+
+def bank_rows(bank):
+    """(rows, width) of a bank's output: n_streams x stations or selected channels, and the int16 per output."""
+    return bank.n_streams * getattr(bank, getattr(bank, "_rows", "n_stations")), bank.width if hasattr(bank, "width") else 2
+
+
 def stream_phase_incs(phase_incs, n_streams):
     """`phase_incs` as a contiguous uint32 [n_streams, n_stations] (a flat list of n_stations is taken for every stream)."""
     incs = np.asarray(phase_incs, dtype=np.uint32)

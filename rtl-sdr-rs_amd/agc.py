@@ -4,9 +4,7 @@ that strong and weak channels of one bank come out at the same level and none of
 depend on how the stream is cut."""
 import ctypes as C
 
-import numpy as np
-
-from ._ffi import BankHandle, DeviceConfig, check, lib
+from ._ffi import DeviceConfig, RowProcessor, bank_rows, check, lib
 
 
 class AgcConfig(C.Structure):
@@ -14,7 +12,7 @@ class AgcConfig(C.Structure):
     _fields_ = [("block", C.c_uint32), ("target", C.c_uint32), ("gain_max", C.c_uint32), ("hang", C.c_uint32), ("decay", C.c_uint32)]
 
 
-class Agc(BankHandle):
+class Agc(RowProcessor):
     """`n_rows` is the rows of the bank whose output it takes (n_streams x stations or channels), `width` 1 or 2 int16 per sample.
     |out| <= target; `gain_max` is Q10 (1024: unity), `hang` blocks of `block` samples are held after an attack, then the gain
     closes decay / 256 of its gap per block.  Block j comes out with the call that completes block j + 1: the last block .. 2 block
@@ -36,48 +34,14 @@ class Agc(BankHandle):
     def out_cap(self, n_in):
         return int(lib().fmd_agc_out_cap(self.block, n_in))
 
-    def counts(self):
-        """(inputs, outputs) per row since creation or reset."""
-        i, o = C.c_uint64(0), C.c_uint64(0)
-        check(self._fn("outputs")(self._h, C.byref(i), C.byref(o)))
-        return i.value, o.value
-
-    def outputs(self):
-        return self.counts()[1]
-
     def gain(self, row=0):
         """(G, h) of `row` after the last emitted block: the Q10 gain and the hang blocks left.  Synchronises."""
         g, h = C.c_uint32(0), C.c_uint32(0)
         check(self._fn("gain")(self._h, int(row), C.byref(g), C.byref(h)))
         return g.value, h.value
 
-    def run_batch(self, x):
-        """x int16 [n_rows, n_in, width] ([n_rows, n_in] at width 1) -> int16 of the same form with n_out outputs per row (none
-        when the call completes no block)."""
-        x = np.ascontiguousarray(x, dtype=np.int16)
-        flat = x.ndim == 2 and self.width == 1
-        if flat:
-            x = x[:, :, None]
-        if x.ndim != 3 or x.shape[0] != self.n_rows or x.shape[2] != self.width:
-            raise ValueError("x must be [n_rows, n_in, width]")
-        cap = max(1, self.out_cap(x.shape[1]))
-        out = np.empty((self.n_rows, cap, self.width), dtype=np.int16)
-        n = C.c_size_t(0)
-        check(self._fn("run_batch")(self._h, x.ctypes.data, x.shape[1], x.shape[1], out.ctypes.data, cap, C.byref(n)))
-        out = out[:, :n.value].copy()
-        return out[:, :, 0] if flat else out
-
-    def run_device(self, d_in, n_in, in_cap, d_out, out_cap, stream=None):
-        """Enqueue on device pointers (d_in [n_rows][in_cap][width], the first n_in samples of each row valid; d_out
-        [n_rows][out_cap][width]); returns the outputs per row, 0 when the call completes no block.  `stream` must stay alive until
-        the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
-        n = C.c_size_t(0)
-        check(self._fn("run_device")(self._h, d_in, n_in, in_cap, d_out, out_cap, C.byref(n), stream))
-        return n.value
-
 
 def leveled(bank, target=12000, block=256, hang=4, decay=32, gain_max=65536, device_id=-1):
     """An Agc matched to `bank`: its rows (n_streams x stations or selected channels) and its width."""
-    rows = bank.n_streams * getattr(bank, getattr(bank, "_rows", "n_stations"))
-    return Agc(n_rows=rows, width=bank.width if hasattr(bank, "width") else 2, target=target, block=block, hang=hang, decay=decay,
-               gain_max=gain_max, device_id=device_id)
+    rows, width = bank_rows(bank)
+    return Agc(n_rows=rows, width=width, target=target, block=block, hang=hang, decay=decay, gain_max=gain_max, device_id=device_id)

@@ -14,14 +14,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <vector>
 
 #include "demod.hpp"
-
-struct CloseFile { void operator()(FILE* f) const { if (f != stdin && f != stdout) fclose(f); } };
-using File = std::unique_ptr<FILE, CloseFile>;
 
 static const char* const kUsage =
     "usage: %s [-c 1|2] [-t target] [-b block] [-H hang] [-d decay] [-g gain_max] [in.s16 [out.s16]]\n"
@@ -29,13 +25,12 @@ static const char* const kUsage =
 
 static int run(const char* in_path, const char* out_path, const fmd_agc_config& cfg, uint32_t width)
 {
-    File in(in_path && strcmp(in_path, "-") ? fopen(in_path, "rb") : stdin);
+    fm::File in(in_path && strcmp(in_path, "-") ? fopen(in_path, "rb") : stdin);
     if (!in) { perror(in_path); return 2; }
     fm::Agc agc(cfg, 1, width);                              // (out of the domain, or no device: before the output exists)
-    File out(out_path ? fopen(out_path, "wb") : stdout);
+    fm::File out(out_path ? fopen(out_path, "wb") : stdout);
     if (!out) { perror(out_path); return 2; }
-    const size_t block = 65536, sample = width * sizeof(int16_t);
-    std::vector<int16_t> buf(block * width);
+    std::vector<int16_t> buf(fm::kReadSamples * width);
     uint64_t taken = 0, written = 0;                         // samples
     const auto emit = [&](const fm::Rows& rows) {
         std::vector<int16_t> y = rows[0];
@@ -45,13 +40,9 @@ static int run(const char* in_path, const char* out_path, const fmd_agc_config& 
         written += n;
     };
     for (;;) {
-        uint8_t* const dst = reinterpret_cast<uint8_t*>(buf.data());
-        size_t fill = 0, got;
-        while (fill < block * sample && (got = fread(dst + fill, 1, block * sample - fill, in.get())) > 0) fill += got;
-        if (fill % sample) fprintf(stderr, "dropped %zu trailing bytes\n", fill % sample);
-        const size_t n = fill / sample;
+        const size_t n = fm::read_samples(in.get(), buf.data(), width);
         if (n) { taken += n; emit(agc.run(buf.data(), n)); }
-        if (fill < block * sample) break;
+        if (n < fm::kReadSamples) break;
     }
     if (taken) {
         const std::vector<int16_t> zeros(2u * cfg.block * width, 0);
@@ -91,10 +82,5 @@ int main(int argc, char** argv)
     }
     if (width != 1 && width != 2) { fprintf(stderr, "bad -c: need 1 or 2\n"); return 2; }
     if (paths.size() > 2) { fprintf(stderr, "too many files\n"); return 2; }
-    try {                                                    // an fm::Error is its message on stderr and exit code 1
-        return run(paths.empty() ? nullptr : paths[0], paths.size() > 1 ? paths[1] : nullptr, cfg, width);
-    } catch (const fm::Error& e) {
-        fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
+    return fm::exit_code([&] { return run(paths.empty() ? nullptr : paths[0], paths.size() > 1 ? paths[1] : nullptr, cfg, width); });
 }

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -842,70 +843,72 @@ inline std::pair<std::vector<int16_t>, uint32_t> resample_taps(uint32_t L, uint3
     throw Error(FMD_ERR_UNSUPPORTED);
 }
 
+// Base of the row processors (fmd_resample_*, fmd_agc_*): owns the handle H of `n_rows` rows of `width` int16 per sample and runs it
+// through its `_run_batch`, `_outputs` and `_reset` entry points.
+template <class H, void (*Free)(H*), auto RunBatch, auto Outputs, auto Reset>
+class RowProcessor {
+public:
+    // (inputs, outputs) per row since creation or reset
+    std::pair<uint64_t, uint64_t> counts() const
+    {
+        uint64_t i = 0, o = 0;
+        check(Outputs(h_, &i, &o));
+        return {i, o};
+    }
+    void reset() { check(Reset(h_)); }
+
+protected:
+    RowProcessor(uint32_t n_rows, uint32_t width) : n_rows_(n_rows), width_(width) {}
+
+    // [n_rows][n_in][width] through the handle into room for `cap` outputs per row: the call's outputs per row, interleaved by
+    // `width`.  The status `empty` (FMD_OK: none) returns empty rows instead of throwing.
+    Rows run_rows(const int16_t* x, size_t n_in, size_t cap, int empty = FMD_OK)
+    {
+        cap = std::max<size_t>(1, cap);
+        std::vector<int16_t> out(width_ * cap * n_rows_);
+        size_t n = 0;
+        const int rc = RunBatch(h_, x, n_in, n_in, out.data(), cap, &n);
+        if (rc != FMD_OK && rc == empty) return Rows(n_rows_);
+        check(rc);
+        return cut_rows(out, n_rows_, cap, n, width_);
+    }
+
+    uint32_t n_rows_, width_;
+    Owned<H, Free> h_;
+};
+
 // Rational resampler (fmd_resample_*): `taps` is [L][T] phase-major; run() takes [n_rows][n_in][width] int16 and returns the
 // call's outputs per row, interleaved by `width`.
-class Resampler {
+class Resampler : public RowProcessor<fmd_resample, fmd_resample_free, fmd_resample_run_batch, fmd_resample_outputs, fmd_resample_reset> {
 public:
     Resampler(const std::vector<int16_t>& taps, uint32_t L, uint32_t M, uint32_t shift, uint32_t n_rows = 1, uint32_t width = 1,
               int32_t device_id = -1)
-        : L_(L), M_(M), n_rows_(n_rows), width_(width)
+        : RowProcessor(n_rows, width), L_(L), M_(M)
     {
         fmd_device_config dev{n_rows, device_id, 0};
         check(fmd_resample_new(taps.data(), L, M, L ? (uint32_t)(taps.size() / L) : 0u, shift, width, &dev, h_.out()));
     }
 
     // FMD_ERR_TOO_SHORT (a call that completes no output) returns empty rows and changes nothing: the samples are not taken.
-    Rows run(const int16_t* x, size_t n_in)
-    {
-        const size_t cap = std::max<size_t>(1, fmd_resample_out_cap(L_, M_, n_in));
-        std::vector<int16_t> out(width_ * cap * n_rows_);
-        size_t n = 0;
-        const int rc = fmd_resample_run_batch(h_, x, n_in, n_in, out.data(), cap, &n);
-        if (rc == FMD_ERR_TOO_SHORT) return Rows(n_rows_);
-        check(rc);
-        return cut_rows(out, n_rows_, cap, n, width_);
-    }
-    // (inputs, outputs) per row since creation or reset
-    std::pair<uint64_t, uint64_t> counts() const
-    {
-        uint64_t i = 0, o = 0;
-        check(fmd_resample_outputs(h_, &i, &o));
-        return {i, o};
-    }
-    void reset() { check(fmd_resample_reset(h_)); }
+    Rows run(const int16_t* x, size_t n_in) { return run_rows(x, n_in, fmd_resample_out_cap(L_, M_, n_in), FMD_ERR_TOO_SHORT); }
 
 private:
-    uint32_t L_, M_, n_rows_, width_;
-    Owned<fmd_resample, fmd_resample_free> h_;
+    uint32_t L_, M_;
 };
 
 // Automatic gain control (fmd_agc_*): run() takes [n_rows][n_in][width] int16 and returns the call's outputs per row, interleaved
 // by `width`: block j comes with the call that completes block j + 1, so a call may return empty rows (its samples are taken), and
 // the last block ... 2 block - 1 samples of a stream come out only behind 2 block further (zero) samples.
-class Agc {
+class Agc : public RowProcessor<fmd_agc, fmd_agc_free, fmd_agc_run_batch, fmd_agc_outputs, fmd_agc_reset> {
 public:
     explicit Agc(const fmd_agc_config& cfg, uint32_t n_rows = 1, uint32_t width = 1, int32_t device_id = -1)
-        : block_(cfg.block), n_rows_(n_rows), width_(width)
+        : RowProcessor(n_rows, width), block_(cfg.block)
     {
         fmd_device_config dev{n_rows, device_id, 0};
         check(fmd_agc_new(&cfg, width, &dev, h_.out()));
     }
 
-    Rows run(const int16_t* x, size_t n_in)
-    {
-        const size_t cap = std::max<size_t>(1, fmd_agc_out_cap(block_, n_in));
-        std::vector<int16_t> out(width_ * cap * n_rows_);
-        size_t n = 0;
-        check(fmd_agc_run_batch(h_, x, n_in, n_in, out.data(), cap, &n));
-        return cut_rows(out, n_rows_, cap, n, width_);
-    }
-    // (inputs, outputs) per row since creation or reset
-    std::pair<uint64_t, uint64_t> counts() const
-    {
-        uint64_t i = 0, o = 0;
-        check(fmd_agc_outputs(h_, &i, &o));
-        return {i, o};
-    }
+    Rows run(const int16_t* x, size_t n_in) { return run_rows(x, n_in, fmd_agc_out_cap(block_, n_in)); }
     // (G, h) of `row` after the last emitted block: the Q10 gain and the hang blocks left
     std::pair<uint32_t, uint32_t> gain(uint32_t row = 0)
     {
@@ -913,12 +916,10 @@ public:
         check(fmd_agc_gain(h_, row, &g, &h));
         return {g, h};
     }
-    void reset() { check(fmd_agc_reset(h_)); }
     uint32_t block() const { return block_; }
 
 private:
-    uint32_t block_, n_rows_, width_;
-    Owned<fmd_agc, fmd_agc_free> h_;
+    uint32_t block_;
 };
 
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.
@@ -926,6 +927,32 @@ inline void output(const std::vector<int16_t>& buf, FILE* f = stdout)
 {
     if (!buf.empty()) fwrite(buf.data(), sizeof(int16_t), buf.size(), f);
     fflush(f);
+}
+
+// An input or output file of an s16 tool; stdin and stdout stay open.
+struct CloseFile { void operator()(FILE* f) const { if (f != stdin && f != stdout) fclose(f); } };
+using File = std::unique_ptr<FILE, CloseFile>;
+
+constexpr size_t kReadSamples = 65536;                   // the s16 tools read their input in blocks of this many samples
+
+// Up to kReadSamples samples of `width` int16 from `in` into `dst`: the whole samples read -- fewer than kReadSamples at the end
+// of the input, where the bytes of a broken last sample are dropped and reported.
+inline size_t read_samples(FILE* in, int16_t* dst, size_t width)
+{
+    const size_t sample = width * sizeof(int16_t), want = kReadSamples * sample;
+    uint8_t* const p = reinterpret_cast<uint8_t*>(dst);
+    size_t fill = 0, got;
+    while (fill < want && (got = fread(p + fill, 1, want - fill, in)) > 0) fill += got;
+    if (fill % sample) fprintf(stderr, "dropped %zu trailing bytes\n", fill % sample);
+    return fill / sample;
+}
+
+// A tool's exit code from `run()`: an fm::Error is its message on stderr and exit code 1.
+template <class Run>
+inline int exit_code(Run run)
+{
+    try { return run(); }
+    catch (const Error& e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }
 }
 
 }  // namespace fm

@@ -30,8 +30,7 @@
 
 #include <new>
 
-#include "fmd_ddc.h"
-#include "fmd_internal.h"
+#include "fmd_rows.h"
 
 namespace fmd_ag {
 
@@ -257,12 +256,10 @@ __global__ void __launch_bounds__(kThreads) fmd_agc_kernel(const AgcLaunch A)
 }  // namespace fmd_ag
 
 struct fmd_agc {
-    FmdDdcCore core;                                      // core.pos: input samples per row since creation or reset
-    FmdDdcPair hist;                                      // [n_rows][hcap][width] int16: the samples not yet emitted
+    FmdRows rows;                                         // the history: the samples not yet emitted, hcap = 2 P
     FmdDdcPair state;                                     // [n_rows][2] int32: gain_max - G, h
-    uint32_t P = 0, lgP = 0, target = 0, gain_max = 0, hang = 0, decay = 0, width = 0, n_rows = 0;
-    uint32_t hcap = 0, ring = 0;
-    size_t lds = 0;
+    uint32_t P = 0, lgP = 0, target = 0, gain_max = 0, hang = 0, decay = 0;
+    uint32_t ring = 0;
 };
 
 namespace {
@@ -276,13 +273,10 @@ uint64_t agc_blocks(const fmd_agc* h, uint64_t n)
 
 int agc_enqueue(fmd_agc* h, const void* d_in, size_t n_in, size_t in_cap, void* d_out, size_t out_cap, size_t* n_out, hipStream_t stream)
 {
-    const uintptr_t mask = 2u * h->width - 1u;
-    if (((uintptr_t)d_in & mask) != 0 || ((uintptr_t)d_out & mask) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
-    if (n_in > in_cap) { fmd_internal_set_err("n_in > in_cap"); return FMD_ERR_CAPACITY; }
-    if (n_in > (1ull << 28)) { fmd_internal_set_err("n_in out of range"); return FMD_ERR_UNSUPPORTED; }
-    if (h->n_rows >= (1ull << 31)) { fmd_internal_set_err("too many rows for the grid"); return FMD_ERR_UNSUPPORTED; }
-    FmdDdcCore& c = h->core;
-    const uint64_t N0 = c.pos, N1 = N0 + n_in;
+    FmdRows& r = h->rows;
+    if (const int rc = fmd_rows_check_call(r, d_in, n_in, in_cap, d_out)) return rc;
+    if (r.n_rows >= (1ull << 31)) { fmd_internal_set_err("too many rows for the grid"); return FMD_ERR_UNSUPPORTED; }
+    const uint64_t N0 = r.core.pos, N1 = N0 + n_in;
     const uint64_t B0 = agc_blocks(h, N0), B1 = agc_blocks(h, N1), cnt = (B1 - B0) << h->lgP;
     if (cnt > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
     if (n_in == 0) {                                         // nothing to take: no launch
@@ -290,26 +284,16 @@ int agc_enqueue(fmd_agc* h, const void* d_in, size_t n_in, size_t in_cap, void* 
         return FMD_OK;
     }
     fmd_ag::AgcLaunch A{};
-    A.in = static_cast<const int16_t*>(d_in); A.in_cap = in_cap; A.n_in = (uint32_t)n_in; A.n_rows = h->n_rows;
-    A.hist_in = h->hist.in<int16_t>(c.cur); A.hist_out = h->hist.out<int16_t>(c.cur);
-    A.hcap = h->hcap;
+    fmd_rows_fill(A, r, d_in, n_in, in_cap, d_out, out_cap);
     A.h = (uint32_t)(N0 - (B0 << h->lgP));                  // <= 2 P - 1
     A.h_next = (uint32_t)(N1 - (B1 << h->lgP));             // <= 2 P - 1
-    A.st_in = h->state.in<int32_t>(c.cur); A.st_out = h->state.out<int32_t>(c.cur);
+    A.st_in = h->state.in<int32_t>(r.core.cur); A.st_out = h->state.out<int32_t>(r.core.cur);
     A.nb = (uint32_t)(B1 - B0);
     A.first = B0 == 0 ? 1u : 0u;
     A.P = h->P; A.lgP = h->lgP; A.ring = h->ring; A.sb = (h->ring >> h->lgP) - 1u;
     A.num = 1024u * h->target; A.gain_max = (int32_t)h->gain_max; A.hang = h->hang; A.decay = h->decay;
-    A.out = static_cast<int16_t*>(d_out); A.out_cap = out_cap;
-    if (A.h >= h->hcap || A.h_next >= h->hcap) { fmd_internal_set_err("internal: history out of range"); return FMD_ERR_BAD_STATE; }
-    FMD_DDC_TRY(c.order.before(stream));
-    const dim3 grid(h->n_rows);
-    if (h->width == 2) hipLaunchKernelGGL(fmd_ag::fmd_agc_kernel<2>, grid, dim3(fmd_ag::kThreads), h->lds, stream, A);
-    else hipLaunchKernelGGL(fmd_ag::fmd_agc_kernel<1>, grid, dim3(fmd_ag::kThreads), h->lds, stream, A);
-    FMD_DDC_TRY(hipGetLastError());
-    fmd_ddc_commit(c, stream, n_in);
-    if (n_out) *n_out = (size_t)cnt;
-    return FMD_OK;
+    if (A.h >= r.hcap || A.h_next >= r.hcap) { fmd_internal_set_err("internal: history out of range"); return FMD_ERR_BAD_STATE; }
+    return fmd_rows_launch(r, fmd_ag::fmd_agc_kernel<1>, fmd_ag::fmd_agc_kernel<2>, r.n_rows, fmd_ag::kThreads, A, stream, n_in, cnt, n_out);
 }
 
 }  // namespace
@@ -324,9 +308,7 @@ size_t fmd_agc_out_cap(uint32_t block, size_t n_in)
 
 int fmd_agc_new(const fmd_agc_config* cfg, uint32_t width, const fmd_device_config* dev, fmd_agc** out)
 {
-    if (!cfg || !dev || !out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *out = nullptr;
-    if (width != 1 && width != 2) { fmd_internal_set_err("need width 1 or 2"); return FMD_ERR_UNSUPPORTED; }
+    if (const int rc = fmd_rows_new_args(cfg, dev, out, width)) return rc;
     if (cfg->block < 16 || cfg->block > 4096 || (cfg->block & (cfg->block - 1u)) != 0) {
         fmd_internal_set_err("need block a power of two in [16, 4096]"); return FMD_ERR_UNSUPPORTED;
     }
@@ -334,68 +316,37 @@ int fmd_agc_new(const fmd_agc_config* cfg, uint32_t width, const fmd_device_conf
     if (cfg->gain_max < 1 || cfg->gain_max > 262144) { fmd_internal_set_err("need 1 <= gain_max <= 262144"); return FMD_ERR_UNSUPPORTED; }
     if (cfg->hang > 65535) { fmd_internal_set_err("need hang <= 65535"); return FMD_ERR_UNSUPPORTED; }
     if (cfg->decay < 1 || cfg->decay > 256) { fmd_internal_set_err("need 1 <= decay <= 256"); return FMD_ERR_UNSUPPORTED; }
-    if (dev->n_channels < 1) { fmd_internal_set_err("need n_rows >= 1"); return FMD_ERR_UNSUPPORTED; }
+    if (const int rc = fmd_rows_count_arg(dev)) return rc;
     fmd_agc* h = new (std::nothrow) fmd_agc();
     if (!h) return FMD_ERR_NOMEM;
     h->P = cfg->block; h->target = cfg->target; h->gain_max = cfg->gain_max; h->hang = cfg->hang; h->decay = cfg->decay;
-    h->width = width; h->n_rows = dev->n_channels;
     while ((1u << h->lgP) < h->P) ++h->lgP;
-    h->hcap = 2u * h->P;                                     // at most 2 P - 1 are carried; rows stay 16-byte aligned
     const uint32_t eb = 2u * width;
     h->ring = fmd_ag::kRingBytes / eb > 2u * h->P ? fmd_ag::kRingBytes / eb : 2u * h->P;
     const uint32_t slots = h->ring >> h->lgP;                // sb + 1
-    h->lds = (size_t)h->ring * eb + 4ull * slots + 4ull * (slots + 1u);
-    fmd_ddc_add_pair(h->core, h->hist, (size_t)h->n_rows * h->hcap * width * sizeof(int16_t));
-    fmd_ddc_add_pair(h->core, h->state, (size_t)h->n_rows * 2 * sizeof(int32_t));
-
-    if (const int rc = fmd_ddc_open(h->core, dev)) { delete h; return rc; }
-    const char* what = nullptr;
-    {
-        FmdDeviceGuard guard(h->core.device);
-        if (guard.error() != hipSuccess) what = "hipSetDevice";
-        if (!what) what = fmd_ddc_upload(h->core, FmdDdcPlan(), 16);   // (an empty plan: history and state are the pairs)
-        if (!what && hipDeviceSynchronize() != hipSuccess) what = "hipDeviceSynchronize";
-    }
-    if (what) { fmd_internal_set_err(what); fmd_agc_free(h); return FMD_ERR_HIP; }
-    *out = h;
-    return FMD_OK;
+    h->rows.lds = (size_t)h->ring * eb + 4ull * slots + 4ull * (slots + 1u);
+    h->rows.width = width; h->rows.n_rows = dev->n_channels; h->rows.hcap = 2u * h->P;   // (at most 2 P - 1 are carried; rows stay 16-byte aligned)
+    fmd_ddc_add_pair(h->rows.core, h->state, (size_t)dev->n_channels * 2 * sizeof(int32_t));
+    return fmd_rows_device(h, dev, fmd_agc_free, out);
 }
 
-void fmd_agc_free(fmd_agc* h)
-{
-    if (!h) return;
-    fmd_ddc_free(h->core);
-    delete h;
-}
-
-int fmd_agc_reset(fmd_agc* h)
-{
-    if (!h) return FMD_ERR_INVALID_ARG;
-    return fmd_ddc_reset(h->core);
-}
-
-int fmd_agc_check(fmd_agc* h)
-{
-    if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    return fmd_ddc_check(h->core);
-}
+void fmd_agc_free(fmd_agc* h) { fmd_rows_free(h); }
+int fmd_agc_reset(fmd_agc* h) { return fmd_rows_reset(h); }
+int fmd_agc_check(fmd_agc* h) { return fmd_rows_check(h); }
 
 int fmd_agc_outputs(const fmd_agc* h, uint64_t* inputs, uint64_t* outputs)
 {
-    if (!h || !inputs || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *inputs = h->core.pos;
-    *outputs = agc_blocks(h, h->core.pos) << h->lgP;
-    return FMD_OK;
+    return fmd_rows_outputs(h, inputs, outputs, [](const fmd_agc* a, uint64_t n) { return agc_blocks(a, n) << a->lgP; });
 }
 
 int fmd_agc_gain(fmd_agc* h, uint32_t row, uint32_t* gain, uint32_t* hang)
 {
     if (!h || !gain || !hang) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    if (row >= h->n_rows) { fmd_internal_set_err("row out of range"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->core.device);
+    if (row >= h->rows.n_rows) { fmd_internal_set_err("row out of range"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->rows.core.device);
     FMD_DDC_TRY(hipDeviceSynchronize());
     int32_t st[2] = {0, 0};
-    FMD_DDC_TRY(hipMemcpy(st, h->state.in<int32_t>(h->core.cur) + 2 * (size_t)row, sizeof st, hipMemcpyDeviceToHost));
+    FMD_DDC_TRY(hipMemcpy(st, h->state.in<int32_t>(h->rows.core.cur) + 2 * (size_t)row, sizeof st, hipMemcpyDeviceToHost));
     *gain = h->gain_max - (uint32_t)st[0];
     *hang = (uint32_t)st[1];
     return FMD_OK;
@@ -403,36 +354,16 @@ int fmd_agc_gain(fmd_agc* h, uint32_t row, uint32_t* gain, uint32_t* hang)
 
 int fmd_agc_run_device(fmd_agc* h, const void* d_in, size_t n_in, size_t in_cap, void* d_out, size_t out_cap, size_t* n_out, void* stream)
 {
-    return fmd_ddc_run_device(h ? &h->core : nullptr, d_in, d_out,
+    return fmd_ddc_run_device(h ? &h->rows.core : nullptr, d_in, d_out,
                               [&] { return agc_enqueue(h, d_in, n_in, in_cap, d_out, out_cap, n_out, static_cast<hipStream_t>(stream)); });
 }
 
+// (a call of no samples has nothing to take: it does not touch the device)
 int fmd_agc_run_batch(fmd_agc* h, const int16_t* in, size_t n_in, size_t in_cap, int16_t* out, size_t out_cap, size_t* n_out)
 {
-    if (!h || !in || !out || !n_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    if (n_in > in_cap) { fmd_internal_set_err("n_in > in_cap"); return FMD_ERR_CAPACITY; }
-    if (n_in == 0) { *n_out = 0; return FMD_OK; }
-    FmdDdcCore& c = h->core;
-    FMD_DDC_ON_DEVICE(c.device);
-    const size_t row = (size_t)h->width * sizeof(int16_t), in_bytes = h->n_rows * in_cap * row, out_bytes = h->n_rows * out_cap * row;
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
-    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, in, in_bytes, hipMemcpyHostToDevice, c.stream));
-    size_t n = 0;
-    if (const int rc = agc_enqueue(h, c.d_iq, n_in, in_cap, c.d_out, out_cap, &n, c.stream)) {
-        (void)hipStreamSynchronize(c.stream);
-        return rc;
-    }
-    if (n) FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
-    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
-    *n_out = n;
-    return FMD_OK;
+    return fmd_rows_run_batch(h, agc_enqueue, in, n_in, in_cap, out, out_cap, n_out, [](size_t n) { return n == 0; });
 }
 
-int fmd_agc_kernel_name(const fmd_agc* h, char* name, size_t cap)
-{
-    if (!h || !name || cap == 0) return FMD_ERR_INVALID_ARG;
-    return fmd_ddc_name_rc(snprintf(name, cap, h->width == 2 ? "fmd_ag::fmd_agc_kernel<2>" : "fmd_ag::fmd_agc_kernel<1>"), cap);
-}
+int fmd_agc_kernel_name(const fmd_agc* h, char* name, size_t cap) { return fmd_rows_kernel_name(h, name, cap, "fmd_ag::fmd_agc_kernel<%u>"); }
 
 }  // extern "C"

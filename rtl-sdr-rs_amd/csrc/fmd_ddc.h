@@ -1,5 +1,6 @@
 // fmd_ddc.h -- what the matrix-core handles share: the five down-converter banks (fmd_stations.hip, fmd_channelizer.hip,
-// fmd_stereo.hip, fmd_narrow.hip, fmd_rds.hip) and the power-spectrum scanner (fmd_spectrum.hip).
+// fmd_stereo.hip, fmd_narrow.hip, fmd_rds.hip) and the power-spectrum scanner (fmd_spectrum.hip).  The handle core also carries the
+// row processors (fmd_resample.hip, fmd_agc.hip), whose own host layer on top of it is fmd_rows.h.
 //   plan (host):        the NCO table, the complex taps of every row, the matrix-core A fragments and their centring constants;
 //   front end (device): the banks' digital down-converter -- staging of the filter windows and the NCO table in LDS, the
 //                       history write, the contraction on the matrix cores, the rotation back to baseband;
@@ -407,6 +408,20 @@ inline const char* fmd_ddc_upload(FmdDdcCore& c, const FmdDdcPlan& P, size_t his
     return nullptr;
 }
 
+// A constructor's device step: the device, the plan, the history, the stream, and what the handle registered on the core.
+// FMD_OK; the device's refusal with *what == nullptr (nothing was allocated: the caller deletes the handle); or FMD_ERR_HIP and
+// what failed (the caller sets the error text and calls its *_free).
+inline int fmd_ddc_core_device(FmdDdcCore& c, const FmdDdcPlan& P, size_t hist_bytes, const fmd_device_config* dev, const char** what)
+{
+    *what = nullptr;
+    if (const int rc = fmd_ddc_open(c, dev)) return rc;
+    FmdDeviceGuard guard(c.device);
+    if (guard.error() != hipSuccess) *what = "hipSetDevice";
+    if (!*what) *what = fmd_ddc_upload(c, P, hist_bytes);
+    if (!*what && hipDeviceSynchronize() != hipSuccess) *what = "hipDeviceSynchronize";
+    return *what ? FMD_ERR_HIP : FMD_OK;
+}
+
 // Back to position 0 with an all-zero history and all-zero pairs (the caller has synchronised the device).  The position, the
 // buffer index and the stream order change only once the device has finished the memsets, so a failure leaves them as they were.
 inline hipError_t fmd_ddc_zero_history(FmdDdcCore& c)
@@ -509,18 +524,10 @@ inline int fmd_ddc_bank_front(FmdDdcBank& b, const int16_t* taps, uint32_t n_tap
     return FMD_OK;
 }
 
-// The constructor's device step: the device, the plan, the history, the stream, and what the handle registered on the core.
-// FMD_OK; the device's refusal with *what == nullptr (nothing was allocated: the caller deletes the handle); or FMD_ERR_HIP and
-// what failed (the caller sets the error text and calls its *_free).
+// The constructor's device step of a down-converter: fmd_ddc_core_device with the bank's plan and history.
 inline int fmd_ddc_bank_device(FmdDdcBank& b, const fmd_device_config* dev, const char** what)
 {
-    *what = nullptr;
-    if (const int rc = fmd_ddc_open(b.core, dev)) return rc;
-    FmdDeviceGuard guard(b.core.device);
-    if (guard.error() != hipSuccess) *what = "hipSetDevice";
-    if (!*what) *what = fmd_ddc_upload(b.core, b.plan, (size_t)b.S * (b.HB ? b.HB : 16));
-    if (!*what && hipDeviceSynchronize() != hipSuccess) *what = "hipDeviceSynchronize";
-    return *what ? FMD_ERR_HIP : FMD_OK;
+    return fmd_ddc_core_device(b.core, b.plan, (size_t)b.S * (b.HB ? b.HB : 16), dev, what);
 }
 
 namespace fmd_ddc {

@@ -29,8 +29,7 @@
 #include <new>
 #include <vector>
 
-#include "fmd_ddc.h"
-#include "fmd_internal.h"
+#include "fmd_rows.h"
 
 namespace fmd_rs {
 
@@ -190,13 +189,11 @@ __global__ void __launch_bounds__(kThreads) fmd_resample_kernel(const RsLaunch P
 }  // namespace fmd_rs
 
 struct fmd_resample {
-    FmdDdcCore core;                                      // core.pos: input samples per row since creation or reset
-    FmdDdcPair hist;                                      // [n_rows][hcap][width] int16
+    FmdRows rows;                                         // hcap = max(1, T - 1)
     void* d_taps = nullptr;                               // [L][tdw] dwords
-    uint32_t L = 0, M = 0, T = 0, shift = 0, width = 0, n_rows = 0;
-    uint32_t npair = 0, tdw = 0, hcap = 0;
+    uint32_t L = 0, M = 0, T = 0, shift = 0;
+    uint32_t npair = 0, tdw = 0;
     uint32_t tile = 0, plane_len = 0, whole = 0;
-    size_t lds = 0;
 };
 
 namespace {
@@ -223,29 +220,24 @@ void rs_tiling(fmd_resample* h)
         const uint32_t span = (uint32_t)(((uint64_t)(h->tile - 1) * h->M + h->L - 1) / h->L) + h->T;
         h->plane_len = (span + fmd_rs::kPlaneSlack + 7u) & ~7u;
         h->whole = h->L <= h->tile ? 1u : 0u;
-        h->lds = 2ull * h->width * h->plane_len + 4ull * (h->whole ? h->L : h->tile) * h->tdw;
-        if (h->lds <= fmd_rs::kLdsBudget || h->tile == 32) break;
+        h->rows.lds = 2ull * h->rows.width * h->plane_len + 4ull * (h->whole ? h->L : h->tile) * h->tdw;
+        if (h->rows.lds <= fmd_rs::kLdsBudget || h->tile == 32) break;
     }
 }
 
 int rs_enqueue(fmd_resample* h, const void* d_in, size_t n_in, size_t in_cap, void* d_out, size_t out_cap, size_t* n_out, hipStream_t stream)
 {
-    const uintptr_t mask = 2u * h->width - 1u;
-    if (((uintptr_t)d_in & mask) != 0 || ((uintptr_t)d_out & mask) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
-    if (n_in > in_cap) { fmd_internal_set_err("n_in > in_cap"); return FMD_ERR_CAPACITY; }
-    if (n_in > (1ull << 28)) { fmd_internal_set_err("n_in out of range"); return FMD_ERR_UNSUPPORTED; }
-    FmdDdcCore& c = h->core;
-    const uint64_t N0 = c.pos, N1 = N0 + n_in;
+    FmdRows& r = h->rows;
+    if (const int rc = fmd_rows_check_call(r, d_in, n_in, in_cap, d_out)) return rc;
+    const uint64_t N0 = r.core.pos, N1 = N0 + n_in;
     const uint64_t out0 = rs_outputs(h, N0), out1 = rs_outputs(h, N1), cnt = out1 - out0;
     if (cnt < 1) { fmd_internal_set_err("the call completes no output"); return FMD_ERR_TOO_SHORT; }
     if (cnt > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
     const uint64_t ntiles = (cnt + h->tile - 1) / h->tile;
-    if (ntiles * h->n_rows >= (1ull << 31)) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
+    if (ntiles * r.n_rows >= (1ull << 31)) { fmd_internal_set_err("call too large for the grid"); return FMD_ERR_UNSUPPORTED; }
     const uint64_t q0 = out0 * h->M, i0 = q0 / h->L, i1 = out1 * h->M / h->L;   // x[i0]: the first sample of the call's first output
     fmd_rs::RsLaunch P{};
-    P.in = static_cast<const int16_t*>(d_in); P.in_cap = in_cap; P.n_in = (uint32_t)n_in; P.n_rows = h->n_rows;
-    P.hist_in = h->hist.in<int16_t>(c.cur); P.hist_out = h->hist.out<int16_t>(c.cur);
-    P.hcap = h->hcap;
+    fmd_rows_fill(P, r, d_in, n_in, in_cap, d_out, out_cap);
     P.h = N0 > i0 ? (uint32_t)(N0 - i0) : 0u;             // <= T - 1
     P.h_next = N1 > i1 ? (uint32_t)(N1 - i1) : 0u;        // <= T - 1 and <= h + n_in
     P.v_first = N0 > i0 ? 0u : (uint32_t)(i0 - N0);       // (inputs before x[i0] are skipped where M / L > T)
@@ -254,15 +246,8 @@ int rs_enqueue(fmd_resample* h, const void* d_in, size_t n_in, size_t in_cap, vo
     P.L = h->L; P.M = h->M; P.T = h->T; P.shift = h->shift; P.npair = h->npair; P.tdw = h->tdw;
     P.tile = h->tile; P.ntiles = (uint32_t)ntiles; P.plane_len = h->plane_len; P.whole = h->whole;
     P.taps = static_cast<const uint32_t*>(h->d_taps);
-    P.out = static_cast<int16_t*>(d_out); P.out_cap = out_cap;
-    FMD_DDC_TRY(c.order.before(stream));
-    const dim3 grid((uint32_t)(ntiles * h->n_rows));
-    if (h->width == 2) hipLaunchKernelGGL(fmd_rs::fmd_resample_kernel<2>, grid, dim3(fmd_rs::kThreads), h->lds, stream, P);
-    else hipLaunchKernelGGL(fmd_rs::fmd_resample_kernel<1>, grid, dim3(fmd_rs::kThreads), h->lds, stream, P);
-    FMD_DDC_TRY(hipGetLastError());
-    fmd_ddc_commit(c, stream, n_in);
-    if (n_out) *n_out = (size_t)cnt;
-    return FMD_OK;
+    return fmd_rows_launch(r, fmd_rs::fmd_resample_kernel<1>, fmd_rs::fmd_resample_kernel<2>, (uint32_t)(ntiles * r.n_rows), fmd_rs::kThreads, P,
+                           stream, n_in, cnt, n_out);
 }
 
 }  // namespace
@@ -294,14 +279,12 @@ size_t fmd_resample_out_cap(uint32_t L, uint32_t M, size_t n_in)
 int fmd_resample_new(const int16_t* taps, uint32_t L, uint32_t M, uint32_t T, uint32_t shift, uint32_t width,
                      const fmd_device_config* dev, fmd_resample** out)
 {
-    if (!taps || !dev || !out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *out = nullptr;
-    if (width != 1 && width != 2) { fmd_internal_set_err("need width 1 or 2"); return FMD_ERR_UNSUPPORTED; }
+    if (const int rc = fmd_rows_new_args(taps, dev, out, width)) return rc;
     if (const int rc = rs_ratio_ok(L, M)) return rc;
     if (T < 1 || T > 256) { fmd_internal_set_err("need 1 <= T <= 256"); return FMD_ERR_UNSUPPORTED; }
     if ((uint64_t)L * T > 16384) { fmd_internal_set_err("need L T <= 16384"); return FMD_ERR_UNSUPPORTED; }
     if (shift > 24) { fmd_internal_set_err("need shift <= 24"); return FMD_ERR_UNSUPPORTED; }
-    if (dev->n_channels < 1) { fmd_internal_set_err("need n_rows >= 1"); return FMD_ERR_UNSUPPORTED; }
+    if (const int rc = fmd_rows_count_arg(dev)) return rc;
     for (uint32_t p = 0; p < L; ++p) {
         uint32_t s = 0;
         for (uint32_t t = 0; t < T; ++t) { const int v = taps[(size_t)p * T + t]; s += (uint32_t)(v < 0 ? -v : v); }
@@ -309,89 +292,36 @@ int fmd_resample_new(const int16_t* taps, uint32_t L, uint32_t M, uint32_t T, ui
     }
     fmd_resample* h = new (std::nothrow) fmd_resample();
     if (!h) return FMD_ERR_NOMEM;
-    h->L = L; h->M = M; h->T = T; h->shift = shift; h->width = width; h->n_rows = dev->n_channels;
+    h->L = L; h->M = M; h->T = T; h->shift = shift;
     h->npair = (T + 1) / 2; h->tdw = h->npair | 1u;
-    h->hcap = T > 1 ? T - 1 : 1;
+    h->rows.width = width; h->rows.n_rows = dev->n_channels; h->rows.hcap = T > 1 ? T - 1 : 1;
     rs_tiling(h);
     std::vector<uint32_t> gp((size_t)L * h->tdw, 0u);        // (g[2 d], g[2 d + 1]), zero taps behind T
     for (uint32_t p = 0; p < L; ++p)
         for (uint32_t t = 0; t < T; ++t)
             gp[(size_t)p * h->tdw + t / 2] |= (uint32_t)(uint16_t)taps[(size_t)p * T + t] << (16 * (t & 1u));
-    fmd_ddc_add_pair(h->core, h->hist, (size_t)h->n_rows * h->hcap * width * sizeof(int16_t));
-    fmd_ddc_add_owned(h->core, h->d_taps, gp.data(), gp.size() * sizeof(uint32_t));
-
-    if (const int rc = fmd_ddc_open(h->core, dev)) { delete h; return rc; }
-    const char* what = nullptr;
-    {
-        FmdDeviceGuard guard(h->core.device);
-        if (guard.error() != hipSuccess) what = "hipSetDevice";
-        if (!what) what = fmd_ddc_upload(h->core, FmdDdcPlan(), 16);   // (an empty plan: the history is the pair, the taps an owned constant)
-        if (!what && hipDeviceSynchronize() != hipSuccess) what = "hipDeviceSynchronize";
-    }
-    if (what) { fmd_internal_set_err(what); fmd_resample_free(h); return FMD_ERR_HIP; }
-    *out = h;
-    return FMD_OK;
+    fmd_ddc_add_owned(h->rows.core, h->d_taps, gp.data(), gp.size() * sizeof(uint32_t));
+    return fmd_rows_device(h, dev, fmd_resample_free, out);
 }
 
-void fmd_resample_free(fmd_resample* h)
-{
-    if (!h) return;
-    fmd_ddc_free(h->core);
-    delete h;
-}
-
-int fmd_resample_reset(fmd_resample* h)
-{
-    if (!h) return FMD_ERR_INVALID_ARG;
-    return fmd_ddc_reset(h->core);
-}
-
-int fmd_resample_check(fmd_resample* h)
-{
-    if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    return fmd_ddc_check(h->core);
-}
-
-int fmd_resample_outputs(const fmd_resample* h, uint64_t* inputs, uint64_t* outputs)
-{
-    if (!h || !inputs || !outputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *inputs = h->core.pos;
-    *outputs = rs_outputs(h, h->core.pos);
-    return FMD_OK;
-}
+void fmd_resample_free(fmd_resample* h) { fmd_rows_free(h); }
+int fmd_resample_reset(fmd_resample* h) { return fmd_rows_reset(h); }
+int fmd_resample_check(fmd_resample* h) { return fmd_rows_check(h); }
+int fmd_resample_outputs(const fmd_resample* h, uint64_t* inputs, uint64_t* outputs) { return fmd_rows_outputs(h, inputs, outputs, rs_outputs); }
 
 int fmd_resample_run_device(fmd_resample* h, const void* d_in, size_t n_in, size_t in_cap, void* d_out, size_t out_cap, size_t* n_out,
                             void* stream)
 {
-    return fmd_ddc_run_device(h ? &h->core : nullptr, d_in, d_out,
+    return fmd_ddc_run_device(h ? &h->rows.core : nullptr, d_in, d_out,
                               [&] { return rs_enqueue(h, d_in, n_in, in_cap, d_out, out_cap, n_out, static_cast<hipStream_t>(stream)); });
 }
 
+// (a call of no samples completes no output: rs_enqueue refuses it like every other such call)
 int fmd_resample_run_batch(fmd_resample* h, const int16_t* in, size_t n_in, size_t in_cap, int16_t* out, size_t out_cap, size_t* n_out)
 {
-    if (!h || !in || !out || !n_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    if (n_in > in_cap) { fmd_internal_set_err("n_in > in_cap"); return FMD_ERR_CAPACITY; }
-    FmdDdcCore& c = h->core;
-    FMD_DDC_ON_DEVICE(c.device);
-    const size_t row = (size_t)h->width * sizeof(int16_t), in_bytes = h->n_rows * in_cap * row, out_bytes = h->n_rows * out_cap * row;
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
-    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, in, in_bytes, hipMemcpyHostToDevice, c.stream));
-    size_t n = 0;
-    if (const int rc = rs_enqueue(h, c.d_iq, n_in, in_cap, c.d_out, out_cap, &n, c.stream)) {
-        (void)hipStreamSynchronize(c.stream);
-        return rc;
-    }
-    FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
-    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
-    *n_out = n;
-    return FMD_OK;
+    return fmd_rows_run_batch(h, rs_enqueue, in, n_in, in_cap, out, out_cap, n_out, [](size_t) { return false; });
 }
 
-int fmd_resample_kernel_name(const fmd_resample* h, char* name, size_t cap)
-{
-    if (!h || !name || cap == 0) return FMD_ERR_INVALID_ARG;
-    return fmd_ddc_name_rc(snprintf(name, cap, h->width == 2 ? "fmd_rs::fmd_resample_kernel<2>" : "fmd_rs::fmd_resample_kernel<1>"), cap);
-}
+int fmd_resample_kernel_name(const fmd_resample* h, char* name, size_t cap) { return fmd_rows_kernel_name(h, name, cap, "fmd_rs::fmd_resample_kernel<%u>"); }
 
 }  // extern "C"

@@ -16,14 +16,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <vector>
 
 #include "demod.hpp"
-
-struct CloseFile { void operator()(FILE* f) const { if (f != stdin) fclose(f); } };
-using File = std::unique_ptr<FILE, CloseFile>;
 
 static const char* const kUsage =
     "usage: %s -i rate_in[/den] -r rate_out [-c 1|2] [-T taps_per_phase] <in.s16 | ->\n"
@@ -31,28 +27,23 @@ static const char* const kUsage =
 
 static int run(const char* path, uint64_t num, uint64_t den, uint64_t rate_out, uint32_t width, uint32_t T)
 {
-    File in(strcmp(path, "-") ? fopen(path, "rb") : stdin);
+    fm::File in(strcmp(path, "-") ? fopen(path, "rb") : stdin);
     if (!in) { perror(path); return 2; }
     const std::pair<uint32_t, uint32_t> lm = fm::resample_ratio(num, den, rate_out);
     const auto g = fm::resample_taps(lm.first, lm.second, T);
     fm::Resampler rs(g.first, lm.first, lm.second, g.second, 1, width);
     fprintf(stderr, "resample: L / M = %u / %u, %u taps per phase, shift %u, %u int16 per sample\n", lm.first, lm.second, T, g.second, width);
-    const size_t block = 65536, sample = width * sizeof(int16_t);
     std::vector<int16_t> buf;
     size_t held = 0;                                         // samples kept from blocks that completed no output
     for (;;) {
-        buf.resize((held + block) * width);
-        uint8_t* const dst = reinterpret_cast<uint8_t*>(buf.data() + held * width);
-        size_t fill = 0, got;
-        while (fill < block * sample && (got = fread(dst + fill, 1, block * sample - fill, in.get())) > 0) fill += got;
-        if (fill % sample) fprintf(stderr, "dropped %zu trailing bytes\n", fill % sample);
-        const size_t n = held + fill / sample;
-        if (n > held) {
+        buf.resize((held + fm::kReadSamples) * width);
+        const size_t got = fm::read_samples(in.get(), buf.data() + held * width, width), n = held + got;
+        if (got) {
             const fm::Rows rows = rs.run(buf.data(), n);
             if (rows[0].empty()) held = n;
             else { fm::output(rows[0]); held = 0; }
         }
-        if (fill < block * sample) break;
+        if (got < fm::kReadSamples) break;
     }
     return 0;
 }
@@ -81,10 +72,5 @@ int main(int argc, char** argv)
     if (width != 1 && width != 2) { fprintf(stderr, "bad -c: need 1 or 2\n"); return 2; }
     if (T < 1 || T > 256) { fprintf(stderr, "bad -T: need 1 ... 256\n"); return 2; }
     if (paths.empty()) { fprintf(stderr, "missing input file (use - for stdin)\n"); return 2; }
-    try {                                                    // an fm::Error is its message on stderr and exit code 1
-        return run(paths[0], num, den, rate_out, width, T);
-    } catch (const fm::Error& e) {
-        fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
+    return fm::exit_code([&] { return run(paths[0], num, den, rate_out, width, T); });
 }

@@ -7,7 +7,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from ._ffi import BankHandle, DeviceConfig, check, lib
+from ._ffi import DeviceConfig, RowProcessor, bank_rows, check, lib
 
 
 def _fraction(rate):
@@ -71,7 +71,7 @@ def resample_taps(L, M, T, cutoff=0.45):
     raise ValueError("no shift keeps every phase's sum |g| <= 32767")
 
 
-class Resampler(BankHandle):
+class Resampler(RowProcessor):
     """`taps` is int16 [L, T] (phase-major), `n_rows` the rows of the bank whose output it takes (n_streams x stations or channels),
     `width` 1 or 2 int16 per sample.  run_batch takes [n_rows, n_in, width] (or [n_rows, n_in] at width 1) on the host;
     run_device takes a bank's d_out as it stands, with the bank's out_cap as in_cap."""
@@ -90,38 +90,6 @@ class Resampler(BankHandle):
 
     def out_cap(self, n_in):
         return int(lib().fmd_resample_out_cap(self.L, self.M, n_in))
-
-    def counts(self):
-        """(inputs, outputs) per row since creation or reset."""
-        i, o = C.c_uint64(0), C.c_uint64(0)
-        check(self._fn("outputs")(self._h, C.byref(i), C.byref(o)))
-        return i.value, o.value
-
-    def outputs(self):
-        return self.counts()[1]
-
-    def run_batch(self, x):
-        """x int16 [n_rows, n_in, width] ([n_rows, n_in] at width 1) -> int16 of the same form with n_out outputs per row."""
-        x = np.ascontiguousarray(x, dtype=np.int16)
-        flat = x.ndim == 2 and self.width == 1
-        if flat:
-            x = x[:, :, None]
-        if x.ndim != 3 or x.shape[0] != self.n_rows or x.shape[2] != self.width:
-            raise ValueError("x must be [n_rows, n_in, width]")
-        cap = max(1, self.out_cap(x.shape[1]))
-        out = np.empty((self.n_rows, cap, self.width), dtype=np.int16)
-        n = C.c_size_t(0)
-        check(self._fn("run_batch")(self._h, x.ctypes.data, x.shape[1], x.shape[1], out.ctypes.data, cap, C.byref(n)))
-        out = out[:, :n.value].copy()
-        return out[:, :, 0] if flat else out
-
-    def run_device(self, d_in, n_in, in_cap, d_out, out_cap, stream=None):
-        """Enqueue on device pointers (d_in [n_rows][in_cap][width], the first n_in samples of each row valid; d_out
-        [n_rows][out_cap][width]); returns the outputs per row.  `stream` must stay alive until the handle's next `run_device` call
-        or `check` has returned (include/fmd.h)."""
-        n = C.c_size_t(0)
-        check(self._fn("run_device")(self._h, d_in, n_in, in_cap, d_out, out_cap, C.byref(n), stream))
-        return n.value
 
 
 def bank_rate(bank, capture_rate=None):
@@ -143,5 +111,5 @@ def fixed_rate(bank, rate_out, taps_per_phase=32, capture_rate=None, device_id=-
     `rate_out` Hz with resample_taps(L, M, taps_per_phase)."""
     L, M = resample_ratio(bank_rate(bank, capture_rate), rate_out)
     g, shift = resample_taps(L, M, taps_per_phase)
-    rows = bank.n_streams * getattr(bank, getattr(bank, "_rows", "n_stations"))
-    return Resampler(g, L, M, shift, n_rows=rows, width=bank.width if hasattr(bank, "width") else 2, device_id=device_id)
+    rows, width = bank_rows(bank)
+    return Resampler(g, L, M, shift, n_rows=rows, width=width, device_id=device_id)

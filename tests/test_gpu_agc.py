@@ -2,7 +2,8 @@
 at both widths and P in {16, 256, 4096}, unaligned rows and odd capacities, call cuts around block edges, calls that complete no
 block, one call of more blocks than an LDS segment holds, full-scale values and zero runs over the configuration's corners, the gain
 read-out, refused calls, reset, a caller's stream, two handles, and composed with the narrow-band bank, the stereo bank, the resampler
-and the command-line tool.  Everything but the tool runs in this process."""
+and the command-line tool; and, for the resampler as well, which check answers a call that two of them refuse.  Everything but the
+tool runs in this process."""
 import os
 import subprocess
 
@@ -12,6 +13,7 @@ import pytest
 import agc_ref as ar
 import narrow_ref as nr
 import resample_ref as rr
+from rows_gpu import SENT, call as _call, iq_bytes
 import stations_ref as sr
 import stereo_ref as st
 
@@ -19,32 +21,12 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAPACITY = -5
-SENT = -12345
 
 
 def _agc(fmd, cfg, rows, width):
     cfg = ar.Cfg(*cfg)
     return fmd.Agc(n_rows=rows, width=width, target=cfg.target, block=cfg.block, hang=cfg.hang, decay=cfg.decay, gain_max=cfg.gain_max,
                    device_id=0)
-
-
-def _call(ag, x, in_cap=None, out_pad=2, stream=None):
-    """One run_device call over x [rows, n_in, width] in a device buffer of `in_cap` samples per row, into an odd out_cap; the
-    outputs [rows, n_out, width].  Nothing beyond them is written.  FmdError when the call is refused."""
-    import torch
-    rows, n_in, W = x.shape
-    in_cap = n_in if in_cap is None else in_cap
-    buf = np.full((rows, max(1, in_cap), W), 12321, np.int16)
-    buf[:, :n_in] = x
-    d_in = torch.from_numpy(buf).cuda()
-    cap = (ag.out_cap(n_in) + out_pad) | 1
-    d_out = torch.full((rows, cap, W), SENT, dtype=torch.int16, device="cuda")
-    torch.cuda.synchronize()
-    n = ag.run_device(d_in.data_ptr(), n_in, in_cap, d_out.data_ptr(), cap, stream)
-    ag.check()
-    got = d_out.cpu().numpy()
-    assert (got[:, n:] == SENT).all()
-    return got[:, :n]
 
 
 def _odd(n):
@@ -218,14 +200,6 @@ def test_reset_a_callers_stream_and_two_handles(fmd):
     assert b.counts() == (2048, ar.outputs(2048, 16))
 
 
-def _iq_bytes(rng, S, n):
-    b = rng.integers(0, 256, (S, n), dtype=np.uint8)
-    b[:, : n // 3] = np.where(rng.random((S, n // 3)) < 0.5, 0, 255)
-    q = slice(n // 2, n // 2 + n // 4)
-    b[:, q] = rng.integers(120, 136, (S, b[:, q].shape[1]), dtype=np.uint8)
-    return b
-
-
 def test_narrow_bank_am_into_leveled_on_device_buffers(fmd):
     """The narrow-band bank in AM mode at gain = 256 (w as it is): its d_out, as it stands and with its out_cap as in_cap, through
     leveled(bank) equals the definition over narrow_ref, call by call."""
@@ -243,7 +217,7 @@ def test_narrow_bank_am_into_leveled_on_device_buffers(fmd):
     ref = ar.Agc(ar.Cfg(64, 10000, 262144, 2, 64))
     total = 0
     for n in (8 * 2403, 8 * 1001, 8 * 9000):
-        data = _iq_bytes(rng, S, n)
+        data = iq_bytes(rng, S, n, quiet=True)
         cap = nb.out_cap(n) + 3
         d_audio = torch.full((S, K, cap), SENT, dtype=torch.int16, device="cuda")
         out_cap = ag.out_cap(cap) | 1
@@ -280,7 +254,7 @@ def test_stereo_bank_into_agc_into_resampler_on_device_buffers(fmd):
     rs = fmd.Resampler(taps, 15, 16, shift, n_rows=S * K, width=2, device_id=0)
     rref = rr.Resampler(taps, 15, 16, shift)
     for n in (8 * 1500, 8 * 701):
-        data = _iq_bytes(rng, S, n)
+        data = iq_bytes(rng, S, n, quiet=True)
         cap = sb.out_cap(n) + 1
         d_audio = torch.full((S, K, cap, 2), SENT, dtype=torch.int16, device="cuda")
         lev_cap = ag.out_cap(cap) | 1
@@ -322,3 +296,52 @@ def test_the_tool_levels_a_file_to_its_own_length(fmd, width, tmp_path):
     assert p.returncode == 0, p.stderr.decode()
     short = np.concatenate([x[:, :1000], np.zeros((1, 2 * P, width), np.int16)], axis=1)
     assert p.stdout == ar.agc_all(short, ar.Cfg(P, 9000, 131072, 2, 128))[0, :1000].tobytes()
+
+
+INVALID_ARG, TOO_SHORT, UNSUPPORTED = -1, -3, -6
+BIG = (1 << 28) + 1
+# (handle, byte offset of d_in, n_in, in_cap, out_cap, status, text): calls over buffers of 2 x 80 samples that two checks refuse, or
+# that lie at the edge of one
+REFUSALS = [(k,) + c for k in ("resample", "agc") for c in [
+    (2, 81, 80, 80, INVALID_ARG, "misaligned device buffer"),
+    (0, 81, 80, 0, CAPACITY, "n_in > in_cap"),
+    (0, BIG, BIG, 0, UNSUPPORTED, "n_in out of range"),      # (out_cap 0: whatever the order of the checks, nothing is launched)
+]] + [
+    ("resample", 0, 63, 62, 80, CAPACITY, "n_in > in_cap"),  # not too-short
+    ("resample", 0, 63, 63, 0, TOO_SHORT, "completes no output"),
+    ("resample", None, 0, 0, 0, TOO_SHORT, ""),              # run_batch of zero samples
+    ("agc", 0, 0, 80, 0, 0, ""),                             # nothing to take: accepted, returns 0
+]
+
+
+@pytest.mark.parametrize("kind,off,n_in,in_cap,out_cap,status,text", REFUSALS,
+                         ids=["%s-%s-%d-%d-%d" % (c[0], c[1], c[2] if c[2] < BIG else -1, c[3] if c[3] < BIG else -1, c[4]) for c in REFUSALS])
+def test_the_order_of_refusals_and_what_they_leave(fmd, kind, off, n_in, in_cap, out_cap, status, text):
+    """3 / 16 at T = 64 and an AGC of P = 16, 2 rows of width 2, fresh: where two checks refuse a call the first one answers -- the
+    alignment, then n_in > in_cap, then the range of n_in, then what the call completes and out_cap -- and a refused call takes
+    nothing and writes nothing."""
+    import torch
+    if kind == "resample":
+        g = np.zeros((3, 64), np.int16)
+        g[:, 0] = 16384
+        h = fmd.Resampler(g, 3, 16, 14, n_rows=2, width=2, device_id=0)
+    else:
+        h = _agc(fmd, (16, 12000, 65536, 4, 32), 2, 2)
+    d_in = torch.full((2, 80, 2), SENT, dtype=torch.int16, device="cuda")
+    d_out = torch.full((2, 80, 2), SENT, dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+    before = h.counts()
+
+    def run():
+        if off is None:
+            return h.run_batch(np.zeros((2, 0, 2), np.int16)).shape[1]
+        return h.run_device(d_in.data_ptr() + off, n_in, in_cap, d_out.data_ptr(), out_cap)
+    if status == 0:
+        assert run() == 0
+    else:
+        with pytest.raises(fmd.FmdError) as e:
+            run()
+        assert e.value.status == status and text in str(e.value), str(e.value)
+    assert h.counts() == before == (0, 0)
+    h.check()
+    assert (d_out.cpu().numpy() == SENT).all() and (d_in.cpu().numpy() == SENT).all()

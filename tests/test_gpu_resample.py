@@ -2,6 +2,7 @@
 (tests/resample_ref.py) over the issue's ratios at both widths, unaligned rows and odd capacities, tile edges, call cuts, the
 skip-ahead path, refused calls, saturation, reset, a caller's stream, two handles, and composed with the stereo bank, the
 channelizer and the command-line tool.  Everything but the tool runs in this process."""
+import functools
 import os
 import subprocess
 
@@ -10,6 +11,7 @@ import pytest
 
 import channelizer_ref as cr
 import resample_ref as rr
+from rows_gpu import SENT, call, iq_bytes
 import stations_ref as sr
 import stereo_ref as st
 
@@ -17,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOO_SHORT, CAPACITY = -3, -5
-SENT = -12345
+_call = functools.partial(call, out_pad=3)
 
 # (L, M, T, samples per row): the issue's shapes; the sample counts give more than one tile of 256 outputs wherever 6000 inputs can
 SHAPES = [(1, 1, 1, 1500), (1, 1, 256, 2000), (15, 16, 32, 3000), (3, 16, 64, 6000), (441, 512, 24, 3000), (160, 147, 48, 2500),
@@ -31,25 +33,6 @@ def _taps(rng, L, T, mag=32767):
     g[p, 0] += (mag - np.abs(g[p]).sum()) * (1 if g[p, 0] >= 0 else -1)
     assert np.abs(g).sum(axis=1).max() == mag
     return g.astype(np.int16)
-
-
-def _call(fmd, rs, x, in_cap=None, out_pad=3, stream=None):
-    """One run_device call over x [rows, n_in, width] in a device buffer of `in_cap` samples per row, into an odd out_cap; the
-    outputs [rows, n_out, width].  Nothing beyond them is written.  FmdError when the call is refused."""
-    import torch
-    rows, n_in, W = x.shape
-    in_cap = n_in if in_cap is None else in_cap
-    buf = np.full((rows, in_cap, W), 12321, np.int16)
-    buf[:, :n_in] = x
-    d_in = torch.from_numpy(buf).cuda()
-    cap = (rs.out_cap(n_in) + out_pad) | 1
-    d_out = torch.full((rows, cap, W), SENT, dtype=torch.int16, device="cuda")
-    torch.cuda.synchronize()
-    n = rs.run_device(d_in.data_ptr(), n_in, in_cap, d_out.data_ptr(), cap, stream)
-    rs.check()
-    got = d_out.cpu().numpy()
-    assert (got[:, n:] == SENT).all()
-    return got[:, :n]
 
 
 def _feed(fmd, rs, ref, x, cuts, odd_caps=True):
@@ -67,10 +50,10 @@ def _feed(fmd, rs, ref, x, cuts, odd_caps=True):
         except rr.TooShort:
             before = rs.counts()
             with pytest.raises(fmd.FmdError) as e:
-                _call(fmd, rs, piece, in_cap)
+                _call(rs, piece, in_cap)
             assert e.value.status == TOO_SHORT and rs.counts() == before
             continue
-        got = _call(fmd, rs, piece, in_cap)
+        got = _call(rs, piece, in_cap)
         assert got.shape == exp.shape and np.array_equal(got, exp), (lo, pos)
         assert rs.counts() == (ref.N, rr.outputs(ref.N, ref.L, ref.M, ref.T))
         out.append(got)
@@ -93,7 +76,7 @@ def test_definition_parity_cut_and_uncut(fmd, L, M, T, N, width):
     got = _feed(fmd, rs, rr.Resampler(g, L, M, shift), x, [7, 1000, 333])
     assert np.array_equal(got, whole)
     one = fmd.Resampler(g, L, M, shift, n_rows=1, width=width, device_id=0)
-    assert np.array_equal(_call(fmd, one, x[:1], in_cap=N + 1), whole[:1])
+    assert np.array_equal(_call(one, x[:1], in_cap=N + 1), whole[:1])
 
 
 @pytest.mark.parametrize("width", [1, 2])
@@ -128,9 +111,9 @@ def test_calls_that_end_at_a_tiles_last_input(fmd, width):
         for n in (303, 304, 305, 576, 577, 578):
             outs = rr.outputs(n, L, M, T)
             rs = fmd.Resampler(g, L, M, shift, n_rows=rows, width=width, device_id=0)
-            got = _call(fmd, rs, xs[:, :n], in_cap=n + 1 + n % 2)
+            got = _call(rs, xs[:, :n], in_cap=n + 1 + n % 2)
             assert got.shape[1] == outs and all(np.array_equal(got[r], whole[0, :outs]) for r in range(rows)), (rows, n)
-            got = _call(fmd, rs, xs[:, n:1200])                  # the rest, with the history of a call that ended there
+            got = _call(rs, xs[:, n:1200])                  # the rest, with the history of a call that ended there
             assert all(np.array_equal(got[r], whole[0, outs:]) for r in range(rows)), (rows, n)
 
 
@@ -159,11 +142,11 @@ def test_refused_calls_change_nothing_and_write_nothing(fmd):
     whole = rr.resample_all(x, g, L, M, 15)
     rs = fmd.Resampler(g, L, M, 15, n_rows=2, width=2, device_id=0)
     with pytest.raises(fmd.FmdError) as e:                  # 63 samples complete nothing
-        _call(fmd, rs, x[:, :63])
+        _call(rs, x[:, :63])
     assert e.value.status == TOO_SHORT and rs.counts() == (0, 0)
-    first = _call(fmd, rs, x[:, :700])
+    first = _call(rs, x[:, :700])
     with pytest.raises(fmd.FmdError) as e:                  # nor do 2 more
-        _call(fmd, rs, x[:, 700:702])
+        _call(rs, x[:, 700:702])
     assert e.value.status == TOO_SHORT and rs.counts() == (700, first.shape[1])
     d_in = torch.from_numpy(x[:, 700:]).cuda()
     d_out = torch.full((2, 400, 2), SENT, dtype=torch.int16, device="cuda")
@@ -177,7 +160,7 @@ def test_refused_calls_change_nothing_and_write_nothing(fmd):
     assert e.value.status == -1 and rs.counts() == before
     rs.check()
     assert (d_out.cpu().numpy() == SENT).all()
-    rest = _call(fmd, rs, x[:, 700:])                        # the next call equals the uncut one
+    rest = _call(rs, x[:, 700:])                        # the next call equals the uncut one
     assert np.array_equal(np.concatenate([first, rest], axis=1), whole)
 
 
@@ -192,9 +175,9 @@ def test_full_scale_input_saturates(fmd, shift):
     exp = rr.resample_all(x, g, 3, 2, shift)
     assert (exp == 32767).any() and (exp == -32768).any() and ((exp > -32768) & (exp < 32767)).any()
     rs = fmd.Resampler(g, 3, 2, shift, n_rows=2, width=2, device_id=0)
-    assert np.array_equal(_call(fmd, rs, x), exp)
+    assert np.array_equal(_call(rs, x), exp)
     mono = fmd.Resampler(g, 3, 2, shift, n_rows=2, width=1, device_id=0)
-    assert np.array_equal(_call(fmd, mono, x[:, :, :1], in_cap=1501), exp[:, :, :1])
+    assert np.array_equal(_call(mono, x[:, :, :1], in_cap=1501), exp[:, :, :1])
 
 
 def test_reset_a_callers_stream_and_two_handles(fmd):
@@ -209,20 +192,14 @@ def test_reset_a_callers_stream_and_two_handles(fmd):
     stream = torch.cuda.Stream()
     first = None
     for lo, hi in ((0, 500), (500, 501), (501, 1500)):      # the two handles interleaved, a on the caller's stream, b on the default one
-        ya = _call(fmd, a, xa[:, lo:hi], stream=stream.cuda_stream)
-        yb = _call(fmd, b, xb[:, 2 * lo:2 * hi], in_cap=2 * (hi - lo) + 1)
+        ya = _call(a, xa[:, lo:hi], stream=stream.cuda_stream)
+        yb = _call(b, xb[:, 2 * lo:2 * hi], in_cap=2 * (hi - lo) + 1)
         assert np.array_equal(ya, ra.push(xa[:, lo:hi])) and np.array_equal(yb, rb.push(xb[:, 2 * lo:2 * hi]))
         first = ya if first is None else first
     a.reset()
     assert a.counts() == (0, 0)
-    assert np.array_equal(_call(fmd, a, xa[:, :500]), first)   # reset reproduces the first call
+    assert np.array_equal(_call(a, xa[:, :500]), first)   # reset reproduces the first call
     assert b.counts() == (3000, rr.outputs(3000, 3, 16, 64))
-
-
-def _iq_bytes(rng, S, n):
-    b = rng.integers(0, 256, (S, n), dtype=np.uint8)
-    b[:, : n // 3] = np.where(rng.random((S, n // 3)) < 0.5, 0, 255)
-    return b
 
 
 def test_stereo_bank_into_fixed_rate_on_device_buffers(fmd):
@@ -241,7 +218,7 @@ def test_stereo_bank_into_fixed_rate_on_device_buffers(fmd):
     assert (rs.L, rs.M, rs.T, rs.n_rows, rs.width) == (3, 8, 32, S * K, 2) and fmd.bank_rate(sb) == 128000
     ref = rr.Resampler(rs.taps, rs.L, rs.M, rs.shift)
     for n in (8 * 1500, 8 * 701):
-        data = _iq_bytes(rng, S, n)
+        data = iq_bytes(rng, S, n)
         cap = sb.out_cap(n) + 1
         d_audio = torch.full((S, K, cap, 2), SENT, dtype=torch.int16, device="cuda")
         out_cap = rs.out_cap(cap) | 1
@@ -272,7 +249,7 @@ def test_channelizer_into_a_width_2_resampler_and_the_tool(fmd, tmp_path):
     ref = rr.Resampler(g, 15, 16, shift)
     rows, outs = [], []
     for n in (8 * 2500, 8 * 1203):
-        data = _iq_bytes(rng, S, n)
+        data = iq_bytes(rng, S, n)
         cap = ch.out_cap(n) + 3
         d_y = torch.full((S, K, cap, 2), SENT, dtype=torch.int16, device="cuda")
         out_cap = rs.out_cap(cap)
