@@ -871,6 +871,81 @@ int fmd_agc_gain(fmd_agc *a, uint32_t row, uint32_t *gain, uint32_t *hang);
 /* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_agc_kernel_name(const fmd_agc *a, char *name, size_t cap);
 
+/* ---- tone squelch: any bank's NFM rows gated by a sub-audible tone (CTCSS) --------------------------------------- */
+/* NEW SURFACE (the reference has no tone decoder).  Every int16 row a bank leaves on the device is correlated, block by block,
+ * against a table of up to 64 windowed reference tones, and gated by the tone that the blocks before decided on -- the first link of
+ * the output chain bank -> tone squelch -> AGC -> resampler; a row is one (stream, channel), `width` int16 per sample: 1 for mono
+ * audio, 2 for interleaved (L, R), whose mean is correlated and whose components share the gate.  Definition (integers only, exact;
+ * tests/tonesq_ref.py), per row, with P = block and i the sample index since creation or reset:
+ *   x[i][c]     int16 input, c < width
+ *   m[i]        = x[i][0]                         (width 1)
+ *               = (x[i][0] + x[i][1]) >> 1        (width 2; arithmetic shift)
+ *   tab[f][r]   = (c_f[r], s_f[r])   int16 pairs, f < F tones, r < P, every |entry| <= 1023
+ *   block j     = samples with floor(i / P) = j,  r = i mod P
+ *   Re_f(j)     = sum_r c_f[r] m[jP + r]          Im_f(j) = sum_r s_f[r] m[jP + r]      (exact; |.| <= 2^38)
+ *   A_f = Re_f >> 14,  B_f = Im_f >> 14           (arithmetic shift: floor)
+ *   W_f         = A_f^2 + B_f^2                   (u64, < 2^50)
+ *   f*          = the smallest f with W_f maximal
+ *   rest        = max W_f over |f - f*| > guard   (0 if there is none)
+ *   hit_j       = f*  if W_f* >= min_power and (W_f* >> dom_shift) >= rest,  else NONE
+ * State per row (t, cand, cnt, h, s_prev, s_cur), starting at (NONE, NONE, 0, 0, 0, 0), stepped once per completed block j:
+ *   hit != NONE:  if hit == cand: cnt = min(cnt + 1, 65535)   else: cand = hit, cnt = 1
+ *   hit == NONE:  cand = NONE, cnt = 0
+ *   then:         cnt >= confirm:  t = cand, h = hang
+ *                 else if h > 0:   h = h - 1
+ *                 else:            t = NONE
+ *   s_j  = 256 if t != NONE and bit t of accept is set, else 0
+ * With s_{-1} = s_{-2} = 0 the gate on block j uses the decisions up to block j - 1: causal, no look-ahead, no added latency:
+ *   Q = ramp (a power of two <= P)
+ *   g[i]      = s_{j-2} + (((s_{j-1} - s_{j-2}) (min(r, Q - 1) + 1)) >> log2 Q)
+ *   out[i][c] = (x[i][c] g[i]) >> 8
+ * An open gate passes x bit for bit, a closed gate writes zeros.
+ * Why |entry| <= 1023: a run of 64 samples gives at most 64 * 32768 * 1023 = 2 145 386 496 < 2^31, so any grouping of at most 64
+ * products sums exactly in i32 (v_dot2_i32_i16) before it goes to an i64 sum; the definition does not depend on the grouping.
+ * Counts and state: every call returns n_out = n_in and fmd_tonesq_out_cap(n_in) = n_in; the handle carries no samples, only the
+ * 2 F partial sums (i64) and the small state per row.  core.pos is the one counter; the rows layer's history is unused.
+ * Cut independence: partial sums of exact integers are associative, so the output and every report are independent of how the
+ * stream is cut into calls, calls of one sample and calls that span several block ends included.
+ * Reset: all-zero state is "closed, nothing carried" (t and cand are stored as t + 1, cand + 1).
+ * n_in == 0 is FMD_OK, launches nothing and changes nothing.  n_in > in_cap or out_cap < n_in -> FMD_ERR_CAPACITY (nothing is
+ * written or taken).  d_out == d_in is allowed when out_cap == in_cap (the gate in place); any other overlap is the caller's error.
+ * Domain (else FMD_ERR_UNSUPPORTED with a text, decided before a device is queried): width 1 or 2; block a power of two in
+ * [64, 8192]; 1 <= n_tones <= 64; n_tones * block <= 262144; every table entry in [-1023, 1023]; guard <= 63; dom_shift <= 32;
+ * min_power >= 1 (a silent block is never a hit); 1 <= confirm <= 255; hang <= 65535; ramp a power of two in [1, block];
+ * n_rows = dev->n_channels >= 1.  Stream lifetime and completion points: as fmd_channelizer_* (fmd_tonesq_check). */
+typedef struct fmd_tonesq fmd_tonesq;
+typedef struct fmd_tonesq_config {
+    uint32_t block;      /* P: samples per decision block                                      */
+    uint32_t guard;      /* tones next to f* that do not count as `rest`                       */
+    uint32_t dom_shift;  /* f* must exceed the rest by 2^dom_shift                             */
+    uint32_t confirm;    /* equal hits in a row that open                                      */
+    uint32_t hang;       /* blocks the tone is held after the last confirmed one               */
+    uint32_t ramp;       /* Q: samples over which the gate moves at the start of a block       */
+    uint64_t min_power;  /* the least W_f* of a hit                                            */
+    uint64_t accept;     /* bit f: tone f opens the gate                                       */
+} fmd_tonesq_config;
+/* table: [n_tones][block][2] int16, (c_f[r], s_f[r]). */
+int fmd_tonesq_new(const fmd_tonesq_config *cfg, const int16_t *table, uint32_t n_tones, uint32_t width,
+                   const fmd_device_config *dev, fmd_tonesq **out);
+void fmd_tonesq_free(fmd_tonesq *t);
+int fmd_tonesq_reset(fmd_tonesq *t);
+/* n_in. */
+size_t fmd_tonesq_out_cap(size_t n_in);
+/* HOST buffers: in [n_rows][in_cap][width], the first n_in samples of each row valid; out [n_rows][out_cap][width]; *n_out = n_in. */
+int fmd_tonesq_run_batch(fmd_tonesq *t, const int16_t *in, size_t n_in, size_t in_cap, int16_t *out, size_t out_cap, size_t *n_out);
+/* DEVICE buffers, enqueued on `stream` without synchronising: d_in is a bank's d_out as it stands, with the bank's out_cap as
+ * in_cap; pointers 4-byte aligned at width 2 and 2-byte aligned at width 1, any in_cap and out_cap. */
+int fmd_tonesq_run_device(fmd_tonesq *t, const void *d_in, size_t n_in, size_t in_cap, void *d_out, size_t out_cap, size_t *n_out,
+                          void *stream);
+int fmd_tonesq_check(fmd_tonesq *t);
+/* Samples taken and produced per row since creation or the last reset (the same number). */
+int fmd_tonesq_outputs(const fmd_tonesq *t, uint64_t *inputs, uint64_t *outputs);
+/* Host arrays [n_rows], after the last completed block: tone = t (-1: NONE), power = W_f* of that block, open = s_j != 0; -1 / 0 /
+ * 0 before the first block.  Synchronises first. */
+int fmd_tonesq_status(fmd_tonesq *t, int32_t *tone, uint64_t *power, uint8_t *open);
+/* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_tonesq_kernel_name(const fmd_tonesq *t, char *name, size_t cap);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

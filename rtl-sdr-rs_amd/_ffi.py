@@ -241,6 +241,16 @@ PROTOTYPES = {
     "fmd_agc_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fmd_agc_gain": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fmd_agc_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_tonesq_new": (C.c_int, [_vp, _i16p, C.c_uint32, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_tonesq_free": (None, [_vp]),
+    "fmd_tonesq_reset": (C.c_int, [_vp]),
+    "fmd_tonesq_out_cap": (_sz, [_sz]),
+    "fmd_tonesq_run_batch": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp]),
+    "fmd_tonesq_run_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_tonesq_check": (C.c_int, [_vp]),
+    "fmd_tonesq_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fmd_tonesq_status": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _u8p]),
+    "fmd_tonesq_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

@@ -843,7 +843,7 @@ inline std::pair<std::vector<int16_t>, uint32_t> resample_taps(uint32_t L, uint3
     throw Error(FMD_ERR_UNSUPPORTED);
 }
 
-// Base of the row processors (fmd_resample_*, fmd_agc_*): owns the handle H of `n_rows` rows of `width` int16 per sample and runs it
+// Base of the row processors (fmd_resample_*, fmd_agc_*, fmd_tonesq_*): owns the handle H of `n_rows` rows of `width` int16 per sample and runs it
 // through its `_run_batch`, `_outputs` and `_reset` entry points.
 template <class H, void (*Free)(H*), auto RunBatch, auto Outputs, auto Reset>
 class RowProcessor {
@@ -915,6 +915,64 @@ public:
         uint32_t g = 0, h = 0;
         check(fmd_agc_gain(h_, row, &g, &h));
         return {g, h};
+    }
+    uint32_t block() const { return block_; }
+
+private:
+    uint32_t block_;
+};
+
+// The 38 standard CTCSS tones, Hz.
+inline const std::vector<double>& ctcss_tones()
+{
+    static const std::vector<double> tones{67.0, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9,
+                                           114.8, 118.8, 123.0, 127.3, 131.8, 136.5, 141.3, 146.2, 151.4, 156.7, 162.2, 167.9, 173.8,
+                                           179.9, 186.2, 192.8, 203.5, 210.7, 218.1, 225.7, 233.6, 241.8, 250.3};
+    return tones;
+}
+
+// The table of a ToneSquelch, entry for entry the Python tone_table(): [freqs][block][2] = (c_f[r], s_f[r]) =
+// rint(1023 w[r] cos(2 pi f r / rate)), rint(-1023 w[r] sin(2 pi f r / rate)) under w[r] = 0.5 - 0.5 cos(2 pi (r + 0.5) / block).
+inline std::vector<int16_t> tone_table(double rate, const std::vector<double>& freqs, uint32_t block)
+{
+    if (!(rate > 0) || block < 1) throw Error(FMD_ERR_INVALID_ARG);
+    std::vector<int16_t> tab(freqs.size() * block * 2);
+    for (size_t k = 0; k < freqs.size(); ++k)
+        for (uint32_t r = 0; r < block; ++r) {
+            const double w = 0.5 - 0.5 * std::cos(2 * detail::pi * ((double)r + 0.5) / (double)block);
+            const double a = 2 * detail::pi * freqs[k] * (double)r / rate;
+            tab[(k * block + r) * 2] = (int16_t)std::rint(1023 * w * std::cos(a));
+            tab[(k * block + r) * 2 + 1] = (int16_t)std::rint(-1023 * w * std::sin(a));
+        }
+    return tab;
+}
+
+// Tone squelch (fmd_tonesq_*): `table` is [n_tones][cfg.block][2] (tone_table); run() takes [n_rows][n_in][width] int16 and returns
+// the same samples per row, gated by the tone the blocks before decided on.
+class ToneSquelch : public RowProcessor<fmd_tonesq, fmd_tonesq_free, fmd_tonesq_run_batch, fmd_tonesq_outputs, fmd_tonesq_reset> {
+public:
+    struct Status { int32_t tone; uint64_t power; bool open; };
+
+    ToneSquelch(const fmd_tonesq_config& cfg, const std::vector<int16_t>& table, uint32_t n_rows = 1, uint32_t width = 1,
+                int32_t device_id = -1)
+        : RowProcessor(n_rows, width), block_(cfg.block)
+    {
+        fmd_device_config dev{n_rows, device_id, 0};
+        const uint32_t n_tones = cfg.block ? (uint32_t)(table.size() / (2ull * cfg.block)) : 0u;
+        check(fmd_tonesq_new(&cfg, table.data(), n_tones, width, &dev, h_.out()));
+    }
+
+    Rows run(const int16_t* x, size_t n_in) { return run_rows(x, n_in, fmd_tonesq_out_cap(n_in)); }
+    // per row after the last completed block: the selected tone (-1: none), W of the strongest tone, whether the gate opens
+    std::vector<Status> status()
+    {
+        std::vector<int32_t> tone(n_rows_);
+        std::vector<uint64_t> power(n_rows_);
+        std::vector<uint8_t> open(n_rows_);
+        check(fmd_tonesq_status(h_, tone.data(), power.data(), open.data()));
+        std::vector<Status> res(n_rows_);
+        for (size_t r = 0; r < n_rows_; ++r) res[r] = Status{tone[r], power[r], open[r] != 0};
+        return res;
     }
     uint32_t block() const { return block_; }
 

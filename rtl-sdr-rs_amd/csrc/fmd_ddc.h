@@ -1,6 +1,6 @@
 // fmd_ddc.h -- what the matrix-core handles share: the five down-converter banks (fmd_stations.hip, fmd_channelizer.hip,
 // fmd_stereo.hip, fmd_narrow.hip, fmd_rds.hip) and the power-spectrum scanner (fmd_spectrum.hip).  The handle core also carries the
-// row processors (fmd_resample.hip, fmd_agc.hip), whose own host layer on top of it is fmd_rows.h.
+// row processors (fmd_resample.hip, fmd_agc.hip, fmd_tonesq.hip), whose own host layer on top of it is fmd_rows.h.
 //   plan (host):        the NCO table, the complex taps of every row, the matrix-core A fragments and their centring constants;
 //   front end (device): the banks' digital down-converter -- staging of the filter windows and the NCO table in LDS, the
 //                       history write, the contraction on the matrix cores, the rotation back to baseband;

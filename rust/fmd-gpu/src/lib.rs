@@ -220,6 +220,25 @@ pub struct fmd_agc_config {
 }
 
 #[repr(C)]
+pub struct fmd_tonesq {
+    _private: [u8; 0],
+}
+
+/// `fmd_tonesq_config` of include/fmd.h (tone squelch).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_tonesq_config {
+    pub block: u32,
+    pub guard: u32,
+    pub dom_shift: u32,
+    pub confirm: u32,
+    pub hang: u32,
+    pub ramp: u32,
+    pub min_power: u64,
+    pub accept: u64,
+}
+
+#[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
 }
@@ -404,6 +423,16 @@ extern "C" {
     pub fn fmd_agc_outputs(a: *const fmd_agc, inputs: *mut u64, outputs: *mut u64) -> c_int;
     pub fn fmd_agc_gain(a: *mut fmd_agc, row: u32, gain: *mut u32, hang: *mut u32) -> c_int;
     pub fn fmd_agc_kernel_name(a: *const fmd_agc, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_tonesq_new(cfg: *const fmd_tonesq_config, table: *const i16, n_tones: u32, width: u32, dev: *const DeviceConfig, out: *mut *mut fmd_tonesq) -> c_int;
+    pub fn fmd_tonesq_free(t: *mut fmd_tonesq);
+    pub fn fmd_tonesq_reset(t: *mut fmd_tonesq) -> c_int;
+    pub fn fmd_tonesq_out_cap(n_in: usize) -> usize;
+    pub fn fmd_tonesq_run_batch(t: *mut fmd_tonesq, input: *const i16, n_in: usize, in_cap: usize, out: *mut i16, out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn fmd_tonesq_run_device(t: *mut fmd_tonesq, d_in: *const c_void, n_in: usize, in_cap: usize, d_out: *mut c_void, out_cap: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_tonesq_check(t: *mut fmd_tonesq) -> c_int;
+    pub fn fmd_tonesq_outputs(t: *const fmd_tonesq, inputs: *mut u64, outputs: *mut u64) -> c_int;
+    pub fn fmd_tonesq_status(t: *mut fmd_tonesq, tone: *mut i32, power: *mut u64, open: *mut u8) -> c_int;
+    pub fn fmd_tonesq_kernel_name(t: *const fmd_tonesq, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
