@@ -28,12 +28,11 @@
 
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <new>
 #include <vector>
 
+#include "fmd_ddc.h"
 #include "fmd_fir_common.h"
-#include "fmd_host.h"
 
 namespace {
 
@@ -462,51 +461,22 @@ __global__ void __launch_bounds__(kFirThreads) fmd_fir_hist_kernel(const FirLaun
     L.hist_out[(uint64_t)c * L.Hw + k] = v;
 }
 
-#define FIR_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof m_, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-            fmd_internal_set_err(m_);                                                       \
-            return FMD_ERR_HIP;                                                             \
-        }                                                                                   \
-    } while (0)
-
-#define FIR_ON_DEVICE(dev)                                                                  \
-    FmdDeviceGuard dev_guard_(dev);                                                         \
-    if (dev_guard_.error() != hipSuccess) { fmd_internal_set_err("hipSetDevice failed"); return FMD_ERR_HIP; }
-
 }  // namespace
 
 struct fmd_fir {
     uint32_t T = 0, M = 0, C = 0, NP = 0, Hw = 0;
-    int device = 0;
-    uint64_t pos = 0;                                     // samples consumed per channel
-    uint32_t* d_wre = nullptr; uint32_t* d_wim = nullptr;
-    uint32_t* d_amat = nullptr;                           // MFMA form: banded tap matrix, fragment order
+    FmdDdcCore core;                                      // pos: samples consumed per channel; d_hist: [C][max(Hw, 1)] raw dwords
+    void* d_wre = nullptr; void* d_wim = nullptr;         // owned constants
+    void* d_amat = nullptr;                               // MFMA form: banded tap matrix, fragment order
     uint32_t n_pass = 0, nku = 0, groups = 0;             // n_pass == 0: VALU kernel only
     uint32_t digits = 0;                                  // tap digits of the matrix-core form (1: every |tap| <= 127; 2); 0 without it
     uint32_t dbg = 0;                                     // ablation bits of the -DFMD_EXPERIMENT build (fmd_host.h), read at creation
     bool swz = false;
     int32_t mre[2] = {0, 0}, mim[2] = {0, 0};
-    uint32_t* d_hist[2] = {nullptr, nullptr};
-    int cur = 0;
     int32_t cre[2] = {0, 0}, cim[2] = {0, 0};
-    hipStream_t stream = nullptr;
-    FmdStreamOrder order;                                 // consecutive launches on different streams (fmd_host.h)
-    uint8_t* d_iq = nullptr; size_t d_iq_cap = 0;
-    int32_t* d_out = nullptr; size_t d_out_cap = 0;
 };
 
 namespace {
-
-void fir_counts(const fmd_fir* f, uint64_t ns, uint64_t* m0, uint64_t* m1)
-{
-    const uint64_t S = f->pos, T = f->T, M = f->M;
-    *m0 = S >= T ? (S - T) / M + 1 : 0;
-    *m1 = S + ns >= T ? (S + ns - T) / M + 1 : 0;
-}
 
 int fir_enqueue(fmd_fir* f, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* n_each, hipStream_t stream)
 {
@@ -514,23 +484,22 @@ int fir_enqueue(fmd_fir* f, const void* d_iq, size_t nbytes, void* d_out, size_t
     if (nbytes == 0 || nbytes > (1ull << 31)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
     if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & 7u) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
     const uint64_t ns = nbytes / 2;
-    uint64_t m0, m1;
-    fir_counts(f, ns, &m0, &m1);
-    const uint64_t n_out = m1 - m0;
+    FmdDdcCore& c = f->core;
+    const uint64_t m0 = fmd_ddc_outputs(f->T, f->M, c.pos), n_out = fmd_ddc_outputs(f->T, f->M, c.pos + ns) - m0;
     if (n_out > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
-    FIR_TRY(f->order.before(stream));                     // the history ping-pong orders launch n+1 behind launch n
+    FMD_DDC_TRY(c.order.before(stream));                  // the history ping-pong orders launch n+1 behind launch n
     FirLaunch L{};
     L.iq = static_cast<const uint32_t*>(d_iq);
     L.stride_w = nbytes / 4;
-    L.hist_in = f->d_hist[f->cur]; L.hist_out = f->d_hist[f->cur ^ 1];
+    L.hist_in = reinterpret_cast<const uint32_t*>(c.d_hist[c.cur]); L.hist_out = reinterpret_cast<uint32_t*>(c.d_hist[c.cur ^ 1]);
     L.Hw = f->Hw;
-    L.wre = f->d_wre; L.wim = f->d_wim;
+    L.wre = static_cast<const uint32_t*>(f->d_wre); L.wim = static_cast<const uint32_t*>(f->d_wim);
     L.cre[0] = f->cre[0]; L.cre[1] = f->cre[1]; L.cim[0] = f->cim[0]; L.cim[1] = f->cim[1];
     L.NP = f->NP; L.half_M = f->M / 2;
     L.n_out = (uint32_t)n_out; L.n_channels = f->C;
     L.out = static_cast<int32_t*>(d_out); L.out_cap = out_cap;
     // first window: stream sample M*m0; virtual sample index = M*m0 - (S - 2*Hw); both even
-    const uint64_t vs0 = f->M * m0 + 2ull * f->Hw - f->pos;
+    const uint64_t vs0 = f->M * m0 + 2ull * f->Hw - c.pos;
     L.wd_first = (uint32_t)(vs0 / 2);
     L.par_first = (uint32_t)((f->M * m0 / 2) & 1u);
     L.par_step = (f->M / 2) & 1u;
@@ -542,7 +511,7 @@ int fir_enqueue(fmd_fir* f, const void* d_iq, size_t nbytes, void* d_out, size_t
     L.dbg = f->dbg;
     if (n_out && f->n_pass) {
         const uint32_t opc = f->digits != 2u ? 8u : 4u;              // outputs per column (one digit, or two on the sparse instruction: eight)
-        L.amat = f->d_amat; L.n_pass = f->n_pass; L.nku = f->nku; L.groups = f->groups; L.col_bytes = 2u * opc * f->M;
+        L.amat = static_cast<const uint32_t*>(f->d_amat); L.n_pass = f->n_pass; L.nku = f->nku; L.groups = f->groups; L.col_bytes = 2u * opc * f->M;
         L.mre[0] = f->mre[0]; L.mre[1] = f->mre[1]; L.mim[0] = f->mim[0]; L.mim[1] = f->mim[1];
         L.out_tile = 16u * opc * f->groups;
         // staged bytes of a full tile, and the furthest byte any fragment read touches
@@ -566,21 +535,19 @@ int fir_enqueue(fmd_fir* f, const void* d_iq, size_t nbytes, void* d_out, size_t
             case 7: launch_mfma<7>(L, g, lds, stream, f->swz, f->digits); break;
             default: launch_mfma<8>(L, g, lds, stream, f->swz, f->digits); break;
         }
-        FIR_TRY(hipGetLastError());
+        FMD_DDC_TRY(hipGetLastError());
     } else if (n_out) {
         const size_t lds = (((size_t)(L.out_tile - 1) * L.half_M + L.NP) * 4 + 15) & ~(size_t)15;
         const uint32_t gy = f->C < 65535u ? f->C : 65535u, gz = (f->C + 65534u) / 65535u;
         hipLaunchKernelGGL(fmd_fir_kernel, dim3((uint32_t)((n_out + ot - 1) / ot), gy, gz), dim3(kFirThreads), lds, stream, L);
-        FIR_TRY(hipGetLastError());
+        FMD_DDC_TRY(hipGetLastError());
     }
     if (f->Hw && !(n_out && f->n_pass)) {               // the MFMA kernel's last tiles wrote it already
         const uint64_t th = (uint64_t)f->C * f->Hw;
         hipLaunchKernelGGL(fmd_fir_hist_kernel, dim3((uint32_t)((th + kFirThreads - 1) / kFirThreads)), dim3(kFirThreads), 0, stream, L);
-        FIR_TRY(hipGetLastError());
+        FMD_DDC_TRY(hipGetLastError());
     }
-    (void)f->order.after(stream);
-    if (f->Hw) f->cur ^= 1;
-    f->pos += ns;
+    fmd_ddc_commit(c, stream, ns);                        // (one tap, Hw == 0: both history buffers hold the same zero dword, never written)
     if (n_each) *n_each = (size_t)n_out;
     return FMD_OK;
 }
@@ -606,18 +573,9 @@ int fmd_fir_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, const fmd_
     }
     for (uint32_t t = 0; t < n_taps; ++t)
         if (taps[t] > 2047 || taps[t] < -2047) { fmd_internal_set_err("|tap| > 2047"); return FMD_ERR_UNSUPPORTED; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { fmd_internal_set_err("no HIP device (this library has no CPU path)"); return FMD_ERR_NO_DEVICE; }
-    int device = dev->device_id;
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    hipDeviceProp_t prop;
-    if (device >= ndev || hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        fmd_internal_set_err("device is not a gfx950");
-        return FMD_ERR_NO_DEVICE;
-    }
     fmd_fir* f = new (std::nothrow) fmd_fir();
     if (!f) return FMD_ERR_NOMEM;
-    f->T = n_taps; f->M = decim; f->C = dev->n_channels; f->device = device;
+    f->T = n_taps; f->M = decim; f->C = dev->n_channels;
     f->NP = ((n_taps + 1) / 2 + 3u) & ~3u;                // tap pairs, zero-padded to a multiple of 4
     const uint32_t H = n_taps - 1, Hp = H + (H & 1u);     // history samples, rounded up to whole dwords
     f->Hw = Hp / 2;
@@ -666,23 +624,15 @@ int fmd_fir_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, const fmd_
         if (split) amat.swap(plan.amat_s); else amat.swap(plan.amat);
         for (int par = 0; par < 2; ++par) { f->mre[par] = plan.mre[par]; f->mim[par] = plan.mim[par]; }
     }
-    auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_fir_free(f); return FMD_ERR_HIP; };
-    FmdDeviceGuard guard(device);                         // the caller's current device comes back on return
-    if (guard.error() != hipSuccess) return fail("hipSetDevice");
-    if (!amat.empty()) {
-        if (hipMalloc(&f->d_amat, amat.size() * 4) != hipSuccess) return fail("hipMalloc(tap matrix)");
-        if (hipMemcpy(f->d_amat, amat.data(), amat.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy(tap matrix)");
+    FmdDdcCore& c = f->core;
+    if (!amat.empty()) fmd_ddc_add_owned(c, f->d_amat, amat.data(), amat.size() * 4);
+    fmd_ddc_add_owned(c, f->d_wre, wre.data(), f->NP * 4);
+    fmd_ddc_add_owned(c, f->d_wim, wim.data(), f->NP * 4);
+    const char* what;
+    if (const int rc = fmd_ddc_core_device(c, FmdDdcPlan(), (size_t)f->C * (f->Hw ? f->Hw : 1) * 4, dev, &what)) {
+        if (!what) { delete f; return rc; }
+        fmd_internal_set_err(what); fmd_fir_free(f); return rc;
     }
-    if (hipMalloc(&f->d_wre, f->NP * 4) != hipSuccess || hipMalloc(&f->d_wim, f->NP * 4) != hipSuccess) return fail("hipMalloc(taps)");
-    if (hipMemcpy(f->d_wre, wre.data(), f->NP * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->d_wim, wim.data(), f->NP * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy(taps)");
-    const size_t hb = (size_t)f->C * (f->Hw ? f->Hw : 1) * 4;
-    for (int i = 0; i < 2; ++i) {
-        if (hipMalloc(&f->d_hist[i], hb) != hipSuccess) return fail("hipMalloc(history)");
-        if (hipMemset(f->d_hist[i], 0, hb) != hipSuccess) return fail("hipMemset(history)");
-    }
-    if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate");
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
     *out = f;
     return FMD_OK;
 }
@@ -690,16 +640,7 @@ int fmd_fir_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, const fmd_
 void fmd_fir_free(fmd_fir* f)
 {
     if (!f) return;
-    FmdDeviceGuard guard(f->device);
-    (void)hipDeviceSynchronize();
-    f->order.destroy();
-    if (f->d_wre) (void)hipFree(f->d_wre);
-    if (f->d_wim) (void)hipFree(f->d_wim);
-    if (f->d_amat) (void)hipFree(f->d_amat);
-    for (int i = 0; i < 2; ++i) if (f->d_hist[i]) (void)hipFree(f->d_hist[i]);
-    if (f->d_iq) (void)hipFree(f->d_iq);
-    if (f->d_out) (void)hipFree(f->d_out);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
+    fmd_ddc_free(f->core);
     delete f;
 }
 
@@ -717,59 +658,39 @@ int fmd_fir_kernel_name(const fmd_fir* f, char* name, size_t cap)
         const bool swz = f->digits != 3u && col_bytes == 64u && f->swz;
         n = snprintf(name, cap, "(anonymous namespace)::fmd_fir_mfma_kernel<%u, %s, %u>", nku, swz ? "true" : "false", f->digits);
     }
-    return n < 0 || (size_t)n >= cap ? FMD_ERR_CAPACITY : FMD_OK;
+    return fmd_ddc_name_rc(n, cap);
 }
 
-int fmd_fir_reset(fmd_fir* f)
-{
-    if (!f) return FMD_ERR_INVALID_ARG;
-    FIR_ON_DEVICE(f->device);
-    FIR_TRY(hipDeviceSynchronize());
-    f->order.reset();
-    const size_t hb = (size_t)f->C * (f->Hw ? f->Hw : 1) * 4;
-    FIR_TRY(hipMemset(f->d_hist[0], 0, hb));
-    FIR_TRY(hipMemset(f->d_hist[1], 0, hb));
-    FIR_TRY(hipDeviceSynchronize());
-    f->pos = 0; f->cur = 0;
-    return FMD_OK;
-}
+int fmd_fir_reset(fmd_fir* f) { return f ? fmd_ddc_reset(f->core) : FMD_ERR_INVALID_ARG; }
 
 int fmd_fir_filter_device(fmd_fir* f, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap, size_t* out_len_each,
                           void* stream)
 {
-    if (!f || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FIR_ON_DEVICE(f->device);
-    return fir_enqueue(f, d_iq, nbytes, d_out, out_cap, out_len_each, static_cast<hipStream_t>(stream));
+    return fmd_ddc_run_device(f ? &f->core : nullptr, d_iq, d_out,
+                              [&] { return fir_enqueue(f, d_iq, nbytes, d_out, out_cap, out_len_each, static_cast<hipStream_t>(stream)); });
 }
 
 int fmd_fir_filter_batch(fmd_fir* f, const uint8_t* iq, size_t nbytes, int32_t* out, size_t out_cap, size_t* out_len)
 {
     if (!f || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FIR_ON_DEVICE(f->device);
+    FmdDdcCore& c = f->core;
+    FMD_DDC_ON_DEVICE(c.device);
     if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    uint64_t m0, m1;
-    fir_counts(f, nbytes / 2, &m0, &m1);
-    if (m1 - m0 > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
-    const size_t in_bytes = nbytes * (size_t)f->C, out_elems = out_cap * (size_t)f->C * 2;
-    if (in_bytes > f->d_iq_cap) {
-        if (f->d_iq) { FIR_TRY(hipFree(f->d_iq)); f->d_iq = nullptr; f->d_iq_cap = 0; }
-        FIR_TRY(hipMalloc(&f->d_iq, in_bytes ? in_bytes : 1));
-        f->d_iq_cap = in_bytes;
-    }
-    if (out_elems > f->d_out_cap) {
-        if (f->d_out) { FIR_TRY(hipFree(f->d_out)); f->d_out = nullptr; f->d_out_cap = 0; }
-        FIR_TRY(hipMalloc(&f->d_out, (out_elems ? out_elems : 1) * sizeof(int32_t)));
-        f->d_out_cap = out_elems;
-    }
-    FIR_TRY(hipMemcpyAsync(f->d_iq, iq, in_bytes, hipMemcpyHostToDevice, f->stream));
+    if (fmd_ddc_outputs(f->T, f->M, c.pos + nbytes / 2) - fmd_ddc_outputs(f->T, f->M, c.pos) > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
+    const size_t in_bytes = nbytes * (size_t)f->C, out_bytes = out_cap * 8 * (size_t)f->C;
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
+    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
     size_t n = 0;
-    int rc = fir_enqueue(f, f->d_iq, nbytes, f->d_out, out_cap, &n, f->stream);
-    if (rc) return rc;
+    if (const int rc = fir_enqueue(f, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream)) {
+        (void)hipStreamSynchronize(c.stream);             // (the copy out of the caller's buffer)
+        return rc;
+    }
     if (n && n * 2 >= out_cap)      // nearly full rows: one linear copy instead of a strided one
-        FIR_TRY(hipMemcpyAsync(out, f->d_out, out_cap * 8 * (size_t)f->C, hipMemcpyDeviceToHost, f->stream));
-    else if (n) FIR_TRY(hipMemcpy2DAsync(out, out_cap * 8, f->d_out, out_cap * 8, n * 8, f->C, hipMemcpyDeviceToHost, f->stream));
-    FIR_TRY(hipStreamSynchronize(f->stream));
-    for (uint32_t c = 0; c < f->C; ++c) out_len[c] = n;
+        FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+    else if (n) FMD_DDC_TRY(hipMemcpy2DAsync(out, out_cap * 8, c.d_out, out_cap * 8, n * 8, f->C, hipMemcpyDeviceToHost, c.stream));
+    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
+    for (uint32_t ch = 0; ch < f->C; ++ch) out_len[ch] = n;
     return FMD_OK;
 }
 

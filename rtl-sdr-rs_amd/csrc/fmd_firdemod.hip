@@ -31,9 +31,9 @@
 #include <new>
 #include <vector>
 
+#include "fmd_ddc.h"
 #include "fmd_device.h"
 #include "fmd_fir_common.h"
-#include "fmd_host.h"
 #include "fmd_internal.h"
 #include "fmd_kernels.h"
 
@@ -845,45 +845,26 @@ void launch(const FirDemodLaunch& L, dim3 g, size_t lds, hipStream_t s)
     else hipLaunchKernelGGL((fmd_firdemod_kernel<NKU, 0>), g, dim3(kThreads), lds, s, L);
 }
 
-#define FD_TRY(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof m_, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-            fmd_internal_set_err(m_);                                                       \
-            return e_ == hipErrorOutOfMemory ? FMD_ERR_NOMEM : FMD_ERR_HIP;                 \
-        }                                                                                   \
-    } while (0)
-
-#define FD_ON_DEVICE(dev)                                                                   \
-    FmdDeviceGuard dev_guard_(dev);                                                         \
-    if (dev_guard_.error() != hipSuccess) { fmd_internal_set_err("hipSetDevice failed"); return FMD_ERR_HIP; }
-
 }  // namespace
 
 struct fmd_firdemod {
     uint32_t T = 0, M = 0, C = 0, NP = 0, Hw = 0, shift = 0;
     uint32_t lp_bound = 0;                                // ceil(128 * sum|taps| / 2^shift): the largest |lp| component
-    int device = 0;
-    uint64_t pos = 0;                                     // samples consumed per channel
+    FmdDdcCore core;                                      // pos: samples consumed per channel; d_hist: [C][max(Hw, 1)] raw dwords
     FmdFirMfmaPlan plan;
-    uint32_t* d_amat = nullptr;
-    uint32_t* d_hist[2] = {nullptr, nullptr};
-    FmdChanState* d_state[2] = {nullptr, nullptr};
-    int cur = 0;
+    void* d_amat = nullptr;                               // owned constant
+    FmdDdcPair state;                                     // [C] FmdChanState
     FmdRates r{};
     uint32_t i0r = 0;                                     // resampler phase of every channel (host mirror)
     uint32_t last_K = 0;
     uint32_t taps_hash = 0;                               // FNV-1a of the taps: a checkpoint names the filter it belongs to
     uint32_t lp_cap = 0, raw_bytes = 0;
-    FmdExcBuf* d_exc = nullptr;
+    void* d_exc = nullptr;                                // FmdExcBuf, owned: starts zeroed
     uint32_t* h_head = nullptr;                           // page-locked copy of the report head (fmd_firdemod_check, see fmd_demod_check)
     double f64_guard = 0x1p-20;
     int32_t f64_skew = 0;
     uint32_t seq = 0;
     uint64_t f64_guarded = 0, f64_patched = 0;
-    FmdStreamOrder order;
     uint32_t dbg = 0;                                     // ablation bits (FMD_DBG, experiment build)
     bool no_rows = false;                                 // FMD_FD_ROWS=0: geometry on the device (A/B)
     bool reuse16 = false;                                 // FMD_FD_REUSE16 (experiment build): fragment reuse at decim 16 too
@@ -892,19 +873,11 @@ struct fmd_firdemod {
     uint32_t reg_ng = 0;                                  // > 0: fmd_firdemod_reg_kernel with this many output groups per column (decimate 8, f32 discriminator)
     bool sparse = false;                                  // the register form's matrix phase on v_smfmac (d_amat holds the compressed matrix)
     size_t lds_budget = 20480;                            // LDS per tile (8 tiles per CU); FMD_FD_LDS (tuning)
-    hipStream_t stream = nullptr;
-    uint8_t* d_iq = nullptr; size_t d_iq_cap = 0;
-    int16_t* d_out = nullptr; size_t d_out_cap = 0;
+    FmdExcBuf* exc() const { return static_cast<FmdExcBuf*>(d_exc); }
+    FmdChanState* st() const { return state.in<FmdChanState>(core.cur); }   // what the most recent launch wrote
 };
 
 namespace {
-
-void fd_counts(const fmd_firdemod* f, uint64_t ns, uint64_t* m0, uint64_t* m1)
-{
-    const uint64_t S = f->pos, T = f->T, M = f->M;
-    *m0 = S >= T ? (S - T) / M + 1 : 0;
-    *m1 = S + ns >= T ? (S + ns - T) / M + 1 : 0;
-}
 
 // Discriminator pass: `lg` lanes per audio group, `ch` consecutive samples per lane, lg * ch >= fa + 1 (a group holds fa
 // or fa + 1 samples).  The smallest ch >= 4 whose kt + 1 groups (the tile's audio samples + the carried partial group)
@@ -962,9 +935,8 @@ int fd_enqueue(fmd_firdemod* f, const void* d_iq, size_t nbytes, void* d_out, si
     if (nbytes == 0 || nbytes > (1ull << 31)) { fmd_internal_set_err("nbytes out of range"); return FMD_ERR_UNSUPPORTED; }
     if (((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & 1u) != 0) { fmd_internal_set_err("misaligned device buffer"); return FMD_ERR_INVALID_ARG; }
     const uint64_t ns = nbytes / 2;
-    uint64_t m0, m1;
-    fd_counts(f, ns, &m0, &m1);
-    const uint64_t Mdec = m1 - m0;
+    FmdDdcCore& c = f->core;
+    const uint64_t m0 = fmd_ddc_outputs(f->T, f->M, c.pos), Mdec = fmd_ddc_outputs(f->T, f->M, c.pos + ns) - m0;
     if (Mdec < 2) { fmd_internal_set_err("the call yields fewer than 2 filter outputs (simple_fm.rs:356 asserts > 1)"); return FMD_ERR_TOO_SHORT; }
     FmdRates r = f->r;
     if (!fmd_ranges_fit32(r, Mdec * r.D)) { fmd_internal_set_err("call exceeds the 32-bit index range for these rates"); return FMD_ERR_UNSUPPORTED; }
@@ -976,21 +948,21 @@ int fd_enqueue(fmd_firdemod* f, const void* d_iq, size_t nbytes, void* d_out, si
     if (L.P.K > out_cap) { fmd_internal_set_err("out_cap too small"); return FMD_ERR_CAPACITY; }
     L.iq = static_cast<const uint32_t*>(d_iq);
     L.stride_w = nbytes / 4;
-    L.hist_in = f->d_hist[f->cur]; L.hist_out = f->d_hist[f->cur ^ 1];
+    L.hist_in = reinterpret_cast<const uint32_t*>(c.d_hist[c.cur]); L.hist_out = reinterpret_cast<uint32_t*>(c.d_hist[c.cur ^ 1]);
     L.Hw = f->Hw; L.NP = f->NP; L.half_M = f->M / 2;
-    const uint64_t vs0 = f->M * m0 + 2ull * f->Hw - f->pos;      // virtual sample index of the first window (even)
+    const uint64_t vs0 = f->M * m0 + 2ull * f->Hw - c.pos;       // virtual sample index of the first window (even)
     L.wd_first = (uint32_t)(vs0 / 2);
     L.par_first = (uint32_t)((f->M * m0 / 2) & 1u);
-    L.amat = f->d_amat; L.n_pass = f->plan.n_pass; L.col_bytes = 8u * f->M; L.shift = f->shift;
+    L.amat = static_cast<const uint32_t*>(f->d_amat); L.n_pass = f->plan.n_pass; L.col_bytes = 8u * f->M; L.shift = f->shift;
     for (int p = 0; p < 2; ++p) { L.mre[p] = f->plan.mre[p]; L.mim[p] = f->plan.mim[p]; }
     L.n_channels = f->C; L.tiles = L.P.nt;
     L.r = r; L.tl = fmd_make_tiling(r);
     L.fa = r.fr / r.sr; L.fb = r.fr % r.sr;
     L.inv_sr = 1.0f / (float)r.sr; L.inv_R = 1.0f / (float)r.R;
     L.lp_cap = f->lp_cap; L.raw_bytes = f->raw_bytes;
-    L.st_in = f->d_state[f->cur]; L.st_out = f->d_state[f->cur ^ 1];
+    L.st_in = f->state.in<FmdChanState>(c.cur); L.st_out = f->state.out<FmdChanState>(c.cur);
     L.out = static_cast<int16_t*>(d_out); L.out_stride = out_cap;
-    L.exc = f->d_exc; L.f64_guard = f->f64_guard; L.seq = f->seq + 1; L.f64_skew = f->f64_skew;
+    L.exc = f->exc(); L.f64_guard = f->f64_guard; L.seq = f->seq + 1; L.f64_skew = f->f64_skew;
     L.dbg = f->dbg;
     fd_lanes(L.fa, r.kt, &L.lg, &L.lg_magic, &L.ch);
     L.reg_ng = f->reg_ng;
@@ -1011,7 +983,7 @@ int fd_enqueue(fmd_firdemod* f, const void* d_iq, size_t nbytes, void* d_out, si
     }
     uint32_t lc, rb; size_t lds;
     if (!fd_sizes(f, r.kt, &lc, &rb, &lds)) { fmd_internal_set_err("tile sizing failed"); return FMD_ERR_UNSUPPORTED; }
-    FD_TRY(f->order.before(stream));
+    FMD_DDC_TRY(c.order.before(stream));
     const uint32_t per = (f->C + 7u) / 8u;
     dim3 g(L.tiles, f->C < 65535u ? f->C : 65535u, (f->C + 65534u) / 65535u);
     if (f->C >= 8u && L.tiles <= 65535u && per <= 65535u) { g = dim3(8u, L.tiles, per); L.xcd = 3u; }
@@ -1048,12 +1020,10 @@ int fd_enqueue(fmd_firdemod* f, const void* d_iq, size_t nbytes, void* d_out, si
         case 7: launch<7>(L, g, lds, stream); break;
         default: launch<8>(L, g, lds, stream); break;
     }
-    FD_TRY(hipGetLastError());
-    (void)f->order.after(stream);
+    FMD_DDC_TRY(hipGetLastError());
+    fmd_ddc_commit(c, stream, ns);
     f->seq += 1;
-    f->cur ^= 1;
     f->i0r = fmd_next_lpr_index_r(r, f->i0r, L.P.M, L.P.K);
-    f->pos += ns;
     f->last_K = L.P.K;
     f->last_rows = (int)L.use_rows;
     if (n_each) *n_each = L.P.K;
@@ -1094,18 +1064,9 @@ int fmd_firdemod_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint3
         fmd_internal_set_err("filter gain too large for the discriminator: need (128 * sum|taps|) >> shift <= 16384");
         return FMD_ERR_UNSUPPORTED;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { fmd_internal_set_err("no HIP device (this library has no CPU path)"); return FMD_ERR_NO_DEVICE; }
-    int device = dev->device_id;
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    hipDeviceProp_t prop;
-    if (device >= ndev || hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        fmd_internal_set_err("device is not a gfx950");
-        return FMD_ERR_NO_DEVICE;
-    }
     fmd_firdemod* f = new (std::nothrow) fmd_firdemod();
     if (!f) return FMD_ERR_NOMEM;
-    f->T = n_taps; f->M = decim; f->C = dev->n_channels; f->device = device; f->shift = shift;
+    f->T = n_taps; f->M = decim; f->C = dev->n_channels; f->shift = shift;
     f->taps_hash = 2166136261u;
     for (uint32_t t = 0; t < n_taps; ++t) {
         f->taps_hash = (f->taps_hash ^ (uint32_t)(taps[t] & 0xFF)) * 16777619u;
@@ -1210,21 +1171,21 @@ int fmd_firdemod_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint3
     if (const char* g = fmd_knob("FMD_F64_GUARD_LOG2")) f->f64_guard = ldexp(1.0, atoi(g));   // experiment build only
     f->f64_skew = fmd_knob_i32("FMD_F64_SKEW", 0);
 
-    auto fail = [&](const char* what) { fmd_internal_set_err(what); fmd_firdemod_free(f); return FMD_ERR_HIP; };
-    FmdDeviceGuard guard(device);
-    if (guard.error() != hipSuccess) return fail("hipSetDevice");
+    FmdDdcCore& c = f->core;
     const std::vector<uint32_t>& amat = f->sparse ? f->plan.amat_s : f->plan.amat;
-    if (hipMalloc(&f->d_amat, amat.size() * 4) != hipSuccess) return fail("hipMalloc(tap matrix)");
-    if (hipMemcpy(f->d_amat, amat.data(), amat.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy(tap matrix)");
-    const size_t hb = (size_t)f->C * (f->Hw ? f->Hw : 1) * 4, sb = (size_t)f->C * sizeof(FmdChanState);
-    for (int i = 0; i < 2; ++i) {
-        if (hipMalloc(&f->d_hist[i], hb) != hipSuccess || hipMemset(f->d_hist[i], 0, hb) != hipSuccess) return fail("hipMalloc(history)");
-        if (hipMalloc(&f->d_state[i], sb) != hipSuccess || hipMemset(f->d_state[i], 0, sb) != hipSuccess) return fail("hipMalloc(state)");
+    const std::vector<char> no_reports(sizeof(FmdExcBuf));
+    fmd_ddc_add_owned(c, f->d_amat, amat.data(), amat.size() * 4);
+    fmd_ddc_add_owned(c, f->d_exc, no_reports.data(), no_reports.size());
+    fmd_ddc_add_pair(c, f->state, (size_t)f->C * sizeof(FmdChanState));
+    const char* what;
+    if (const int rc = fmd_ddc_core_device(c, FmdDdcPlan(), (size_t)f->C * (f->Hw ? f->Hw : 1) * 4, dev, &what)) {
+        if (!what) { delete f; return rc; }
+        fmd_internal_set_err(what); fmd_firdemod_free(f); return rc;
     }
-    if (hipMalloc(&f->d_exc, sizeof(FmdExcBuf)) != hipSuccess || hipMemset(f->d_exc, 0, sizeof(FmdExcBuf)) != hipSuccess) return fail("hipMalloc(reports)");
-    if (hipHostMalloc(reinterpret_cast<void**>(&f->h_head), 16, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc(report head)");
-    if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate");
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
+    FmdDeviceGuard guard(c.device);
+    if (guard.error() != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&f->h_head), 16, hipHostMallocDefault) != hipSuccess) {
+        fmd_internal_set_err("hipHostMalloc(report head)"); fmd_firdemod_free(f); return FMD_ERR_HIP;
+    }
     *out = f;
     return FMD_OK;
 }
@@ -1232,92 +1193,78 @@ int fmd_firdemod_new(const int16_t* taps, uint32_t n_taps, uint32_t decim, uint3
 void fmd_firdemod_free(fmd_firdemod* f)
 {
     if (!f) return;
-    FmdDeviceGuard guard(f->device);
-    (void)hipDeviceSynchronize();
-    f->order.destroy();
-    if (f->d_amat) (void)hipFree(f->d_amat);
-    for (int i = 0; i < 2; ++i) { if (f->d_hist[i]) (void)hipFree(f->d_hist[i]); if (f->d_state[i]) (void)hipFree(f->d_state[i]); }
-    if (f->d_exc) (void)hipFree(f->d_exc);
     if (f->h_head) (void)hipHostFree(f->h_head);
-    if (f->d_iq) (void)hipFree(f->d_iq);
-    if (f->d_out) (void)hipFree(f->d_out);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
+    fmd_ddc_free(f->core);
     delete f;
 }
 
+// fmd_ddc_reset and what is this handle's own: the head of the report buffer, the resampler phase, the last call's output count.
 int fmd_firdemod_reset(fmd_firdemod* f)
 {
     if (!f) return FMD_ERR_INVALID_ARG;
-    FD_ON_DEVICE(f->device);
-    FD_TRY(hipDeviceSynchronize());
-    const size_t hb = (size_t)f->C * (f->Hw ? f->Hw : 1) * 4, sb = (size_t)f->C * sizeof(FmdChanState);
-    for (int i = 0; i < 2; ++i) { FD_TRY(hipMemset(f->d_hist[i], 0, hb)); FD_TRY(hipMemset(f->d_state[i], 0, sb)); }
-    FD_TRY(hipMemset(f->d_exc, 0, 16));
-    FD_TRY(hipDeviceSynchronize());
-    f->pos = 0; f->cur = 0; f->i0r = 0; f->last_K = 0;
-    f->order.reset();
+    FmdDdcCore& c = f->core;
+    FMD_DDC_ON_DEVICE(c.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    FMD_DDC_TRY(hipMemset(f->d_exc, 0, 16));
+    FMD_DDC_TRY(fmd_ddc_zero_history(c));                 // (ends with the device synchronised; only then the host fields)
+    f->i0r = 0; f->last_K = 0;
     return FMD_OK;
 }
 
 int fmd_firdemod_demodulate_device(fmd_firdemod* f, const void* d_iq, size_t nbytes, void* d_out, size_t out_cap,
                                    size_t* out_len_each, void* stream)
 {
-    if (!f || !d_iq || !d_out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FD_ON_DEVICE(f->device);
-    return fd_enqueue(f, d_iq, nbytes, d_out, out_cap, out_len_each, static_cast<hipStream_t>(stream));
+    return fmd_ddc_run_device(f ? &f->core : nullptr, d_iq, d_out,
+                              [&] { return fd_enqueue(f, d_iq, nbytes, d_out, out_cap, out_len_each, static_cast<hipStream_t>(stream)); });
 }
 
 int fmd_firdemod_check(fmd_firdemod* f)
 {
     if (!f) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FD_ON_DEVICE(f->device);
-    if (f->order.have_last && f->h_head) {                   // one stream synchronisation in the common case (see fmd_demod_check)
+    FMD_DDC_ON_DEVICE(f->core.device);
+    const FmdStreamOrder& order = f->core.order;
+    if (order.have_last && f->h_head) {                      // one stream synchronisation in the common case (see fmd_demod_check)
         f->h_head[0] = f->h_head[1] = ~0u;
-        hipError_t e = hipMemcpyAsync(f->h_head, f->d_exc, 16, hipMemcpyDeviceToHost, f->order.last);
-        if (e == hipSuccess) e = hipStreamSynchronize(f->order.last);
+        hipError_t e = hipMemcpyAsync(f->h_head, f->d_exc, 16, hipMemcpyDeviceToHost, order.last);
+        if (e == hipSuccess) e = hipStreamSynchronize(order.last);
         if (e == hipSuccess && f->h_head[0] == 0u && f->h_head[1] == 0u) return FMD_OK;
         if (e != hipSuccess) (void)hipGetLastError();
     }
-    FD_TRY(hipDeviceSynchronize());
-    return fmd_internal_resolve_exc(f->d_exc, f->r.R, f->seq, f->seq, f->d_state[f->cur], nullptr, 0, &f->f64_guarded, &f->f64_patched);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    return fmd_internal_resolve_exc(f->exc(), f->r.R, f->seq, f->seq, f->st(), nullptr, 0, &f->f64_guarded, &f->f64_patched);
 }
 
 int fmd_firdemod_demodulate_batch(fmd_firdemod* f, const uint8_t* iq, size_t nbytes, int16_t* out, size_t out_cap,
                                   size_t* out_len)
 {
     if (!f || !iq || !out || !out_len) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FD_ON_DEVICE(f->device);
+    FMD_DDC_ON_DEVICE(f->core.device);
     if (nbytes % 8 != 0) { fmd_internal_set_err("nbytes % 8 != 0"); return FMD_ERR_BAD_LENGTH; }
-    const size_t in_bytes = nbytes * (size_t)f->C, out_elems = out_cap * (size_t)f->C;
-    if (in_bytes > f->d_iq_cap) {
-        if (f->d_iq) { FD_TRY(hipFree(f->d_iq)); f->d_iq = nullptr; f->d_iq_cap = 0; }
-        FD_TRY(hipMalloc(&f->d_iq, in_bytes ? in_bytes : 1));
-        f->d_iq_cap = in_bytes;
-    }
-    if (out_elems > f->d_out_cap) {
-        if (f->d_out) { FD_TRY(hipFree(f->d_out)); f->d_out = nullptr; f->d_out_cap = 0; }
-        FD_TRY(hipMalloc(&f->d_out, (out_elems ? out_elems : 1) * sizeof(int16_t)));
-        f->d_out_cap = out_elems;
-    }
-    FD_TRY(hipMemcpyAsync(f->d_iq, iq, in_bytes, hipMemcpyHostToDevice, f->stream));
+    FmdDdcCore& c = f->core;
+    const size_t in_bytes = nbytes * (size_t)f->C, out_bytes = out_cap * (size_t)f->C * sizeof(int16_t);
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, out_bytes));
+    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, iq, in_bytes, hipMemcpyHostToDevice, c.stream));
     size_t n = 0;
-    int rc = fd_enqueue(f, f->d_iq, nbytes, f->d_out, out_cap, &n, f->stream);
-    if (rc) return rc;
-    if (n) FD_TRY(hipMemcpyAsync(out, f->d_out, out_elems * sizeof(int16_t), hipMemcpyDeviceToHost, f->stream));
-    FD_TRY(hipStreamSynchronize(f->stream));
-    for (uint32_t c = 0; c < f->C; ++c) out_len[c] = n;
-    return fmd_internal_resolve_exc(f->d_exc, f->r.R, f->seq, f->seq, f->d_state[f->cur], out, out_cap, &f->f64_guarded, &f->f64_patched);
+    if (const int rc = fd_enqueue(f, c.d_iq, nbytes, c.d_out, out_cap, &n, c.stream)) {
+        (void)hipStreamSynchronize(c.stream);             // (the copy out of the caller's buffer)
+        return rc;
+    }
+    if (n) FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+    FMD_DDC_TRY(hipStreamSynchronize(c.stream));
+    for (uint32_t ch = 0; ch < f->C; ++ch) out_len[ch] = n;
+    return fmd_internal_resolve_exc(f->exc(), f->r.R, f->seq, f->seq, f->st(), out, out_cap, &f->f64_guarded, &f->f64_patched);
 }
 
 int fmd_firdemod_get_state(fmd_firdemod* f, uint32_t channel, fmd_demod_state* state)
 {
     if (!f || !state || channel >= f->C) { fmd_internal_set_err("bad argument"); return FMD_ERR_INVALID_ARG; }
-    FD_ON_DEVICE(f->device);
-    FD_TRY(hipDeviceSynchronize());
-    int rc = fmd_internal_resolve_exc(f->d_exc, f->r.R, f->seq, f->seq, f->d_state[f->cur], nullptr, 0, &f->f64_guarded, &f->f64_patched);
+    FMD_DDC_ON_DEVICE(f->core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    int rc = fmd_internal_resolve_exc(f->exc(), f->r.R, f->seq, f->seq, f->st(), nullptr, 0, &f->f64_guarded, &f->f64_patched);
     if (rc) return rc;
     FmdChanState s;
-    FD_TRY(hipMemcpy(&s, f->d_state[f->cur] + channel, sizeof(s), hipMemcpyDeviceToHost));
+    FMD_DDC_TRY(hipMemcpy(&s, f->st() + channel, sizeof(s), hipMemcpyDeviceToHost));
     memset(state, 0, sizeof(*state));
     state->now_lpr = s.now_lpr;
     state->prev_lpr_index = (int32_t)(s.lpr_index_r * f->r.g);
@@ -1361,16 +1308,16 @@ int fmd_firdemod_checkpoint(fmd_firdemod* f, void* blob, size_t cap)
 {
     if (!f || !blob) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
     if (cap < fd_ckpt_size(f)) { fmd_internal_set_err("checkpoint buffer smaller than fmd_firdemod_checkpoint_size"); return FMD_ERR_CAPACITY; }
-    FD_ON_DEVICE(f->device);
-    FD_TRY(hipDeviceSynchronize());
-    int rc = fmd_internal_resolve_exc(f->d_exc, f->r.R, f->seq, f->seq, f->d_state[f->cur], nullptr, 0, &f->f64_guarded, &f->f64_patched);
+    FMD_DDC_ON_DEVICE(f->core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    int rc = fmd_internal_resolve_exc(f->exc(), f->r.R, f->seq, f->seq, f->st(), nullptr, 0, &f->f64_guarded, &f->f64_patched);
     if (rc) return rc;
-    FdCkptHeader h{kFdCkptMagic, kFdCkptVersion, f->T, f->M, f->C, f->Hw, f->shift, f->taps_hash, f->r.fast, f->r.slow, f->i0r, f->last_K, f->pos, 0ull};
+    FdCkptHeader h{kFdCkptMagic, kFdCkptVersion, f->T, f->M, f->C, f->Hw, f->shift, f->taps_hash, f->r.fast, f->r.slow, f->i0r, f->last_K, f->core.pos, 0ull};
     uint8_t* const payload = static_cast<uint8_t*>(blob) + sizeof(h);
     uint8_t* p = payload;
-    FD_TRY(hipMemcpy(p, f->d_state[f->cur], (size_t)f->C * sizeof(FmdChanState), hipMemcpyDeviceToHost));
+    FMD_DDC_TRY(hipMemcpy(p, f->st(), (size_t)f->C * sizeof(FmdChanState), hipMemcpyDeviceToHost));
     p += (size_t)f->C * sizeof(FmdChanState);
-    if (f->Hw) FD_TRY(hipMemcpy(p, f->d_hist[f->cur], (size_t)f->C * f->Hw * 4, hipMemcpyDeviceToHost));
+    if (f->Hw) FMD_DDC_TRY(hipMemcpy(p, f->core.d_hist[f->core.cur], (size_t)f->C * f->Hw * 4, hipMemcpyDeviceToHost));
     h.checksum = fd_ckpt_checksum(h, payload, fd_ckpt_size(f) - sizeof(h));
     memcpy(blob, &h, sizeof(h));
     return FMD_OK;
@@ -1407,17 +1354,17 @@ int fmd_firdemod_resume(fmd_firdemod* f, const void* blob, size_t size)
             return FMD_ERR_BAD_STATE;
         }
     }
-    FD_ON_DEVICE(f->device);
-    FD_TRY(hipDeviceSynchronize());
+    FMD_DDC_ON_DEVICE(f->core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
     // Both arrays go into the INACTIVE halves of the ping-pong; `cur` flips only once both copies have succeeded, so a
     // failing second copy cannot leave the channels' state restored and their filter history not.
-    const int nxt = f->cur ^ 1;
-    FD_TRY(hipMemcpy(f->d_state[nxt], payload, (size_t)f->C * sizeof(FmdChanState), hipMemcpyHostToDevice));
-    if (f->Hw) FD_TRY(hipMemcpy(f->d_hist[nxt], payload + (size_t)f->C * sizeof(FmdChanState), (size_t)f->C * f->Hw * 4, hipMemcpyHostToDevice));
-    FD_TRY(hipMemset(f->d_exc, 0, 16));
-    FD_TRY(hipDeviceSynchronize());
-    f->cur = nxt;
-    f->pos = h.pos; f->i0r = h.i0r; f->last_K = h.last_K;
+    const int nxt = f->core.cur ^ 1;
+    FMD_DDC_TRY(hipMemcpy(f->state.p[nxt], payload, (size_t)f->C * sizeof(FmdChanState), hipMemcpyHostToDevice));
+    if (f->Hw) FMD_DDC_TRY(hipMemcpy(f->core.d_hist[nxt], payload + (size_t)f->C * sizeof(FmdChanState), (size_t)f->C * f->Hw * 4, hipMemcpyHostToDevice));
+    FMD_DDC_TRY(hipMemset(f->d_exc, 0, 16));
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    f->core.cur = nxt;
+    f->core.pos = h.pos; f->i0r = h.i0r; f->last_K = h.last_K;
     return FMD_OK;
 }
 
@@ -1440,7 +1387,7 @@ int fmd_firdemod_kernel_name(const fmd_firdemod* f, char* name, size_t cap)
     const bool rows = f->last_rows < 0 ? !f->no_rows : f->last_rows != 0;
     const int n = f->reg_ng ? snprintf(name, cap, "(anonymous namespace)::fmd_firdemod_reg%s%s_kernel<%u, %u, %s>", f->plan.digits == 1u ? "1" : "", f->sparse ? "s" : "", nku, f->reg_ng, rows ? "true" : "false")
                             : snprintf(name, cap, "(anonymous namespace)::fmd_firdemod_kernel<%u, %u>", nku, reuse ? 1u : 0u);
-    return n < 0 || (size_t)n >= cap ? FMD_ERR_CAPACITY : FMD_OK;
+    return fmd_ddc_name_rc(n, cap);
 }
 
 int fmd_firdemod_tiling(const fmd_firdemod* f, uint32_t* audio_per_tile, uint32_t* lds_bytes)

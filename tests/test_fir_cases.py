@@ -62,7 +62,7 @@ def test_table_matches_the_sources():
     assert all(a == b for a, b in cases) and "default: launch<8>" in fd
     assert tuple(sorted({a for a, _ in cases} | {8})) == fc.NKU
     # the column parameters and mappings launch<> dispatches to in the shipped library
-    body = fd[fd.index("void launch(const FirDemodLaunch& L"):fd.index("#define FD_TRY")]
+    body = fd[fd.index("void launch(const FirDemodLaunch& L"):fd.index("struct fmd_firdemod {")]
     assert "FMD_EXPERIMENT" in body
     body = shipped(body)
     regx = {}

@@ -69,6 +69,30 @@ def test_fails_loudly_without_device(fmd):
         assert p.returncode == 1 and b"no usable gfx950 device" in p.stderr
 
 
+def test_fir_handles_refuse_their_domain_before_the_device(fmd):
+    """Without a gfx950 the two FIR handles answer as every bank does: whatever their domain excludes is FMD_ERR_UNSUPPORTED, and
+    only arguments they would accept reach the device check."""
+    import numpy as np
+    if fmd.device_count() > 0:
+        pytest.skip("a GPU is present")
+    UNSUPPORTED, NO_DEVICE = -6, -8
+    ones = np.ones(8, np.int16)
+
+    def status(make):
+        with pytest.raises(fmd.FmdError) as ei:
+            make()
+        return ei.value.status, str(ei.value)
+
+    assert status(lambda: fmd.FirBank(ones, 8))[0] == NO_DEVICE
+    assert status(lambda: fmd.FirBank(ones, 3))[0] == UNSUPPORTED                       # odd decimation
+    assert status(lambda: fmd.FirDemodBank(ones, 8, 2500000, 48000))[0] == NO_DEVICE
+    assert status(lambda: fmd.FirDemodBank(np.ones(1024, np.int16), 64, 37500, 8000))[0] == NO_DEVICE   # (1024 taps at decimation 64 fit)
+    for fast, text in ((48000 * 600, "rate ratio outside the exact-small-divide range"), (48000 * 500, "one audio sample does not fit a tile")):
+        for taps in (ones, np.ones(1024, np.int16)):
+            st, err = status(lambda: fmd.FirDemodBank(taps, 64, fast, 48000))
+            assert st == UNSUPPORTED and text in err, (fast, taps.size, err)
+
+
 def test_missing_library_is_an_error_not_a_fallback():
     """Without the built HIP library the package must raise, never compute on the CPU."""
     code = "import rtl_sdr_rs_amd as f\ntry:\n    f.lib()\nexcept ImportError as e:\n    print('IMPORTERROR', e)\n"
