@@ -11,28 +11,20 @@ import pytest
 
 import channelizer_ref as cr
 import resample_ref as rr
-from rows_gpu import SENT, call, iq_bytes
+from rows_cases import taps as _taps
+from rows_gpu import SENT, TOO_SHORT, call, iq_bytes
 import stations_ref as sr
 import stereo_ref as st
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOO_SHORT, CAPACITY = -3, -5
+CAPACITY = -5
 _call = functools.partial(call, out_pad=3)
 
 # (L, M, T, samples per row): the issue's shapes; the sample counts give more than one tile of 256 outputs wherever 6000 inputs can
 SHAPES = [(1, 1, 1, 1500), (1, 1, 256, 2000), (15, 16, 32, 3000), (3, 16, 64, 6000), (441, 512, 24, 3000), (160, 147, 48, 2500),
           (6, 1, 8, 1400), (1, 32, 256, 6000), (1024, 1023, 16, 2500)]
-
-
-def _taps(rng, L, T, mag=32767):
-    """random taps of both signs, every phase with sum |g| <= mag and one phase with exactly mag"""
-    g = rng.integers(-(mag // T), mag // T + 1, (L, T))
-    p = int(rng.integers(0, L))
-    g[p, 0] += (mag - np.abs(g[p]).sum()) * (1 if g[p, 0] >= 0 else -1)
-    assert np.abs(g).sum(axis=1).max() == mag
-    return g.astype(np.int16)
 
 
 def _feed(fmd, rs, ref, x, cuts, odd_caps=True):
