@@ -946,6 +946,89 @@ int fmd_tonesq_status(fmd_tonesq *t, int32_t *tone, uint64_t *power, uint8_t *op
 /* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_tonesq_kernel_name(const fmd_tonesq *t, char *name, size_t cap);
 
+/* ---- packet demodulator: AX.25 frames (APRS) out of any bank's NFM rows --------------------------------------------- */
+/* NEW SURFACE (the reference has no data decoder).  1200 baud AFSK packet in two halves, as fmd_rds_* and fmd_rds_decoder_* are for
+ * RDS: fmd_afsk_* on the GPU turns every mono int16 row a bank leaves on the device into signed soft decisions, a few per bit;
+ * fmd_ax25_decoder_* on the host, one per row, turns them into frames.
+ *
+ * fmd_afsk_*: the tone-pair demodulator, a row processor like the resampler; a row is one (stream, channel), width 1 only (the NFM
+ * rows are mono; width 2 is FMD_ERR_UNSUPPORTED).  Definition (integers only, exact; tests/afsk_ref.py), per row:
+ *   x[i]        int16 input, i counted from creation or reset
+ *   tab[q][t]   int16, q < 4: mark-cos, mark-sin, space-cos, space-sin; t < T; every |entry| <= 1023
+ *   i_n         = n D
+ *   S_q[n]      = sum_{t < T} tab[q][t] x[i_n + t]     (exact in i32: 64 * 32768 * 1023 = 2 145 386 496 < 2^31, hence T <= 64)
+ *   A_q         = S_q >> pre_shift                     (arithmetic shift: floor)
+ *   E_m = A_0^2 + A_1^2,  E_s = A_2^2 + A_3^2          (i64; each below 2^63 even at pre_shift 0)
+ *   out[n]      = sat16((E_m - E_s) >> out_shift)      (arithmetic shift; positive: mark)
+ * Counting (the resampler's rule at L = 1, M = D): after N inputs, N >= T ? ceil((N - T + 1) / D) : 0 outputs exist; output n comes
+ * with the call in which x[i_n + T - 1] arrives; the handle carries at most T - 1 samples.  fmd_afsk_out_cap(D, n_in) = ceil(n_in / D)
+ * + 1 bounds a call's outputs.  A call that completes no output returns FMD_ERR_TOO_SHORT and takes nothing (hand the same samples
+ * over again, with more behind them).  n_in > in_cap, or out_cap below the call's outputs -> FMD_ERR_CAPACITY, nothing is written or
+ * taken.  The output does not depend on how the stream is cut into calls.  core.pos is the only counter: reset forgets the carried
+ * samples, output 0 follows.
+ * Levels: the designers (afsk_table in Python, fm::afsk_table in csrc/demod.hpp) give rectangular windows one bit long, pre_shift 8
+ * and the smallest out_shift at which a full window of either tone at amplitude 1024 stays inside int16.  Louder input saturates at
+ * +-32767 / -32768; that is harmless, because the decoder reads only signs and where they change.
+ * Domain (else FMD_ERR_UNSUPPORTED with a text, decided before a device is queried): width 1; 2 <= T <= 64; 1 <= D <= min(T, 32);
+ * pre_shift <= 16; out_shift <= 48; every table entry in [-1023, 1023]; n_rows = dev->n_channels >= 1.  Stream lifetime and
+ * completion points: as fmd_channelizer_* (fmd_afsk_check). */
+typedef struct fmd_afsk fmd_afsk;
+/* table: [4][T] int16. */
+int fmd_afsk_new(const int16_t *table, uint32_t T, uint32_t D, uint32_t pre_shift, uint32_t out_shift, uint32_t width,
+                 const fmd_device_config *dev, fmd_afsk **out);
+void fmd_afsk_free(fmd_afsk *a);
+int fmd_afsk_reset(fmd_afsk *a);
+/* ceil(n_in / D) + 1; 0 when D is 0. */
+size_t fmd_afsk_out_cap(uint32_t D, size_t n_in);
+/* HOST buffers: in [n_rows][in_cap], the first n_in samples of each row valid; out [n_rows][out_cap]; *n_out outputs per row. */
+int fmd_afsk_run_batch(fmd_afsk *a, const int16_t *in, size_t n_in, size_t in_cap, int16_t *out, size_t out_cap, size_t *n_out);
+/* DEVICE buffers, enqueued on `stream` without synchronising: d_in is a bank's d_out as it stands, with the bank's out_cap as
+ * in_cap; pointers 2-byte aligned, any in_cap and out_cap. */
+int fmd_afsk_run_device(fmd_afsk *a, const void *d_in, size_t n_in, size_t in_cap, void *d_out, size_t out_cap, size_t *n_out,
+                        void *stream);
+int fmd_afsk_check(fmd_afsk *a);
+/* Samples taken and soft decisions produced per row since creation or the last reset. */
+int fmd_afsk_outputs(const fmd_afsk *a, uint64_t *inputs, uint64_t *outputs);
+/* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_afsk_kernel_name(const fmd_afsk *a, char *name, size_t cap);
+
+/* fmd_ax25_decoder_*: the frame decoder of one row, on the host, no GPU.  Definition (integers only; tests/ax25_ref.py; the result
+ * does not depend on how the samples are cut into pushes), with mod = rate_num and step = baud * rate_den (u64), the soft decisions
+ * arriving at rate_num / rate_den per second (the audio rate over D):
+ *   clock   ph = 0 at the start.  Per soft sample v: cur = (v >= 0); if cur differs from the sample before (1 at the start):
+ *           ph -= (ph - mod / 2) >> 2 (arithmetic shift of the signed difference); then ph += step; when ph >= mod: ph -= mod and a
+ *           bit is taken.
+ *   NRZI    bit = (cur == the level at the previous take) (1 at the start).
+ *   HDLC    per bit, in this order: the bit enters an 8-bit shift register from the top; the register equal to 0x7E is a flag, which
+ *           closes the open frame and opens the next; else a 1 counts, and seven 1s in a row abort the open frame and close the
+ *           receiver until the next flag; a 0 after exactly five 1s is dropped; every other bit goes to the open frame, LSB first.
+ *   closing the flag's first seven bits, which went in, are removed.  No bits left: nothing (flags back to back).  A frame has whole
+ *           bytes, 17 <= bytes <= 514 with its FCS, and the CRC-16/X.25 (reflected 0x1021, init and final xor 0xFFFF; "123456789"
+ *           -> 0x906E) of all but the last two bytes equal to those two, low byte first.  What fails any of it is counted in
+ *           bad_fcs and not delivered.
+ * Every buffer is fixed and every write bounded: a frame's bits behind 514 bytes are counted, not stored; frames that do not fit
+ * `frames` wait in a ring of 64, whose oldest gives way when a caller lets it fill.
+ * Domain: 4 <= (rate_num / rate_den) / baud <= 64, else FMD_ERR_UNSUPPORTED ("need 4 <= rate / baud <= 64"). */
+typedef struct fmd_ax25_decoder fmd_ax25_decoder;
+typedef struct fmd_ax25_frame {
+    uint8_t data[512];       /* address, control, PID and information fields; the FCS is checked and left out */
+    uint32_t len;
+    uint64_t end_sample;     /* index, since creation or reset, of the soft sample that took the closing flag's last bit */
+} fmd_ax25_frame;
+typedef struct fmd_ax25_info {
+    uint64_t frames_ok;      /* frames that passed, delivered or waiting                               */
+    uint64_t bad_fcs;        /* bits between two flags that were not a frame (length, whole bytes, FCS) */
+    uint64_t aborts;         /* open frames ended by seven 1s                                           */
+    int in_frame;            /* a flag was seen and no abort since                                      */
+} fmd_ax25_info;
+int fmd_ax25_decoder_new(uint32_t rate_num, uint32_t rate_den, uint32_t baud, fmd_ax25_decoder **out);
+void fmd_ax25_decoder_free(fmd_ax25_decoder *d);
+int fmd_ax25_decoder_reset(fmd_ax25_decoder *d);
+/* n soft decisions in; up to `cap` frames out, oldest first.  Frames that do not fit stay queued and come with the next push
+ * (n may be 0, soft then NULL). */
+int fmd_ax25_decoder_push(fmd_ax25_decoder *d, const int16_t *soft, size_t n, fmd_ax25_frame *frames, size_t cap, size_t *n_frames);
+int fmd_ax25_decoder_info(const fmd_ax25_decoder *d, fmd_ax25_info *info);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

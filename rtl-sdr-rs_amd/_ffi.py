@@ -251,6 +251,20 @@ PROTOTYPES = {
     "fmd_tonesq_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fmd_tonesq_status": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _u8p]),
     "fmd_tonesq_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_afsk_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_afsk_free": (None, [_vp]),
+    "fmd_afsk_reset": (C.c_int, [_vp]),
+    "fmd_afsk_out_cap": (_sz, [C.c_uint32, _sz]),
+    "fmd_afsk_run_batch": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp]),
+    "fmd_afsk_run_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_afsk_check": (C.c_int, [_vp]),
+    "fmd_afsk_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fmd_afsk_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_ax25_decoder_new": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "fmd_ax25_decoder_free": (None, [_vp]),
+    "fmd_ax25_decoder_reset": (C.c_int, [_vp]),
+    "fmd_ax25_decoder_push": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "fmd_ax25_decoder_info": (C.c_int, [_vp, _vp]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

@@ -980,6 +980,143 @@ private:
     uint32_t block_;
 };
 
+// The table of an AfskDemod with its shifts, entry for entry the Python afsk_table(): rectangular windows one bit long, T = taps or
+// round(rate / baud); tab[4][T] = mark-cos, mark-sin, space-cos, space-sin = rint(1023 cos(2 pi f t / rate)), rint(-1023 sin(...));
+// pre_shift 8; out_shift the smallest at which a full window of either tone at amplitude 1024 stays inside int16.
+struct AfskTable {
+    std::vector<int16_t> tab;
+    uint32_t T, pre_shift, out_shift;
+};
+
+inline AfskTable afsk_table(double rate, double baud = 1200, double mark = 1200, double space = 2200, uint32_t taps = 0)
+{
+    if (!(rate > 0) || !(baud > 0)) throw Error(FMD_ERR_INVALID_ARG);
+    const double tr = taps ? (double)taps : std::rint(rate / baud);
+    if (!(tr >= 2 && tr <= 64)) throw Error(FMD_ERR_UNSUPPORTED);
+    const uint32_t T = (uint32_t)tr;
+    AfskTable res{std::vector<int16_t>((size_t)4 * T), T, 8, 0};
+    const double freqs[2] = {mark, space};
+    for (size_t k = 0; k < 2; ++k)
+        for (uint32_t t = 0; t < T; ++t) {
+            const double a = 2 * detail::pi * freqs[k] * (double)t / rate;
+            res.tab[2 * k * T + t] = (int16_t)std::rint(1023 * std::cos(a));
+            res.tab[(2 * k + 1) * T + t] = (int16_t)std::rint(-1023 * std::sin(a));
+        }
+    int64_t peak = 0;
+    for (size_t k = 0; k < 2; ++k) {
+        int64_t A[4];
+        for (size_t q = 0; q < 4; ++q) {
+            int64_t s = 0;
+            for (uint32_t t = 0; t < T; ++t)
+                s += (int64_t)res.tab[q * T + t] * (int64_t)std::rint(1024 * std::cos(2 * detail::pi * freqs[k] * (double)t / rate));
+            A[q] = s >> res.pre_shift;
+        }
+        const int64_t v = A[0] * A[0] + A[1] * A[1] - A[2] * A[2] - A[3] * A[3];
+        peak = std::max(peak, v < 0 ? -v : v);
+    }
+    while ((peak >> res.out_shift) > 32767) ++res.out_shift;
+    return res;
+}
+
+// The default stride of a window of `taps` samples: a fifth of a bit, at least 1 and at most 32.
+inline uint32_t afsk_stride(uint32_t taps) { return std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(32, taps), (2 * taps + 5) / 10)); }
+
+// Tone-pair demodulator (fmd_afsk_*): `table` is [4][T] (afsk_table); run() takes [n_rows][n_in] int16 and returns the call's soft
+// decisions per row, one per `stride` samples, positive for mark.
+class AfskDemod : public RowProcessor<fmd_afsk, fmd_afsk_free, fmd_afsk_run_batch, fmd_afsk_outputs, fmd_afsk_reset> {
+public:
+    AfskDemod(const std::vector<int16_t>& table, uint32_t stride, uint32_t pre_shift, uint32_t out_shift, uint32_t n_rows = 1,
+              uint32_t width = 1, int32_t device_id = -1)
+        : RowProcessor(n_rows, width), stride_(stride)
+    {
+        fmd_device_config dev{n_rows, device_id, 0};
+        check(fmd_afsk_new(table.data(), (uint32_t)(table.size() / 4), stride, pre_shift, out_shift, width, &dev, h_.out()));
+    }
+
+    // FMD_ERR_TOO_SHORT (a call that completes no output) returns empty rows and changes nothing: the samples are not taken.
+    Rows run(const int16_t* x, size_t n_in) { return run_rows(x, n_in, fmd_afsk_out_cap(stride_, n_in), FMD_ERR_TOO_SHORT); }
+    uint32_t stride() const { return stride_; }
+
+private:
+    uint32_t stride_;
+};
+
+// AX.25 frame decoder of one row (fmd_ax25_decoder_*, host only): push() takes an AfskDemod's soft decisions at rate_num / rate_den
+// per second (the audio rate over the stride) and returns the frames completed since.
+class Ax25Decoder {
+public:
+    Ax25Decoder(uint32_t rate_num, uint32_t rate_den, uint32_t baud = 1200) { check(fmd_ax25_decoder_new(rate_num, rate_den, baud, h_.out())); }
+
+    std::vector<fmd_ax25_frame> push(const int16_t* soft, size_t n)
+    {
+        std::vector<fmd_ax25_frame> res;
+        fmd_ax25_frame buf[16];
+        size_t k = 0;
+        check(fmd_ax25_decoder_push(h_, soft, n, buf, 16, &k));
+        for (;;) {
+            res.insert(res.end(), buf, buf + k);
+            if (k < 16) return res;
+            check(fmd_ax25_decoder_push(h_, nullptr, 0, buf, 16, &k));
+        }
+    }
+    std::vector<fmd_ax25_frame> push(const std::vector<int16_t>& soft) { return push(soft.data(), soft.size()); }
+    fmd_ax25_info info() const { return value_of<fmd_ax25_info>(fmd_ax25_decoder_info, h_); }
+    void reset() { check(fmd_ax25_decoder_reset(h_)); }
+
+private:
+    Owned<fmd_ax25_decoder, fmd_ax25_decoder_free> h_;
+};
+
+namespace detail {
+// "CALL" or "CALL-SSID" of a 7-byte address; empty where it is malformed (a character that is not shifted ASCII upper case or digit,
+// or one behind a padding space)
+inline std::string ax25_call(const uint8_t* a)
+{
+    std::string name;
+    bool pad = false;
+    for (int i = 0; i < 6; ++i) {
+        if (a[i] & 1) return "";
+        const char c = (char)(a[i] >> 1);
+        if (c == ' ') { pad = true; continue; }
+        if (pad || !((c >= '0' && c <= '9') || (c >= 'A' && c <= 'Z'))) return "";
+        name += c;
+    }
+    if (name.empty()) return "";
+    const unsigned ssid = (a[6] >> 1) & 15u;
+    return ssid ? name + "-" + std::to_string(ssid) : name;
+}
+}  // namespace detail
+
+// A frame in TNC2 form `SRC>DST,DIGI*:info`, character for character the Python ax25_text(): `*` behind a digipeater whose has-been-
+// repeated bit is set, non-printable bytes as `.`, control 0x03 and PID 0xF0 (UI) left out; hex where the address field is malformed.
+inline std::string ax25_text(const uint8_t* data, size_t len)
+{
+    const auto hex = [&] {
+        static const char* const digits = "0123456789abcdef";
+        std::string s;
+        for (size_t i = 0; i < len; ++i) { s += digits[data[i] >> 4]; s += digits[data[i] & 15]; }
+        return s;
+    };
+    std::vector<std::pair<std::string, bool>> addrs;
+    size_t pos = 0;
+    for (;;) {
+        if (pos + 7 > len || addrs.size() == 10) return hex();
+        const std::string name = detail::ax25_call(data + pos);
+        if (name.empty()) return hex();
+        addrs.emplace_back(name, (data[pos + 6] & 0x80) != 0);
+        pos += 7;
+        if (data[pos - 1] & 1) break;
+    }
+    if (addrs.size() < 2) return hex();
+    if (pos + 2 <= len && data[pos] == 0x03 && data[pos + 1] == 0xF0) pos += 2;
+    std::string s = addrs[1].first + ">" + addrs[0].first;
+    for (size_t i = 2; i < addrs.size(); ++i) s += "," + addrs[i].first + (addrs[i].second ? "*" : "");
+    s += ":";
+    for (; pos < len; ++pos) s += data[pos] >= 32 && data[pos] < 127 ? (char)data[pos] : '.';
+    return s;
+}
+inline std::string ax25_text(const fmd_ax25_frame& f) { return ax25_text(f.data, std::min<size_t>(f.len, sizeof f.data)); }
+
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.
 inline void output(const std::vector<int16_t>& buf, FILE* f = stdout)
 {

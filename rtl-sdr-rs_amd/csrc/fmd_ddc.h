@@ -1,6 +1,6 @@
 // fmd_ddc.h -- what the matrix-core handles share: the five down-converter banks (fmd_stations.hip, fmd_channelizer.hip,
 // fmd_stereo.hip, fmd_narrow.hip, fmd_rds.hip) and the power-spectrum scanner (fmd_spectrum.hip).  The handle core also carries the
-// row processors (fmd_resample.hip, fmd_agc.hip, fmd_tonesq.hip), whose own host layer on top of it is fmd_rows.h, and the FIR and
+// row processors (fmd_resample.hip, fmd_agc.hip, fmd_tonesq.hip, fmd_afsk.hip), whose own host layer on top of it is fmd_rows.h, and the FIR and
 // the fused FIR-demod handle (fmd_fir.hip, fmd_firdemod.hip: raw dwords in d_hist, their own kernels, call checks and batch copies).
 // Only the demod handle (fmd_api.cpp), with its ring of three settle and replay slots, keeps a host side of its own.
 //   plan (host):        the NCO table, the complex taps of every row, the matrix-core A fragments and their centring constants;

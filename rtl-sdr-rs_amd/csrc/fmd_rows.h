@@ -1,5 +1,5 @@
 // fmd_rows.h -- what the row processors share on the host: the handles that post-process the int16 rows a bank leaves on the device
-// (fmd_resample.hip, fmd_agc.hip, fmd_tonesq.hip).  Their common contract: n_rows rows of `width` 1 or 2 int16 per sample, d_in
+// (fmd_resample.hip, fmd_agc.hip, fmd_tonesq.hip, fmd_afsk.hip).  Their common contract: n_rows rows of `width` 1 or 2 int16 per sample, d_in
 // [n_rows][in_cap][width] with n_in valid samples per row, d_out [n_rows][out_cap][width], a history pair of the samples in front
 // of the call, core.pos counting input samples, and an output that does not depend on how the stream is cut.
 // A handle embeds an FmdRows as its member `rows` and keeps its kernels, its launch struct, its own fields and domain checks, its

@@ -239,6 +239,35 @@ pub struct fmd_tonesq_config {
 }
 
 #[repr(C)]
+pub struct fmd_afsk {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
+pub struct fmd_ax25_decoder {
+    _private: [u8; 0],
+}
+
+/// `fmd_ax25_frame` of include/fmd.h: one AX.25 frame as the host decoder delivers it, without the FCS.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct fmd_ax25_frame {
+    pub data: [u8; 512],
+    pub len: u32,
+    pub end_sample: u64,
+}
+
+/// `fmd_ax25_info` of include/fmd.h: the host decoder's counters.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_ax25_info {
+    pub frames_ok: u64,
+    pub bad_fcs: u64,
+    pub aborts: u64,
+    pub in_frame: c_int,
+}
+
+#[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
 }
@@ -433,6 +462,20 @@ extern "C" {
     pub fn fmd_tonesq_outputs(t: *const fmd_tonesq, inputs: *mut u64, outputs: *mut u64) -> c_int;
     pub fn fmd_tonesq_status(t: *mut fmd_tonesq, tone: *mut i32, power: *mut u64, open: *mut u8) -> c_int;
     pub fn fmd_tonesq_kernel_name(t: *const fmd_tonesq, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_afsk_new(table: *const i16, t: u32, d: u32, pre_shift: u32, out_shift: u32, width: u32, dev: *const DeviceConfig, out: *mut *mut fmd_afsk) -> c_int;
+    pub fn fmd_afsk_free(a: *mut fmd_afsk);
+    pub fn fmd_afsk_reset(a: *mut fmd_afsk) -> c_int;
+    pub fn fmd_afsk_out_cap(d: u32, n_in: usize) -> usize;
+    pub fn fmd_afsk_run_batch(a: *mut fmd_afsk, input: *const i16, n_in: usize, in_cap: usize, out: *mut i16, out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn fmd_afsk_run_device(a: *mut fmd_afsk, d_in: *const c_void, n_in: usize, in_cap: usize, d_out: *mut c_void, out_cap: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_afsk_check(a: *mut fmd_afsk) -> c_int;
+    pub fn fmd_afsk_outputs(a: *const fmd_afsk, inputs: *mut u64, outputs: *mut u64) -> c_int;
+    pub fn fmd_afsk_kernel_name(a: *const fmd_afsk, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_ax25_decoder_new(rate_num: u32, rate_den: u32, baud: u32, out: *mut *mut fmd_ax25_decoder) -> c_int;
+    pub fn fmd_ax25_decoder_free(d: *mut fmd_ax25_decoder);
+    pub fn fmd_ax25_decoder_reset(d: *mut fmd_ax25_decoder) -> c_int;
+    pub fn fmd_ax25_decoder_push(d: *mut fmd_ax25_decoder, soft: *const i16, n: usize, frames: *mut fmd_ax25_frame, cap: usize, n_frames: *mut usize) -> c_int;
+    pub fn fmd_ax25_decoder_info(d: *const fmd_ax25_decoder, info: *mut fmd_ax25_info) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
