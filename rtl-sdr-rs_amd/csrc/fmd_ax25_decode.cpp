@@ -141,7 +141,9 @@ int fmd_ax25_decoder_new(uint32_t rate_num, uint32_t rate_den, uint32_t baud, fm
     if (!out) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
     *out = nullptr;
     const uint64_t mod = rate_num, step = (uint64_t)baud * rate_den;
-    if (step < 1 || 4 * step > mod || mod > 64 * step) { fmd_internal_set_err("need 4 <= rate / baud <= 64"); return FMD_ERR_UNSUPPORTED; }
+    // step up to 2^64 - 2^33 + 1: `step > mod / 4` (the same as 4 step > mod in integers) comes first and bounds step by 2^30, so that
+    // 64 * step cannot wrap
+    if (step < 1 || step > mod / 4 || mod > 64 * step) { fmd_internal_set_err("need 4 <= rate / baud <= 64"); return FMD_ERR_UNSUPPORTED; }
     fmd_ax25_decoder* d = new (std::nothrow) fmd_ax25_decoder();
     if (!d) return FMD_ERR_NOMEM;
     d->mod = (int64_t)mod; d->step = (int64_t)step; d->half = (int64_t)(mod / 2);

@@ -184,6 +184,10 @@ int main()
     if (fmd_ax25_decoder_new(4799, 1, 1200, &d) != FMD_ERR_UNSUPPORTED || d) return fail("rate below 4 per bit accepted");
     if (fmd_ax25_decoder_new(76801, 1, 1200, &d) != FMD_ERR_UNSUPPORTED || d) return fail("rate above 64 per bit accepted");
     if (fmd_ax25_decoder_new(4800, 0, 1200, &d) != FMD_ERR_UNSUPPORTED || d) return fail("zero denominator accepted");
+    // baud * rate_den = 2^62: four times and 64 times that are 0 in 64 bits (no push follows a refusal)
+    if (fmd_ax25_decoder_new(0, 1u << 31, 1u << 31, &d) != FMD_ERR_UNSUPPORTED || d) return fail("a step of 2^62 against rate 0 accepted");
+    if (fmd_ax25_decoder_new(1, 1u << 31, 1u << 31, &d) != FMD_ERR_UNSUPPORTED || d) return fail("a step of 2^62 against rate 1 accepted");
+    if (fmd_ax25_decoder_new(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, &d) != FMD_ERR_UNSUPPORTED || d) return fail("the largest step accepted");
     if (fmd_ax25_decoder_new(0xFFFFFFFFu, 0xFFFFFFFFu / 4800u, 1200, &d) != FMD_OK || !d) return fail("the largest numbers refused");
     int16_t one = -5;
     if (fmd_ax25_decoder_push(d, &one, 1, nullptr, 0, &k) != FMD_OK || k != 0) return fail("push with cap 0 failed");

@@ -118,7 +118,8 @@ def test_domain_edges_are_decided_without_a_device(fmd, inside, outside, text):
 
 def test_decoder_rate_domain(fmd):
     lib, d = fmd.lib(), C.c_void_p()
-    for num, den, baud in ((4799, 1, 1200), (76801, 1, 1200), (6000, 0, 1200), (6000, 1, 0), (12000, 3, 1200), (0, 1, 1200)):
+    for num, den, baud in ((4799, 1, 1200), (76801, 1, 1200), (6000, 0, 1200), (6000, 1, 0), (12000, 3, 1200), (0, 1, 1200),
+                           (0, 1 << 31, 1 << 31), (1, 1 << 31, 1 << 31)):      # baud * rate_den = 2^62: 4 and 64 times it wrap to 0 in u64
         assert lib.fmd_ax25_decoder_new(num, den, baud, C.byref(d)) == UNSUPPORTED and not d.value, (num, den, baud)
         assert lib.fmd_last_error().decode() == "need 4 <= rate / baud <= 64"
         with pytest.raises(ValueError):
