@@ -86,15 +86,17 @@ def ranges_fit32(r, ns):
     return ns <= 1 << 30 and 2 * r.fr + ((r.D - 1 + ns) // r.D) * r.sr < 1 << 32 and (r.kt + 2) * r.fr < 1 << 32
 
 
-def fast_mode(r, P, nch, nbytes, stream, tiles_limit=FAST_ROWS):
-    """fmd_fast_geometry for a bank in ONE phase class on the XCD-aware grid: 2 the table, 1 the closed form, 0 neither."""
+def fast_mode(r, P, nch, nbytes, stream, tiles_limit=FAST_ROWS, out_cap=None):
+    """fmd_fast_geometry for a bank in ONE phase class on the XCD-aware grid: 2 the table, 1 the closed form, 0 neither.  `out_cap`
+    is the caller's output pitch in samples: the table addresses the output with 32-bit products and is refused from
+    nch * out_cap * 2 == 2^32 bytes on (the closed form then takes the call where it applies); None is an output far below that."""
     if nch < 8 or nbytes % 16 or P.nt == 0 or nbytes >= 1 << 31:
         return 0
     ns, g = nbytes // 2, make_tiling(r)
     lc, rc = lp_cap(r), raw_cap(r)
     tiles = [tile_fast(r, P, g, ns, t) for t in range(P.nt)]
     fits = all(T.jB - T.jA + 2 <= lc and (stream or 2 * (T.nHi - T.nLo) + 30 <= rc) for T in tiles)
-    if P.nt <= tiles_limit:
+    if P.nt <= tiles_limit and (out_cap is None or nch * out_cap * 2 < 1 << 32):
         return 2 if fits else 0
     if g.Rt:
         return 0
@@ -164,8 +166,8 @@ class PlannerTile(ValueError):
 class Model:
     """Host bookkeeping of one DemodBank: the phase classes and what enqueue() would launch for a call."""
 
-    def __init__(self, D, fast, slow, nch, kt=None, block=0):
-        self.D, self.fast, self.slow, self.nch, self.kt, self.block = D, fast, slow, nch, kt, block
+    def __init__(self, D, fast, slow, nch, kt=None, block=0, out_cap=None):
+        self.D, self.fast, self.slow, self.nch, self.kt, self.block, self.out_cap = D, fast, slow, nch, kt, block, out_cap
         self.r = rates(D, fast, slow, kt or 1)
         self.kts = None if kt else stream_tile(D, fast, slow)
         self.classes = [(0, 0)]                                    # (p0, i0r) per class
@@ -184,18 +186,20 @@ class Model:
         if self.kts and self.nch >= 8 and not self.block and one and p0s[0] % 2 == 0 and nbytes >= 64 * D:
             rs = rates(D, self.fast, self.slow, self.kts)
             P = make_plan(rs, *self.classes[0], ns)
-            mode = fast_mode(rs, P, self.nch, nbytes, True)
+            mode = fast_mode(rs, P, self.nch, nbytes, True, out_cap=self.out_cap)
             if mode:
                 res = NS(kernel=name(D, mode, True), mode=mode, nt=P.nt, stream=True)
         plans = [make_plan(r, p0, i0r, ns) for p0, i0r in self.classes]
         if res is None and self.kt:
-            mode = fast_mode(r, plans[0], self.nch, nbytes, False) if one else 0
+            mode = fast_mode(r, plans[0], self.nch, nbytes, False, out_cap=self.out_cap) if one else 0
             res = NS(kernel=name(D, mode), mode=mode, nt=max(P.nt for P in plans), stream=False)
         elif res is None:
             # the planner's own LDS tile: only what holds for every tile it can choose is claimed
             K, bound = max(P.K for P in plans), default_tile_bound(r)
             if self.nch < 8 or nbytes % 16 or not one:
                 mode = 0
+            elif self.out_cap is not None and self.nch * self.out_cap * 2 >= 1 << 32:
+                raise PlannerTile("without the table, the prologue of this call depends on the planner's tile")
             elif K <= FAST_ROWS:
                 mode = 2                                           # at most 32 tiles whatever the tile
             elif r.sr > 1 and bound <= r.sr and K > FAST_ROWS * bound:
@@ -363,10 +367,10 @@ def _extreme(D, j):
     return kinds[(D + j) % len(kinds)]
 
 
-def _case(cases, cause, D, fast, slow, nch, kt, steps, block=0, pre=0, exact=True):
+def _case(cases, cause, D, fast, slow, nch, kt, steps, block=0, pre=0, exact=True, out_cap=None):
     """steps: (want_nt or ('bytes', n), options) per call.  Every case gets random data in one call and an extreme kind in
-    another (the first two), then alternates."""
-    m = Model(D, fast, slow, nch, kt, block)
+    another (the first two), then alternates.  `out_cap`: the output pitch the case's calls will be given (fast_mode)."""
+    m = Model(D, fast, slow, nch, kt, block, out_cap)
     while pre and not m.split(pre):
         pre += 8                                                   # (the same phases again: a little more)
     case = NS(i=len(cases), cause=cause, D=D, fast=fast, slow=slow, nch=nch, kt=kt, block=block, pre=pre, calls=[],

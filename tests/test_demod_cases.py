@@ -169,6 +169,37 @@ def test_tile_limit_decides_the_names_at_32_and_33_tiles():
     assert n32 >= 2 * len(dc.ALL_FACTORS) and n33 >= 2 * len(dc.ALL_FACTORS)
 
 
+def test_output_size_decides_the_table():
+    """fmd_fast_geometry takes the table only while n_channels * out_stride * 2 < 2^32 (it addresses the output with 32-bit products):
+    at the three sizes of tests/test_gpu_big_demod.py every table call of the deterministic sweep stays a table call just under 2^32
+    bytes, and leaves the table at exactly 2^32 bytes and at a pitch of 2^31 - 256 bytes -- for the closed form where the tiles repeat
+    and the call has what the closed form needs, else for the general prologue.  A call that is no table call is not changed by
+    any of the sizes, and the default is the output far below the line that every other caller has."""
+    src = open(os.path.join(ROOT, "rtl-sdr-rs_amd", "csrc", "fmd_tile_launch.hip")).read()
+    assert "(uint64_t)L.n_channels * L.out_stride * 2ull < (1ull << 32)" in src
+    seen = {0: 0, 1: 0}
+    for c in TABLE:
+        if not c.kt or not one_class(c) or c.nch < 8:
+            continue
+        r = dc.rates(c.D, c.fast, c.slow, c.kt)
+        under = -(-(1 << 31) // c.nch) - 1                         # the largest out_cap with nch * out_cap * 2 < 2^32
+        for k in c.calls:
+            if k.nbytes % 16:
+                continue
+            P = dc.make_plan(r, k.p0[0], k.i0r[0], k.nbytes // 2)
+            modes = [dc.fast_mode(r, P, c.nch, k.nbytes, False, out_cap=cap) for cap in (None, k.K[0], under, under + 1, ((1 << 31) - 256) // 2)]
+            assert modes[:3] == [k.mode] * 3 and c.nch * under * 2 < 1 << 32 <= c.nch * (under + 1) * 2
+            if k.mode != 2:
+                assert modes[3:] == [k.mode] * 2
+                continue
+            closed = dc.fast_mode(r, P, c.nch, k.nbytes, False, tiles_limit=0)
+            assert modes[3:] == [closed] * 2 and closed in (0, 1) and (closed == 0 or dc.make_tiling(r).Rt == 0)
+            seen[closed] += 1
+    assert seen[0] >= len(dc.ALL_FACTORS) and seen[1] >= len(dc.ALL_FACTORS)
+    # 8 channels: out_cap 2^28 - 8 is under the line (the array ends 128 bytes below 2^32), 2^28 is on it
+    assert 8 * ((1 << 28) - 8) * 2 == (1 << 32) - 128 and 8 * (1 << 28) * 2 == 1 << 32
+
+
 # ---- the references ----------------------------------------------------------------------------------------------------------------
 
 def group(g):
