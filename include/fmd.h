@@ -946,6 +946,95 @@ int fmd_tonesq_status(fmd_tonesq *t, int32_t *tone, uint64_t *power, uint8_t *op
 /* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_tonesq_kernel_name(const fmd_tonesq *t, char *name, size_t cap);
 
+/* ---- code squelch: any bank's NFM rows gated by a digital code (DCS) ------------------------------------------------ */
+/* NEW SURFACE (the reference has no code decoder).  DCS, the digital-coded squelch, sends a 23-bit Golay word at 134.4 bit/s NRZ
+ * under the voice band, continuously.  Every int16 row a bank leaves on the device is searched for one of up to 128 such words and
+ * gated by the code that the blocks before decided on -- beside the tone squelch at the head of the output chain bank -> squelch ->
+ * AGC -> resampler; a row is one (stream, channel), `width` int16 per sample: 1 for mono audio, 2 for interleaved (L, R), whose
+ * mean is searched and whose components share the gate.  There is no clock recovery: every decimated sample k forms a word from
+ * samples one bit apart back in time and compares it un-rotated; the code repeats, so every alignment comes by once per word
+ * period (171 ms), and all k are independent.  Definition (integers only, exact; tests/dcs_ref.py), per row, with i the sample
+ * index since creation or reset; everything at a negative index is 0:
+ *   x[i][c]     int16 input, c < width
+ *   m[i]        = x[i][0]                         (width 1)
+ *               = (x[i][0] + x[i][1]) >> 1        (width 2; arithmetic shift)
+ *   box         b[k]    = (sum_{r<B} m[k B + r]) >> log2 B                     B = box, a power of two; b is int16 by construction
+ *   low-pass    soft[k] = sat16((sum_{t<T} lp[t] b[k - (T-1) + t]) >> lshift)  T = n_taps, |lp[t]| <= 1023; the sum is exact in
+ *                                                                              i32: 64 * 32768 * 1023 < 2^31 (as the tone squelch)
+ *   word        bit j of w[k] = 1 iff 23 soft[k - tap[j]] > sum_{j'<23} soft[k - tap[j']]
+ *               (tap[0] = 0, non-decreasing, tap[22] <= 511.  The threshold is the mean of the 23 samples: a mistuned channel's
+ *               DC does not move the slicer, and no high-pass is needed.)
+ *   match       d_f = popcount(w[k] ^ u_f) over the table u_f, f < F <= 128;  f(k) = the smallest f with d_f minimal;
+ *               k is a hit on f(k) if that d_f <= tol
+ *   block j     = samples [j P, (j+1) P), P = block; its k are j P / B <= k < (j+1) P / B
+ *               hits_f = the block's hits on f;  f* = the smallest f with hits_f maximal
+ *               hit_j  = f*  if hits_f* >= min_hits,  else NONE
+ * State per row and gate: exactly the tone squelch's.  (t, cand, cnt, h, s_prev, s_cur) from (NONE, NONE, 0, 0, 0, 0), stepped once
+ * per completed block j:
+ *   hit != NONE:  if hit == cand: cnt = min(cnt + 1, 65535)   else: cand = hit, cnt = 1
+ *   hit == NONE:  cand = NONE, cnt = 0
+ *   then:         cnt >= confirm:  t = cand, h = hang
+ *                 else if h > 0:   h = h - 1
+ *                 else:            t = NONE
+ *   s_j  = 256 if t != NONE and bit (t & 63) of accept[t >> 6] is set, else 0
+ * With s_{-1} = s_{-2} = 0, r = i mod P and Q = ramp (a power of two <= P):
+ *   g[i]      = s_{j-2} + (((s_{j-1} - s_{j-2}) (min(r, Q - 1) + 1)) >> log2 Q)
+ *   out[i][c] = (x[i][c] g[i]) >> 8
+ * An open gate passes x bit for bit, a closed gate writes zeros.
+ * Table bit order: bit j of u_f is compared with the sample tap[j] back, so bit 0 is the newest bit.  A DCS word c (bit 0 sent
+ * first) is therefore stored reversed: table bit j = bit 22 - j of c (fm::dcs_word, dcs_word of the Python package).
+ * Polarity: a discriminator of the other sign complements every word.  The complement of each of the 104 standard words is a
+ * rotation of another of the 104, so a table of all 104 still reports such a station, under its partner's index.
+ * Counts and state: every call returns n_out = n_in and fmd_dcs_out_cap(n_in) = n_in.  Per row the handle carries the open box's
+ * partial sum, the last T - 1 b, the last tap[22] soft, the F hit counters of the open block and eight int32 of state.  core.pos
+ * is the one counter; the rows layer's history is unused.
+ * Cut independence: everything carried is an exact integer, so the output and every report are independent of how the stream is
+ * cut into calls, calls of one sample and calls that span several block ends included.
+ * Reset: all-zero state is "closed, nothing carried" (t and cand are stored as t + 1, cand + 1).
+ * n_in == 0 is FMD_OK, launches nothing and changes nothing.  n_in > in_cap or out_cap < n_in -> FMD_ERR_CAPACITY (nothing is
+ * written or taken).  d_out == d_in is allowed when out_cap == in_cap (the gate in place); any other overlap is the caller's error.
+ * Domain (else FMD_ERR_UNSUPPORTED with a text, decided before a device is queried): width 1 or 2; block a multiple of 64 in
+ * [64, 32768]; box a power of two in [1, 64]; 1 <= n_taps <= 64; every lp entry in [-1023, 1023]; lshift <= 31; tap[0] = 0, tap
+ * non-decreasing, tap[22] <= 511; 1 <= n_words <= 128; every word below 2^23; tol <= 23; min_hits >= 1; 1 <= confirm <= 255;
+ * hang <= 65535; ramp a power of two in [1, block]; n_rows = dev->n_channels >= 1.  Stream lifetime and completion points: as
+ * fmd_channelizer_* (fmd_dcs_check). */
+typedef struct fmd_dcs fmd_dcs;
+typedef struct fmd_dcs_config {
+    uint32_t block;      /* P: samples per decision block                                      */
+    uint32_t box;        /* B: samples per decimated sample                                    */
+    uint32_t n_taps;     /* T: taps of the low-pass                                            */
+    int16_t lp[64];      /* the low-pass, lp[T - 1] on the newest b; entries behind T unused   */
+    uint32_t lshift;     /* the low-pass sum's shift                                           */
+    uint32_t tap[23];    /* decimated samples from the newest bit back to bit j                */
+    uint32_t tol;        /* bit errors a matching word may have                                */
+    uint32_t min_hits;   /* the least hits_f* of a block that is a hit                         */
+    uint32_t confirm;    /* equal hits in a row that open                                      */
+    uint32_t hang;       /* blocks the code is held after the last confirmed one               */
+    uint32_t ramp;       /* Q: samples over which the gate moves at the start of a block       */
+    uint64_t accept[2];  /* bit f & 63 of accept[f >> 6]: word f opens the gate                */
+} fmd_dcs_config;
+/* words: [n_words] table words u_f, 23 bits each. */
+int fmd_dcs_new(const fmd_dcs_config *cfg, const uint32_t *words, uint32_t n_words, uint32_t width,
+                const fmd_device_config *dev, fmd_dcs **out);
+void fmd_dcs_free(fmd_dcs *d);
+int fmd_dcs_reset(fmd_dcs *d);
+/* n_in. */
+size_t fmd_dcs_out_cap(size_t n_in);
+/* HOST buffers: in [n_rows][in_cap][width], the first n_in samples of each row valid; out [n_rows][out_cap][width]; *n_out = n_in. */
+int fmd_dcs_run_batch(fmd_dcs *d, const int16_t *in, size_t n_in, size_t in_cap, int16_t *out, size_t out_cap, size_t *n_out);
+/* DEVICE buffers, enqueued on `stream` without synchronising: d_in is a bank's d_out as it stands, with the bank's out_cap as
+ * in_cap; pointers 4-byte aligned at width 2 and 2-byte aligned at width 1, any in_cap and out_cap. */
+int fmd_dcs_run_device(fmd_dcs *d, const void *d_in, size_t n_in, size_t in_cap, void *d_out, size_t out_cap, size_t *n_out,
+                       void *stream);
+int fmd_dcs_check(fmd_dcs *d);
+/* Samples taken and produced per row since creation or the last reset (the same number). */
+int fmd_dcs_outputs(const fmd_dcs *d, uint64_t *inputs, uint64_t *outputs);
+/* Host arrays [n_rows], after the last completed block: code = t (-1: NONE), hits = hits_f* of that block, open = s_j != 0; -1 / 0 /
+ * 0 before the first block.  Synchronises first. */
+int fmd_dcs_status(fmd_dcs *d, int32_t *code, uint32_t *hits, uint8_t *open);
+/* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_dcs_kernel_name(const fmd_dcs *d, char *name, size_t cap);
+
 /* ---- packet demodulator: AX.25 frames (APRS) out of any bank's NFM rows --------------------------------------------- */
 /* NEW SURFACE (the reference has no data decoder).  1200 baud AFSK packet in two halves, as fmd_rds_* and fmd_rds_decoder_* are for
  * RDS: fmd_afsk_* on the GPU turns every mono int16 row a bank leaves on the device into signed soft decisions, a few per bit;

@@ -251,6 +251,16 @@ PROTOTYPES = {
     "fmd_tonesq_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fmd_tonesq_status": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _u8p]),
     "fmd_tonesq_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_dcs_new": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_dcs_free": (None, [_vp]),
+    "fmd_dcs_reset": (C.c_int, [_vp]),
+    "fmd_dcs_out_cap": (_sz, [_sz]),
+    "fmd_dcs_run_batch": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp]),
+    "fmd_dcs_run_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_dcs_check": (C.c_int, [_vp]),
+    "fmd_dcs_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fmd_dcs_status": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _u8p]),
+    "fmd_dcs_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_afsk_new": (C.c_int, [_i16p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
     "fmd_afsk_free": (None, [_vp]),
     "fmd_afsk_reset": (C.c_int, [_vp]),

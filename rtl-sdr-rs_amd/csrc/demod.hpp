@@ -980,6 +980,122 @@ private:
     uint32_t block_;
 };
 
+// The 104 standard DCS codes (written in octal).
+inline const std::vector<uint32_t>& dcs_codes()
+{
+    static const std::vector<uint32_t> codes{
+        0023, 0025, 0026, 0031, 0032, 0036, 0043, 0047, 0051, 0053, 0054, 0065, 0071, 0072, 0073, 0074,
+        0114, 0115, 0116, 0122, 0125, 0131, 0132, 0134, 0143, 0145, 0152, 0155, 0156, 0162, 0165, 0172, 0174,
+        0205, 0212, 0223, 0225, 0226, 0243, 0244, 0245, 0246, 0251, 0252, 0255, 0261, 0263, 0265, 0266, 0271, 0274,
+        0306, 0311, 0315, 0325, 0331, 0332, 0343, 0346, 0351, 0356, 0364, 0365, 0371,
+        0411, 0412, 0413, 0423, 0431, 0432, 0445, 0446, 0452, 0454, 0455, 0462, 0464, 0465, 0466,
+        0503, 0506, 0516, 0523, 0526, 0532, 0546, 0565,
+        0606, 0612, 0624, 0627, 0631, 0632, 0654, 0662, 0664,
+        0703, 0712, 0723, 0731, 0732, 0734, 0743, 0754};
+    return codes;
+}
+
+// c(x) mod the DCS polynomial x^11 + x^10 + x^6 + x^5 + x^4 + x^2 + 1 (0xC75), c below 2^23.
+inline uint32_t dcs_remainder(uint32_t c)
+{
+    for (int i = 22; i > 10; --i)
+        if ((c >> i) & 1u) c ^= 0xC75u << (i - 11);
+    return c;
+}
+
+// The 23-bit word c = (p << 12) | 0x800 | code of a 9-bit code, bit 0 sent first: the 11 parity bits p make c(x) divisible by the DCS
+// polynomial.  dcs_codeword(023) = 0x763813.
+inline uint32_t dcs_codeword(uint32_t code)
+{
+    if (code >= 512) throw Error(FMD_ERR_INVALID_ARG);
+    const uint32_t d = 0x800u | code;
+    for (uint32_t p = 0; p < 2048; ++p)
+        if (dcs_remainder((p << 12) | d) == 0) return (p << 12) | d;
+    throw Error(FMD_ERR_INVALID_ARG);
+}
+
+// The table word of a code for a CodeSquelch, word for word the Python dcs_word(): the codeword, complemented if `inverted`, in the
+// order of arrival: table bit j = bit 22 - j of the codeword.  dcs_word(023) = 0x640E37.
+inline uint32_t dcs_word(uint32_t code, bool inverted = false)
+{
+    uint32_t c = dcs_codeword(code), w = 0;
+    if (inverted) c ^= 0x7FFFFFu;
+    for (uint32_t j = 0; j < 23; ++j) w |= ((c >> (22 - j)) & 1u) << j;
+    return w;
+}
+
+// The configuration of a CodeSquelch for DCS at the sample rate `rate`, entry for entry the Python dcs_design(): box the power of
+// two that puts rate / box nearest 1500 Hz; lp a Hamming-windowed sinc of 32 taps at 200 Hz, scaled to peak 1023; lshift =
+// ceil(log2(sum |lp|)); tap[j] = floor(j rate / (134.4 box) + 0.5); block two whole word periods, up to a multiple of 64; tol 1,
+// min_hits 8, confirm 1, hang 1, ramp 64; accept every word.
+inline fmd_dcs_config dcs_design(double rate)
+{
+    if (!(rate > 0)) throw Error(FMD_ERR_INVALID_ARG);
+    fmd_dcs_config cfg{};
+    uint32_t box = 1;
+    double best = std::fabs(rate - 1500.0);
+    for (uint32_t lg = 1; lg < 7; ++lg) {
+        const double d = std::fabs(rate / (double)(1u << lg) - 1500.0);
+        if (d < best) { box = 1u << lg; best = d; }
+    }
+    const uint32_t T = 32;
+    const double fc = 200.0 * (double)box / rate;
+    double h[32], peak = 0;
+    for (uint32_t t = 0; t < T; ++t) {
+        const double x = 2 * detail::pi * fc * ((double)t - (double)(T - 1) / 2.0);
+        h[t] = detail::sinc(x) * (0.54 - 0.46 * std::cos(2 * detail::pi * (double)t / (double)(T - 1)));
+        if (t == 0 || h[t] > peak) peak = h[t];
+    }
+    uint32_t mag = 0;
+    for (uint32_t t = 0; t < T; ++t) {
+        cfg.lp[t] = (int16_t)std::rint(1023.0 * h[t] / peak);
+        mag += (uint32_t)(cfg.lp[t] < 0 ? -cfg.lp[t] : cfg.lp[t]);
+    }
+    while ((1u << cfg.lshift) < mag) ++cfg.lshift;
+    for (uint32_t j = 0; j < 23; ++j) cfg.tap[j] = (uint32_t)std::floor((double)j * rate / (134.4 * (double)box) + 0.5);
+    const double blocks = std::ceil(46.0 * rate / (134.4 * 64.0));
+    if (cfg.tap[22] > 511 || blocks > 512) throw Error(FMD_ERR_UNSUPPORTED);
+    cfg.block = 64u * (uint32_t)blocks;
+    cfg.box = box; cfg.n_taps = T;
+    cfg.tol = 1; cfg.min_hits = 8; cfg.confirm = 1; cfg.hang = 1; cfg.ramp = 64;
+    cfg.accept[0] = cfg.accept[1] = ~0ull;
+    return cfg;
+}
+
+// Code squelch (fmd_dcs_*): `words` is the table of 23-bit words (dcs_word); run() takes [n_rows][n_in][width] int16 and returns the
+// same samples per row, gated by the code the blocks before decided on.  A station whose discriminator has the other sign is
+// reported under its code's inverse partner (023 as 047).
+class CodeSquelch : public RowProcessor<fmd_dcs, fmd_dcs_free, fmd_dcs_run_batch, fmd_dcs_outputs, fmd_dcs_reset> {
+public:
+    struct Status { int32_t code; uint32_t hits; bool open; };
+
+    CodeSquelch(const fmd_dcs_config& cfg, const std::vector<uint32_t>& words, uint32_t n_rows = 1, uint32_t width = 1,
+                int32_t device_id = -1)
+        : RowProcessor(n_rows, width), block_(cfg.block)
+    {
+        fmd_device_config dev{n_rows, device_id, 0};
+        check(fmd_dcs_new(&cfg, words.data(), (uint32_t)words.size(), width, &dev, h_.out()));
+    }
+
+    Rows run(const int16_t* x, size_t n_in) { return run_rows(x, n_in, fmd_dcs_out_cap(n_in)); }
+    // per row after the last completed block: the selected word's index (-1: none), the hits of the block's most-hit word, whether
+    // the gate opens
+    std::vector<Status> status()
+    {
+        std::vector<int32_t> code(n_rows_);
+        std::vector<uint32_t> hits(n_rows_);
+        std::vector<uint8_t> open(n_rows_);
+        check(fmd_dcs_status(h_, code.data(), hits.data(), open.data()));
+        std::vector<Status> res(n_rows_);
+        for (size_t r = 0; r < n_rows_; ++r) res[r] = Status{code[r], hits[r], open[r] != 0};
+        return res;
+    }
+    uint32_t block() const { return block_; }
+
+private:
+    uint32_t block_;
+};
+
 // The table of an AfskDemod with its shifts, entry for entry the Python afsk_table(): rectangular windows one bit long, T = taps or
 // round(rate / baud); tab[4][T] = mark-cos, mark-sin, space-cos, space-sin = rint(1023 cos(2 pi f t / rate)), rint(-1023 sin(...));
 // pre_shift 8; out_shift the smallest at which a full window of either tone at amplitude 1024 stays inside int16.

@@ -239,6 +239,29 @@ pub struct fmd_tonesq_config {
 }
 
 #[repr(C)]
+pub struct fmd_dcs {
+    _private: [u8; 0],
+}
+
+/// `fmd_dcs_config` of include/fmd.h (code squelch).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fmd_dcs_config {
+    pub block: u32,
+    pub box_: u32,
+    pub n_taps: u32,
+    pub lp: [i16; 64],
+    pub lshift: u32,
+    pub tap: [u32; 23],
+    pub tol: u32,
+    pub min_hits: u32,
+    pub confirm: u32,
+    pub hang: u32,
+    pub ramp: u32,
+    pub accept: [u64; 2],
+}
+
+#[repr(C)]
 pub struct fmd_afsk {
     _private: [u8; 0],
 }
@@ -462,6 +485,16 @@ extern "C" {
     pub fn fmd_tonesq_outputs(t: *const fmd_tonesq, inputs: *mut u64, outputs: *mut u64) -> c_int;
     pub fn fmd_tonesq_status(t: *mut fmd_tonesq, tone: *mut i32, power: *mut u64, open: *mut u8) -> c_int;
     pub fn fmd_tonesq_kernel_name(t: *const fmd_tonesq, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_dcs_new(cfg: *const fmd_dcs_config, words: *const u32, n_words: u32, width: u32, dev: *const DeviceConfig, out: *mut *mut fmd_dcs) -> c_int;
+    pub fn fmd_dcs_free(d: *mut fmd_dcs);
+    pub fn fmd_dcs_reset(d: *mut fmd_dcs) -> c_int;
+    pub fn fmd_dcs_out_cap(n_in: usize) -> usize;
+    pub fn fmd_dcs_run_batch(d: *mut fmd_dcs, input: *const i16, n_in: usize, in_cap: usize, out: *mut i16, out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn fmd_dcs_run_device(d: *mut fmd_dcs, d_in: *const c_void, n_in: usize, in_cap: usize, d_out: *mut c_void, out_cap: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_dcs_check(d: *mut fmd_dcs) -> c_int;
+    pub fn fmd_dcs_outputs(d: *const fmd_dcs, inputs: *mut u64, outputs: *mut u64) -> c_int;
+    pub fn fmd_dcs_status(d: *mut fmd_dcs, code: *mut i32, hits: *mut u32, open: *mut u8) -> c_int;
+    pub fn fmd_dcs_kernel_name(d: *const fmd_dcs, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_afsk_new(table: *const i16, t: u32, d: u32, pre_shift: u32, out_shift: u32, width: u32, dev: *const DeviceConfig, out: *mut *mut fmd_afsk) -> c_int;
     pub fn fmd_afsk_free(a: *mut fmd_afsk);
     pub fn fmd_afsk_reset(a: *mut fmd_afsk) -> c_int;
