@@ -1118,6 +1118,135 @@ int fmd_ax25_decoder_reset(fmd_ax25_decoder *d);
 int fmd_ax25_decoder_push(fmd_ax25_decoder *d, const int16_t *soft, size_t n, fmd_ax25_frame *frames, size_t cap, size_t *n_frames);
 int fmd_ax25_decoder_info(const fmd_ax25_decoder *d, fmd_ax25_info *info);
 
+/* ---- pager decoder: POCSAG messages out of any bank's NFM rows --------------------------------------------------------- */
+/* NEW SURFACE (the reference has no data decoder).  POCSAG paging (direct 2-FSK at 512, 1200 or 2400 bit/s) in two halves:
+ * fmd_fsk_* on the GPU turns every mono int16 row a bank leaves on the device into soft decisions, a few per bit, and reports
+ * where a 32-bit sync word ends; fmd_pocsag_decoder_* on the host, one per row, reads the batches behind those reports.  There is no
+ * clock recovery: every batch starts with the sync codeword 0x7CD215D8, the kernel tests every soft sample for it, and what it
+ * finds gives the host the bit timing, the slicer level (which holds the DC a mistuned channel leaves on the discriminator) and
+ * the polarity.
+ *
+ * fmd_fsk_*: a row processor; a row is one (stream, channel), width 1 only (width 2 is FMD_ERR_UNSUPPORTED).  Definition (integers
+ * only, exact; tests/fsk_ref.py), per row; everything at a negative index is 0:
+ *   x[i]      int16 input, i counted from creation or reset
+ *   box       b[k]    = sum_{r < D} x[k D + r]                         (i32)
+ *   soft      soft[k] = (sum_{t < W} b[k - t]) >> shift                (arithmetic shift; D W <= 2^shift, so soft is an int16 by
+ *                                                                      construction and nothing saturates)
+ *   out[k]    = soft[k]; output k comes with the call that brings x[k D + D - 1]
+ *   word      thr[k]  = sum_{j < 32} soft[k - tap[j]]                  (tap[0] = 0, non-decreasing, tap[31] <= 255)
+ *             bit j of w[k] = 1 iff 32 soft[k - tap[j]] > thr[k]       (equality: 0)
+ *   match     d[k]    = popcount(w[k] ^ sync)
+ *             C[k]    = sum_j (bit j of sync ? +1 : -1) soft[k - tap[j]]        (|C| <= 2^20)
+ *   hit       normal   if d <= tol       and  C >= min_corr
+ *             inverted if d >= 32 - tol  and -C >= min_corr            (tol <= 15, so never both)
+ *   record    fmd_fsk_hit of every hit; k_rel = index of out[k] in THIS call
+ * Bit order: POCSAG sends bit 31 first, so the newest bit is bit 0; table bit j is bit j of the codeword and sync is 0x7CD215D8
+ * as written.
+ * Counting: a call gives floor((pos + n_in) / D) - floor(pos / D) outputs; fmd_fsk_out_cap(D, n_in) = ceil(n_in / D) + 1 bounds
+ * them.  A call that completes no box is taken (FMD_OK, 0 outputs, the partial sum carried).  n_in == 0 launches nothing and leaves
+ * the last call's hits as they are.  n_in > in_cap, or out_cap below the call's outputs -> FMD_ERR_CAPACITY, nothing is written or
+ * taken.
+ * Per call and row: count, the number of hits, all of them; and the first min(count, hit_cap) records, in increasing k.  Both live
+ * in device memory of the handle, are replaced by the next call that launches, and are read with fmd_fsk_hits.
+ * Carried per row: the open box's partial sum, the last W - 1 b, the last tap[31] soft.  All zeros is "nothing carried", which is
+ * what reset leaves.  Everything carried is an exact integer, so outputs and records are independent of how the stream is cut
+ * into calls, calls of one sample and calls that complete no box included.
+ * Domain (else FMD_ERR_UNSUPPORTED with a text, decided before a device is queried): width 1; 1 <= D <= 64; 1 <= W <= 16;
+ * shift <= 10 and D W <= 2^shift; tap[0] = 0, tap non-decreasing, tap[31] <= 255; tol <= 15; 0 <= min_corr <= 2^20;
+ * 1 <= hit_cap <= 64; n_rows = dev->n_channels >= 1.  Stream lifetime and completion points: as fmd_channelizer_*
+ * (fmd_fsk_check).  The designers (fsk_design in Python, fm::fsk_design in csrc/demod.hpp): D = max(1, floor(rate / (5 baud) +
+ * 0.5)), W = floor(rate / (baud D) + 0.5), shift = ceil(log2(D W)), tap[j] = floor(j rate / (baud D) + 0.5), sync 0x7CD215D8,
+ * tol 2, min_corr 1024, hit_cap 16. */
+typedef struct fmd_fsk fmd_fsk;
+typedef struct fmd_fsk_config {
+    uint32_t D;          /* samples per box: the decimation                        */
+    uint32_t W;          /* boxes per soft decision: D W samples are about one bit */
+    uint32_t shift;      /* the soft decision's shift                              */
+    uint32_t tap[32];    /* soft samples from the newest bit back to bit j         */
+    uint32_t sync;       /* the word searched for                                  */
+    uint32_t tol;        /* bit errors a hit may have                              */
+    int32_t min_corr;    /* the least |C| of a hit                                 */
+    uint32_t hit_cap;    /* records kept per row and call                          */
+} fmd_fsk_config;
+typedef struct fmd_fsk_hit {
+    uint32_t k_rel;      /* index of out[k] in the call that reported it           */
+    uint32_t d;          /* bits that differ, | 1 << 31 for an inverted hit        */
+    int32_t corr;        /* C                                                      */
+    int32_t thr;         /* the sum of the 32 soft samples: slice 32 soft > thr    */
+} fmd_fsk_hit;
+int fmd_fsk_new(const fmd_fsk_config *cfg, uint32_t width, const fmd_device_config *dev, fmd_fsk **out);
+void fmd_fsk_free(fmd_fsk *f);
+int fmd_fsk_reset(fmd_fsk *f);
+/* ceil(n_in / D) + 1; 0 when D is 0. */
+size_t fmd_fsk_out_cap(uint32_t D, size_t n_in);
+/* HOST buffers: in [n_rows][in_cap], the first n_in samples of each row valid; out [n_rows][out_cap]; *n_out outputs per row. */
+int fmd_fsk_run_batch(fmd_fsk *f, const int16_t *in, size_t n_in, size_t in_cap, int16_t *out, size_t out_cap, size_t *n_out);
+/* DEVICE buffers, enqueued on `stream` without synchronising: d_in is a bank's d_out as it stands, with the bank's out_cap as
+ * in_cap; pointers 2-byte aligned, any in_cap and out_cap. */
+int fmd_fsk_run_device(fmd_fsk *f, const void *d_in, size_t n_in, size_t in_cap, void *d_out, size_t out_cap, size_t *n_out,
+                       void *stream);
+int fmd_fsk_check(fmd_fsk *f);
+/* Samples taken and soft decisions produced per row since creation or the last reset. */
+int fmd_fsk_outputs(const fmd_fsk *f, uint64_t *inputs, uint64_t *outputs);
+/* Host arrays of the last call that launched: counts [n_rows], hits [n_rows][hit_cap] (zeros behind a row's records).  Either may
+ * be NULL.  Synchronises first. */
+int fmd_fsk_hits(fmd_fsk *f, uint32_t *counts, fmd_fsk_hit *hits);
+/* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_fsk_kernel_name(const fmd_fsk *f, char *name, size_t cap);
+
+/* fmd_pocsag_decoder_*: the batch decoder of one row, on the host, no GPU.  Definition (integers only; tests/pocsag_ref.py; the
+ * result does not depend on how the samples and records are cut into pushes), with mod = rate_num and step = baud * rate_den (u64),
+ * the soft decisions arriving at rate_num / rate_den per second (the audio rate over D), r = (2 mod + step) / (2 step) soft samples
+ * per bit, and a ring of the last 64 soft samples.  Sample and record indices count from creation or reset; a record belongs to the
+ * sample k_rel of its push, records whose k_rel is not below n or not in increasing order are ignored.  Per sample, in this order:
+ * the sample enters the ring; its records are taken; a search window that is due closes; the bits and the slot that are due are read.
+ *   search  the first record opens a window anchored at its index k1; a later record with k <= k1 + r and strictly larger |corr|
+ *           replaces the candidate; when sample k1 + r has arrived the decoder locks on the candidate: k0, thr, inverted.
+ *   locked  bit n >= 1 is (32 soft[p(n)] > thr) xor inverted, p(n) = k0 + (2 n mod + step) / (2 step); word i = 0 ... 15 is bits
+ *           32 i + 1 ... 32 i + 32, first bit highest.  Slot 16 is the next sync, and the records alone decide it: when sample
+ *           p(544) + r / 2 has arrived, of the records with |k - p(544)| <= r / 2 and the lock's polarity the one with the largest
+ *           |corr|, the first such, becomes the new (k0, thr) and the next batch follows; with none the lock is lost, the open
+ *           message closes and the decoder searches again.  Other records are ignored while locked.
+ *   word    the corrected word is the unique valid codeword within Hamming distance max_errors over all 32 bits; valid: bits 31..1
+ *           divisible by x^10 + x^9 + x^8 + x^6 + x^5 + x^3 + 1 (0x769) and even parity over all 32.  The minimum distance is 6,
+ *           so it is unique for max_errors <= 2.  With none, bad_codewords counts and the open message closes.
+ *           0x7A89C197 (idle) closes the open message.  Bit 31 = 0: an address word, closes the open message and opens one with
+ *           address = ((cw >> 13) & 0x3FFFF) << 3 | (i >> 1), function = (cw >> 11) & 3.  Bit 31 = 1: a message word, appends
+ *           (cw >> 11) & 0xFFFFF, highest bit first, to the open message (bits behind 2560 are counted, not stored); with no
+ *           message open it counts in orphans.
+ * A closed message is delivered.  Messages that do not fit `msgs` wait in a ring of 64, whose oldest gives way when it fills.
+ * Domain: 2 <= (rate_num / rate_den) / baud <= 32 ("need 2 <= rate / baud <= 32") and max_errors <= 2 ("need max_errors <= 2"),
+ * else FMD_ERR_UNSUPPORTED. */
+typedef struct fmd_pocsag_decoder fmd_pocsag_decoder;
+typedef struct fmd_pocsag_msg {
+    uint32_t address;        /* 21 bits: 18 of the address word, 3 of its frame                          */
+    uint32_t function;       /* 0 ... 3                                                                  */
+    uint32_t n_bits;         /* message bits, 20 per message word; 0: a tone-only page                   */
+    uint8_t bits[320];       /* the first 2560 of them, the first in bit 7 of bits[0]                    */
+    uint32_t corrected;      /* bits corrected in the message's codewords                                */
+    uint32_t inverted;       /* the lock's polarity                                                      */
+    uint64_t end_sample;     /* index of the soft sample that gave the last bit of its last codeword     */
+} fmd_pocsag_msg;
+typedef struct fmd_pocsag_info {
+    uint64_t messages;       /* messages closed, delivered or waiting                  */
+    uint64_t batches;        /* sync words the decoder locked on or followed           */
+    uint64_t bad_codewords;  /* words with no valid codeword within max_errors         */
+    uint64_t orphans;        /* message words with no message open                     */
+    int locked;              /* inside a batch or waiting for the next sync word       */
+    int searching;           /* a record opened a search window that is not due yet    */
+} fmd_pocsag_info;
+int fmd_pocsag_decoder_new(uint32_t rate_num, uint32_t rate_den, uint32_t baud, uint32_t max_errors, fmd_pocsag_decoder **out);
+void fmd_pocsag_decoder_free(fmd_pocsag_decoder *d);
+int fmd_pocsag_decoder_reset(fmd_pocsag_decoder *d);
+/* n soft decisions and this call's n_hits records of the row in (k_rel counted into soft); up to `cap` messages out, oldest first.
+ * Messages that do not fit stay queued and come with the next push (n may be 0, soft then NULL: it drains). */
+int fmd_pocsag_decoder_push(fmd_pocsag_decoder *d, const int16_t *soft, size_t n, const fmd_fsk_hit *hits, size_t n_hits,
+                            fmd_pocsag_msg *msgs, size_t cap, size_t *n_msgs);
+int fmd_pocsag_decoder_info(const fmd_pocsag_decoder *d, fmd_pocsag_info *info);
+/* The corrected codeword of `word` within `max_errors` (<= 2) bit errors in *cw and the bits flipped in *n_fixed (either may be
+ * NULL): FMD_OK, or FMD_ERR_BAD_STATE when there is none. */
+int fmd_pocsag_correct(uint32_t word, uint32_t max_errors, uint32_t *cw, uint32_t *n_fixed);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

@@ -275,6 +275,22 @@ PROTOTYPES = {
     "fmd_ax25_decoder_reset": (C.c_int, [_vp]),
     "fmd_ax25_decoder_push": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
     "fmd_ax25_decoder_info": (C.c_int, [_vp, _vp]),
+    "fmd_fsk_new": (C.c_int, [_vp, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_fsk_free": (None, [_vp]),
+    "fmd_fsk_reset": (C.c_int, [_vp]),
+    "fmd_fsk_out_cap": (_sz, [C.c_uint32, _sz]),
+    "fmd_fsk_run_batch": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp]),
+    "fmd_fsk_run_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _szp, _vp]),
+    "fmd_fsk_check": (C.c_int, [_vp]),
+    "fmd_fsk_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fmd_fsk_hits": (C.c_int, [_vp, _vp, _vp]),
+    "fmd_fsk_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_pocsag_decoder_new": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "fmd_pocsag_decoder_free": (None, [_vp]),
+    "fmd_pocsag_decoder_reset": (C.c_int, [_vp]),
+    "fmd_pocsag_decoder_push": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _szp]),
+    "fmd_pocsag_decoder_info": (C.c_int, [_vp, _vp]),
+    "fmd_pocsag_correct": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

@@ -1233,6 +1233,141 @@ inline std::string ax25_text(const uint8_t* data, size_t len)
 }
 inline std::string ax25_text(const fmd_ax25_frame& f) { return ax25_text(f.data, std::min<size_t>(f.len, sizeof f.data)); }
 
+// fsk_design(rate, baud) of the Python package, entry for entry (scalar libm in the same order): the FSK front end's parameters for
+// POCSAG at `baud` bit/s in audio at `rate` Hz.  A pair whose result leaves the kernel's domain throws std::invalid_argument.
+inline fmd_fsk_config fsk_design(double rate, double baud = 1200)
+{
+    if (!(rate > 0) || !(baud > 0)) throw std::invalid_argument("need rate > 0 and baud > 0");
+    fmd_fsk_config cfg{};
+    const double d = std::floor(rate / (5.0 * baud) + 0.5);
+    if (d > 64) throw std::invalid_argument("rate / baud out of range");
+    cfg.D = std::max<uint32_t>(1, (uint32_t)d);
+    const double w = std::floor(rate / (baud * (double)cfg.D) + 0.5);
+    if (!(w >= 1 && w <= 16)) throw std::invalid_argument("rate / baud out of range");
+    cfg.W = (uint32_t)w;
+    while ((1u << cfg.shift) < cfg.D * cfg.W) ++cfg.shift;
+    bool ok = cfg.shift <= 10;
+    for (uint32_t j = 0; j < 32; ++j) {
+        const double t = std::floor((double)j * rate / (baud * (double)cfg.D) + 0.5);
+        ok = ok && t <= 255;
+        cfg.tap[j] = ok ? (uint32_t)t : 0;
+        ok = ok && (j == 0 || cfg.tap[j] >= cfg.tap[j - 1]);
+    }
+    if (!ok) throw std::invalid_argument("rate / baud out of range");
+    cfg.sync = 0x7CD215D8u; cfg.tol = 2; cfg.min_corr = 1024; cfg.hit_cap = 16;
+    return cfg;
+}
+
+// FSK front end of the pager decoder (fmd_fsk_*): run() takes [n_rows][n_in] int16 and returns the call's soft decisions per row,
+// one per cfg.D samples (none from a call that completes no box); hits() what that call found.
+class FskDemod : public RowProcessor<fmd_fsk, fmd_fsk_free, fmd_fsk_run_batch, fmd_fsk_outputs, fmd_fsk_reset> {
+public:
+    explicit FskDemod(const fmd_fsk_config& cfg, uint32_t n_rows = 1, uint32_t width = 1, int32_t device_id = -1)
+        : RowProcessor(n_rows, width), cfg_(cfg)
+    {
+        fmd_device_config dev{n_rows, device_id, 0};
+        check(fmd_fsk_new(&cfg, width, &dev, h_.out()));
+    }
+
+    Rows run(const int16_t* x, size_t n_in) { return run_rows(x, n_in, fmd_fsk_out_cap(cfg_.D, n_in)); }
+
+    // per row: the records of the last call that launched, the first min(count, hit_cap) of them; counts (optional): all hits
+    std::vector<std::vector<fmd_fsk_hit>> hits(std::vector<uint32_t>* counts = nullptr)
+    {
+        std::vector<uint32_t> cnt(n_rows_);
+        std::vector<fmd_fsk_hit> rec((size_t)n_rows_ * cfg_.hit_cap);
+        check(fmd_fsk_hits(h_, cnt.data(), rec.data()));
+        std::vector<std::vector<fmd_fsk_hit>> res(n_rows_);
+        for (size_t r = 0; r < n_rows_; ++r)
+            res[r].assign(rec.begin() + r * cfg_.hit_cap, rec.begin() + r * cfg_.hit_cap + std::min<uint32_t>(cnt[r], cfg_.hit_cap));
+        if (counts) *counts = cnt;
+        return res;
+    }
+    const fmd_fsk_config& config() const { return cfg_; }
+
+private:
+    fmd_fsk_config cfg_;
+};
+
+// POCSAG batch decoder of one row (fmd_pocsag_decoder_*, host only): push() takes an FskDemod's soft decisions at rate_num /
+// rate_den per second (the audio rate over D) with the row's records of the same call and returns the messages closed since.
+class PocsagDecoder {
+public:
+    PocsagDecoder(uint32_t rate_num, uint32_t rate_den, uint32_t baud = 1200, uint32_t max_errors = 1)
+    {
+        check(fmd_pocsag_decoder_new(rate_num, rate_den, baud, max_errors, h_.out()));
+    }
+
+    std::vector<fmd_pocsag_msg> push(const int16_t* soft, size_t n, const fmd_fsk_hit* hits, size_t n_hits)
+    {
+        std::vector<fmd_pocsag_msg> res;
+        std::vector<fmd_pocsag_msg> buf(16);
+        size_t k = 0;
+        check(fmd_pocsag_decoder_push(h_, soft, n, hits, n_hits, buf.data(), 16, &k));
+        for (;;) {
+            res.insert(res.end(), buf.begin(), buf.begin() + k);
+            if (k < 16) return res;
+            check(fmd_pocsag_decoder_push(h_, nullptr, 0, nullptr, 0, buf.data(), 16, &k));
+        }
+    }
+    std::vector<fmd_pocsag_msg> push(const std::vector<int16_t>& soft, const std::vector<fmd_fsk_hit>& hits)
+    {
+        return push(soft.data(), soft.size(), hits.data(), hits.size());
+    }
+    fmd_pocsag_info info() const { return value_of<fmd_pocsag_info>(fmd_pocsag_decoder_info, h_); }
+    void reset() { check(fmd_pocsag_decoder_reset(h_)); }
+
+private:
+    Owned<fmd_pocsag_decoder, fmd_pocsag_decoder_free> h_;
+};
+
+namespace detail {
+// message bit i, the first in bit 7 of bits[0]; the stored bits only
+inline uint32_t pocsag_bit(const fmd_pocsag_msg& m, uint32_t i) { return (m.bits[i >> 3] >> (7 - (i & 7u))) & 1u; }
+inline uint32_t pocsag_stored(const fmd_pocsag_msg& m) { return std::min<uint32_t>(m.n_bits, 8 * sizeof m.bits); }
+}  // namespace detail
+
+// The message's bits as numeric text, character for character the Python pocsag_numeric(): 4 bits per character, each nibble
+// bit-reversed, from the table 0123456789*U -)(.
+inline std::string pocsag_numeric(const fmd_pocsag_msg& m)
+{
+    static const char* const table = "0123456789*U -)(";
+    std::string s;
+    for (uint32_t i = 0; i + 4 <= detail::pocsag_stored(m); i += 4) {
+        uint32_t v = 0;
+        for (uint32_t j = 0; j < 4; ++j) v |= detail::pocsag_bit(m, i + j) << j;
+        s += table[v];
+    }
+    return s;
+}
+
+// The message's bits as text, as pocsag_alpha() of the Python package: 7 bits per character, each reversed; trailing NUL, ETX and
+// EOT dropped, other non-printable characters as `.`.
+inline std::string pocsag_alpha(const fmd_pocsag_msg& m)
+{
+    std::vector<uint32_t> ch;
+    for (uint32_t i = 0; i + 7 <= detail::pocsag_stored(m); i += 7) {
+        uint32_t v = 0;
+        for (uint32_t j = 0; j < 7; ++j) v |= detail::pocsag_bit(m, i + j) << j;
+        ch.push_back(v);
+    }
+    while (!ch.empty() && (ch.back() == 0 || ch.back() == 3 || ch.back() == 4)) ch.pop_back();
+    std::string s;
+    for (uint32_t c : ch) s += c >= 32 && c < 127 ? (char)c : '.';
+    return s;
+}
+
+// One line per message, as pocsag_text() of the Python package; mode 0: auto (function 0 numeric, the rest alpha), 1: numeric,
+// 2: alpha.
+inline std::string pocsag_text(const fmd_pocsag_msg& m, uint32_t baud = 1200, int mode = 0)
+{
+    char head[96];
+    snprintf(head, sizeof head, "POCSAG%u: Address: %07u  Function: %u  ", baud, m.address, m.function);
+    if (m.n_bits == 0) return std::string(head) + "Tone: ";
+    if (mode == 1 || (mode == 0 && m.function == 0)) return std::string(head) + "Numeric: " + pocsag_numeric(m);
+    return std::string(head) + "Alpha: " + pocsag_alpha(m);
+}
+
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.
 inline void output(const std::vector<int16_t>& buf, FILE* f = stdout)
 {

@@ -291,6 +291,65 @@ pub struct fmd_ax25_info {
 }
 
 #[repr(C)]
+pub struct fmd_fsk {
+    _private: [u8; 0],
+}
+
+/// `fmd_fsk_config` of include/fmd.h (FSK front end of the pager decoder).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fmd_fsk_config {
+    pub d: u32,
+    pub w: u32,
+    pub shift: u32,
+    pub tap: [u32; 32],
+    pub sync: u32,
+    pub tol: u32,
+    pub min_corr: i32,
+    pub hit_cap: u32,
+}
+
+/// `fmd_fsk_hit` of include/fmd.h: one place where the sync word ends.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_fsk_hit {
+    pub k_rel: u32,
+    pub d: u32,
+    pub corr: i32,
+    pub thr: i32,
+}
+
+#[repr(C)]
+pub struct fmd_pocsag_decoder {
+    _private: [u8; 0],
+}
+
+/// `fmd_pocsag_msg` of include/fmd.h: one POCSAG message as the host decoder delivers it.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct fmd_pocsag_msg {
+    pub address: u32,
+    pub function: u32,
+    pub n_bits: u32,
+    pub bits: [u8; 320],
+    pub corrected: u32,
+    pub inverted: u32,
+    pub end_sample: u64,
+}
+
+/// `fmd_pocsag_info` of include/fmd.h: the host decoder's counters.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_pocsag_info {
+    pub messages: u64,
+    pub batches: u64,
+    pub bad_codewords: u64,
+    pub orphans: u64,
+    pub locked: c_int,
+    pub searching: c_int,
+}
+
+#[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
 }
@@ -509,6 +568,22 @@ extern "C" {
     pub fn fmd_ax25_decoder_reset(d: *mut fmd_ax25_decoder) -> c_int;
     pub fn fmd_ax25_decoder_push(d: *mut fmd_ax25_decoder, soft: *const i16, n: usize, frames: *mut fmd_ax25_frame, cap: usize, n_frames: *mut usize) -> c_int;
     pub fn fmd_ax25_decoder_info(d: *const fmd_ax25_decoder, info: *mut fmd_ax25_info) -> c_int;
+    pub fn fmd_fsk_new(cfg: *const fmd_fsk_config, width: u32, dev: *const DeviceConfig, out: *mut *mut fmd_fsk) -> c_int;
+    pub fn fmd_fsk_free(f: *mut fmd_fsk);
+    pub fn fmd_fsk_reset(f: *mut fmd_fsk) -> c_int;
+    pub fn fmd_fsk_out_cap(d: u32, n_in: usize) -> usize;
+    pub fn fmd_fsk_run_batch(f: *mut fmd_fsk, input: *const i16, n_in: usize, in_cap: usize, out: *mut i16, out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn fmd_fsk_run_device(f: *mut fmd_fsk, d_in: *const c_void, n_in: usize, in_cap: usize, d_out: *mut c_void, out_cap: usize, n_out: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_fsk_check(f: *mut fmd_fsk) -> c_int;
+    pub fn fmd_fsk_outputs(f: *const fmd_fsk, inputs: *mut u64, outputs: *mut u64) -> c_int;
+    pub fn fmd_fsk_hits(f: *mut fmd_fsk, counts: *mut u32, hits: *mut fmd_fsk_hit) -> c_int;
+    pub fn fmd_fsk_kernel_name(f: *const fmd_fsk, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_pocsag_decoder_new(rate_num: u32, rate_den: u32, baud: u32, max_errors: u32, out: *mut *mut fmd_pocsag_decoder) -> c_int;
+    pub fn fmd_pocsag_decoder_free(d: *mut fmd_pocsag_decoder);
+    pub fn fmd_pocsag_decoder_reset(d: *mut fmd_pocsag_decoder) -> c_int;
+    pub fn fmd_pocsag_decoder_push(d: *mut fmd_pocsag_decoder, soft: *const i16, n: usize, hits: *const fmd_fsk_hit, n_hits: usize, msgs: *mut fmd_pocsag_msg, cap: usize, n_msgs: *mut usize) -> c_int;
+    pub fn fmd_pocsag_decoder_info(d: *const fmd_pocsag_decoder, info: *mut fmd_pocsag_info) -> c_int;
+    pub fn fmd_pocsag_correct(word: u32, max_errors: u32, cw: *mut u32, n_fixed: *mut u32) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
