@@ -1097,7 +1097,8 @@ int fmd_afsk_kernel_name(const fmd_afsk *a, char *name, size_t cap);
  *           bad_fcs and not delivered.
  * Every buffer is fixed and every write bounded: a frame's bits behind 514 bytes are counted, not stored; frames that do not fit
  * `frames` wait in a ring of 64, whose oldest gives way when a caller lets it fill.
- * Domain: 4 <= (rate_num / rate_den) / baud <= 64, else FMD_ERR_UNSUPPORTED ("need 4 <= rate / baud <= 64"). */
+ * Domain: 4 <= (rate_num / rate_den) / baud <= 64, else FMD_ERR_UNSUPPORTED ("need 4 <= rate / baud <= 64").
+ * The same decoder for every row of a bank at once, on the device: fmd_hdlc_* below. */
 typedef struct fmd_ax25_decoder fmd_ax25_decoder;
 typedef struct fmd_ax25_frame {
     uint8_t data[512];       /* address, control, PID and information fields; the FCS is checked and left out */
@@ -1117,6 +1118,47 @@ int fmd_ax25_decoder_reset(fmd_ax25_decoder *d);
  * (n may be 0, soft then NULL). */
 int fmd_ax25_decoder_push(fmd_ax25_decoder *d, const int16_t *soft, size_t n, fmd_ax25_frame *frames, size_t cap, size_t *n_frames);
 int fmd_ax25_decoder_info(const fmd_ax25_decoder *d, fmd_ax25_info *info);
+
+/* fmd_hdlc_*: the frame bank, the same decoder for every row ON THE DEVICE: a seventh row processor, which takes fmd_afsk's d_out as
+ * it stands and returns only the frames.  There is no new arithmetic.  For any number of rows and any cutting of the stream into
+ * calls, row r behaves as an fmd_ax25_decoder(rate_num, rate_den, baud) of its own would that is pushed exactly row r's n_in samples
+ * of each call, with room for every frame (tests/hdlc_ref.py).  A call leaves, per row:
+ *   count   the frames that passed in this call, all of them;
+ *   frames  the first min(count, frame_cap) of them as fmd_ax25_frame, in the order they closed: data is zero behind len, end_sample
+ *           is counted from creation or reset as the host decoder counts it;
+ *   info    the row's fmd_ax25_info after the call, cumulative since creation or reset.
+ * A row with count > frame_cap has lost count - frame_cap frames for delivery; frames_ok counts them all the same.  How many a call
+ * can complete: every sample takes at most one bit, and the clock's phase gains at most step + (mod / 2 + 3) / 4 per sample (the
+ * step and the largest pull, from phase 0), so a call of n soft decisions takes at most
+ *   B(n) = min(n, (mod - 1 + n (step + (mod / 2 + 3) / 4)) / mod)   bits (integer divisions)
+ * and, the shortest frame being 144 line bits with one flag (17 bytes, no stuffed bit), completes at most (B(n) + 143) / 144 frames
+ * per row -- the first may have all but its last bit in front of the call.  At rate / baud = 5 (mod = 5 step) that is about 0.325 n bits:
+ * frame_cap 1 holds every frame of calls up to about 440 soft decisions, frame_cap 4 of calls up to about 1770.
+ * Domain (else FMD_ERR_UNSUPPORTED with a text, decided before a device is queried): the host decoder's rate test with its text
+ * ("need 4 <= rate / baud <= 64"); 1 <= frame_cap <= 16 ("need 1 <= frame_cap <= 16"); n_rows = dev->n_channels >= 1 ("need n_rows >=
+ * 1").  Calls: every call with 1 <= n_in <= 2^28 is taken (there is no FMD_ERR_TOO_SHORT); n_in == 0 launches nothing and leaves the
+ * last call's counts and frames; n_in > in_cap is FMD_ERR_CAPACITY, with nothing taken.  Stream lifetime and completion points: as
+ * fmd_channelizer_* (fmd_hdlc_check).  Reset: position 0, every row as new. */
+typedef struct fmd_hdlc fmd_hdlc;
+int fmd_hdlc_new(uint32_t rate_num, uint32_t rate_den, uint32_t baud, uint32_t frame_cap, const fmd_device_config *dev, fmd_hdlc **out);
+void fmd_hdlc_free(fmd_hdlc *f);
+int fmd_hdlc_reset(fmd_hdlc *f);
+/* HOST rows: in [n_rows][in_cap], the first n_in samples of each row valid.  Returns when the call has completed. */
+int fmd_hdlc_run_batch(fmd_hdlc *f, const int16_t *in, size_t n_in, size_t in_cap);
+/* DEVICE rows, enqueued on `stream` without synchronising: d_in is fmd_afsk's d_out as it stands, with its out_cap as in_cap;
+ * 2-byte aligned, any in_cap. */
+int fmd_hdlc_run_device(fmd_hdlc *f, const void *d_in, size_t n_in, size_t in_cap, void *stream);
+int fmd_hdlc_check(fmd_hdlc *f);
+/* Samples taken per row since creation or the last reset. */
+int fmd_hdlc_inputs(const fmd_hdlc *f, uint64_t *inputs);
+/* The last call's results, behind a synchronisation.  counts: host array [n_rows] (all 0 before the first call and after reset).
+ * frames: host array [n_sel][frame_cap] for the rows listed in `rows` only, zero behind each row's min(count, frame_cap); a row
+ * index at or beyond n_rows is FMD_ERR_INVALID_ARG, with nothing written.  info: host array [n_rows]. */
+int fmd_hdlc_counts(fmd_hdlc *f, uint32_t *counts);
+int fmd_hdlc_frames(fmd_hdlc *f, const uint32_t *rows, size_t n_sel, fmd_ax25_frame *frames);
+int fmd_hdlc_info(fmd_hdlc *f, fmd_ax25_info *info);
+/* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_hdlc_kernel_name(const fmd_hdlc *f, char *name, size_t cap);
 
 /* ---- pager decoder: POCSAG messages out of any bank's NFM rows --------------------------------------------------------- */
 /* NEW SURFACE (the reference has no data decoder).  POCSAG paging (direct 2-FSK at 512, 1200 or 2400 bit/s) in two halves:

@@ -275,6 +275,17 @@ PROTOTYPES = {
     "fmd_ax25_decoder_reset": (C.c_int, [_vp]),
     "fmd_ax25_decoder_push": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
     "fmd_ax25_decoder_info": (C.c_int, [_vp, _vp]),
+    "fmd_hdlc_new": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_hdlc_free": (None, [_vp]),
+    "fmd_hdlc_reset": (C.c_int, [_vp]),
+    "fmd_hdlc_run_batch": (C.c_int, [_vp, _vp, _sz, _sz]),
+    "fmd_hdlc_run_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp]),
+    "fmd_hdlc_check": (C.c_int, [_vp]),
+    "fmd_hdlc_inputs": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "fmd_hdlc_counts": (C.c_int, [_vp, _vp]),
+    "fmd_hdlc_frames": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmd_hdlc_info": (C.c_int, [_vp, _vp]),
+    "fmd_hdlc_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_fsk_new": (C.c_int, [_vp, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
     "fmd_fsk_free": (None, [_vp]),
     "fmd_fsk_reset": (C.c_int, [_vp]),

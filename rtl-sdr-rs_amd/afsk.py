@@ -1,13 +1,14 @@
 """Host-side wrapper of the packet demodulator (include/fmd.h): the tone-pair demodulator fmd_afsk_* -- every mono int16 row a bank
 leaves on the device correlated against a mark and a space tone, one signed soft decision per `stride` samples -- and the host's
 AX.25 frame decoder fmd_ax25_decoder_* (clock recovery, NRZI, HDLC, FCS), one per row: 1200 baud AFSK packet (APRS) out of any bank's
-NFM rows.  Both are exact in integers and independent of how the stream is cut."""
+NFM rows; and the frame bank fmd_hdlc_*, the same decoder for every row on the device, which returns only the frames.  All are exact
+in integers and independent of how the stream is cut."""
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._ffi import DeviceConfig, RowProcessor, bank_rows, check, lib
+from ._ffi import BankHandle, DeviceConfig, RowProcessor, bank_rows, check, lib
 
 
 class Ax25Frame(C.Structure):
@@ -184,3 +185,117 @@ def decode_rows(demod, calls):
         for r in range(demod.n_rows):
             frames[r] += decs[r].push(soft[r])
     return [dict(decs[r].info(), frames=frames[r]) for r in range(demod.n_rows)]
+
+
+def _frame_dict(f):
+    return {"data": bytes(f.data[:f.len]), "end_sample": f.end_sample}
+
+
+def ax25_max_frames(rate_num, rate_den, baud, n):
+    """The frames one row can complete in a call of n soft decisions at most (include/fmd.h, fmd_hdlc_*): a sample takes at most one
+    bit, the clock's phase gains at most step + (mod // 2 + 3) // 4 per sample, and the shortest frame is 144 line bits."""
+    mod, step, n = int(rate_num), int(baud) * int(rate_den), int(n)
+    bits = min(n, (mod - 1 + n * (step + (mod // 2 + 3) // 4)) // mod)
+    return (bits + 143) // 144
+
+
+class Ax25Framer(BankHandle):
+    """The frame bank (fmd_hdlc_*): an Ax25Decoder(rate_num, rate_den, baud) per row, on the device.  run_batch takes int16 [n_rows,
+    n_in] on the host, run_device an AfskDemod's d_out as it stands with its out_cap as in_cap; both return nothing.  Behind a call:
+    counts() uint32 [n_rows], the frames that passed in it; frames(rows) the first min(count, frame_cap) of each listed row as dicts
+    {"data", "end_sample"}, in the order they closed; info() the rows' cumulative counters as Ax25Decoder.info() gives them."""
+    _prefix = "hdlc"
+
+    def __init__(self, rate_num, rate_den=1, baud=1200, frame_cap=4, n_rows=1, device_id=-1):
+        self.rate_num, self.rate_den, self.baud = int(rate_num), int(rate_den), int(baud)
+        self.frame_cap, self.n_rows = int(frame_cap), int(n_rows)
+        for name in ("rate_num", "rate_den", "baud", "frame_cap", "n_rows"):
+            if not 0 <= getattr(self, name) < 1 << 32:
+                raise ValueError("%s out of range" % name)
+        self._h = C.c_void_p()
+        dev = DeviceConfig(self.n_rows, device_id, 0)
+        check(lib().fmd_hdlc_new(self.rate_num, self.rate_den, self.baud, self.frame_cap, C.byref(dev), C.byref(self._h)))
+
+    def max_frames(self, n_in):
+        return ax25_max_frames(self.rate_num, self.rate_den, self.baud, n_in)
+
+    def inputs(self):
+        """Samples taken per row since creation or reset."""
+        n = C.c_uint64(0)
+        check(lib().fmd_hdlc_inputs(self._h, C.byref(n)))
+        return n.value
+
+    def run_batch(self, soft):
+        soft = np.ascontiguousarray(soft, dtype=np.int16)
+        if soft.ndim != 2 or soft.shape[0] != self.n_rows:
+            raise ValueError("soft must be [n_rows, n_in]")
+        check(lib().fmd_hdlc_run_batch(self._h, soft.ctypes.data, soft.shape[1], soft.shape[1]))
+
+    def run_device(self, d_in, n_in, in_cap, stream=None):
+        """Enqueue on a device pointer (d_in [n_rows][in_cap], the first n_in samples of each row valid).  `stream` must stay alive
+        until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
+        check(lib().fmd_hdlc_run_device(self._h, d_in, n_in, in_cap, stream))
+
+    def counts(self):
+        c = np.zeros(self.n_rows, np.uint32)
+        check(lib().fmd_hdlc_counts(self._h, c.ctypes.data))
+        return c
+
+    def frame_records(self, rows):
+        """The Ax25Frame records [len(rows)][frame_cap] of the listed rows, zero behind each row's frames."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        buf = (Ax25Frame * (self.frame_cap * max(1, rows.shape[0])))()
+        check(lib().fmd_hdlc_frames(self._h, rows.ctypes.data, rows.shape[0], buf))
+        return [[buf[s * self.frame_cap + k] for k in range(self.frame_cap)] for s in range(rows.shape[0])]
+
+    def frames(self, rows, counts=None):
+        """A list per listed row of the frames the last call delivered for it."""
+        counts = self.counts() if counts is None else counts
+        rec = self.frame_records(rows)
+        return [[_frame_dict(f) for f in rec[s][:min(int(counts[r]), self.frame_cap)]] for s, r in enumerate(rows)]
+
+    def info(self):
+        buf = (Ax25Info * self.n_rows)()
+        check(lib().fmd_hdlc_info(self._h, buf))
+        return [{"frames_ok": i.frames_ok, "bad_fcs": i.bad_fcs, "aborts": i.aborts, "in_frame": int(i.in_frame)} for i in buf]
+
+
+def framed(demod, frame_cap=4, device_id=-1):
+    """An Ax25Framer matched to `demod` (an AfskDemod that knows its `rate`): its rows, rate / stride soft decisions per second, its
+    baud."""
+    if demod.rate is None:
+        raise ValueError("the demodulator does not know its rate")
+    return Ax25Framer(int(demod.rate), demod.stride, demod.baud, frame_cap, n_rows=demod.n_rows, device_id=device_id)
+
+
+def decode_rows_gpu(demod, calls):
+    """What decode_rows(demod, calls) returns, with the decoders on the device: the soft rows go from the demodulator to a framer
+    (framed(demod, 16)) without leaving the device; after each call only the counts come back, and the frames of only the rows whose
+    count is not zero.  A call's soft decisions are handed over in pieces short enough that no row can complete more than 16 frames
+    in one."""
+    import torch
+    framer = framed(demod, 16)
+    piece = 1
+    while framer.max_frames(2 * piece) <= framer.frame_cap:  # (>= 2161: a sample takes at most one bit)
+        piece *= 2
+    frames = [[] for _ in range(demod.n_rows)]
+    for x in calls:
+        x = np.ascontiguousarray(x, dtype=np.int16)
+        if x.ndim != 2 or x.shape[0] != demod.n_rows:
+            raise ValueError("a call must be [n_rows, n_in]")
+        n_in = x.shape[1]
+        d_in = torch.from_numpy(np.ascontiguousarray(x) if n_in else np.zeros((demod.n_rows, 1), np.int16)).cuda()
+        cap = max(1, demod.out_cap(n_in))
+        d_soft = torch.empty((demod.n_rows, cap), dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()
+        n = demod.run_device(d_in.data_ptr(), n_in, max(1, n_in), d_soft.data_ptr(), cap)
+        for lo in range(0, n, piece):
+            framer.run_device(d_soft.data_ptr() + 2 * lo, min(piece, n - lo), cap)
+            counts = framer.counts()
+            hit = np.nonzero(counts)[0]
+            if hit.size:
+                for r, got in zip(hit.tolist(), framer.frames(hit, counts)):
+                    frames[r] += got
+    info = framer.info()
+    framer.close()
+    return [dict(info[r], frames=frames[r]) for r in range(demod.n_rows)]

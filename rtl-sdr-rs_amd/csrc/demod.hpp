@@ -1183,6 +1183,50 @@ private:
     Owned<fmd_ax25_decoder, fmd_ax25_decoder_free> h_;
 };
 
+// The frame bank (fmd_hdlc_*): an Ax25Decoder per row on the device.  run() takes the soft decisions [n_rows][n_in] of an AfskDemod;
+// behind it counts() gives the frames that passed in the call per row, frames(rows) the first min(count, frame_cap) of each listed
+// row in the order they closed, info() the rows' cumulative counters.
+class Ax25Framer {
+public:
+    Ax25Framer(uint32_t rate_num, uint32_t rate_den, uint32_t baud = 1200, uint32_t frame_cap = 4, uint32_t n_rows = 1, int32_t device_id = -1)
+        : n_rows_(n_rows), frame_cap_(frame_cap)
+    {
+        fmd_device_config dev{n_rows, device_id, 0};
+        check(fmd_hdlc_new(rate_num, rate_den, baud, frame_cap, &dev, h_.out()));
+    }
+
+    void run(const int16_t* soft, size_t n_in) { check(fmd_hdlc_run_batch(h_, soft, n_in, n_in)); }
+    std::vector<uint32_t> counts()
+    {
+        std::vector<uint32_t> c(n_rows_);
+        check(fmd_hdlc_counts(h_, c.data()));
+        return c;
+    }
+    std::vector<std::vector<fmd_ax25_frame>> frames(const std::vector<uint32_t>& rows)
+    {
+        const std::vector<uint32_t> c = counts();
+        std::vector<fmd_ax25_frame> buf(std::max<size_t>(1, rows.size() * frame_cap_));
+        check(fmd_hdlc_frames(h_, rows.data(), rows.size(), buf.data()));
+        std::vector<std::vector<fmd_ax25_frame>> res(rows.size());
+        for (size_t s = 0; s < rows.size(); ++s)
+            res[s].assign(buf.begin() + s * frame_cap_, buf.begin() + s * frame_cap_ + std::min<size_t>(c[rows[s]], frame_cap_));
+        return res;
+    }
+    std::vector<fmd_ax25_info> info()
+    {
+        std::vector<fmd_ax25_info> i(n_rows_);
+        check(fmd_hdlc_info(h_, i.data()));
+        return i;
+    }
+    uint64_t inputs() const { return value_of<uint64_t>(fmd_hdlc_inputs, h_); }
+    void reset() { check(fmd_hdlc_reset(h_)); }
+    uint32_t frame_cap() const { return frame_cap_; }
+
+private:
+    uint32_t n_rows_, frame_cap_;
+    Owned<fmd_hdlc, fmd_hdlc_free> h_;
+};
+
 namespace detail {
 // "CALL" or "CALL-SSID" of a 7-byte address; empty where it is malformed (a character that is not shifted ASCII upper case or digit,
 // or one behind a padding space)

@@ -290,6 +290,12 @@ pub struct fmd_ax25_info {
     pub in_frame: c_int,
 }
 
+/// The frame bank of include/fmd.h: an `fmd_ax25_decoder` per row on the device.
+#[repr(C)]
+pub struct fmd_hdlc {
+    _private: [u8; 0],
+}
+
 #[repr(C)]
 pub struct fmd_fsk {
     _private: [u8; 0],
@@ -568,6 +574,17 @@ extern "C" {
     pub fn fmd_ax25_decoder_reset(d: *mut fmd_ax25_decoder) -> c_int;
     pub fn fmd_ax25_decoder_push(d: *mut fmd_ax25_decoder, soft: *const i16, n: usize, frames: *mut fmd_ax25_frame, cap: usize, n_frames: *mut usize) -> c_int;
     pub fn fmd_ax25_decoder_info(d: *const fmd_ax25_decoder, info: *mut fmd_ax25_info) -> c_int;
+    pub fn fmd_hdlc_new(rate_num: u32, rate_den: u32, baud: u32, frame_cap: u32, dev: *const DeviceConfig, out: *mut *mut fmd_hdlc) -> c_int;
+    pub fn fmd_hdlc_free(f: *mut fmd_hdlc);
+    pub fn fmd_hdlc_reset(f: *mut fmd_hdlc) -> c_int;
+    pub fn fmd_hdlc_run_batch(f: *mut fmd_hdlc, input: *const i16, n_in: usize, in_cap: usize) -> c_int;
+    pub fn fmd_hdlc_run_device(f: *mut fmd_hdlc, d_in: *const c_void, n_in: usize, in_cap: usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_hdlc_check(f: *mut fmd_hdlc) -> c_int;
+    pub fn fmd_hdlc_inputs(f: *const fmd_hdlc, inputs: *mut u64) -> c_int;
+    pub fn fmd_hdlc_counts(f: *mut fmd_hdlc, counts: *mut u32) -> c_int;
+    pub fn fmd_hdlc_frames(f: *mut fmd_hdlc, rows: *const u32, n_sel: usize, frames: *mut fmd_ax25_frame) -> c_int;
+    pub fn fmd_hdlc_info(f: *mut fmd_hdlc, info: *mut fmd_ax25_info) -> c_int;
+    pub fn fmd_hdlc_kernel_name(f: *const fmd_hdlc, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_fsk_new(cfg: *const fmd_fsk_config, width: u32, dev: *const DeviceConfig, out: *mut *mut fmd_fsk) -> c_int;
     pub fn fmd_fsk_free(f: *mut fmd_fsk);
     pub fn fmd_fsk_reset(f: *mut fmd_fsk) -> c_int;
