@@ -128,14 +128,18 @@ def watches(kind, k, signed):
 
 ROWS = 5
 CALLS = (2400, 2304)                                               # samples per row and call: behind 4 * delta bytes + EDGE at width 1
-HANDLES = ("resample", "agc", "tonesq", "afsk")
-WIDTHS = {"resample": (1, 2), "agc": (1, 2), "tonesq": (1, 2), "afsk": (1,)}
+HANDLES = ("resample", "agc", "tonesq", "afsk", "dcs")
+WIDTHS = {"resample": (1, 2), "agc": (1, 2), "tonesq": (1, 2), "afsk": (1,), "dcs": (1, 2)}
 RS = NS(L=3, M=2, T=8, shift=12)
 AGC = ag.Cfg(block=256, target=12000, gain_max=65536, hang=2, decay=32)
 AGC_CALLS = (2816, 2560)                                           # 10 blocks out per call (block j comes with block j + 1)
 TQ = NS(block=256, rate=8000, freqs=(250.0, 500.0, 1000.0), guard=0, dom_shift=2, confirm=1, hang=2, ramp=64, min_power=20_000_000,
         accept=0b111)
 AF = NS(rate=9600, taps=8, stride=1)
+# the code squelch: every k matches some word (tol 23) and one hit decides a block, so every block confirms one of the words and all are
+# accepted: the gate ramps up over block 1 and is open from block 2 on
+DCS = NS(block=256, box=8, lp=(300, -200, 1023, -1023, 77), lshift=6, tap=tuple(range(0, 44, 2)) + (47,), tol=23, min_hits=1, confirm=1,
+         hang=0, ramp=64, accept=(1 << 128) - 1, words=(0x2AAAAA, 0x555555, 0x0F0F0F))
 
 
 def row_n_in(handle):

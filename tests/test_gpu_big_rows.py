@@ -1,4 +1,4 @@
-"""The row processors (Resampler, Agc, ToneSquelch, AfskDemod) with rows 2^31 - delta bytes apart: rows 1, 2 and 4 of five start just
+"""The row processors (Resampler, Agc, ToneSquelch, AfskDemod, CodeSquelch) with rows 2^31 - delta bytes apart: rows 1, 2 and 4 of five start just
 below byte 2^31, 2^32 and 2^33 of the buffer (element 2^31 and 2^32 in int16, W-sample 2^31 at width 2), and two calls of ~2400
 samples per row read (the input pitched) or write (the output pitched) across each line -- the second call with the carried history
 in front.  The pitch is 16-byte aligned in one case and not in the other, so the vector and the element paths both cross.
@@ -14,6 +14,7 @@ import pytest
 import afsk_ref as ar
 import agc_ref as ag
 import big_cases as bc
+import dcs_ref as dr
 import resample_ref as rr
 import tonesq_ref as tr
 from big_gpu import Pitched
@@ -42,6 +43,11 @@ def _make(fmd, c, rng):
         tab = fmd.tone_table(q.rate, q.freqs, q.block)
         return (fmd.ToneSquelch(tab, n_rows=bc.ROWS, width=c.width, accept=q.accept, guard=q.guard, dom_shift=q.dom_shift, min_power=q.min_power,
                                 confirm=q.confirm, hang=q.hang, ramp=q.ramp, device_id=0), tr.ToneSquelch(tab, _tq_cfg()))
+    if c.handle == "dcs":
+        q = bc.DCS
+        cfg = dr.Cfg(q.block, q.box, list(q.lp), q.lshift, list(q.tap), q.tol, q.min_hits, q.confirm, q.hang, q.ramp, q.accept)
+        return (fmd.CodeSquelch(list(q.words), q.block, q.box, cfg.lp, q.lshift, cfg.tap, n_rows=bc.ROWS, width=c.width, accept=q.accept, tol=q.tol,
+                                min_hits=q.min_hits, confirm=q.confirm, hang=q.hang, ramp=q.ramp, device_id=0), dr.CodeSquelch(list(q.words), cfg))
     tab, pre, out = fmd.afsk_table(bc.AF.rate, taps=bc.AF.taps)
     ref = ar.AfskDemod(tab, bc.AF.stride, pre, out, rows=bc.ROWS)
 
@@ -52,8 +58,8 @@ def _make(fmd, c, rng):
 
 
 def _input(c, rng, n, first):
-    """int16 [rows, n, width]: full-range noise; for the tone squelch row r carries tone r mod 3 of its table under the noise, so that
-    the gate opens and the output depends on every sample."""
+    """int16 [rows, n, width]: full-range noise (the code squelch's configuration opens on it); for the tone squelch row r carries
+    tone r mod 3 of its table under the noise, so that the gate opens and the output depends on every sample."""
     if c.handle != "tonesq":
         return rng.integers(-32768, 32768, (bc.ROWS, n, c.width)).astype(np.int16)
     t = (first + np.arange(n))[None, :, None]
@@ -108,6 +114,12 @@ def test_rows_across_the_lines(fmd, c):
             rt, rp, rg = ref.status()
             assert [int(v) for v in tone] == rt and [int(v) for v in power] == rp and [bool(v) for v in gate] == rg
             assert all(rg) and rt == [r % 3 for r in range(bc.ROWS)]     # the gates are open: the outputs carried the samples
+        if c.handle == "dcs":
+            code, hits, gate = h.status()
+            rc, rh, rg = ref.status()
+            assert code.tolist() == rc and [int(v) for v in hits] == rh and gate.tolist() == rg
+            # every completed block decided on an accepted word: the gate ramps up over block 1 and is open from block 2 on
+            assert all(rg) and len(ref.hits) == 18 * bc.ROWS and all(hit != dr.NONE for _, _, hit, _, _ in ref.hits)
     finally:
         big.release()
         h.close()

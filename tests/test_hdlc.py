@@ -13,6 +13,7 @@ import pytest
 
 import ax25_ref as xr
 import hdlc_ref as hr
+from digital_cases import CASES, WANT, Model, _body, _find, _soft, cases  # noqa: F401  (the lines and the per-bit step live there)
 from test_ax25_domain import EDGES as RATE_EDGES, WRAP
 from test_isa_invariants import code_objects  # noqa: F401  (module fixture: the library's gfx950 code objects)
 
@@ -99,129 +100,7 @@ def test_the_u64_wrap_tuples_and_the_order_of_the_refusals(fmd):
     assert _new(fmd, 6000, 1, 1200, 4, 0) == (UNSUPPORTED, ROWS)
 
 
-# ---- the streams -------------------------------------------------------------------------------------------------------------------
-def _soft(bits, num=5, den=1, amp=9000):
-    return hr.levels_to_soft(xr.nrzi(bits), num, den, amp)
-
-
-def _body(rng, n):
-    return bytes(rng.integers(0, 256, n, dtype=np.uint8).tolist())
-
-
-def _find(rng, n, pred):
-    """a random frame of n bytes without the FCS whose stuffed bits satisfy `pred(data, stuffed bits)`"""
-    for _ in range(20000):
-        d = _body(rng, n)
-        if pred(d, xr.stuffed_bits(xr.with_fcs(d))):
-            return d
-    raise AssertionError("no such frame")
-
-
-def _stuffed_in_fcs(d, bits):
-    f = xr.with_fcs(d)
-    return len(xr.stuffed_bits(f[-2:])) > 16 and len(bits) - len(xr.stuffed_bits(f[:-2])) > 16
-
-
-def cases():
-    """{name: the bits on the line}, flags and frames; every case ends with a few flags"""
-    rng = np.random.default_rng(2025)
-    F = xr.FLAG
-    out = {}
-    for n in (16, 17, 514, 515, 3000):                       # bytes with the FCS: one below and at either limit, and far beyond
-        out["bytes-%d" % n] = xr.frame_bits(_body(rng, n - 2), flags=3, closing=2)
-    a, b, c = _body(rng, 20), _body(rng, 33), _body(rng, 15)
-    out["shared-flag"] = F * 2 + xr.stuffed_bits(xr.with_fcs(a)) + F + xr.stuffed_bits(xr.with_fcs(b)) + F + xr.stuffed_bits(xr.with_fcs(c)) + F * 2
-    out["abort"] = F * 2 + xr.stuffed_bits(a)[:77] + [1] * 9 + [0, 1, 0] + xr.frame_bits(b, flags=2, closing=2)
-    out["abort-outside"] = F + [1] * 12 + xr.frame_bits(a, flags=2) + [1] * 8 + F
-    out["stuffed-in-fcs"] = xr.frame_bits(_find(rng, 25, _stuffed_in_fcs), flags=2, closing=2)
-    out["stuffed-before-flag"] = xr.frame_bits(_find(rng, 25, lambda d, s: s[-6:] == [1, 1, 1, 1, 1, 0]), flags=2, closing=2)
-    out["ff-514"] = xr.frame_bits(b"\xff" * 512, flags=2, closing=2)
-    out["ff-514-raw"] = F * 2 + xr.stuffed_bits(b"\xff" * 514) + F * 2           # 514 bytes of 0xFF with no FCS behind them
-    good = xr.stuffed_bits(xr.with_fcs(b))
-    for k in (0, 100, len(good) - 1):
-        bad = list(good)
-        bad[k] ^= 1
-        out["flipped-%d" % k] = F * 2 + bad + F * 2
-    for extra in (1, 3, 7):
-        out["bits-plus-%d" % extra] = F * 2 + good + [0, 1, 0, 0, 1, 0, 1][:extra] + F + xr.stuffed_bits(xr.with_fcs(a)) + F
-    out["bits-minus-1"] = F * 2 + good[:-1] + F * 2
-    out["flags-back-to-back"] = F * 9 + xr.stuffed_bits(xr.with_fcs(a)) + F * 7
-    out["seven-bits"] = F * 2 + [0, 1, 0, 0, 1, 0, 0] + F + [0] + F + xr.stuffed_bits(xr.with_fcs(c)) + F
-    return out
-
-
-CASES = cases()
-
-
-# ---- the kernel's per-bit step (DESIGN.md 9p) --------------------------------------------------------------------------------------
-class Model:
-    """One row of the frame bank as the kernel runs it.  The clock and NRZI are the definition's; per bit, the open frame keeps
-    nbits, the last 16 stored bits (`hist`, the newest at bit 15) and a CRC register that takes the bit stored seven bits ago, and
-    writes a byte to `mem` per eight stored bits; the flag accepts on the residue 0xF0B8 and copies mem[:len] out."""
-
-    def __init__(self, rate_num, rate_den=1, baud=1200):
-        self.mod, self.step = int(rate_num), int(baud) * int(rate_den)
-        assert self.step >= 1 and 4 * self.step <= self.mod <= 64 * self.step
-        self.ph, self.prev_inv, self.level_inv = 0, 0, 0     # all zero: the reset state (prev and level are stored inverted)
-        self.sr = self.ones = self.nbits = self.in_frame = self.hist = self.crc = 0
-        self.frames_ok = self.bad_fcs = self.aborts = 0
-        self.n = 0
-        self.mem = bytearray(520)
-
-    def info(self):
-        return {"frames_ok": self.frames_ok, "bad_fcs": self.bad_fcs, "aborts": self.aborts, "in_frame": self.in_frame}
-
-    def _bit(self, bit, frames):
-        self.sr = (self.sr >> 1) | (bit << 7)
-        if self.sr == 0x7E:
-            if self.in_frame and self.nbits > 7:
-                nb = self.nbits - 7
-                if nb % 8 == 0 and self.nbits <= 514 * 8 + 7 and 17 <= nb // 8 <= 514 and self.crc == 0xF0B8:
-                    self.frames_ok += 1
-                    frames.append({"data": bytes(self.mem[:nb // 8 - 2]), "end_sample": self.n})
-                else:
-                    self.bad_fcs += 1
-            self.in_frame, self.nbits, self.ones, self.crc = 1, 0, 0, 0xFFFF
-            return
-        store = self.in_frame == 1
-        if bit:
-            self.ones += 1
-            if self.ones >= 7:
-                self.aborts += self.in_frame
-                self.in_frame, self.ones, store = 0, 7, False
-        else:
-            if self.ones == 5:
-                store = False
-            self.ones = 0
-        if store:
-            if self.nbits < 514 * 8 + 7:
-                if self.nbits >= 7:
-                    fb = (self.crc ^ (self.hist >> 9)) & 1
-                    self.crc = (self.crc >> 1) ^ (0x8408 if fb else 0)
-                self.hist = (self.hist >> 1) | (bit << 15)
-                if self.nbits & 7 == 7:
-                    self.mem[self.nbits >> 3] = self.hist >> 8
-            if self.nbits <= 514 * 8 + 7:
-                self.nbits += 1
-
-    def push(self, soft):
-        frames = []
-        half = self.mod // 2
-        for v in np.asarray(soft, np.int16).tolist():
-            cur = 1 if v >= 0 else 0
-            if cur != self.prev_inv ^ 1:
-                self.ph -= (self.ph - half) >> 2
-            self.prev_inv = cur ^ 1
-            self.ph += self.step
-            if self.ph >= self.mod:
-                self.ph -= self.mod
-                self._bit(1 if cur == self.level_inv ^ 1 else 0, frames)
-                self.level_inv = cur ^ 1
-            self.n += 1
-        assert 0 <= self.ph < self.mod < 1 << 32 and self.hist < 1 << 16 and self.crc < 1 << 16 and self.nbits <= 514 * 8 + 8
-        return frames
-
-
+# ---- the kernel's per-bit step (tests/digital_cases.py: cases, Model) over the lines ---------------------------------
 def _hold(name, soft, num, den, cuts=(1, 7, 1000, 333)):
     ref, mod = xr.Decoder(num, den), Model(num, den)
     lo, total = 0, []
@@ -238,11 +117,7 @@ def test_per_bit_step_model_equals_the_definition(name):
     total, info = _hold(name, _soft(CASES[name]), 6000, 1)
     total2, info2 = _hold(name, _soft(CASES[name], 11025, 2400), 11025, 2)      # 4.59375 samples per bit
     assert [f["data"] for f in total] == [f["data"] for f in total2] and info == info2
-    want = {"bytes-16": (0, 1, 0), "bytes-17": (1, 0, 0), "bytes-514": (1, 0, 0), "bytes-515": (0, 1, 0), "bytes-3000": (0, 1, 0),
-            "shared-flag": (3, 0, 0), "abort": (1, 0, 1), "abort-outside": (1, 0, 2), "stuffed-in-fcs": (1, 0, 0),
-            "stuffed-before-flag": (1, 0, 0), "ff-514": (1, 0, 0), "ff-514-raw": (0, 1, 0), "flipped-0": (0, 1, 0), "flipped-100": (0, 1, 0),
-            "bits-plus-1": (1, 1, 0), "bits-plus-3": (1, 1, 0), "bits-plus-7": (1, 1, 0), "bits-minus-1": (0, 1, 0),
-            "flags-back-to-back": (1, 0, 0), "seven-bits": (1, 2, 0)}
+    want = WANT
     if name in want:
         assert (info["frames_ok"], info["bad_fcs"], info["aborts"]) == want[name], info
     if name == "ff-514":
