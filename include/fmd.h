@@ -1233,6 +1233,11 @@ int fmd_fsk_outputs(const fmd_fsk *f, uint64_t *inputs, uint64_t *outputs);
 /* Host arrays of the last call that launched: counts [n_rows], hits [n_rows][hit_cap] (zeros behind a row's records).  Either may
  * be NULL.  Synchronises first. */
 int fmd_fsk_hits(fmd_fsk *f, uint32_t *counts, fmd_fsk_hit *hits);
+/* The same results where they lie, so that a later kernel (fmd_pager_run_device) takes them without a visit to the host: DEVICE
+ * pointers to what the last call that launched wrote, *d_counts [n_rows] uint32 and *d_hits [n_rows][hit_cap] fmd_fsk_hit (16-byte
+ * aligned; behind a row's min(count, hit_cap) records lies whatever an earlier call left).  Does not synchronise: the contents are
+ * complete once the call that wrote them is.  Valid until the handle's next call that launches, its reset, or its free. */
+int fmd_pager_fsk_hits(fmd_fsk *f, const void **d_counts, const void **d_hits);
 /* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
 int fmd_fsk_kernel_name(const fmd_fsk *f, char *name, size_t cap);
 
@@ -1288,6 +1293,63 @@ int fmd_pocsag_decoder_info(const fmd_pocsag_decoder *d, fmd_pocsag_info *info);
 /* The corrected codeword of `word` within `max_errors` (<= 2) bit errors in *cw and the bits flipped in *n_fixed (either may be
  * NULL): FMD_OK, or FMD_ERR_BAD_STATE when there is none. */
 int fmd_pocsag_correct(uint32_t word, uint32_t max_errors, uint32_t *cw, uint32_t *n_fixed);
+
+/* fmd_pager_*: the page bank, the same decoder for every row ON THE DEVICE: an eighth row processor, which takes fmd_fsk's d_out and
+ * its records as they stand and returns only the messages.  There is no new arithmetic.  For any number of rows and any cutting of
+ * the stream into calls, row r behaves as an fmd_pocsag_decoder(rate_num, rate_den, baud, max_errors) of its own would that is pushed
+ * exactly row r's n_in soft decisions of each call and the first min(count_r, hit_cap) records of that call, with room for every
+ * message (tests/pager_ref.py); the host decoder's ring of 64 waiting messages has no counterpart here.  A call leaves, per row:
+ *   count   the messages that closed in this call, all of them;
+ *   msgs    the first min(count, msg_cap) of them as fmd_pocsag_msg, in the order they closed: bits is zero behind (min(n_bits,
+ *           2560) + 7) / 8 bytes, end_sample is counted from creation or reset as the host decoder counts it;
+ *   info    the row's fmd_pocsag_info after the call, cumulative since creation or reset, with locked and searching.
+ * A row with count > msg_cap has lost count - msg_cap messages for delivery; `messages` counts them all the same.
+ * How many a call can complete.  A bit read in a call lies at a sample of that call: p(n) <= the sample that makes it due.  Inside a
+ * batch two bit positions are at least q = mod / step (integer division) apart, since p(n + 1) - p(n) >= floor(mod / step); an anchor
+ * made at sample s, after a search or at slot 16, puts p(1) = k + r >= s, behind every bit read before it.  So the bits a call of n
+ * samples reads lie at distinct samples at least q apart within each batch and in increasing order across batches: at most B =
+ * ceil(n / q) of them.  A codeword completes at its 32nd bit and all but that bit may lie in front of the call: at most (B + 31) / 32
+ * codewords, each of which closes at most one message.  The only other close is a lost lock, which takes a whole batch of 512 bits
+ * since the anchor: one whose bits all lie in front of the call, and one more per 512 bits read in it.  Hence at most
+ *   M(n) = (B + 31) / 32 + 1 + B / 512   messages per row and call (fmd_pager_max_messages; 0 outside the rate domain).
+ * At rate / baud = 5 a call of 256 soft decisions gives 3, and msg_cap 16 holds every message of calls up to 2400.
+ * Domain (else FMD_ERR_UNSUPPORTED with a text, decided before a device is queried): the host decoder's tests in its order with its
+ * texts ("need 2 <= rate / baud <= 32", "need max_errors <= 2"); 1 <= msg_cap <= 16 ("need 1 <= msg_cap <= 16"); n_rows =
+ * dev->n_channels >= 1 ("need n_rows >= 1"); per call 1 <= hit_cap <= 64 ("need 1 <= hit_cap <= 64").  Calls: every call with 1 <=
+ * n_in <= 2^28 is taken; n_in == 0 launches nothing and leaves the last call's counts and messages; n_in > in_cap is
+ * FMD_ERR_CAPACITY, with nothing taken.  Records follow the host decoder's rule: one with k_rel >= n_in, or one that is not in
+ * increasing order, is passed over and never used as an index; a count above hit_cap reads hit_cap records.  Stream lifetime and
+ * completion points: as fmd_channelizer_* (fmd_pager_check).  Reset: position 0, every row as new. */
+typedef struct fmd_pager fmd_pager;
+int fmd_pager_new(uint32_t rate_num, uint32_t rate_den, uint32_t baud, uint32_t max_errors, uint32_t msg_cap,
+                  const fmd_device_config *dev, fmd_pager **out);
+void fmd_pager_free(fmd_pager *p);
+int fmd_pager_reset(fmd_pager *p);
+/* HOST arrays: soft [n_rows][in_cap], the first n_in of each row valid; counts [n_rows]; hits [n_rows][hit_cap].  Returns when the
+ * call has completed. */
+int fmd_pager_run_batch(fmd_pager *p, const int16_t *soft, size_t n_in, size_t in_cap, const uint32_t *counts, const fmd_fsk_hit *hits,
+                        uint32_t hit_cap);
+/* DEVICE arrays, enqueued on `stream` without synchronising: d_soft is fmd_fsk's d_out as it stands, with its out_cap as in_cap
+ * (2-byte aligned, any in_cap); d_counts and d_hits are what the same fsk call wrote (fmd_pager_fsk_hits; 4- and 16-byte aligned). */
+int fmd_pager_run_device(fmd_pager *p, const void *d_soft, size_t n_in, size_t in_cap, const void *d_counts, const void *d_hits,
+                         uint32_t hit_cap, void *stream);
+int fmd_pager_check(fmd_pager *p);
+/* Samples taken per row since creation or the last reset. */
+int fmd_pager_inputs(const fmd_pager *p, uint64_t *inputs);
+/* The last call's results, behind a synchronisation.  counts: host array [n_rows] (all 0 before the first call and after reset).
+ * msgs: host array [n_sel][msg_cap] for the rows listed in `rows` only, zero behind each row's min(count, msg_cap); a row index at
+ * or beyond n_rows is FMD_ERR_INVALID_ARG, with nothing written.  info: host array [n_rows]. */
+int fmd_pager_counts(fmd_pager *p, uint32_t *counts);
+int fmd_pager_msgs(fmd_pager *p, const uint32_t *rows, size_t n_sel, fmd_pocsag_msg *msgs);
+int fmd_pager_info(fmd_pager *p, fmd_pocsag_info *info);
+/* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_pager_kernel_name(const fmd_pager *p, char *name, size_t cap);
+/* The kernel's correction table for `max_errors` (<= 2), 2048 flip masks: entry (s << 1 | parity) is the bits to flip in a word
+ * whose bits 31 ... 1 leave the remainder s by 0x769 and whose 32 bits have that parity, 0xFFFFFFFF where no codeword lies within
+ * max_errors bits.  Host only. */
+int fmd_pager_table(uint32_t max_errors, uint32_t *table);
+/* M(n) above; 0 where rate / baud < 2. */
+size_t fmd_pager_max_messages(uint32_t rate_num, uint32_t rate_den, uint32_t baud, size_t n);
 
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example

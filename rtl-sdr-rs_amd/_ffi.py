@@ -295,6 +295,7 @@ PROTOTYPES = {
     "fmd_fsk_check": (C.c_int, [_vp]),
     "fmd_fsk_outputs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fmd_fsk_hits": (C.c_int, [_vp, _vp, _vp]),
+    "fmd_pager_fsk_hits": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "fmd_fsk_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_pocsag_decoder_new": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     "fmd_pocsag_decoder_free": (None, [_vp]),
@@ -302,6 +303,19 @@ PROTOTYPES = {
     "fmd_pocsag_decoder_push": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _szp]),
     "fmd_pocsag_decoder_info": (C.c_int, [_vp, _vp]),
     "fmd_pocsag_correct": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "fmd_pager_new": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_pager_free": (None, [_vp]),
+    "fmd_pager_reset": (C.c_int, [_vp]),
+    "fmd_pager_run_batch": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, C.c_uint32]),
+    "fmd_pager_run_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, C.c_uint32, _vp]),
+    "fmd_pager_check": (C.c_int, [_vp]),
+    "fmd_pager_inputs": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "fmd_pager_counts": (C.c_int, [_vp, _vp]),
+    "fmd_pager_msgs": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmd_pager_info": (C.c_int, [_vp, _vp]),
+    "fmd_pager_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_pager_table": (C.c_int, [C.c_uint32, _vp]),
+    "fmd_pager_max_messages": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, _sz]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

@@ -1365,6 +1365,63 @@ private:
     Owned<fmd_pocsag_decoder, fmd_pocsag_decoder_free> h_;
 };
 
+// The page bank (fmd_pager_*): a PocsagDecoder per row on the device.  run() takes the soft decisions [n_rows][n_in] of an FskDemod
+// with the records of the same call as FskDemod::hits() gives them; behind it counts() gives the messages that closed in the call
+// per row, msgs(rows) the first min(count, msg_cap) of each listed row in the order they closed, info() the rows' cumulative counters.
+class Pager {
+public:
+    Pager(uint32_t rate_num, uint32_t rate_den, uint32_t baud = 1200, uint32_t max_errors = 1, uint32_t msg_cap = 4, uint32_t n_rows = 1,
+          int32_t device_id = -1)
+        : n_rows_(n_rows), msg_cap_(msg_cap), rate_num_(rate_num), rate_den_(rate_den), baud_(baud)
+    {
+        fmd_device_config dev{n_rows, device_id, 0};
+        check(fmd_pager_new(rate_num, rate_den, baud, max_errors, msg_cap, &dev, h_.out()));
+    }
+
+    void run(const int16_t* soft, size_t n_in, const std::vector<std::vector<fmd_fsk_hit>>& hits)
+    {
+        size_t cap = 1;
+        for (const std::vector<fmd_fsk_hit>& h : hits) cap = std::max(cap, std::min<size_t>(h.size(), 64));
+        std::vector<uint32_t> cnt(n_rows_, 0u);
+        std::vector<fmd_fsk_hit> rec((size_t)n_rows_ * cap);
+        for (size_t r = 0; r < n_rows_ && r < hits.size(); ++r) {
+            cnt[r] = (uint32_t)std::min<size_t>(hits[r].size(), cap);
+            std::copy(hits[r].begin(), hits[r].begin() + cnt[r], rec.begin() + r * cap);
+        }
+        check(fmd_pager_run_batch(h_, soft, n_in, n_in, cnt.data(), rec.data(), (uint32_t)cap));
+    }
+    std::vector<uint32_t> counts()
+    {
+        std::vector<uint32_t> c(n_rows_);
+        check(fmd_pager_counts(h_, c.data()));
+        return c;
+    }
+    std::vector<std::vector<fmd_pocsag_msg>> msgs(const std::vector<uint32_t>& rows)
+    {
+        const std::vector<uint32_t> c = counts();
+        std::vector<fmd_pocsag_msg> buf(std::max<size_t>(1, rows.size() * msg_cap_));
+        check(fmd_pager_msgs(h_, rows.data(), rows.size(), buf.data()));
+        std::vector<std::vector<fmd_pocsag_msg>> res(rows.size());
+        for (size_t s = 0; s < rows.size(); ++s)
+            res[s].assign(buf.begin() + s * msg_cap_, buf.begin() + s * msg_cap_ + std::min<size_t>(c[rows[s]], msg_cap_));
+        return res;
+    }
+    std::vector<fmd_pocsag_info> info()
+    {
+        std::vector<fmd_pocsag_info> i(n_rows_);
+        check(fmd_pager_info(h_, i.data()));
+        return i;
+    }
+    size_t max_messages(size_t n) const { return fmd_pager_max_messages(rate_num_, rate_den_, baud_, n); }
+    uint64_t inputs() const { return value_of<uint64_t>(fmd_pager_inputs, h_); }
+    void reset() { check(fmd_pager_reset(h_)); }
+    uint32_t msg_cap() const { return msg_cap_; }
+
+private:
+    uint32_t n_rows_, msg_cap_, rate_num_, rate_den_, baud_;
+    Owned<fmd_pager, fmd_pager_free> h_;
+};
+
 namespace detail {
 // message bit i, the first in bit 7 of bits[0]; the stored bits only
 inline uint32_t pocsag_bit(const fmd_pocsag_msg& m, uint32_t i) { return (m.bits[i >> 3] >> (7 - (i & 7u))) & 1u; }

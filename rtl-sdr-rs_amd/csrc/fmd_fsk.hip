@@ -319,6 +319,16 @@ int fmd_fsk_hits(fmd_fsk* h, uint32_t* counts, fmd_fsk_hit* hits)
     return FMD_OK;
 }
 
+// where fmd_fsk_hits reads from (no synchronisation: a kernel behind the call that wrote them reads them in stream order)
+int fmd_pager_fsk_hits(fmd_fsk* h, const void** d_counts, const void** d_hits)
+{
+    if (!h || !d_counts || !d_hits) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    const uint8_t* const src = h->hits.in<uint8_t>(h->rows.core.cur);          // what the last call wrote
+    *d_counts = src;
+    *d_hits = src + h->rec_off;
+    return FMD_OK;
+}
+
 int fmd_fsk_run_device(fmd_fsk* h, const void* d_in, size_t n_in, size_t in_cap, void* d_out, size_t out_cap, size_t* n_out, void* stream)
 {
     return fmd_ddc_run_device(h ? &h->rows.core : nullptr, d_in, d_out,

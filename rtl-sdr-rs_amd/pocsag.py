@@ -1,15 +1,16 @@
 """Host-side wrapper of the pager decoder (include/fmd.h): the FSK front end fmd_fsk_* -- every mono int16 row a bank leaves on the
 device through a box matched filter one bit long, one soft decision per `D` samples, and a record wherever the 32-bit sync word
 ends -- and the host's POCSAG batch decoder fmd_pocsag_decoder_*, one per row, which reads bit timing, slicer level and polarity
-from those records: pager messages at 512, 1200 or 2400 bit/s out of any bank's NFM rows.  Both are exact in integers and
-independent of how the stream is cut."""
+from those records: pager messages at 512, 1200 or 2400 bit/s out of any bank's NFM rows; and the page bank fmd_pager_*, the same
+decoder for every row on the device, which takes the soft decisions and records where they lie and returns only the messages.  All
+are exact in integers and independent of how the stream is cut."""
 import ctypes as C
 import math
 from collections import namedtuple
 
 import numpy as np
 
-from ._ffi import DeviceConfig, RowProcessor, bank_rows, check, lib
+from ._ffi import BankHandle, DeviceConfig, RowProcessor, bank_rows, check, lib
 
 POCSAG_SYNC = 0x7CD215D8
 POCSAG_IDLE = 0x7A89C197
@@ -115,6 +116,13 @@ class FskDemod(RowProcessor):
         counts, rec = np.zeros(self.n_rows, np.uint32), np.zeros((self.n_rows, self.hit_cap), HIT_DTYPE)
         check(self._fn("hits")(self._h, counts.ctypes.data, rec.ctypes.data))
         return counts, rec
+
+    def hits_device(self):
+        """(d_counts, d_hits): device addresses of what hits() would read, uint32 [n_rows] and records [n_rows][hit_cap].  Does not
+        synchronise; valid until the handle's next call that launches, its reset or its close."""
+        c, h = C.c_void_p(), C.c_void_p()
+        check(lib().fmd_pager_fsk_hits(self._h, C.byref(c), C.byref(h)))
+        return c.value, h.value
 
 
 def pocsag_valid(w):
@@ -332,3 +340,133 @@ def decode_pages(demod, calls):
             i = decs[r].info()
             busy[r] = bool(i["locked"] or i["searching"])
     return [dict(decs[r].info(), messages_list=found[r], pushes=pushes[r]) for r in range(demod.n_rows)]
+
+
+def _msg_dict(m):
+    return {"address": m.address, "function": m.function, "n_bits": m.n_bits, "bits": bytes(m.bits[:(min(m.n_bits, 2560) + 7) // 8]),
+            "corrected": m.corrected, "inverted": m.inverted, "end_sample": m.end_sample}
+
+
+def pocsag_max_messages(rate_num, rate_den, baud, n):
+    """The messages one row can complete in a call of n soft decisions at most (include/fmd.h, fmd_pager_*): with q = mod // step and
+    B = ceil(n / q) bits, (B + 31) // 32 + 1 + B // 512."""
+    return int(lib().fmd_pager_max_messages(int(rate_num), int(rate_den), int(baud), int(n)))
+
+
+class Pager(BankHandle):
+    """The page bank (fmd_pager_*): a PocsagDecoder(rate_num, rate_den, baud, max_errors) per row, on the device.  run_batch takes
+    int16 [n_rows, n_in] with the counts [n_rows] and records [n_rows, hit_cap] of FskDemod.hits() on the host; run_device an
+    FskDemod's d_out as it stands with its out_cap as in_cap, and the addresses of FskDemod.hits_device(); both return nothing.  Behind
+    a call: counts() uint32 [n_rows], the messages that closed in it; msgs(rows) the first min(count, msg_cap) of each listed row as
+    PocsagDecoder.push returns them, in the order they closed; info() the rows' cumulative counters as PocsagDecoder.info() gives
+    them."""
+    _prefix = "pager"
+
+    def __init__(self, rate_num, rate_den=1, baud=1200, max_errors=1, msg_cap=4, n_rows=1, device_id=-1):
+        self.rate_num, self.rate_den, self.baud = int(rate_num), int(rate_den), int(baud)
+        self.max_errors, self.msg_cap, self.n_rows = int(max_errors), int(msg_cap), int(n_rows)
+        for name in ("rate_num", "rate_den", "baud", "max_errors", "msg_cap", "n_rows"):
+            if not 0 <= getattr(self, name) < 1 << 32:
+                raise ValueError("%s out of range" % name)
+        self._h = C.c_void_p()
+        dev = DeviceConfig(self.n_rows, device_id, 0)
+        check(lib().fmd_pager_new(self.rate_num, self.rate_den, self.baud, self.max_errors, self.msg_cap, C.byref(dev), C.byref(self._h)))
+
+    def max_messages(self, n_in):
+        return pocsag_max_messages(self.rate_num, self.rate_den, self.baud, n_in)
+
+    def inputs(self):
+        """Samples taken per row since creation or reset."""
+        n = C.c_uint64(0)
+        check(lib().fmd_pager_inputs(self._h, C.byref(n)))
+        return n.value
+
+    def run_batch(self, soft, counts, hits):
+        soft = np.ascontiguousarray(soft, dtype=np.int16)
+        if soft.ndim != 2 or soft.shape[0] != self.n_rows:
+            raise ValueError("soft must be [n_rows, n_in]")
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        if counts.shape[0] != self.n_rows or hits.ndim != 2 or hits.shape[0] != self.n_rows:
+            raise ValueError("counts must be [n_rows] and hits [n_rows, hit_cap]")
+        check(lib().fmd_pager_run_batch(self._h, soft.ctypes.data, soft.shape[1], soft.shape[1], counts.ctypes.data, hits.ctypes.data,
+                                        hits.shape[1]))
+
+    def run_device(self, d_soft, n_in, in_cap, d_counts, d_hits, hit_cap, stream=None):
+        """Enqueue on device pointers (d_soft [n_rows][in_cap], the first n_in samples of each row valid; d_counts [n_rows] uint32;
+        d_hits [n_rows][hit_cap] records).  `stream` must stay alive until the handle's next `run_device` call or `check` has
+        returned (include/fmd.h)."""
+        check(lib().fmd_pager_run_device(self._h, d_soft, n_in, in_cap, d_counts, d_hits, hit_cap, stream))
+
+    def counts(self):
+        c = np.zeros(self.n_rows, np.uint32)
+        check(lib().fmd_pager_counts(self._h, c.ctypes.data))
+        return c
+
+    def msg_records(self, rows):
+        """The PocsagMsg records [len(rows)][msg_cap] of the listed rows, zero behind each row's messages."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        buf = (PocsagMsg * (self.msg_cap * max(1, rows.shape[0])))()
+        check(lib().fmd_pager_msgs(self._h, rows.ctypes.data, rows.shape[0], buf))
+        return [[buf[s * self.msg_cap + k] for k in range(self.msg_cap)] for s in range(rows.shape[0])]
+
+    def msgs(self, rows, counts=None):
+        """A list per listed row of the messages the last call delivered for it."""
+        counts = self.counts() if counts is None else counts
+        rec = self.msg_records(rows)
+        return [[_msg_dict(m) for m in rec[s][:min(int(counts[r]), self.msg_cap)]] for s, r in enumerate(rows)]
+
+    def info(self):
+        buf = (PocsagInfo * self.n_rows)()
+        check(lib().fmd_pager_info(self._h, buf))
+        return [{"messages": i.messages, "batches": i.batches, "bad_codewords": i.bad_codewords, "orphans": i.orphans,
+                 "locked": int(i.locked), "searching": int(i.searching)} for i in buf]
+
+
+def paged(demod, msg_cap=4, device_id=-1):
+    """A Pager matched to `demod` (an FskDemod that knows its `rate`): its rows, rate / D soft decisions per second, its baud and
+    max_errors."""
+    if demod.rate is None:
+        raise ValueError("the demodulator does not know its rate")
+    return Pager(int(demod.rate), demod.D, demod.baud, demod.max_errors, msg_cap, n_rows=demod.n_rows, device_id=device_id)
+
+
+def decode_pages_gpu(demod, calls):
+    """What decode_pages(demod, calls) returns, without the "pushes" key, with the decoders on the device: the soft rows and the
+    records go from the demodulator to a page bank (paged(demod, 16)) without leaving the device; after each call only the counts
+    come back, and the messages of only the rows whose count is not zero.  Every input call is handed to the demodulator in pieces
+    short enough that no row can complete more than 16 messages in one (the front end is exact under cuts).  Equal to decode_pages
+    where no row has more than hit_cap hits in a call: there the records kept differ with the cuts."""
+    import torch
+    pager = paged(demod, 16)
+    piece = 1
+    while pager.max_messages(2 * piece) <= pager.msg_cap:
+        piece *= 2
+    piece *= demod.D                                         # input samples: a piece completes at most ceil(piece / D) soft decisions
+    found = [[] for _ in range(demod.n_rows)]
+    for x in calls:
+        x = np.ascontiguousarray(x, dtype=np.int16)
+        if x.ndim != 2 or x.shape[0] != demod.n_rows:
+            raise ValueError("a call must be [n_rows, n_in]")
+        n_in = x.shape[1]
+        if n_in == 0:
+            continue
+        d_in = torch.from_numpy(x).cuda()
+        cap = max(1, demod.out_cap(min(piece, n_in)))
+        d_soft = torch.empty((demod.n_rows, cap), dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()
+        for lo in range(0, n_in, piece):
+            m = min(piece, n_in - lo)
+            n = demod.run_device(d_in.data_ptr() + 2 * lo, m, n_in, d_soft.data_ptr(), cap)
+            d_counts, d_hits = demod.hits_device()
+            pager.run_device(d_soft.data_ptr(), n, cap, d_counts, d_hits, demod.hit_cap)
+            if n == 0:
+                continue
+            counts = pager.counts()
+            hit = np.nonzero(counts)[0]
+            if hit.size:
+                for r, got in zip(hit.tolist(), pager.msgs(hit, counts)):
+                    found[r] += got
+    info = pager.info()
+    pager.close()
+    return [dict(info[r], messages_list=found[r]) for r in range(demod.n_rows)]

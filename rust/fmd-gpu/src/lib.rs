@@ -301,6 +301,12 @@ pub struct fmd_fsk {
     _private: [u8; 0],
 }
 
+/// The page bank of include/fmd.h: an `fmd_pocsag_decoder` per row on the device.
+#[repr(C)]
+pub struct fmd_pager {
+    _private: [u8; 0],
+}
+
 /// `fmd_fsk_config` of include/fmd.h (FSK front end of the pager decoder).
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -594,6 +600,7 @@ extern "C" {
     pub fn fmd_fsk_check(f: *mut fmd_fsk) -> c_int;
     pub fn fmd_fsk_outputs(f: *const fmd_fsk, inputs: *mut u64, outputs: *mut u64) -> c_int;
     pub fn fmd_fsk_hits(f: *mut fmd_fsk, counts: *mut u32, hits: *mut fmd_fsk_hit) -> c_int;
+    pub fn fmd_pager_fsk_hits(f: *mut fmd_fsk, d_counts: *mut *const c_void, d_hits: *mut *const c_void) -> c_int;
     pub fn fmd_fsk_kernel_name(f: *const fmd_fsk, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_pocsag_decoder_new(rate_num: u32, rate_den: u32, baud: u32, max_errors: u32, out: *mut *mut fmd_pocsag_decoder) -> c_int;
     pub fn fmd_pocsag_decoder_free(d: *mut fmd_pocsag_decoder);
@@ -601,6 +608,19 @@ extern "C" {
     pub fn fmd_pocsag_decoder_push(d: *mut fmd_pocsag_decoder, soft: *const i16, n: usize, hits: *const fmd_fsk_hit, n_hits: usize, msgs: *mut fmd_pocsag_msg, cap: usize, n_msgs: *mut usize) -> c_int;
     pub fn fmd_pocsag_decoder_info(d: *const fmd_pocsag_decoder, info: *mut fmd_pocsag_info) -> c_int;
     pub fn fmd_pocsag_correct(word: u32, max_errors: u32, cw: *mut u32, n_fixed: *mut u32) -> c_int;
+    pub fn fmd_pager_max_messages(rate_num: u32, rate_den: u32, baud: u32, n: usize) -> usize;
+    pub fn fmd_pager_new(rate_num: u32, rate_den: u32, baud: u32, max_errors: u32, msg_cap: u32, dev: *const DeviceConfig, out: *mut *mut fmd_pager) -> c_int;
+    pub fn fmd_pager_free(p: *mut fmd_pager);
+    pub fn fmd_pager_reset(p: *mut fmd_pager) -> c_int;
+    pub fn fmd_pager_run_batch(p: *mut fmd_pager, soft: *const i16, n_in: usize, in_cap: usize, counts: *const u32, hits: *const fmd_fsk_hit, hit_cap: u32) -> c_int;
+    pub fn fmd_pager_run_device(p: *mut fmd_pager, d_soft: *const c_void, n_in: usize, in_cap: usize, d_counts: *const c_void, d_hits: *const c_void, hit_cap: u32, stream: *mut c_void) -> c_int;
+    pub fn fmd_pager_check(p: *mut fmd_pager) -> c_int;
+    pub fn fmd_pager_inputs(p: *const fmd_pager, inputs: *mut u64) -> c_int;
+    pub fn fmd_pager_counts(p: *mut fmd_pager, counts: *mut u32) -> c_int;
+    pub fn fmd_pager_msgs(p: *mut fmd_pager, rows: *const u32, n_sel: usize, msgs: *mut fmd_pocsag_msg) -> c_int;
+    pub fn fmd_pager_info(p: *mut fmd_pager, info: *mut fmd_pocsag_info) -> c_int;
+    pub fn fmd_pager_kernel_name(p: *const fmd_pager, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_pager_table(max_errors: u32, table: *mut u32) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
