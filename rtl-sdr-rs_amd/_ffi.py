@@ -507,6 +507,73 @@ class RowProcessor(BankHandle):
         return n.value
 
 
+class RecordBank(BankHandle):
+    """Base of the record banks (fmd_hdlc_*, fmd_pager_*): a decoder per row on the device, which takes the rows' soft decisions and
+    leaves up to `cap` records per row and call.  A subclass gives `_cap` (the name its capacity goes by), `_reader` (the entry point
+    that reads records), `_record` and `_info` (the ctypes structs), `_as_dict(record)`, max_records(n_in) and its run_*."""
+
+    def _new(self, device_id, **fields):
+        """The uint32 `fields` as attributes, range-checked: the arguments of fmd_<_prefix>_new in its order, `n_rows` last."""
+        for name, v in fields.items():
+            setattr(self, name, int(v))
+        for name in fields:
+            if not 0 <= getattr(self, name) < 1 << 32:
+                raise ValueError("%s out of range" % name)
+        self._h = C.c_void_p()
+        dev = DeviceConfig(self.n_rows, device_id, 0)
+        check(self._fn("new")(*[getattr(self, name) for name in fields if name != "n_rows"], C.byref(dev), C.byref(self._h)))
+
+    @property
+    def cap(self):
+        return getattr(self, self._cap)
+
+    def inputs(self):
+        """Samples taken per row since creation or reset."""
+        n = C.c_uint64(0)
+        check(self._fn("inputs")(self._h, C.byref(n)))
+        return n.value
+
+    def counts(self):
+        """uint32 [n_rows]: the records each row completed in the last call."""
+        c = np.zeros(self.n_rows, np.uint32)
+        check(self._fn("counts")(self._h, c.ctypes.data))
+        return c
+
+    def records(self, rows):
+        """The records [len(rows)][cap] of the listed rows, zero behind each row's own."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        buf = (self._record * (self.cap * max(1, rows.shape[0])))()
+        check(self._fn(self._reader)(self._h, rows.ctypes.data, rows.shape[0], buf))
+        return [[buf[s * self.cap + k] for k in range(self.cap)] for s in range(rows.shape[0])]
+
+    def delivered(self, rows, counts=None):
+        """A list per listed row of what the last call delivered for it, as dicts."""
+        counts = self.counts() if counts is None else counts
+        rec = self.records(rows)
+        return [[self._as_dict(m) for m in rec[s][:min(int(counts[r]), self.cap)]] for s, r in enumerate(rows)]
+
+    def info(self):
+        """The rows' cumulative counters, a dict per row."""
+        buf = (self._info * self.n_rows)()
+        check(self._fn("info")(self._h, buf))
+        return [{name: int(getattr(i, name)) for name, _ in self._info._fields_} for i in buf]
+
+    def piece(self):
+        """The largest power of two of soft decisions whose double still cannot complete more than `cap` records in a row."""
+        piece = 1
+        while self.max_records(2 * piece) <= self.cap:
+            piece *= 2
+        return piece
+
+    def harvest(self, found):
+        """Behind a call: the counts back, then the records of only the rows whose count is not zero, onto the lists found[row]."""
+        counts = self.counts()
+        hit = np.nonzero(counts)[0]
+        if hit.size:
+            for r, got in zip(hit.tolist(), self.delivered(hit, counts)):
+                found[r] += got
+
+
 def bank_rows(bank):
     """(rows, width) of a bank's output: n_streams x stations or selected channels, and the int16 per output."""
     return bank.n_streams * getattr(bank, getattr(bank, "_rows", "n_stations")), bank.width if hasattr(bank, "width") else 2

@@ -8,7 +8,7 @@ import math
 
 import numpy as np
 
-from ._ffi import BankHandle, DeviceConfig, RowProcessor, bank_rows, check, lib
+from ._ffi import DeviceConfig, RecordBank, RowProcessor, bank_rows, check, lib
 
 
 class Ax25Frame(C.Structure):
@@ -199,31 +199,20 @@ def ax25_max_frames(rate_num, rate_den, baud, n):
     return (bits + 143) // 144
 
 
-class Ax25Framer(BankHandle):
+class Ax25Framer(RecordBank):
     """The frame bank (fmd_hdlc_*): an Ax25Decoder(rate_num, rate_den, baud) per row, on the device.  run_batch takes int16 [n_rows,
     n_in] on the host, run_device an AfskDemod's d_out as it stands with its out_cap as in_cap; both return nothing.  Behind a call:
     counts() uint32 [n_rows], the frames that passed in it; frames(rows) the first min(count, frame_cap) of each listed row as dicts
     {"data", "end_sample"}, in the order they closed; info() the rows' cumulative counters as Ax25Decoder.info() gives them."""
-    _prefix = "hdlc"
+    _prefix, _cap, _reader, _record, _info, _as_dict = "hdlc", "frame_cap", "frames", Ax25Frame, Ax25Info, staticmethod(_frame_dict)
+    frame_records, frames = RecordBank.records, RecordBank.delivered
 
     def __init__(self, rate_num, rate_den=1, baud=1200, frame_cap=4, n_rows=1, device_id=-1):
-        self.rate_num, self.rate_den, self.baud = int(rate_num), int(rate_den), int(baud)
-        self.frame_cap, self.n_rows = int(frame_cap), int(n_rows)
-        for name in ("rate_num", "rate_den", "baud", "frame_cap", "n_rows"):
-            if not 0 <= getattr(self, name) < 1 << 32:
-                raise ValueError("%s out of range" % name)
-        self._h = C.c_void_p()
-        dev = DeviceConfig(self.n_rows, device_id, 0)
-        check(lib().fmd_hdlc_new(self.rate_num, self.rate_den, self.baud, self.frame_cap, C.byref(dev), C.byref(self._h)))
+        self._new(device_id, rate_num=rate_num, rate_den=rate_den, baud=baud, frame_cap=frame_cap, n_rows=n_rows)
 
     def max_frames(self, n_in):
         return ax25_max_frames(self.rate_num, self.rate_den, self.baud, n_in)
-
-    def inputs(self):
-        """Samples taken per row since creation or reset."""
-        n = C.c_uint64(0)
-        check(lib().fmd_hdlc_inputs(self._h, C.byref(n)))
-        return n.value
+    max_records = max_frames
 
     def run_batch(self, soft):
         soft = np.ascontiguousarray(soft, dtype=np.int16)
@@ -235,29 +224,6 @@ class Ax25Framer(BankHandle):
         """Enqueue on a device pointer (d_in [n_rows][in_cap], the first n_in samples of each row valid).  `stream` must stay alive
         until the handle's next `run_device` call or `check` has returned (include/fmd.h)."""
         check(lib().fmd_hdlc_run_device(self._h, d_in, n_in, in_cap, stream))
-
-    def counts(self):
-        c = np.zeros(self.n_rows, np.uint32)
-        check(lib().fmd_hdlc_counts(self._h, c.ctypes.data))
-        return c
-
-    def frame_records(self, rows):
-        """The Ax25Frame records [len(rows)][frame_cap] of the listed rows, zero behind each row's frames."""
-        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        buf = (Ax25Frame * (self.frame_cap * max(1, rows.shape[0])))()
-        check(lib().fmd_hdlc_frames(self._h, rows.ctypes.data, rows.shape[0], buf))
-        return [[buf[s * self.frame_cap + k] for k in range(self.frame_cap)] for s in range(rows.shape[0])]
-
-    def frames(self, rows, counts=None):
-        """A list per listed row of the frames the last call delivered for it."""
-        counts = self.counts() if counts is None else counts
-        rec = self.frame_records(rows)
-        return [[_frame_dict(f) for f in rec[s][:min(int(counts[r]), self.frame_cap)]] for s, r in enumerate(rows)]
-
-    def info(self):
-        buf = (Ax25Info * self.n_rows)()
-        check(lib().fmd_hdlc_info(self._h, buf))
-        return [{"frames_ok": i.frames_ok, "bad_fcs": i.bad_fcs, "aborts": i.aborts, "in_frame": int(i.in_frame)} for i in buf]
 
 
 def framed(demod, frame_cap=4, device_id=-1):
@@ -275,9 +241,7 @@ def decode_rows_gpu(demod, calls):
     in one."""
     import torch
     framer = framed(demod, 16)
-    piece = 1
-    while framer.max_frames(2 * piece) <= framer.frame_cap:  # (>= 2161: a sample takes at most one bit)
-        piece *= 2
+    piece = framer.piece()                                   # (>= 2161: a sample takes at most one bit)
     frames = [[] for _ in range(demod.n_rows)]
     for x in calls:
         x = np.ascontiguousarray(x, dtype=np.int16)
@@ -291,11 +255,7 @@ def decode_rows_gpu(demod, calls):
         n = demod.run_device(d_in.data_ptr(), n_in, max(1, n_in), d_soft.data_ptr(), cap)
         for lo in range(0, n, piece):
             framer.run_device(d_soft.data_ptr() + 2 * lo, min(piece, n - lo), cap)
-            counts = framer.counts()
-            hit = np.nonzero(counts)[0]
-            if hit.size:
-                for r, got in zip(hit.tolist(), framer.frames(hit, counts)):
-                    frames[r] += got
+            framer.harvest(frames)
     info = framer.info()
     framer.close()
     return [dict(info[r], frames=frames[r]) for r in range(demod.n_rows)]

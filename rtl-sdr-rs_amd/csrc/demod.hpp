@@ -877,6 +877,45 @@ protected:
     Owned<H, Free> h_;
 };
 
+// Base of the record banks (fmd_hdlc_*, fmd_pager_*): owns the handle H of `n_rows` rows that leave up to `cap` records Rec per row
+// and call.  Behind a run: counts() per row, records(rows) the first min(count, cap) of each listed row in the order they closed,
+// info() the rows' cumulative counters.
+template <class H, void (*Free)(H*), class Rec, class Info, auto Counts, auto Records, auto InfoOf, auto Inputs, auto Reset>
+class RecordBank {
+public:
+    std::vector<uint32_t> counts()
+    {
+        std::vector<uint32_t> c(n_rows_);
+        check(Counts(h_, c.data()));
+        return c;
+    }
+    std::vector<Info> info()
+    {
+        std::vector<Info> i(n_rows_);
+        check(InfoOf(h_, i.data()));
+        return i;
+    }
+    uint64_t inputs() const { return value_of<uint64_t>(Inputs, h_); }
+    void reset() { check(Reset(h_)); }
+
+protected:
+    RecordBank(uint32_t n_rows, uint32_t cap) : n_rows_(n_rows), cap_(cap) {}
+
+    std::vector<std::vector<Rec>> records(const std::vector<uint32_t>& rows)
+    {
+        const std::vector<uint32_t> c = counts();
+        std::vector<Rec> buf(std::max<size_t>(1, rows.size() * cap_));
+        check(Records(h_, rows.data(), rows.size(), buf.data()));
+        std::vector<std::vector<Rec>> res(rows.size());
+        for (size_t s = 0; s < rows.size(); ++s)
+            res[s].assign(buf.begin() + s * cap_, buf.begin() + s * cap_ + std::min<size_t>(c[rows[s]], cap_));
+        return res;
+    }
+
+    uint32_t n_rows_, cap_;
+    Owned<H, Free> h_;
+};
+
 // Rational resampler (fmd_resample_*): `taps` is [L][T] phase-major; run() takes [n_rows][n_in][width] int16 and returns the
 // call's outputs per row, interleaved by `width`.
 class Resampler : public RowProcessor<fmd_resample, fmd_resample_free, fmd_resample_run_batch, fmd_resample_outputs, fmd_resample_reset> {
@@ -1186,45 +1225,19 @@ private:
 // The frame bank (fmd_hdlc_*): an Ax25Decoder per row on the device.  run() takes the soft decisions [n_rows][n_in] of an AfskDemod;
 // behind it counts() gives the frames that passed in the call per row, frames(rows) the first min(count, frame_cap) of each listed
 // row in the order they closed, info() the rows' cumulative counters.
-class Ax25Framer {
+class Ax25Framer : public RecordBank<fmd_hdlc, fmd_hdlc_free, fmd_ax25_frame, fmd_ax25_info, fmd_hdlc_counts, fmd_hdlc_frames, fmd_hdlc_info,
+                                     fmd_hdlc_inputs, fmd_hdlc_reset> {
 public:
     Ax25Framer(uint32_t rate_num, uint32_t rate_den, uint32_t baud = 1200, uint32_t frame_cap = 4, uint32_t n_rows = 1, int32_t device_id = -1)
-        : n_rows_(n_rows), frame_cap_(frame_cap)
+        : RecordBank(n_rows, frame_cap)
     {
         fmd_device_config dev{n_rows, device_id, 0};
         check(fmd_hdlc_new(rate_num, rate_den, baud, frame_cap, &dev, h_.out()));
     }
 
     void run(const int16_t* soft, size_t n_in) { check(fmd_hdlc_run_batch(h_, soft, n_in, n_in)); }
-    std::vector<uint32_t> counts()
-    {
-        std::vector<uint32_t> c(n_rows_);
-        check(fmd_hdlc_counts(h_, c.data()));
-        return c;
-    }
-    std::vector<std::vector<fmd_ax25_frame>> frames(const std::vector<uint32_t>& rows)
-    {
-        const std::vector<uint32_t> c = counts();
-        std::vector<fmd_ax25_frame> buf(std::max<size_t>(1, rows.size() * frame_cap_));
-        check(fmd_hdlc_frames(h_, rows.data(), rows.size(), buf.data()));
-        std::vector<std::vector<fmd_ax25_frame>> res(rows.size());
-        for (size_t s = 0; s < rows.size(); ++s)
-            res[s].assign(buf.begin() + s * frame_cap_, buf.begin() + s * frame_cap_ + std::min<size_t>(c[rows[s]], frame_cap_));
-        return res;
-    }
-    std::vector<fmd_ax25_info> info()
-    {
-        std::vector<fmd_ax25_info> i(n_rows_);
-        check(fmd_hdlc_info(h_, i.data()));
-        return i;
-    }
-    uint64_t inputs() const { return value_of<uint64_t>(fmd_hdlc_inputs, h_); }
-    void reset() { check(fmd_hdlc_reset(h_)); }
-    uint32_t frame_cap() const { return frame_cap_; }
-
-private:
-    uint32_t n_rows_, frame_cap_;
-    Owned<fmd_hdlc, fmd_hdlc_free> h_;
+    std::vector<std::vector<fmd_ax25_frame>> frames(const std::vector<uint32_t>& rows) { return records(rows); }
+    uint32_t frame_cap() const { return cap_; }
 };
 
 namespace detail {
@@ -1368,11 +1381,12 @@ private:
 // The page bank (fmd_pager_*): a PocsagDecoder per row on the device.  run() takes the soft decisions [n_rows][n_in] of an FskDemod
 // with the records of the same call as FskDemod::hits() gives them; behind it counts() gives the messages that closed in the call
 // per row, msgs(rows) the first min(count, msg_cap) of each listed row in the order they closed, info() the rows' cumulative counters.
-class Pager {
+class Pager : public RecordBank<fmd_pager, fmd_pager_free, fmd_pocsag_msg, fmd_pocsag_info, fmd_pager_counts, fmd_pager_msgs, fmd_pager_info,
+                                fmd_pager_inputs, fmd_pager_reset> {
 public:
     Pager(uint32_t rate_num, uint32_t rate_den, uint32_t baud = 1200, uint32_t max_errors = 1, uint32_t msg_cap = 4, uint32_t n_rows = 1,
           int32_t device_id = -1)
-        : n_rows_(n_rows), msg_cap_(msg_cap), rate_num_(rate_num), rate_den_(rate_den), baud_(baud)
+        : RecordBank(n_rows, msg_cap), rate_num_(rate_num), rate_den_(rate_den), baud_(baud)
     {
         fmd_device_config dev{n_rows, device_id, 0};
         check(fmd_pager_new(rate_num, rate_den, baud, max_errors, msg_cap, &dev, h_.out()));
@@ -1390,36 +1404,12 @@ public:
         }
         check(fmd_pager_run_batch(h_, soft, n_in, n_in, cnt.data(), rec.data(), (uint32_t)cap));
     }
-    std::vector<uint32_t> counts()
-    {
-        std::vector<uint32_t> c(n_rows_);
-        check(fmd_pager_counts(h_, c.data()));
-        return c;
-    }
-    std::vector<std::vector<fmd_pocsag_msg>> msgs(const std::vector<uint32_t>& rows)
-    {
-        const std::vector<uint32_t> c = counts();
-        std::vector<fmd_pocsag_msg> buf(std::max<size_t>(1, rows.size() * msg_cap_));
-        check(fmd_pager_msgs(h_, rows.data(), rows.size(), buf.data()));
-        std::vector<std::vector<fmd_pocsag_msg>> res(rows.size());
-        for (size_t s = 0; s < rows.size(); ++s)
-            res[s].assign(buf.begin() + s * msg_cap_, buf.begin() + s * msg_cap_ + std::min<size_t>(c[rows[s]], msg_cap_));
-        return res;
-    }
-    std::vector<fmd_pocsag_info> info()
-    {
-        std::vector<fmd_pocsag_info> i(n_rows_);
-        check(fmd_pager_info(h_, i.data()));
-        return i;
-    }
+    std::vector<std::vector<fmd_pocsag_msg>> msgs(const std::vector<uint32_t>& rows) { return records(rows); }
     size_t max_messages(size_t n) const { return fmd_pager_max_messages(rate_num_, rate_den_, baud_, n); }
-    uint64_t inputs() const { return value_of<uint64_t>(fmd_pager_inputs, h_); }
-    void reset() { check(fmd_pager_reset(h_)); }
-    uint32_t msg_cap() const { return msg_cap_; }
+    uint32_t msg_cap() const { return cap_; }
 
 private:
-    uint32_t n_rows_, msg_cap_, rate_num_, rate_den_, baud_;
-    Owned<fmd_pager, fmd_pager_free> h_;
+    uint32_t rate_num_, rate_den_, baud_;
 };
 
 namespace detail {

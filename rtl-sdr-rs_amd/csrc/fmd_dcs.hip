@@ -462,10 +462,8 @@ int fmd_dcs_outputs(const fmd_dcs* h, uint64_t* inputs, uint64_t* outputs)
 int fmd_dcs_status(fmd_dcs* h, int32_t* code, uint32_t* hits, uint8_t* open)
 {
     if (!h || !code || !hits || !open) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->rows.core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    std::vector<int32_t> st((size_t)h->rows.n_rows * fmd_dc::kState);
-    FMD_DDC_TRY(hipMemcpy(st.data(), h->state.in<int32_t>(h->rows.core.cur), st.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<int32_t> st;
+    if (const int rc = fmd_rows_read_state(h->rows, h->state, fmd_dc::kState, st)) return rc;
     for (size_t r = 0; r < h->rows.n_rows; ++r) {
         const int32_t* s = &st[r * fmd_dc::kState];
         code[r] = s[0] - 1;

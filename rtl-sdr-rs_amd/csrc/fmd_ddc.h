@@ -316,8 +316,9 @@ struct FmdDdcPair {
     template <class T> T* out(int cur) const { return static_cast<T*>(p[cur ^ 1]); }
 };
 
-// A further device buffer of the handle: a constant uploaded by the constructor (src != nullptr) or call-sized scratch that
-// fmd_ddc_grow allocates in the calls (src == nullptr).
+// A further device buffer of the handle: a constant uploaded by the constructor (src != nullptr), a buffer the kernels update in
+// place, which the constructor allocates and zeroes and reset leaves alone (src == nullptr, bytes != 0), or call-sized scratch that
+// fmd_ddc_grow allocates in the calls (src == nullptr, bytes == 0).
 struct FmdDdcOwned {
     void** slot = nullptr;
     const void* src = nullptr;
@@ -376,8 +377,8 @@ inline int fmd_ddc_open(FmdDdcCore& c, const fmd_device_config* dev)
 }
 
 // On c.device: the plan's buffers that are not empty (the NCO table with the phase steps; a handle whose front end is another
-// handle's leaves its plan empty), a zeroed history of `hist_bytes` twice when non-zero, the stream, the registered pairs zeroed
-// and the registered constants.  nullptr, or what failed.
+// handle's leaves its plan empty), a zeroed history of `hist_bytes` twice when non-zero, the stream, the registered pairs zeroed,
+// the registered constants and the registered in-place buffers zeroed.  nullptr, or what failed.
 inline const char* fmd_ddc_upload(FmdDdcCore& c, const FmdDdcPlan& P, size_t hist_bytes)
 {
     if (!P.amat.empty() && (hipMalloc(&c.d_amat, P.amat.size() * 4) != hipSuccess || hipMemcpy(c.d_amat, P.amat.data(), P.amat.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
@@ -405,6 +406,8 @@ inline const char* fmd_ddc_upload(FmdDdcCore& c, const FmdDdcPlan& P, size_t his
         FmdDdcOwned& o = c.owned[k];
         if (o.src && (hipMalloc(o.slot, o.bytes) != hipSuccess || hipMemcpy(*o.slot, o.src, o.bytes, hipMemcpyHostToDevice) != hipSuccess))
             return "hipMalloc(handle constants)";
+        if (!o.src && o.bytes && (hipMalloc(o.slot, o.bytes) != hipSuccess || hipMemset(*o.slot, 0, o.bytes) != hipSuccess))
+            return "hipMalloc(handle buffers)";
         o.src = nullptr;
     }
     return nullptr;

@@ -220,10 +220,8 @@ struct fmd_fsk {
     FmdRows rows;                                         // width 1 (its history is unused: hcap = 1, the smallest the layer takes)
     FmdDdcPair bsum;                                      // [n_rows][kBState] int32
     FmdDdcPair soft;                                      // [n_rows][kSCarry] int16
-    FmdDdcPair hits;                                      // [n_rows] uint32 (up to a multiple of 16 bytes), then [n_rows][hit_cap] records:
-                                                          // written by a call, read behind it (the pair's other side is the call before)
+    FmdRowRecords recs;                                   // fmd_fsk_hit, hit_cap per row
     fmd_fsk_config cfg{};
-    size_t rec_off = 0;                                   // bytes of the counts in `hits`
 };
 
 namespace {
@@ -243,8 +241,8 @@ int fk_enqueue(fmd_fsk* h, const void* d_in, size_t n_in, size_t in_cap, void* d
     fmd_rows_fill(A, r, d_in, n_in, in_cap, d_out, out_cap);
     A.b_in = h->bsum.in<int32_t>(r.core.cur); A.b_out = h->bsum.out<int32_t>(r.core.cur);
     A.s_in = h->soft.in<int16_t>(r.core.cur); A.s_out = h->soft.out<int16_t>(r.core.cur);
-    A.cnt_out = h->hits.out<uint32_t>(r.core.cur);
-    A.rec_out = reinterpret_cast<fmd_fk::i4*>(h->hits.out<uint8_t>(r.core.cur) + h->rec_off);
+    A.cnt_out = h->recs.cnt_out(r.core.cur);
+    A.rec_out = reinterpret_cast<fmd_fk::i4*>(h->recs.rec_out(r.core.cur));
     A.pos_r = (uint32_t)pos_r;
     A.k0 = (uint32_t)((r.core.pos / D) & 0xFFFFu);
     A.n_out = (uint32_t)cnt;
@@ -285,10 +283,9 @@ int fmd_fsk_new(const fmd_fsk_config* cfg, uint32_t width, const fmd_device_conf
     h->rows.width = 1; h->rows.n_rows = dev->n_channels; h->rows.hcap = 1u;
     h->rows.lds = (size_t)fmd_fk::kRows * fmd_fk::kChunk * cfg->D * sizeof(int16_t);    // the staging buffers; the rings are static
     const size_t n = dev->n_channels;
-    h->rec_off = (n * sizeof(uint32_t) + 15u) & ~(size_t)15u;
     fmd_ddc_add_pair(h->rows.core, h->bsum, n * fmd_fk::kBState * sizeof(int32_t));
     fmd_ddc_add_pair(h->rows.core, h->soft, n * fmd_fk::kSCarry * sizeof(int16_t));
-    fmd_ddc_add_pair(h->rows.core, h->hits, h->rec_off + n * cfg->hit_cap * sizeof(fmd_fsk_hit));
+    fmd_rows_add_records(h->rows, h->recs, cfg->hit_cap, sizeof(fmd_fsk_hit));
     return fmd_rows_device(h, dev, fmd_fsk_free, out);
 }
 
@@ -305,17 +302,13 @@ int fmd_fsk_hits(fmd_fsk* h, uint32_t* counts, fmd_fsk_hit* hits)
 {
     if (!h) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
     FMD_DDC_ON_DEVICE(h->rows.core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    const size_t n = h->rows.n_rows;
-    const uint8_t* const src = h->hits.in<uint8_t>(h->rows.core.cur);          // what the last call wrote
+    const size_t n = h->rows.n_rows, cap = h->recs.cap;
     std::vector<uint32_t> cnt(n);
-    FMD_DDC_TRY(hipMemcpy(cnt.data(), src, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (const int rc = fmd_rows_read_counts(h->rows, h->recs, cnt.data())) return rc;
     if (counts) memcpy(counts, cnt.data(), n * sizeof(uint32_t));
     if (!hits) return FMD_OK;
-    const size_t cap = h->cfg.hit_cap;
-    FMD_DDC_TRY(hipMemcpy(hits, src + h->rec_off, n * cap * sizeof(fmd_fsk_hit), hipMemcpyDeviceToHost));
-    for (size_t r = 0; r < n; ++r)                           // behind a row's records: zeros, not what an earlier call left
-        if (cnt[r] < cap) memset(hits + r * cap + cnt[r], 0, (cap - cnt[r]) * sizeof(fmd_fsk_hit));
+    FMD_DDC_TRY(hipMemcpy(hits, h->recs.records(h->rows.core.cur), n * cap * sizeof(fmd_fsk_hit), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < n; ++r) fmd_rows_zero_behind(h->recs, cnt[r], hits + r * cap);
     return FMD_OK;
 }
 
@@ -323,9 +316,8 @@ int fmd_fsk_hits(fmd_fsk* h, uint32_t* counts, fmd_fsk_hit* hits)
 int fmd_pager_fsk_hits(fmd_fsk* h, const void** d_counts, const void** d_hits)
 {
     if (!h || !d_counts || !d_hits) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    const uint8_t* const src = h->hits.in<uint8_t>(h->rows.core.cur);          // what the last call wrote
-    *d_counts = src;
-    *d_hits = src + h->rec_off;
+    *d_counts = h->recs.counts(h->rows.core.cur);
+    *d_hits = h->recs.records(h->rows.core.cur);
     return FMD_OK;
 }
 

@@ -259,12 +259,10 @@ static_assert(sizeof(fmd_ax25_frame) == 528 && offsetof(fmd_ax25_frame, len) == 
 struct fmd_hdlc {
     FmdRows rows;                                         // width 1 (its history is unused: hcap = 1, the smallest the layer takes)
     FmdDdcPair state;                                     // [n_rows][kState] uint32
-    FmdDdcPair res;                                       // [n_rows] uint32 (up to a multiple of 16 bytes), then [n_rows][frame_cap] records:
-                                                          // written by a call, read behind it (the pair's other side is the call before)
+    FmdRowRecords recs;                                   // fmd_ax25_frame, frame_cap per row
     void* d_open = nullptr;                               // [n_rows][kOpen] bytes, in place (reset need not clear it: with nbits = 0
                                                           // nothing of it is read before it is written)
-    uint32_t mod = 0, step = 0, frame_cap = 0;
-    size_t rec_off = 0;                                   // bytes of the counts in `res`
+    uint32_t mod = 0, step = 0;
 };
 
 namespace {
@@ -278,21 +276,12 @@ int hd_enqueue(fmd_hdlc* h, const void* d_in, size_t n_in, size_t in_cap, hipStr
     A.in = static_cast<const int16_t*>(d_in); A.in_cap = in_cap; A.n_in = (uint32_t)n_in; A.n_rows = r.n_rows;
     A.st_in = h->state.in<uint32_t>(r.core.cur); A.st_out = h->state.out<uint32_t>(r.core.cur);
     A.open = static_cast<uint8_t*>(h->d_open);
-    A.cnt_out = h->res.out<uint32_t>(r.core.cur);
-    A.rec_out = h->res.out<uint8_t>(r.core.cur) + h->rec_off;
+    A.cnt_out = h->recs.cnt_out(r.core.cur);
+    A.rec_out = h->recs.rec_out(r.core.cur);
     A.pos = r.core.pos;
-    A.mod = h->mod; A.step = h->step; A.frame_cap = h->frame_cap;
+    A.mod = h->mod; A.step = h->step; A.frame_cap = h->recs.cap;
     const uint32_t grid = (r.n_rows + fmd_hd::kRows - 1u) / fmd_hd::kRows;
     return fmd_rows_launch(r, fmd_hd::fmd_hdlc_kernel, fmd_hd::fmd_hdlc_kernel, grid, fmd_hd::kThreads, A, stream, n_in, 0, nullptr);
-}
-
-// the counts of the last call, behind a device synchronisation (the caller holds the device guard)
-int hd_counts(fmd_hdlc* h, std::vector<uint32_t>& cnt)
-{
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    cnt.resize(h->rows.n_rows);
-    FMD_DDC_TRY(hipMemcpy(cnt.data(), h->res.in<uint8_t>(h->rows.core.cur), cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return FMD_OK;
 }
 
 }  // namespace
@@ -309,75 +298,29 @@ int fmd_hdlc_new(uint32_t rate_num, uint32_t rate_den, uint32_t baud, uint32_t f
     if (const int rc = fmd_rows_count_arg(dev)) return rc;
     fmd_hdlc* h = new (std::nothrow) fmd_hdlc();
     if (!h) return FMD_ERR_NOMEM;
-    h->mod = (uint32_t)mod; h->step = (uint32_t)step; h->frame_cap = frame_cap;
+    h->mod = (uint32_t)mod; h->step = (uint32_t)step;
     h->rows.width = 1; h->rows.n_rows = dev->n_channels; h->rows.hcap = 1u;
     h->rows.lds = 0;                                         // the tile is static
     const size_t n = dev->n_channels;
-    h->rec_off = (n * sizeof(uint32_t) + 15u) & ~(size_t)15u;
     fmd_ddc_add_pair(h->rows.core, h->state, n * fmd_hd::kState * sizeof(uint32_t));
-    fmd_ddc_add_pair(h->rows.core, h->res, h->rec_off + n * frame_cap * sizeof(fmd_ax25_frame));
-    fmd_ddc_add_owned(h->rows.core, h->d_open);              // (no source: allocated below, freed with the core)
-    if (const int rc = fmd_rows_device(h, dev, fmd_hdlc_free, out)) return rc;
-    FmdDeviceGuard guard(h->rows.core.device);
-    if (guard.error() != hipSuccess || hipMalloc(&h->d_open, n * fmd_hd::kOpen) != hipSuccess ||
-        hipMemset(h->d_open, 0, n * fmd_hd::kOpen) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        fmd_internal_set_err("hipMalloc(open frames)");
-        fmd_hdlc_free(h);
-        *out = nullptr;
-        return FMD_ERR_HIP;
-    }
-    return FMD_OK;
+    fmd_rows_add_records(h->rows, h->recs, frame_cap, sizeof(fmd_ax25_frame));
+    fmd_ddc_add_owned(h->rows.core, h->d_open, nullptr, n * fmd_hd::kOpen);
+    return fmd_rows_device(h, dev, fmd_hdlc_free, out);
 }
 
 void fmd_hdlc_free(fmd_hdlc* h) { fmd_rows_free(h); }
 int fmd_hdlc_reset(fmd_hdlc* h) { return fmd_rows_reset(h); }
 int fmd_hdlc_check(fmd_hdlc* h) { return fmd_rows_check(h); }
-
-int fmd_hdlc_inputs(const fmd_hdlc* h, uint64_t* inputs)
-{
-    if (!h || !inputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *inputs = h->rows.core.pos;
-    return FMD_OK;
-}
-
-int fmd_hdlc_counts(fmd_hdlc* h, uint32_t* counts)
-{
-    if (!h || !counts) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->rows.core.device);
-    std::vector<uint32_t> cnt;
-    if (const int rc = hd_counts(h, cnt)) return rc;
-    memcpy(counts, cnt.data(), cnt.size() * sizeof(uint32_t));
-    return FMD_OK;
-}
-
-int fmd_hdlc_frames(fmd_hdlc* h, const uint32_t* rows, size_t n_sel, fmd_ax25_frame* frames)
-{
-    if (!h || (n_sel && (!rows || !frames))) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    for (size_t s = 0; s < n_sel; ++s)
-        if (rows[s] >= h->rows.n_rows) { fmd_internal_set_err("row out of range"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->rows.core.device);
-    std::vector<uint32_t> cnt;
-    if (const int rc = hd_counts(h, cnt)) return rc;
-    const size_t cap = h->frame_cap;
-    const uint8_t* const src = h->res.in<uint8_t>(h->rows.core.cur) + h->rec_off;
-    for (size_t s = 0; s < n_sel; ++s) {                     // behind a row's records: zeros, not what an earlier call left
-        const size_t k = cnt[rows[s]] < cap ? cnt[rows[s]] : cap;
-        fmd_ax25_frame* const dst = frames + s * cap;
-        if (k) FMD_DDC_TRY(hipMemcpy(dst, src + (size_t)rows[s] * cap * sizeof(fmd_ax25_frame), k * sizeof(fmd_ax25_frame), hipMemcpyDeviceToHost));
-        if (k < cap) memset(dst + k, 0, (cap - k) * sizeof(fmd_ax25_frame));
-    }
-    return FMD_OK;
-}
+int fmd_hdlc_inputs(const fmd_hdlc* h, uint64_t* inputs) { return fmd_rows_inputs(h, inputs); }
+int fmd_hdlc_counts(fmd_hdlc* h, uint32_t* counts) { return fmd_rows_counts(h, counts); }
+int fmd_hdlc_frames(fmd_hdlc* h, const uint32_t* rows, size_t n_sel, fmd_ax25_frame* frames) { return fmd_rows_records(h, rows, n_sel, frames); }
 
 int fmd_hdlc_info(fmd_hdlc* h, fmd_ax25_info* info)
 {
     if (!h || !info) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->rows.core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    const size_t n = h->rows.n_rows;
-    std::vector<uint32_t> st(n * fmd_hd::kState);
-    FMD_DDC_TRY(hipMemcpy(st.data(), h->state.in<uint32_t>(h->rows.core.cur), st.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (size_t r = 0; r < n; ++r) {
+    std::vector<uint32_t> st;
+    if (const int rc = fmd_rows_read_state(h->rows, h->state, fmd_hd::kState, st)) return rc;
+    for (size_t r = 0; r < h->rows.n_rows; ++r) {
         const uint32_t* const s = &st[r * fmd_hd::kState];
         memset(&info[r], 0, sizeof info[r]);
         info[r].frames_ok = s[4] | (uint64_t)s[5] << 32;
@@ -394,23 +337,10 @@ int fmd_hdlc_run_device(fmd_hdlc* h, const void* d_in, size_t n_in, size_t in_ca
                               [&] { return hd_enqueue(h, d_in, n_in, in_cap, static_cast<hipStream_t>(stream)); });
 }
 
-// Host rows in, nothing out: the results stay on the device until they are asked for.  (fmd_rows_run_batch is for handles with int16
-// output rows.)  A call of no samples does not touch the device.
 int fmd_hdlc_run_batch(fmd_hdlc* h, const int16_t* in, size_t n_in, size_t in_cap)
 {
-    if (!h || !in) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    if (n_in > in_cap) { fmd_internal_set_err("n_in > in_cap"); return FMD_ERR_CAPACITY; }
-    if (n_in == 0) return FMD_OK;
-    FmdDdcCore& c = h->rows.core;
-    FMD_DDC_ON_DEVICE(c.device);
-    const size_t in_bytes = (size_t)h->rows.n_rows * in_cap * sizeof(int16_t);
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
-    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, in, in_bytes, hipMemcpyHostToDevice, c.stream));
-    const int rc = hd_enqueue(h, c.d_iq, n_in, in_cap, c.stream);
-    const hipError_t e = hipStreamSynchronize(c.stream);
-    if (rc) return rc;
-    FMD_DDC_TRY(e);
-    return FMD_OK;
+    return fmd_rows_feed_batch(h, in, n_in, in_cap, [](FmdDdcCore&) -> int { return FMD_OK; },
+                               [&](const void* d_in, hipStream_t s) { return hd_enqueue(h, d_in, n_in, in_cap, s); });
 }
 
 int fmd_hdlc_kernel_name(const fmd_hdlc* h, char* name, size_t cap) { return fmd_rows_kernel_name(h, name, cap, "fmd_hd::fmd_hdlc_kernel"); }

@@ -360,14 +360,12 @@ static_assert(sizeof(fmd_fsk_hit) == 16, "the kernel reads fmd_fsk_hit as four d
 struct fmd_pager {
     FmdRows rows;                                         // width 1; its history pair is the tail: hcap = 64
     FmdDdcPair state;                                     // [n_rows][kState] uint32
-    FmdDdcPair res;                                       // [n_rows] uint32 (up to a multiple of 16 bytes), then [n_rows][msg_cap] records:
-                                                          // written by a call, read behind it (the pair's other side is the call before)
+    FmdRowRecords recs;                                   // fmd_pocsag_msg, msg_cap per row
     void* d_open = nullptr;                               // [n_rows][kOpen] bytes, in place (reset need not clear it: with n_bits = 0
                                                           // nothing of it is read before it is written)
     void* d_table = nullptr;                              // [kTable] uint32
     uint64_t mod = 0, step = 0;
-    uint32_t max_errors = 0, msg_cap = 0;
-    size_t rec_off = 0;                                   // bytes of the counts in `res`
+    uint32_t max_errors = 0;
 };
 
 namespace {
@@ -406,25 +404,16 @@ int pg_enqueue(fmd_pager* h, const void* d_in, size_t n_in, size_t in_cap, const
     A.open = static_cast<uint8_t*>(h->d_open);
     A.table = static_cast<const uint32_t*>(h->d_table);
     A.hcnt = static_cast<const uint32_t*>(d_counts); A.hrec = static_cast<const uint32_t*>(d_hits);
-    A.cnt_out = h->res.out<uint32_t>(r.core.cur);
-    A.rec_out = h->res.out<uint8_t>(r.core.cur) + h->rec_off;
+    A.cnt_out = h->recs.cnt_out(r.core.cur);
+    A.rec_out = h->recs.rec_out(r.core.cur);
     A.pos = r.core.pos;
-    A.hit_cap = hit_cap; A.msg_cap = h->msg_cap;
+    A.hit_cap = hit_cap; A.msg_cap = h->recs.cap;
     A.r = (uint32_t)((2 * mod + step) / (2 * step)); A.half = A.r / 2;
     A.q544 = (uint32_t)((2 * 544 * mod + step) / (2 * step));
     A.qd = (uint32_t)(mod / step); A.rd = (uint32_t)(2 * (mod % step)); A.rem1 = (uint32_t)((2 * mod + step) % (2 * step));
     A.two_step = (uint32_t)(2 * step);
     const uint32_t grid = (r.n_rows + fmd_pg::kRows - 1u) / fmd_pg::kRows;
     return fmd_rows_launch(r, fmd_pg::fmd_pager_kernel, fmd_pg::fmd_pager_kernel, grid, fmd_pg::kThreads, A, stream, n_in, 0, nullptr);
-}
-
-// the counts of the last call, behind a device synchronisation (the caller holds the device guard)
-int pg_counts(fmd_pager* h, std::vector<uint32_t>& cnt)
-{
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    cnt.resize(h->rows.n_rows);
-    FMD_DDC_TRY(hipMemcpy(cnt.data(), h->res.in<uint8_t>(h->rows.core.cur), cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return FMD_OK;
 }
 
 }  // namespace
@@ -467,78 +456,32 @@ int fmd_pager_new(uint32_t rate_num, uint32_t rate_den, uint32_t baud, uint32_t 
     if (const int rc = fmd_rows_count_arg(dev)) return rc;
     fmd_pager* h = new (std::nothrow) fmd_pager();
     if (!h) return FMD_ERR_NOMEM;
-    h->mod = rate_num; h->step = (uint64_t)baud * rate_den; h->max_errors = max_errors; h->msg_cap = msg_cap;
+    h->mod = rate_num; h->step = (uint64_t)baud * rate_den; h->max_errors = max_errors;
     h->rows.width = 1; h->rows.n_rows = dev->n_channels; h->rows.hcap = fmd_pg::kTail;
     h->rows.lds = 0;                                         // the table is static
     const size_t n = dev->n_channels;
     std::vector<uint32_t> table(fmd_pg::kTable);
     (void)fmd_pager_table(max_errors, table.data());
-    h->rec_off = (n * sizeof(uint32_t) + 15u) & ~(size_t)15u;
     fmd_ddc_add_pair(h->rows.core, h->state, n * fmd_pg::kState * sizeof(uint32_t));
-    fmd_ddc_add_pair(h->rows.core, h->res, h->rec_off + n * msg_cap * sizeof(fmd_pocsag_msg));
+    fmd_rows_add_records(h->rows, h->recs, msg_cap, sizeof(fmd_pocsag_msg));
     fmd_ddc_add_owned(h->rows.core, h->d_table, table.data(), table.size() * sizeof(uint32_t));
-    fmd_ddc_add_owned(h->rows.core, h->d_open);              // (no source: allocated below, freed with the core)
-    if (const int rc = fmd_rows_device(h, dev, fmd_pager_free, out)) return rc;
-    FmdDeviceGuard guard(h->rows.core.device);
-    if (guard.error() != hipSuccess || hipMalloc(&h->d_open, n * fmd_pg::kOpen) != hipSuccess ||
-        hipMemset(h->d_open, 0, n * fmd_pg::kOpen) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        fmd_internal_set_err("hipMalloc(open messages)");
-        fmd_pager_free(h);
-        *out = nullptr;
-        return FMD_ERR_HIP;
-    }
-    return FMD_OK;
+    fmd_ddc_add_owned(h->rows.core, h->d_open, nullptr, n * fmd_pg::kOpen);
+    return fmd_rows_device(h, dev, fmd_pager_free, out);
 }
 
 void fmd_pager_free(fmd_pager* h) { fmd_rows_free(h); }
 int fmd_pager_reset(fmd_pager* h) { return fmd_rows_reset(h); }
 int fmd_pager_check(fmd_pager* h) { return fmd_rows_check(h); }
-
-int fmd_pager_inputs(const fmd_pager* h, uint64_t* inputs)
-{
-    if (!h || !inputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    *inputs = h->rows.core.pos;
-    return FMD_OK;
-}
-
-int fmd_pager_counts(fmd_pager* h, uint32_t* counts)
-{
-    if (!h || !counts) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->rows.core.device);
-    std::vector<uint32_t> cnt;
-    if (const int rc = pg_counts(h, cnt)) return rc;
-    memcpy(counts, cnt.data(), cnt.size() * sizeof(uint32_t));
-    return FMD_OK;
-}
-
-int fmd_pager_msgs(fmd_pager* h, const uint32_t* rows, size_t n_sel, fmd_pocsag_msg* msgs)
-{
-    if (!h || (n_sel && (!rows || !msgs))) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    for (size_t s = 0; s < n_sel; ++s)
-        if (rows[s] >= h->rows.n_rows) { fmd_internal_set_err("row out of range"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->rows.core.device);
-    std::vector<uint32_t> cnt;
-    if (const int rc = pg_counts(h, cnt)) return rc;
-    const size_t cap = h->msg_cap;
-    const uint8_t* const src = h->res.in<uint8_t>(h->rows.core.cur) + h->rec_off;
-    for (size_t s = 0; s < n_sel; ++s) {                     // behind a row's records: zeros, not what an earlier call left
-        const size_t k = cnt[rows[s]] < cap ? cnt[rows[s]] : cap;
-        fmd_pocsag_msg* const dst = msgs + s * cap;
-        if (k) FMD_DDC_TRY(hipMemcpy(dst, src + (size_t)rows[s] * cap * sizeof(fmd_pocsag_msg), k * sizeof(fmd_pocsag_msg), hipMemcpyDeviceToHost));
-        if (k < cap) memset(dst + k, 0, (cap - k) * sizeof(fmd_pocsag_msg));
-    }
-    return FMD_OK;
-}
+int fmd_pager_inputs(const fmd_pager* h, uint64_t* inputs) { return fmd_rows_inputs(h, inputs); }
+int fmd_pager_counts(fmd_pager* h, uint32_t* counts) { return fmd_rows_counts(h, counts); }
+int fmd_pager_msgs(fmd_pager* h, const uint32_t* rows, size_t n_sel, fmd_pocsag_msg* msgs) { return fmd_rows_records(h, rows, n_sel, msgs); }
 
 int fmd_pager_info(fmd_pager* h, fmd_pocsag_info* info)
 {
     if (!h || !info) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
-    FMD_DDC_ON_DEVICE(h->rows.core.device);
-    FMD_DDC_TRY(hipDeviceSynchronize());
-    const size_t n = h->rows.n_rows;
-    std::vector<uint32_t> st(n * fmd_pg::kState);
-    FMD_DDC_TRY(hipMemcpy(st.data(), h->state.in<uint32_t>(h->rows.core.cur), st.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (size_t r = 0; r < n; ++r) {
+    std::vector<uint32_t> st;
+    if (const int rc = fmd_rows_read_state(h->rows, h->state, fmd_pg::kState, st)) return rc;
+    for (size_t r = 0; r < h->rows.n_rows; ++r) {
         const uint32_t* const s = &st[r * fmd_pg::kState];
         memset(&info[r], 0, sizeof info[r]);
         info[r].messages = s[20] | (uint64_t)s[21] << 32;
@@ -559,31 +502,25 @@ int fmd_pager_run_device(fmd_pager* h, const void* d_soft, size_t n_in, size_t i
                               [&] { return pg_enqueue(h, d_soft, n_in, in_cap, d_counts, d_hits, hit_cap, static_cast<hipStream_t>(stream)); });
 }
 
-// Host rows, counts and records in, nothing out: the results stay on the device until they are asked for.  A call of no samples
-// does not touch the device.
+// Host rows, counts and records in, nothing out: the front end's counts and records are staged into core.d_out, laid out as an
+// FmdRowRecords is.
 int fmd_pager_run_batch(fmd_pager* h, const int16_t* soft, size_t n_in, size_t in_cap, const uint32_t* counts, const fmd_fsk_hit* hits,
                         uint32_t hit_cap)
 {
     if (!h || !soft || !counts || !hits) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
     if (hit_cap < 1 || hit_cap > 64) { fmd_internal_set_err("need 1 <= hit_cap <= 64"); return FMD_ERR_UNSUPPORTED; }
-    if (n_in > in_cap) { fmd_internal_set_err("n_in > in_cap"); return FMD_ERR_CAPACITY; }
-    if (n_in == 0) return FMD_OK;
-    FmdDdcCore& c = h->rows.core;
-    FMD_DDC_ON_DEVICE(c.device);
-    const size_t n = h->rows.n_rows;
-    const size_t in_bytes = n * in_cap * sizeof(int16_t), cnt_bytes = (n * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-    const size_t hit_bytes = n * hit_cap * sizeof(fmd_fsk_hit);
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
-    FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, cnt_bytes + hit_bytes));
-    uint8_t* const d_rec = static_cast<uint8_t*>(c.d_out);
-    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, soft, in_bytes, hipMemcpyHostToDevice, c.stream));
-    FMD_DDC_TRY(hipMemcpyAsync(d_rec, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
-    FMD_DDC_TRY(hipMemcpyAsync(d_rec + cnt_bytes, hits, hit_bytes, hipMemcpyHostToDevice, c.stream));
-    const int rc = pg_enqueue(h, c.d_iq, n_in, in_cap, d_rec, d_rec + cnt_bytes, hit_cap, c.stream);
-    const hipError_t e = hipStreamSynchronize(c.stream);
-    if (rc) return rc;
-    FMD_DDC_TRY(e);
-    return FMD_OK;
+    const size_t n = h->rows.n_rows, cnt_bytes = fmd_rows_counts_bytes(n), hit_bytes = n * hit_cap * sizeof(fmd_fsk_hit);
+    const auto stage = [&](FmdDdcCore& c) -> int {
+        FMD_DDC_TRY(fmd_ddc_grow(c.d_out, c.d_out_cap, cnt_bytes + hit_bytes));
+        uint8_t* const d_rec = static_cast<uint8_t*>(c.d_out);
+        FMD_DDC_TRY(hipMemcpyAsync(d_rec, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+        FMD_DDC_TRY(hipMemcpyAsync(d_rec + cnt_bytes, hits, hit_bytes, hipMemcpyHostToDevice, c.stream));
+        return FMD_OK;
+    };
+    return fmd_rows_feed_batch(h, soft, n_in, in_cap, stage, [&](const void* d_in, hipStream_t s) {
+        const uint8_t* const d_rec = static_cast<const uint8_t*>(h->rows.core.d_out);
+        return pg_enqueue(h, d_in, n_in, in_cap, d_rec, d_rec + cnt_bytes, hit_cap, s);
+    });
 }
 
 int fmd_pager_kernel_name(const fmd_pager* h, char* name, size_t cap) { return fmd_rows_kernel_name(h, name, cap, "fmd_pg::fmd_pager_kernel"); }

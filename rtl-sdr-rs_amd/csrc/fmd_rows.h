@@ -1,9 +1,15 @@
 // fmd_rows.h -- what the row processors share on the host: the handles that post-process the int16 rows a bank leaves on the device
-// (fmd_resample.hip, fmd_agc.hip, fmd_tonesq.hip, fmd_afsk.hip).  Their common contract: n_rows rows of `width` 1 or 2 int16 per sample, d_in
+// (fmd_resample.hip, fmd_agc.hip, fmd_tonesq.hip, fmd_dcs.hip, fmd_afsk.hip, fmd_fsk.hip) and the record banks that read such rows
+// and leave records (fmd_hdlc.hip, fmd_pager.hip).  Their common contract: n_rows rows of `width` 1 or 2 int16 per sample, d_in
 // [n_rows][in_cap][width] with n_in valid samples per row, d_out [n_rows][out_cap][width], a history pair of the samples in front
 // of the call, core.pos counting input samples, and an output that does not depend on how the stream is cut.
 // A handle embeds an FmdRows as its member `rows` and keeps its kernels, its launch struct, its own fields and domain checks, its
 // counting function and the part of its enqueue that plans a call; where the handles differ they pass a callable.
+// The record side (fmd_fsk.hip's hits, fmd_hdlc.hip, fmd_pager.hip): a call leaves [n_rows] counts and [n_rows][cap] fixed-size
+// records on the device in an FmdRowRecords of the handle; behind the call the host reads the counts and min(count, cap) records of
+// a row with zeros behind them.  The record banks have no d_out: their batch takes host rows and returns nothing.  Cumulative
+// counters of the rows live in a `state` pair of the handle and are read by fmd_rows_read_state (fmd_tonesq.hip and fmd_dcs.hip
+// read their status the same way); bytes a bank updates in place are an owned buffer of the core with a size and no source.
 #pragma once
 
 #include "fmd_ddc.h"
@@ -147,5 +153,116 @@ inline int fmd_rows_run_batch(H* h, Enqueue enqueue, const int16_t* in, size_t n
     if (n) FMD_DDC_TRY(hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
     FMD_DDC_TRY(hipStreamSynchronize(c.stream));
     *n_out = n;
+    return FMD_OK;
+}
+
+// ---- the record side ------------------------------------------------------------------------------------------------------------
+
+// The results of a call: [n_rows] uint32 counts (up to a multiple of 16 bytes), then [n_rows][cap] records of rec_size bytes: written
+// by a call, read behind it (the pair's other side is the call before).
+struct FmdRowRecords {
+    FmdDdcPair res;
+    size_t rec_off = 0, rec_size = 0;                     // bytes of the counts in `res`, bytes of a record
+    uint32_t cap = 0;                                     // records per row
+    uint32_t* cnt_out(int cur) const { return res.out<uint32_t>(cur); }        // what the call that is being enqueued writes
+    uint8_t* rec_out(int cur) const { return res.out<uint8_t>(cur) + rec_off; }
+    const uint8_t* counts(int cur) const { return res.in<uint8_t>(cur); }      // what the last call wrote
+    const uint8_t* records(int cur) const { return res.in<uint8_t>(cur) + rec_off; }
+};
+
+// bytes of [n_rows] counts in front of records that are read 16 bytes at a time
+inline size_t fmd_rows_counts_bytes(size_t n_rows) { return (n_rows * sizeof(uint32_t) + 15u) & ~(size_t)15u; }
+
+// In a *_new, behind n_rows: sizes the results and registers them on the core.
+inline void fmd_rows_add_records(FmdRows& r, FmdRowRecords& q, uint32_t cap, size_t rec_size)
+{
+    q.cap = cap; q.rec_size = rec_size; q.rec_off = fmd_rows_counts_bytes(r.n_rows);
+    fmd_ddc_add_pair(r.core, q.res, q.rec_off + (size_t)r.n_rows * cap * rec_size);
+}
+
+// the counts of the last call into cnt[n_rows], behind a device synchronisation (the caller holds the device guard)
+inline int fmd_rows_read_counts(const FmdRows& r, const FmdRowRecords& q, uint32_t* cnt)
+{
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    FMD_DDC_TRY(hipMemcpy(cnt, q.counts(r.core.cur), r.n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return FMD_OK;
+}
+
+// behind the min(count, cap) records of a row at `dst`: zeros, not what an earlier call left.  Returns min(count, cap).
+inline size_t fmd_rows_zero_behind(const FmdRowRecords& q, uint32_t count, void* dst)
+{
+    const size_t k = count < q.cap ? count : q.cap;
+    memset(static_cast<uint8_t*>(dst) + k * q.rec_size, 0, (q.cap - k) * q.rec_size);
+    return k;
+}
+
+// The bodies of a record bank's entry points, over a handle H with the members `rows` and `recs`.
+template <class H>
+inline int fmd_rows_inputs(const H* h, uint64_t* inputs)
+{
+    if (!h || !inputs) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    *inputs = h->rows.core.pos;
+    return FMD_OK;
+}
+
+template <class H>
+inline int fmd_rows_counts(H* h, uint32_t* counts)
+{
+    if (!h || !counts) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(h->rows.core.device);
+    return fmd_rows_read_counts(h->rows, h->recs, counts);
+}
+
+// The records of the listed rows into recs[n_sel][cap], in the order listed; nothing is touched before every argument has passed.
+template <class H>
+inline int fmd_rows_records(H* h, const uint32_t* rows, size_t n_sel, void* recs)
+{
+    if (!h || (n_sel && (!rows || !recs))) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    const FmdRows& r = h->rows;
+    const FmdRowRecords& q = h->recs;
+    for (size_t s = 0; s < n_sel; ++s)
+        if (rows[s] >= r.n_rows) { fmd_internal_set_err("row out of range"); return FMD_ERR_INVALID_ARG; }
+    FMD_DDC_ON_DEVICE(r.core.device);
+    std::vector<uint32_t> cnt(r.n_rows);
+    if (const int rc = fmd_rows_read_counts(r, q, cnt.data())) return rc;
+    const size_t row_bytes = q.cap * q.rec_size;
+    for (size_t s = 0; s < n_sel; ++s) {
+        uint8_t* const dst = static_cast<uint8_t*>(recs) + s * row_bytes;
+        const size_t k = fmd_rows_zero_behind(q, cnt[rows[s]], dst);
+        if (k) FMD_DDC_TRY(hipMemcpy(dst, q.records(r.core.cur) + rows[s] * row_bytes, k * q.rec_size, hipMemcpyDeviceToHost));
+    }
+    return FMD_OK;
+}
+
+// The rows' carried state, `per_row` T each, as the last call left it: behind a device synchronisation, into `st`.
+template <class T>
+inline int fmd_rows_read_state(const FmdRows& r, const FmdDdcPair& state, size_t per_row, std::vector<T>& st)
+{
+    FMD_DDC_ON_DEVICE(r.core.device);
+    FMD_DDC_TRY(hipDeviceSynchronize());
+    st.resize(r.n_rows * per_row);
+    FMD_DDC_TRY(hipMemcpy(st.data(), state.in<T>(r.core.cur), st.size() * sizeof(T), hipMemcpyDeviceToHost));
+    return FMD_OK;
+}
+
+// A record bank's `_run_batch`: host rows in, nothing out -- the results stay on the device until they are asked for.  `more(core)`
+// stages whatever the call reads beside the rows (a status other than FMD_OK ends the call), the rows go into core.d_iq, then
+// enqueue(d_in, stream) on the handle's own stream.  A call of no samples does not touch the device.
+template <class H, class More, class Enqueue>
+inline int fmd_rows_feed_batch(H* h, const int16_t* in, size_t n_in, size_t in_cap, More more, Enqueue enqueue)
+{
+    if (!h || !in) { fmd_internal_set_err("null argument"); return FMD_ERR_INVALID_ARG; }
+    if (n_in > in_cap) { fmd_internal_set_err("n_in > in_cap"); return FMD_ERR_CAPACITY; }
+    if (n_in == 0) return FMD_OK;
+    FmdDdcCore& c = h->rows.core;
+    FMD_DDC_ON_DEVICE(c.device);
+    const size_t in_bytes = (size_t)h->rows.n_rows * in_cap * sizeof(int16_t);
+    FMD_DDC_TRY(fmd_ddc_grow(c.d_iq, c.d_iq_cap, in_bytes));
+    if (const int rc = more(c)) return rc;
+    FMD_DDC_TRY(hipMemcpyAsync(c.d_iq, in, in_bytes, hipMemcpyHostToDevice, c.stream));
+    const int rc = enqueue(c.d_iq, c.stream);
+    const hipError_t e = hipStreamSynchronize(c.stream);
+    if (rc) return rc;                                       // (the enqueue's status wins over the synchronise's)
+    FMD_DDC_TRY(e);
     return FMD_OK;
 }

@@ -10,7 +10,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._ffi import BankHandle, DeviceConfig, RowProcessor, bank_rows, check, lib
+from ._ffi import DeviceConfig, RecordBank, RowProcessor, bank_rows, check, lib
 
 POCSAG_SYNC = 0x7CD215D8
 POCSAG_IDLE = 0x7A89C197
@@ -353,33 +353,22 @@ def pocsag_max_messages(rate_num, rate_den, baud, n):
     return int(lib().fmd_pager_max_messages(int(rate_num), int(rate_den), int(baud), int(n)))
 
 
-class Pager(BankHandle):
+class Pager(RecordBank):
     """The page bank (fmd_pager_*): a PocsagDecoder(rate_num, rate_den, baud, max_errors) per row, on the device.  run_batch takes
     int16 [n_rows, n_in] with the counts [n_rows] and records [n_rows, hit_cap] of FskDemod.hits() on the host; run_device an
     FskDemod's d_out as it stands with its out_cap as in_cap, and the addresses of FskDemod.hits_device(); both return nothing.  Behind
     a call: counts() uint32 [n_rows], the messages that closed in it; msgs(rows) the first min(count, msg_cap) of each listed row as
     PocsagDecoder.push returns them, in the order they closed; info() the rows' cumulative counters as PocsagDecoder.info() gives
     them."""
-    _prefix = "pager"
+    _prefix, _cap, _reader, _record, _info, _as_dict = "pager", "msg_cap", "msgs", PocsagMsg, PocsagInfo, staticmethod(_msg_dict)
+    msg_records, msgs = RecordBank.records, RecordBank.delivered
 
     def __init__(self, rate_num, rate_den=1, baud=1200, max_errors=1, msg_cap=4, n_rows=1, device_id=-1):
-        self.rate_num, self.rate_den, self.baud = int(rate_num), int(rate_den), int(baud)
-        self.max_errors, self.msg_cap, self.n_rows = int(max_errors), int(msg_cap), int(n_rows)
-        for name in ("rate_num", "rate_den", "baud", "max_errors", "msg_cap", "n_rows"):
-            if not 0 <= getattr(self, name) < 1 << 32:
-                raise ValueError("%s out of range" % name)
-        self._h = C.c_void_p()
-        dev = DeviceConfig(self.n_rows, device_id, 0)
-        check(lib().fmd_pager_new(self.rate_num, self.rate_den, self.baud, self.max_errors, self.msg_cap, C.byref(dev), C.byref(self._h)))
+        self._new(device_id, rate_num=rate_num, rate_den=rate_den, baud=baud, max_errors=max_errors, msg_cap=msg_cap, n_rows=n_rows)
 
     def max_messages(self, n_in):
         return pocsag_max_messages(self.rate_num, self.rate_den, self.baud, n_in)
-
-    def inputs(self):
-        """Samples taken per row since creation or reset."""
-        n = C.c_uint64(0)
-        check(lib().fmd_pager_inputs(self._h, C.byref(n)))
-        return n.value
+    max_records = max_messages
 
     def run_batch(self, soft, counts, hits):
         soft = np.ascontiguousarray(soft, dtype=np.int16)
@@ -398,30 +387,6 @@ class Pager(BankHandle):
         returned (include/fmd.h)."""
         check(lib().fmd_pager_run_device(self._h, d_soft, n_in, in_cap, d_counts, d_hits, hit_cap, stream))
 
-    def counts(self):
-        c = np.zeros(self.n_rows, np.uint32)
-        check(lib().fmd_pager_counts(self._h, c.ctypes.data))
-        return c
-
-    def msg_records(self, rows):
-        """The PocsagMsg records [len(rows)][msg_cap] of the listed rows, zero behind each row's messages."""
-        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        buf = (PocsagMsg * (self.msg_cap * max(1, rows.shape[0])))()
-        check(lib().fmd_pager_msgs(self._h, rows.ctypes.data, rows.shape[0], buf))
-        return [[buf[s * self.msg_cap + k] for k in range(self.msg_cap)] for s in range(rows.shape[0])]
-
-    def msgs(self, rows, counts=None):
-        """A list per listed row of the messages the last call delivered for it."""
-        counts = self.counts() if counts is None else counts
-        rec = self.msg_records(rows)
-        return [[_msg_dict(m) for m in rec[s][:min(int(counts[r]), self.msg_cap)]] for s, r in enumerate(rows)]
-
-    def info(self):
-        buf = (PocsagInfo * self.n_rows)()
-        check(lib().fmd_pager_info(self._h, buf))
-        return [{"messages": i.messages, "batches": i.batches, "bad_codewords": i.bad_codewords, "orphans": i.orphans,
-                 "locked": int(i.locked), "searching": int(i.searching)} for i in buf]
-
 
 def paged(demod, msg_cap=4, device_id=-1):
     """A Pager matched to `demod` (an FskDemod that knows its `rate`): its rows, rate / D soft decisions per second, its baud and
@@ -439,10 +404,7 @@ def decode_pages_gpu(demod, calls):
     where no row has more than hit_cap hits in a call: there the records kept differ with the cuts."""
     import torch
     pager = paged(demod, 16)
-    piece = 1
-    while pager.max_messages(2 * piece) <= pager.msg_cap:
-        piece *= 2
-    piece *= demod.D                                         # input samples: a piece completes at most ceil(piece / D) soft decisions
+    piece = pager.piece() * demod.D                          # input samples: a piece completes at most ceil(piece / D) soft decisions
     found = [[] for _ in range(demod.n_rows)]
     for x in calls:
         x = np.ascontiguousarray(x, dtype=np.int16)
@@ -460,13 +422,8 @@ def decode_pages_gpu(demod, calls):
             n = demod.run_device(d_in.data_ptr() + 2 * lo, m, n_in, d_soft.data_ptr(), cap)
             d_counts, d_hits = demod.hits_device()
             pager.run_device(d_soft.data_ptr(), n, cap, d_counts, d_hits, demod.hit_cap)
-            if n == 0:
-                continue
-            counts = pager.counts()
-            hit = np.nonzero(counts)[0]
-            if hit.size:
-                for r, got in zip(hit.tolist(), pager.msgs(hit, counts)):
-                    found[r] += got
+            if n:
+                pager.harvest(found)
     info = pager.info()
     pager.close()
     return [dict(info[r], messages_list=found[r]) for r in range(demod.n_rows)]

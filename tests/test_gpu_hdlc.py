@@ -307,6 +307,26 @@ def test_refused_calls_and_calls_of_no_samples_leave_the_last_results(fmd):
     assert sum(i["frames_ok"] for i in fr.info()) == 2 * rows
 
 
+def test_a_selection_out_of_order_with_a_repeat_and_a_selection_of_no_rows(fmd):
+    rng = np.random.default_rng(20)
+    rows = 5
+    x = _signal(rng, rows, 5, frames=1, lo=25, hi=40)        # (about 2000 soft decisions, a frame in every row)
+    fr, ref = _framer(fmd, 6000, rows=rows), hr.Framer(6000, rows=rows)
+    assert _feed(fmd, fr, ref, x, [], batch=True) == rows
+    every = _records(fmd, fr, np.arange(rows))
+    assert every[0].tobytes() != every[4].tobytes()
+    # each listed row's records in the order listed, byte for byte the identity selection's
+    got = _records(fmd, fr, [4, 0, 0])
+    assert [g.tobytes() for g in got] == [every[r].tobytes() for r in (4, 0, 0)]
+    assert fr.frames([4, 0, 0]) == [ref.last[2][r][:fr.frame_cap] for r in (4, 0, 0)]
+    # no rows: null pointers pass, and nothing is written where there is a buffer
+    assert fmd.lib().fmd_hdlc_frames(fr._h, None, 0, None) == 0
+    rec = np.full(fr.frame_cap * hr.FRAME_DTYPE.itemsize, 0x5A, np.uint8)
+    assert fmd.lib().fmd_hdlc_frames(fr._h, None, 0, rec.ctypes.data) == 0 and (rec == 0x5A).all()
+    assert fr.frame_records([]) == [] and fr.frames([]) == []
+    _same(fmd, fr, ref)
+
+
 def test_reset_inside_a_frame_a_callers_stream_and_two_handles(fmd):
     import torch
     rng = np.random.default_rng(19)

@@ -347,6 +347,25 @@ def test_refused_calls_and_calls_of_no_samples_leave_the_last_results(fmd):
     assert sum(i["messages"] for i in pg.info()) == rows
 
 
+def test_a_selection_out_of_order_with_a_repeat_and_a_selection_of_no_rows(fmd):
+    rows, rate = 5, pc.RATES["2"]                         # (about 2000 soft decisions, a page in every row)
+    x, hits = pc.stack([_page(fmd, r, rate) for r in range(rows)])
+    pg, ref = _pager(fmd, rate, rows=rows), _ref(rate, rows=rows)
+    assert _feed(fmd, pg, ref, x, hits, [], batch=True) == rows
+    every = _records(fmd, pg, np.arange(rows))
+    assert every[0].tobytes() != every[4].tobytes()
+    # each listed row's records in the order listed, byte for byte the identity selection's
+    got = _records(fmd, pg, [4, 0, 0])
+    assert [g.tobytes() for g in got] == [every[r].tobytes() for r in (4, 0, 0)]
+    assert pg.msgs([4, 0, 0]) == [ref.last[2][r][:pg.msg_cap] for r in (4, 0, 0)]
+    # no rows: null pointers pass, and nothing is written where there is a buffer
+    assert fmd.lib().fmd_pager_msgs(pg._h, None, 0, None) == 0
+    out = np.full(pg.msg_cap * gr.MSG_DTYPE.itemsize, 0x5A, np.uint8)
+    assert fmd.lib().fmd_pager_msgs(pg._h, None, 0, out.ctypes.data) == 0 and (out == 0x5A).all()
+    assert pg.msg_records([]) == [] and pg.msgs([]) == []
+    _same(fmd, pg, ref)
+
+
 def test_reset_inside_a_batch_a_callers_stream_and_two_handles(fmd):
     import torch
     xa, ha = pc.stack([_page(fmd, r) for r in range(70)])

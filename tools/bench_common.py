@@ -1,9 +1,12 @@
 """What the down-converter bench tools (bench_{stations,channelizer,stereo,narrow,rds,spectrum,uniform,bandplan}.py) share: the repository
 and tests/ on sys.path, the front-end prototype, the stations' phase increments, the two synthetic device buffers, HIP-event timing,
-the common arguments, and the tail that prints every row and writes them to --out."""
+the common arguments, and the tail that prints every row and writes them to --out; and what the record-bank tools (bench_hdlc.py,
+bench_pager.py) share beside that: the host decoder pool's library, the copy baselines and the pool's timing."""
 import argparse
+import ctypes
 import json
 import os
+import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,6 +58,44 @@ def time_calls(launch, iters, reps=3, warmup=3):
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) / iters)
     return sorted(ts)[len(ts) // 2], ts
+
+
+def hostbench(name, argtypes):
+    """tools/<name>_hostbench.so, built from its .cpp where that is newer than it: hostbench_push(*argtypes) -> seconds."""
+    so, src = (os.path.join(ROOT, "tools", "%s_hostbench.%s" % (name, ext)) for ext in ("so", "cpp"))
+    pkg = os.path.join(ROOT, "rtl-sdr-rs_amd")
+    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", so, "-L", pkg, "-lfmd_hip", "-Wl,-rpath," + pkg])
+    lib = ctypes.CDLL(so)
+    lib.hostbench_push.restype = ctypes.c_double
+    lib.hostbench_push.argtypes = argtypes
+    return lib
+
+
+def copy_baselines(name, soft, iters, pick=lambda rows: rows):
+    """Beside a record bank over soft[period][rows][cap] on the device, (ms, runs) each: a device-to-device copy of one call's rows,
+    and the copy of pick(rows) of a call to pinned host memory."""
+    d_copy = torch.zeros_like(soft[0])
+    copy = time_calls(lambda i: d_copy.copy_(soft[i % len(soft)]), iters)
+    if not torch.equal(d_copy, soft[(iters - 1) % len(soft)]):
+        raise SystemExit("%s: the copy did not copy" % name)
+    h_soft = torch.empty(pick(soft[0]).shape, dtype=torch.int16, pin_memory=True)
+    return copy, time_calls(lambda i: h_soft.copy_(pick(soft[i % len(soft)]), non_blocking=True), 20)
+
+
+def host_push(soft, push):
+    """{threads: ms} of the host decoders on 1 and 16 threads: push(p, h_rows, threads) -> seconds over call p's rows in pinned host
+    memory at h_rows; a lap to warm up, then the median of 24 calls."""
+    h_all = torch.empty(soft[0].shape, dtype=torch.int16, pin_memory=True)
+    res = {}
+    for threads in (1, 16):
+        ts = []
+        for i in range(1 + 3 * len(soft)):
+            h_all.copy_(soft[i % len(soft)])
+            torch.cuda.synchronize()
+            ts.append(1e3 * push(i % len(soft), h_all.data_ptr(), threads))
+        res[threads] = float(np.median(ts[1:]))
+    return res
 
 
 def parity_sample(S, parity_streams):

@@ -13,8 +13,6 @@ host memory, and fmd_ax25_decoder_push over all rows on one thread and on 16 (to
 interpreter).  Four sampled rows, two of them frame rows, are compared with tests/hdlc_ref.py over twelve calls: counts, records and
 counters.  Writes profiles/hdlc_bench.json."""
 import ctypes as C
-import os
-import subprocess
 
 import bench_common as bc
 from bench_common import fmd, np, torch
@@ -24,19 +22,7 @@ import hdlc_ref as hr
 
 SHAPES = [("narrow", 4096, 655, 12000), ("bandplan", 65536, 1024, 24000)]
 BAUD, PERIOD = 1200, 8
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def hostbench():
-    so = os.path.join(HERE, "hdlc_hostbench.so")
-    src = os.path.join(HERE, "hdlc_hostbench.cpp")
-    pkg = os.path.join(bc.ROOT, "rtl-sdr-rs_amd")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", so, "-L", pkg, "-lfmd_hip", "-Wl,-rpath," + pkg])
-    lib = C.CDLL(so)
-    lib.hostbench_push.restype = C.c_double
-    lib.hostbench_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(C.c_uint64)]
-    return lib
+PUSH_ARGS = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint, C.POINTER(C.c_uint64)]
 
 
 def bench(name, rows, n, rate, iters, host):
@@ -93,26 +79,15 @@ def bench(name, rows, n, rate, iters, host):
     fb.check()
     info = fb.info()
     calls = 3 + 3 * iters
-    d_copy = torch.zeros_like(soft[0])
-    copy_ms, copy_all = bc.time_calls(lambda i: d_copy.copy_(soft[i % PERIOD]), iters)
-    if not torch.equal(d_copy, soft[(iters - 1) % PERIOD]):
-        raise SystemExit("%s: the copy did not copy" % name)
     # the path this replaces: the soft rows to the host, and a host decoder per row
-    h_soft = torch.empty((rows, cap), dtype=torch.int16, pin_memory=True)
-    d2h_ms, d2h_all = bc.time_calls(lambda i: h_soft.copy_(soft[i % PERIOD], non_blocking=True), 20)
+    (copy_ms, copy_all), (d2h_ms, d2h_all) = bc.copy_baselines(name, soft, iters)
     decs = (C.c_void_p * rows)()
     for r in range(rows):
         d = C.c_void_p()
         fmd.check(fmd.lib().fmd_ax25_decoder_new(rate, pk.stride, BAUD, C.byref(d)))
         decs[r] = d
-    push = {}
-    for threads in (1, 16):
-        ts, got = [], C.c_uint64(0)
-        for i in range(1 + 3 * PERIOD):                      # (a lap to warm up, then the median of 24 calls)
-            h_soft.copy_(soft[i % PERIOD])
-            torch.cuda.synchronize()
-            ts.append(1e3 * host.hostbench_push(decs, h_soft.data_ptr(), rows, ks[i % PERIOD], cap, threads, C.byref(got)))
-        push[threads] = float(np.median(ts[1:]))
+    got = C.c_uint64(0)
+    push = bc.host_push(soft, lambda p, h_rows, threads: host.hostbench_push(decs, h_rows, rows, ks[p], cap, threads, C.byref(got)))
     for r in range(rows):
         fmd.lib().fmd_ax25_decoder_free(C.c_void_p(decs[r]))
     n_soft = rows * ks[0]
@@ -139,7 +114,7 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     bc.add_out(ap, "hdlc_bench.json")
     a = ap.parse_args()
-    host = hostbench()
+    host = bc.hostbench("hdlc", PUSH_ARGS)
     rows = [bench(*s, a.iters, host) for s in SHAPES]
     bc.write_rows(a.out, baud=BAUD, iters=a.iters, period=PERIOD, rows=rows)
 

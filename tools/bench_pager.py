@@ -15,8 +15,6 @@ record, or a decoder locked or searching) to pinned host memory, fmd_pocsag_deco
 calls, timed between two requests for input).  Four sampled rows, two of them traffic rows, are compared with tests/pager_ref.py over twelve calls: counts,
 records and counters.  Writes profiles/pager_bench.json."""
 import ctypes as C
-import os
-import subprocess
 import time
 
 import bench_common as bc
@@ -26,21 +24,9 @@ import pager_ref as gr
 
 SHAPES = [("narrow", 4096, 655, 12000), ("bandplan", 65536, 1024, 24000)]
 BAUD, PERIOD, MSG_CAP = 1200, 8, 4
-HERE = os.path.dirname(os.path.abspath(__file__))
 FSK_MS_COMMITTED = {"narrow": 0.0278, "bandplan": 0.1953}    # profiles/pocsag_bench.json
-
-
-def hostbench():
-    so = os.path.join(HERE, "pager_hostbench.so")
-    src = os.path.join(HERE, "pager_hostbench.cpp")
-    pkg = os.path.join(bc.ROOT, "rtl-sdr-rs_amd")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", so, "-L", pkg, "-lfmd_hip", "-Wl,-rpath," + pkg])
-    lib = C.CDLL(so)
-    lib.hostbench_push.restype = C.c_double
-    lib.hostbench_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                   C.c_uint, C.POINTER(C.c_uint64)]
-    return lib
+PUSH_ARGS = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint,
+             C.POINTER(C.c_uint64)]
 
 
 def bench(name, rows, n, rate, iters, host):
@@ -113,14 +99,9 @@ def bench(name, rows, n, rate, iters, host):
     calls = 3 + 3 * iters
     last = (iters - 1) % PERIOD
     busy = np.nonzero((h_cnt[last] > 0) | np.array([i["locked"] or i["searching"] for i in info]))[0].astype(np.uint32)
-    d_copy = torch.zeros_like(soft[0])
-    copy_ms, copy_all = bc.time_calls(lambda i: d_copy.copy_(soft[i % PERIOD]), iters)
-    if not torch.equal(d_copy, soft[(iters - 1) % PERIOD]):
-        raise SystemExit("%s: the copy did not copy" % name)
     # the path this replaces: the busy rows to the host, and a host decoder for each of them
     d_busy = torch.from_numpy(busy.astype(np.int64)).cuda()
-    h_soft = torch.empty((len(busy), cap), dtype=torch.int16, pin_memory=True)
-    d2h_ms, d2h_all = bc.time_calls(lambda i: h_soft.copy_(soft[i % PERIOD].index_select(0, d_busy), non_blocking=True), 20)
+    (copy_ms, copy_all), (d2h_ms, d2h_all) = bc.copy_baselines(name, soft, iters, lambda s: s.index_select(0, d_busy))
     t0 = time.perf_counter()
     for r in busy.tolist():                                  # as decode_pages copies them: a copy per row
         soft[last][r, :ks[last]].cpu()
@@ -130,20 +111,11 @@ def bench(name, rows, n, rate, iters, host):
         dd = C.c_void_p()
         fmd.check(fmd.lib().fmd_pocsag_decoder_new(rate, d.D, BAUD, 1, C.byref(dd)))
         decs[r] = dd
-    push = {}
-    h_all = torch.empty((rows, cap), dtype=torch.int16, pin_memory=True)
-    for threads in (1, 16):
-        ts, got = [], C.c_uint64(0)
-        for i in range(1 + 3 * PERIOD):                      # (a lap to warm up, then the median of 24 calls)
-            p = i % PERIOD
-            h_all.copy_(soft[p])
-            torch.cuda.synchronize()
-            ts.append(1e3 * host.hostbench_push(decs, h_all.data_ptr(), ks[p], cap, h_cnt[p].ctypes.data, h_hit[p].ctypes.data, d.hit_cap,
-                                                busy.ctypes.data, len(busy), threads, C.byref(got)))
-        push[threads] = float(np.median(ts[1:]))
+    got = C.c_uint64(0)
+    push = bc.host_push(soft, lambda p, h_rows, threads: host.hostbench_push(
+        decs, h_rows, ks[p], cap, h_cnt[p].ctypes.data, h_hit[p].ctypes.data, d.hit_cap, busy.ctypes.data, len(busy), threads, C.byref(got)))
     for r in busy.tolist():
         fmd.lib().fmd_pocsag_decoder_free(C.c_void_p(decs[r]))
-    del h_all, h_soft
     # decode_pages end to end: the calls come from a generator that notes when each is asked for, so the time between two requests is
     # one call of decode_pages, the upload of its input included; the last call's, whose rows are busy from the calls before, is taken
     asked = []
@@ -182,7 +154,7 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     bc.add_out(ap, "pager_bench.json")
     a = ap.parse_args()
-    host = hostbench()
+    host = bc.hostbench("pager", PUSH_ARGS)
     rows = [bench(*s, a.iters, host) for s in SHAPES]
     bc.write_rows(a.out, baud=BAUD, iters=a.iters, period=PERIOD, rows=rows)
 
