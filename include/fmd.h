@@ -1351,6 +1351,102 @@ int fmd_pager_table(uint32_t max_errors, uint32_t *table);
 /* M(n) above; 0 where rate / baud < 2. */
 size_t fmd_pager_max_messages(uint32_t rate_num, uint32_t rate_den, uint32_t baud, size_t n);
 
+/* ---- Mode S bank: ADS-B messages (1090 MHz extended squitter) decoded on the device per stream ------------------------- */
+/* NEW SURFACE: rtl_adsb's job at bank size.  Mode S is pulse-position modulation on the raw magnitude, so this handle sits behind
+ * no discriminator: it takes the u8 IQ of many 2 Msample/s streams as read_sync delivers it and leaves each stream's messages.
+ * Integers only; the results do not depend on how a stream is cut into calls.  Definition (tests/modes_ref.py), per stream, i
+ * counting samples from creation or reset, everything at a negative index 0:
+ *   m[i]   = ((2 b[2i] - 255)^2 + (2 b[2i+1] - 255)^2) >> 1        (the sum of two odd squares is 2 mod 8: the shift loses nothing;
+ *                                                                    0 <= m <= 65025, a u16)
+ *   a_j    = m[p + j], j < 240, for a position p >= 0
+ *   S(p)   = a0 + a2 + a7 + a9                                      (the four 0.5 us preamble pulses at 0, 1.0, 3.5 and 4.5 us)
+ *   pre(p) = a0 > a1 and a1 < a2 and a2 > a3 and a3 < a0 and a4 < a0 and a5 < a0 and a6 < a0 and a7 > a8 and a8 < a9 and a9 > a6
+ *            and 6 a_j < S for j in {4, 5, 11, 12, 13, 14} and S >= min_power
+ *   bit t  = 1 iff m[p + 16 + 2t] > m[p + 17 + 2t]                  (equality: 0; t = 0 is sent first and is the MSB of byte 0)
+ *   DF     = bits 0 ... 4;  n = 112 if bit 0 is 1 (DF >= 16), else 56
+ *   syn    = the remainder of bits 0 ... n-25 under the generator 0xFFF409, XOR bits n-24 ... n-1 (24 bits, MSB-first shift register,
+ *            initial value 0) = XOR over the set bits t of T_n[t]; T_112[t] = x^(111 - t) mod the generator: T_112[0] = 0x3935EA,
+ *            T_112[87] = 0xFFF409, T_112[88] = 0x800000, T_112[111] = 1; T_56[t] = T_112[t + 56]; all 112 entries are distinct
+ *   accept   DF in {17, 18} and syn == 0
+ *       or   DF == 11 and df11 and (syn & 0xFFFF80) == 0
+ *       or   DF in {17, 18} and fix_errors and syn == T_112[t] for one t in 5 ... 111: bit t is flipped in the record and
+ *            fixed_bit = t (the DF field is never touched).
+ * Each accepted p gives one record, in increasing p; overlapping acceptances are not suppressed on the device.  Position p is
+ * decided by the call that brings sample p + 239, for both message lengths: a call over the samples [pos, pos + n) decides
+ * max(0, pos - 239) <= p < pos + n - 239, and k_rel = p - pos runs from -239 upward.  Carried per stream: the m of its last 240
+ * samples and the cumulative counters; all zeros is what reset leaves.  A call shorter than 240 samples is taken and may decide
+ * nothing; nbytes == 0 launches nothing and leaves the last call's results.  Per call and stream `count` is every acceptance and the
+ * first min(count, msg_cap) records are kept, whatever the scheduling.
+ * Domain (else FMD_ERR_UNSUPPORTED with a text, decided before a device is queried): min_power <= 262144, fix_errors and df11 0 or 1,
+ * 1 <= msg_cap <= 256, n_streams = dev->n_channels >= 1 (0: FMD_ERR_INVALID_ARG).  Calls: nbytes % 8 != 0 is FMD_ERR_BAD_LENGTH,
+ * nbytes > cap_bytes FMD_ERR_CAPACITY, cap_bytes % 4 != 0 or a d_iq that is not 4-byte aligned FMD_ERR_INVALID_ARG.  Stream lifetime
+ * and completion points: as fmd_channelizer_* (fmd_modes_check).  Out of scope: the address/parity-overlaid formats (DF 0, 4, 5, 16,
+ * 20, 21), 2.4 Msample/s input, two-bit correction, suppression of overlapping acceptances and a flush of the last 239 samples. */
+typedef struct fmd_modes fmd_modes;
+typedef struct fmd_modes_config {
+    uint32_t min_power;   /* 0 .. 262144 */
+    uint32_t fix_errors;  /* 0 | 1 */
+    uint32_t df11;        /* 0 | 1 */
+    uint32_t msg_cap;     /* 1 .. 256 */
+} fmd_modes_config;
+typedef struct fmd_modes_msg {                                                  /* 32 bytes */
+    int32_t  k_rel;
+    uint32_t power;       /* S */
+    uint8_t  n_bytes;     /* 7 | 14 */
+    uint8_t  fixed_bit;   /* 0xFF: none */
+    uint8_t  df;
+    uint8_t  rsv;
+    uint8_t  bytes[14];   /* after the fix; zeros behind 7 */
+    uint8_t  pad[6];
+} fmd_modes_msg;
+/* per stream, cumulative since creation or reset: samples taken, positions that passed pre(p), acceptances, acceptances with a fix.
+ * (Read by fmd_modes_info; C keeps functions and typedefs in one name space, so the struct goes by another name.) */
+typedef struct fmd_modes_totals {
+    uint64_t samples, candidates, messages, fixed;
+} fmd_modes_totals;
+
+int fmd_modes_new(const fmd_modes_config *cfg, const fmd_device_config *dev, fmd_modes **out);   /* n_streams = dev->n_channels */
+void fmd_modes_free(fmd_modes *h);
+int fmd_modes_reset(fmd_modes *h);
+/* HOST array iq [n_streams][cap_bytes], the first nbytes of each stream valid.  Returns when the call has completed. */
+int fmd_modes_run_batch(fmd_modes *h, const uint8_t *iq, size_t nbytes, size_t cap_bytes);
+/* DEVICE array of the same form, enqueued on `stream` without synchronising. */
+int fmd_modes_run_device(fmd_modes *h, const void *d_iq, size_t nbytes, size_t cap_bytes, void *stream);
+int fmd_modes_check(fmd_modes *h);
+/* The last call's results, behind a synchronisation.  counts: host array [n_streams] (all 0 before the first call and after reset).
+ * msgs: host array [n_sel][msg_cap] for the streams listed in `streams` only, in the order listed, zero behind each one's
+ * min(count, msg_cap); an index at or beyond n_streams is FMD_ERR_INVALID_ARG, with nothing written.  info: host array [n_streams]. */
+int fmd_modes_counts(fmd_modes *h, uint32_t *counts);
+int fmd_modes_msgs(fmd_modes *h, const uint32_t *streams, size_t n_sel, fmd_modes_msg *msgs);
+int fmd_modes_info(fmd_modes *h, fmd_modes_totals *info);
+/* Name of the kernel of pass 0 (the tiles: preamble test, decode, syndrome) or 1 (per stream: the records in tile order, the carried
+ * samples, the counters), as `rocprofv3 --kernel-trace` prints it. */
+int fmd_modes_kernel_name(const fmd_modes *h, uint32_t pass, char *name, size_t cap);
+/* Positions per workgroup of pass 0.  Host only. */
+uint32_t fmd_modes_tile(void);
+/* T_56 or T_112 above into table[n_bits] (n_bits 56 or 112, else FMD_ERR_UNSUPPORTED).  Host only. */
+int fmd_modes_table(uint32_t n_bits, uint32_t *table);
+/* syn above of a message of 7 or 14 bytes (else FMD_ERR_BAD_LENGTH).  Host only. */
+int fmd_modes_syndrome(const uint8_t *bytes, size_t n_bytes, uint32_t *syn);
+/* The fields of an extended squitter (DF 17, 18; host only).  has: bit 0 callsign (type codes 1-4: eight characters, trailing
+ * blanks dropped), bit 1 altitude_ft (type codes 9-18 with the Q bit: 25 N - 1000), bit 2 the 17-bit CPR latitude and longitude with
+ * the odd flag (type codes 9-18), bit 3 speed_kt, track_deg (clockwise from north) and vrate_fpm (type code 19, subtypes 1 and 2;
+ * a component or a rate that is "not available" clears the bit).  Another DF or length: FMD_ERR_UNSUPPORTED. */
+typedef struct fmd_modes_fields {
+    uint32_t df, icao, type_code, subtype, has;
+    int32_t  altitude_ft;
+    uint32_t cpr_odd, cpr_lat, cpr_lon;
+    int32_t  vrate_fpm;
+    double   speed_kt, track_deg;
+    char     callsign[16];
+} fmd_modes_fields;
+int fmd_modes_decode(const uint8_t *bytes, size_t n_bytes, fmd_modes_fields *out);
+/* The globally unambiguous position of one even and one odd CPR pair of the same aircraft; latest_odd says which of the two is the
+ * newer, whose position is returned in degrees.  FMD_ERR_BAD_STATE when the two lie in different longitude zones
+ * or give no latitude within +-90 degrees (they are not a pair). */
+int fmd_modes_cpr_global(uint32_t lat_even, uint32_t lon_even, uint32_t lat_odd, uint32_t lon_odd, int latest_odd, double *lat,
+                         double *lon);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

@@ -316,6 +316,21 @@ PROTOTYPES = {
     "fmd_pager_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "fmd_pager_table": (C.c_int, [C.c_uint32, _vp]),
     "fmd_pager_max_messages": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, _sz]),
+    "fmd_modes_new": (C.c_int, [_vp, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_modes_free": (None, [_vp]),
+    "fmd_modes_reset": (C.c_int, [_vp]),
+    "fmd_modes_run_batch": (C.c_int, [_vp, _vp, _sz, _sz]),
+    "fmd_modes_run_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp]),
+    "fmd_modes_check": (C.c_int, [_vp]),
+    "fmd_modes_counts": (C.c_int, [_vp, _vp]),
+    "fmd_modes_msgs": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmd_modes_info": (C.c_int, [_vp, _vp]),
+    "fmd_modes_kernel_name": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "fmd_modes_tile": (C.c_uint32, []),
+    "fmd_modes_table": (C.c_int, [C.c_uint32, _vp]),
+    "fmd_modes_syndrome": (C.c_int, [_vp, _sz, C.POINTER(C.c_uint32)]),
+    "fmd_modes_decode": (C.c_int, [_vp, _sz, _vp]),
+    "fmd_modes_cpr_global": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

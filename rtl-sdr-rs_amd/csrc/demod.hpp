@@ -1459,6 +1459,57 @@ inline std::string pocsag_text(const fmd_pocsag_msg& m, uint32_t baud = 1200, in
     return std::string(head) + "Alpha: " + pocsag_alpha(m);
 }
 
+// The Mode S bank (fmd_modes_*): the ADS-B messages of `n_streams` 2 Msample/s u8 IQ streams, decoded on the device.  run() takes
+// [n_streams][nbytes]; behind it counts() gives every stream's acceptances in the call, messages(streams) the first min(count,
+// msg_cap) records of each listed stream in increasing position, info() the streams' cumulative counters.
+class ModeSBank {
+public:
+    explicit ModeSBank(const fmd_modes_config& cfg, uint32_t n_streams = 1, int32_t device_id = -1) : n_streams_(n_streams), cap_(cfg.msg_cap)
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_modes_new(&cfg, &dev, h_.out()));
+    }
+
+    void run(const uint8_t* iq, size_t nbytes) { check(fmd_modes_run_batch(h_, iq, nbytes, nbytes)); }
+    void reset() { check(fmd_modes_reset(h_)); }
+    std::vector<uint32_t> counts()
+    {
+        std::vector<uint32_t> c(n_streams_);
+        check(fmd_modes_counts(h_, c.data()));
+        return c;
+    }
+    std::vector<std::vector<fmd_modes_msg>> messages(const std::vector<uint32_t>& streams)
+    {
+        const std::vector<uint32_t> c = counts();
+        std::vector<fmd_modes_msg> buf(std::max<size_t>(1, streams.size() * cap_));
+        check(fmd_modes_msgs(h_, streams.data(), streams.size(), buf.data()));
+        std::vector<std::vector<fmd_modes_msg>> res(streams.size());
+        for (size_t s = 0; s < streams.size(); ++s)
+            res[s].assign(buf.begin() + s * cap_, buf.begin() + s * cap_ + std::min<size_t>(c[streams[s]], cap_));
+        return res;
+    }
+    std::vector<fmd_modes_totals> info()
+    {
+        std::vector<fmd_modes_totals> i(n_streams_);
+        check(fmd_modes_info(h_, i.data()));
+        return i;
+    }
+    uint32_t msg_cap() const { return cap_; }
+
+private:
+    uint32_t n_streams_, cap_;
+    Owned<fmd_modes, fmd_modes_free> h_;
+};
+
+// `*HEX;`, rtl_adsb's line for a message
+inline std::string modes_hex(const fmd_modes_msg& m)
+{
+    std::string s = "*";
+    char b[3];
+    for (uint32_t i = 0; i < m.n_bytes && i < sizeof m.bytes; ++i) { snprintf(b, sizeof b, "%02X", m.bytes[i]); s += b; }
+    return s + ";";
+}
+
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.
 inline void output(const std::vector<int16_t>& buf, FILE* f = stdout)
 {

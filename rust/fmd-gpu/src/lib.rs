@@ -361,6 +361,65 @@ pub struct fmd_pocsag_info {
     pub searching: c_int,
 }
 
+/// The Mode S bank of include/fmd.h: ADS-B messages decoded on the device per stream.
+#[repr(C)]
+pub struct fmd_modes {
+    _private: [u8; 0],
+}
+
+/// `fmd_modes_config` of include/fmd.h.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_modes_config {
+    pub min_power: u32,
+    pub fix_errors: u32,
+    pub df11: u32,
+    pub msg_cap: u32,
+}
+
+/// `fmd_modes_msg` of include/fmd.h: one accepted Mode S message.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_modes_msg {
+    pub k_rel: i32,
+    pub power: u32,
+    pub n_bytes: u8,
+    pub fixed_bit: u8,
+    pub df: u8,
+    pub rsv: u8,
+    pub bytes: [u8; 14],
+    pub pad: [u8; 6],
+}
+
+/// `fmd_modes_totals` of include/fmd.h: a stream's cumulative counters.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_modes_totals {
+    pub samples: u64,
+    pub candidates: u64,
+    pub messages: u64,
+    pub fixed: u64,
+}
+
+/// `fmd_modes_fields` of include/fmd.h: what an extended squitter says.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_modes_fields {
+    pub df: u32,
+    pub icao: u32,
+    pub type_code: u32,
+    pub subtype: u32,
+    pub has: u32,
+    pub altitude_ft: i32,
+    pub cpr_odd: u32,
+    pub cpr_lat: u32,
+    pub cpr_lon: u32,
+    pub vrate_fpm: i32,
+    pub speed_kt: f64,
+    pub track_deg: f64,
+    pub callsign: [c_char; 16],
+}
+
 #[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
@@ -621,6 +680,21 @@ extern "C" {
     pub fn fmd_pager_info(p: *mut fmd_pager, info: *mut fmd_pocsag_info) -> c_int;
     pub fn fmd_pager_kernel_name(p: *const fmd_pager, name: *mut c_char, cap: usize) -> c_int;
     pub fn fmd_pager_table(max_errors: u32, table: *mut u32) -> c_int;
+    pub fn fmd_modes_new(cfg: *const fmd_modes_config, dev: *const DeviceConfig, out: *mut *mut fmd_modes) -> c_int;
+    pub fn fmd_modes_free(h: *mut fmd_modes);
+    pub fn fmd_modes_reset(h: *mut fmd_modes) -> c_int;
+    pub fn fmd_modes_run_batch(h: *mut fmd_modes, iq: *const u8, nbytes: usize, cap_bytes: usize) -> c_int;
+    pub fn fmd_modes_run_device(h: *mut fmd_modes, d_iq: *const c_void, nbytes: usize, cap_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_modes_check(h: *mut fmd_modes) -> c_int;
+    pub fn fmd_modes_counts(h: *mut fmd_modes, counts: *mut u32) -> c_int;
+    pub fn fmd_modes_msgs(h: *mut fmd_modes, streams: *const u32, n_sel: usize, msgs: *mut fmd_modes_msg) -> c_int;
+    pub fn fmd_modes_info(h: *mut fmd_modes, info: *mut fmd_modes_totals) -> c_int;
+    pub fn fmd_modes_kernel_name(h: *const fmd_modes, pass: u32, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_modes_tile() -> u32;
+    pub fn fmd_modes_table(n_bits: u32, table: *mut u32) -> c_int;
+    pub fn fmd_modes_syndrome(bytes: *const u8, n_bytes: usize, syn: *mut u32) -> c_int;
+    pub fn fmd_modes_decode(bytes: *const u8, n_bytes: usize, out: *mut fmd_modes_fields) -> c_int;
+    pub fn fmd_modes_cpr_global(lat_even: u32, lon_even: u32, lat_odd: u32, lon_odd: u32, latest_odd: c_int, lat: *mut f64, lon: *mut f64) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
