@@ -1447,6 +1447,101 @@ int fmd_modes_decode(const uint8_t *bytes, size_t n_bytes, fmd_modes_fields *out
 int fmd_modes_cpr_global(uint32_t lat_even, uint32_t lon_even, uint32_t lat_odd, uint32_t lon_odd, int latest_odd, double *lat,
                          double *lon);
 
+/* ---- Pulse bank: the on-off-keyed pulses of every stream as width / gap / level records, with a host slicer ------------- */
+/* NEW SURFACE: the front half of rtl_433 at bank size.  The remotes, weather stations, tyre sensors and doorbells of the 315 / 433 /
+ * 868 MHz bands key their carrier on and off; this handle takes the u8 IQ of many streams as read_sync delivers it and leaves every
+ * pulse of every stream: its width, the gap in front of it and its level.  Integers only; the results do not depend on how a stream
+ * is cut into calls.  Definition (tests/pulses_ref.py), per stream, i counting samples from creation or reset, everything at a
+ * negative index 0:
+ *   m[i]  = ((2 b[2i] - 255)^2 + (2 b[2i+1] - 255)^2) >> 1          (exactly the Mode S bank's m; a u16)
+ *   e[i]  = m[i] + m[i-1] + ... + m[i-W+1]                            (a box of W samples; e <= 64 * 65025)
+ *   s[i]  = 1 if e[i] >= hi;  0 if e[i] < lo;  else s[i-1];   s[-1] = 0     (a comparator with hysteresis)
+ *   rise at i: s[i] = 1, s[i-1] = 0.     fall at i: s[i] = 0, s[i-1] = 1.
+ * Every fall at f gives one record, in increasing f: k_rel = f - pos (0 <= k_rel < n: a fall is decided by the call that brings
+ * sample f, there is no look-ahead); width = f - r, r the rise before f; gap = r - f_prev, f_prev the fall before r, and 0 if there
+ * has been no fall since creation or reset; level = e[f - 1], the box over the pulse's last W samples.  width and gap saturate at
+ * 2^32 - 1.  Per call and stream `count` is every fall of the call and the first min(count, pulse_cap) records are kept, whatever
+ * the scheduling: overflow is decided by position alone.  Cumulative per stream (fmd_pulses_totals): samples, pulses (falls), rises,
+ * the current s and `run`, the samples since the last edge or since reset -- `state == 0 && run >= reset` lets the host close a
+ * package without waiting for the next pulse.  Carried per stream: the m of its last 64 samples, s, the run, the open pulse's gap and
+ * the counters; all zeros is what reset leaves.  nbytes == 0 launches nothing and leaves the last call's results.
+ * Domain (else FMD_ERR_UNSUPPORTED with a text, decided before a device is queried): 1 <= W <= 64, 1 <= lo <= hi <= 64 * 65025,
+ * 1 <= pulse_cap <= 1024, n_streams = dev->n_channels >= 1.  Calls: as fmd_modes_run_*: nbytes % 8 != 0 is FMD_ERR_BAD_LENGTH,
+ * nbytes > cap_bytes FMD_ERR_CAPACITY, cap_bytes % 4 != 0 or a d_iq that is not 4-byte aligned FMD_ERR_INVALID_ARG.  Stream lifetime
+ * and completion points: as fmd_channelizer_* (fmd_pulses_check).  Out of scope: adaptive thresholds on the device, FSK pulse
+ * detection, a peak or mean over the whole pulse, glitch merging below a minimum width, slicing on the device. */
+typedef struct fmd_pulses fmd_pulses;
+typedef struct fmd_pulses_config {
+    uint32_t W;           /* 1 .. 64 */
+    uint32_t lo, hi;      /* 1 <= lo <= hi <= 64 * 65025 */
+    uint32_t pulse_cap;   /* 1 .. 1024 */
+} fmd_pulses_config;
+typedef struct fmd_pulses_rec {                                                 /* 16 bytes */
+    int32_t  k_rel;
+    uint32_t width, gap, level;
+} fmd_pulses_rec;
+/* (Read by fmd_pulses_info; the struct goes by another name as fmd_modes_totals does.) */
+typedef struct fmd_pulses_totals {                                              /* 40 bytes */
+    uint64_t samples, pulses, rises;
+    uint32_t state;       /* the current s */
+    uint32_t rsv;
+    uint64_t run;
+} fmd_pulses_totals;
+
+int fmd_pulses_new(const fmd_pulses_config *cfg, const fmd_device_config *dev, fmd_pulses **out);   /* n_streams = dev->n_channels */
+void fmd_pulses_free(fmd_pulses *h);
+int fmd_pulses_reset(fmd_pulses *h);
+/* HOST array iq [n_streams][cap_bytes], the first nbytes of each stream valid.  Returns when the call has completed. */
+int fmd_pulses_run_batch(fmd_pulses *h, const uint8_t *iq, size_t nbytes, size_t cap_bytes);
+/* DEVICE array of the same form, enqueued on `stream` without synchronising. */
+int fmd_pulses_run_device(fmd_pulses *h, const void *d_iq, size_t nbytes, size_t cap_bytes, void *stream);
+int fmd_pulses_check(fmd_pulses *h);
+/* The last call's results, behind a synchronisation.  counts: host array [n_streams] (all 0 before the first call and after reset).
+ * recs: host array [n_sel][pulse_cap] for the streams listed in `streams` only, in the order listed, zero behind each one's
+ * min(count, pulse_cap); an index at or beyond n_streams is FMD_ERR_INVALID_ARG, with nothing written.  info: host array [n_streams]. */
+int fmd_pulses_counts(fmd_pulses *h, uint32_t *counts);
+int fmd_pulses_recs(fmd_pulses *h, const uint32_t *streams, size_t n_sel, fmd_pulses_rec *recs);
+int fmd_pulses_info(fmd_pulses *h, fmd_pulses_totals *info);
+/* Name of the kernel of pass 0 (the tiles: box, comparator, edges) or 1 (per stream: the records in tile order, the runs across
+ * tiles and calls, the carried state), as `rocprofv3 --kernel-trace` prints it. */
+int fmd_pulses_kernel_name(const fmd_pulses *h, uint32_t pass, char *name, size_t cap);
+/* Positions per workgroup of pass 0.  Host only. */
+uint32_t fmd_pulses_tile(void);
+
+/* The host slicer behind the pulse bank (host only, fixed buffers; definition tests/pulse_slice_ref.py): pulse records of one stream
+ * in, bit packages out.  A package is a maximal run of pulses in which every pulse but the first has gap < reset; it closes on the
+ * next record with gap >= reset, or on fmd_pulse_slicer_idle with state == 0 && run >= reset.  Bits, as rtl_433 slices them -- PWM:
+ * a pulse gives a 1 if |width - short_w| <= tol, else a 0 if |width - long_w| <= tol; PPM: every pulse but the package's first gives
+ * a bit from its gap, 0 if |gap - short_w| <= tol, else 1 if |gap - long_w| <= tol.  A pulse that fits neither sets FMD_PULSE_BAD,
+ * and the rest of the package gives no bits.  Up to 256 bits are kept, MSB first; a bit beyond sets FMD_PULSE_TRUNCATED.  n_pulses
+ * counts every pulse of the package.  start is the absolute sample of the first pulse's rise.  Up to 64 closed packages wait for
+ * fmd_pulse_slicer_take; one that closes while 64 wait is dropped.  The state lives in the object: a package may span calls.
+ * Domain (else FMD_ERR_UNSUPPORTED): modulation 0 or 1, short_w, long_w and reset >= 1. */
+#define FMD_PULSE_PWM 0u
+#define FMD_PULSE_PPM 1u
+#define FMD_PULSE_BAD 1u
+#define FMD_PULSE_TRUNCATED 2u
+typedef struct fmd_pulse_slicer fmd_pulse_slicer;
+typedef struct fmd_pulse_slicer_config {
+    uint32_t modulation;  /* FMD_PULSE_PWM | FMD_PULSE_PPM */
+    uint32_t short_w, long_w, tol, reset;
+} fmd_pulse_slicer_config;
+typedef struct fmd_pulse_package {                                              /* 56 bytes */
+    uint64_t start;
+    uint32_t n_pulses, n_bits;
+    uint8_t  bits[32];
+    uint32_t flags;       /* FMD_PULSE_BAD | FMD_PULSE_TRUNCATED */
+    uint32_t rsv;
+} fmd_pulse_package;
+int fmd_pulse_slicer_new(const fmd_pulse_slicer_config *cfg, fmd_pulse_slicer **out);
+void fmd_pulse_slicer_free(fmd_pulse_slicer *p);
+/* n records of one call, whose first sample is the absolute sample `pos` (a record's fall is at pos + k_rel). */
+int fmd_pulse_slicer_push(fmd_pulse_slicer *p, const fmd_pulses_rec *recs, size_t n, uint64_t pos);
+/* The stream's state and run behind a call (fmd_pulses_totals): closes the open package when the stream has been low for `reset`. */
+int fmd_pulse_slicer_idle(fmd_pulse_slicer *p, uint32_t state, uint64_t run);
+/* Moves the oldest min(waiting, cap) closed packages into packages[cap]; *n is how many. */
+int fmd_pulse_slicer_take(fmd_pulse_slicer *p, fmd_pulse_package *packages, size_t cap, size_t *n);
+
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example
  * does have: receive() fills a buffer with RtlSdr::read_sync (src/lib.rs:153) and sends it down an mpsc channel,

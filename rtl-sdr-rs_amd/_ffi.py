@@ -331,6 +331,22 @@ PROTOTYPES = {
     "fmd_modes_syndrome": (C.c_int, [_vp, _sz, C.POINTER(C.c_uint32)]),
     "fmd_modes_decode": (C.c_int, [_vp, _sz, _vp]),
     "fmd_modes_cpr_global": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fmd_pulses_new": (C.c_int, [_vp, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_pulses_free": (None, [_vp]),
+    "fmd_pulses_reset": (C.c_int, [_vp]),
+    "fmd_pulses_run_batch": (C.c_int, [_vp, _vp, _sz, _sz]),
+    "fmd_pulses_run_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp]),
+    "fmd_pulses_check": (C.c_int, [_vp]),
+    "fmd_pulses_counts": (C.c_int, [_vp, _vp]),
+    "fmd_pulses_recs": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmd_pulses_info": (C.c_int, [_vp, _vp]),
+    "fmd_pulses_kernel_name": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "fmd_pulses_tile": (C.c_uint32, []),
+    "fmd_pulse_slicer_new": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "fmd_pulse_slicer_free": (None, [_vp]),
+    "fmd_pulse_slicer_push": (C.c_int, [_vp, _vp, _sz, C.c_uint64]),
+    "fmd_pulse_slicer_idle": (C.c_int, [_vp, C.c_uint32, C.c_uint64]),
+    "fmd_pulse_slicer_take": (C.c_int, [_vp, _vp, _sz, C.POINTER(C.c_size_t)]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

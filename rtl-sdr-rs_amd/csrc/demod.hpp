@@ -1510,6 +1510,80 @@ inline std::string modes_hex(const fmd_modes_msg& m)
     return s + ";";
 }
 
+// The pulse bank (fmd_pulses_*): the on-off-keyed pulses of `n_streams` u8 IQ streams.  run() takes [n_streams][nbytes]; behind it
+// counts() gives every stream's falls in the call, pulses(streams) the first min(count, pulse_cap) records of each listed stream in
+// increasing position, info() the streams' cumulative counters with the current state and run.
+class PulseBank {
+public:
+    explicit PulseBank(const fmd_pulses_config& cfg, uint32_t n_streams = 1, int32_t device_id = -1) : n_streams_(n_streams), cap_(cfg.pulse_cap)
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_pulses_new(&cfg, &dev, h_.out()));
+    }
+
+    void run(const uint8_t* iq, size_t nbytes) { check(fmd_pulses_run_batch(h_, iq, nbytes, nbytes)); }
+    void reset() { check(fmd_pulses_reset(h_)); }
+    std::vector<uint32_t> counts()
+    {
+        std::vector<uint32_t> c(n_streams_);
+        check(fmd_pulses_counts(h_, c.data()));
+        return c;
+    }
+    std::vector<std::vector<fmd_pulses_rec>> pulses(const std::vector<uint32_t>& streams)
+    {
+        const std::vector<uint32_t> c = counts();
+        std::vector<fmd_pulses_rec> buf(std::max<size_t>(1, streams.size() * cap_));
+        check(fmd_pulses_recs(h_, streams.data(), streams.size(), buf.data()));
+        std::vector<std::vector<fmd_pulses_rec>> res(streams.size());
+        for (size_t s = 0; s < streams.size(); ++s)
+            res[s].assign(buf.begin() + s * cap_, buf.begin() + s * cap_ + std::min<size_t>(c[streams[s]], cap_));
+        return res;
+    }
+    std::vector<fmd_pulses_totals> info()
+    {
+        std::vector<fmd_pulses_totals> i(n_streams_);
+        check(fmd_pulses_info(h_, i.data()));
+        return i;
+    }
+    uint32_t pulse_cap() const { return cap_; }
+
+private:
+    uint32_t n_streams_, cap_;
+    Owned<fmd_pulses, fmd_pulses_free> h_;
+};
+
+// The host slicer behind it (fmd_pulse_slicer_*): one stream's records in, its closed bit packages out.
+class PulseSlicer {
+public:
+    explicit PulseSlicer(const fmd_pulse_slicer_config& cfg) { check(fmd_pulse_slicer_new(&cfg, h_.out())); }
+
+    // the records of a call whose first sample is `pos`, then the stream's state and run behind the call
+    void push(const std::vector<fmd_pulses_rec>& recs, uint64_t pos) { check(fmd_pulse_slicer_push(h_, recs.data(), recs.size(), pos)); }
+    void idle(uint32_t state, uint64_t run) { check(fmd_pulse_slicer_idle(h_, state, run)); }
+    std::vector<fmd_pulse_package> take()
+    {
+        std::vector<fmd_pulse_package> out(64);
+        size_t n = 0;
+        check(fmd_pulse_slicer_take(h_, out.data(), out.size(), &n));
+        out.resize(n);
+        return out;
+    }
+
+private:
+    Owned<fmd_pulse_slicer, fmd_pulse_slicer_free> h_;
+};
+
+// `start_sample n_bits hex`, ook_gpu's line for a package
+inline std::string pulse_line(const fmd_pulse_package& k)
+{
+    char head[48];
+    snprintf(head, sizeof head, "%llu %u ", (unsigned long long)k.start, k.n_bits);
+    std::string s = head;
+    char b[3];
+    for (uint32_t i = 0; i < (k.n_bits + 7u) / 8u && i < sizeof k.bits; ++i) { snprintf(b, sizeof b, "%02X", k.bits[i]); s += b; }
+    return s;
+}
+
 // output(buf: Vec<i16>), simple_fm.rs:430-438: raw native-endian s16 to stdout, flushed.
 inline void output(const std::vector<int16_t>& buf, FILE* f = stdout)
 {

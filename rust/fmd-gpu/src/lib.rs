@@ -420,6 +420,78 @@ pub struct fmd_modes_fields {
     pub callsign: [c_char; 16],
 }
 
+/// The pulse bank of include/fmd.h: on-off-keyed pulse and gap records per stream.
+#[repr(C)]
+pub struct fmd_pulses {
+    _private: [u8; 0],
+}
+
+/// `fmd_pulses_config` of include/fmd.h.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_pulses_config {
+    pub w: u32,
+    pub lo: u32,
+    pub hi: u32,
+    pub pulse_cap: u32,
+}
+
+/// `fmd_pulses_rec` of include/fmd.h: one pulse, decided at its fall.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_pulses_rec {
+    pub k_rel: i32,
+    pub width: u32,
+    pub gap: u32,
+    pub level: u32,
+}
+
+/// `fmd_pulses_totals` of include/fmd.h: a stream's cumulative counters, its state and its run.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_pulses_totals {
+    pub samples: u64,
+    pub pulses: u64,
+    pub rises: u64,
+    pub state: u32,
+    pub rsv: u32,
+    pub run: u64,
+}
+
+/// The host slicer behind the pulse bank.
+#[repr(C)]
+pub struct fmd_pulse_slicer {
+    _private: [u8; 0],
+}
+
+pub const FMD_PULSE_PWM: u32 = 0;
+pub const FMD_PULSE_PPM: u32 = 1;
+pub const FMD_PULSE_BAD: u32 = 1;
+pub const FMD_PULSE_TRUNCATED: u32 = 2;
+
+/// `fmd_pulse_slicer_config` of include/fmd.h.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_pulse_slicer_config {
+    pub modulation: u32,
+    pub short_w: u32,
+    pub long_w: u32,
+    pub tol: u32,
+    pub reset: u32,
+}
+
+/// `fmd_pulse_package` of include/fmd.h: one closed package of bits.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_pulse_package {
+    pub start: u64,
+    pub n_pulses: u32,
+    pub n_bits: u32,
+    pub bits: [u8; 32],
+    pub flags: u32,
+    pub rsv: u32,
+}
+
 #[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
@@ -695,6 +767,22 @@ extern "C" {
     pub fn fmd_modes_syndrome(bytes: *const u8, n_bytes: usize, syn: *mut u32) -> c_int;
     pub fn fmd_modes_decode(bytes: *const u8, n_bytes: usize, out: *mut fmd_modes_fields) -> c_int;
     pub fn fmd_modes_cpr_global(lat_even: u32, lon_even: u32, lat_odd: u32, lon_odd: u32, latest_odd: c_int, lat: *mut f64, lon: *mut f64) -> c_int;
+    pub fn fmd_pulses_new(cfg: *const fmd_pulses_config, dev: *const DeviceConfig, out: *mut *mut fmd_pulses) -> c_int;
+    pub fn fmd_pulses_free(h: *mut fmd_pulses);
+    pub fn fmd_pulses_reset(h: *mut fmd_pulses) -> c_int;
+    pub fn fmd_pulses_run_batch(h: *mut fmd_pulses, iq: *const u8, nbytes: usize, cap_bytes: usize) -> c_int;
+    pub fn fmd_pulses_run_device(h: *mut fmd_pulses, d_iq: *const c_void, nbytes: usize, cap_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn fmd_pulses_check(h: *mut fmd_pulses) -> c_int;
+    pub fn fmd_pulses_counts(h: *mut fmd_pulses, counts: *mut u32) -> c_int;
+    pub fn fmd_pulses_recs(h: *mut fmd_pulses, streams: *const u32, n_sel: usize, recs: *mut fmd_pulses_rec) -> c_int;
+    pub fn fmd_pulses_info(h: *mut fmd_pulses, info: *mut fmd_pulses_totals) -> c_int;
+    pub fn fmd_pulses_kernel_name(h: *const fmd_pulses, pass: u32, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_pulses_tile() -> u32;
+    pub fn fmd_pulse_slicer_new(cfg: *const fmd_pulse_slicer_config, out: *mut *mut fmd_pulse_slicer) -> c_int;
+    pub fn fmd_pulse_slicer_free(p: *mut fmd_pulse_slicer);
+    pub fn fmd_pulse_slicer_push(p: *mut fmd_pulse_slicer, recs: *const fmd_pulses_rec, n: usize, pos: u64) -> c_int;
+    pub fn fmd_pulse_slicer_idle(p: *mut fmd_pulse_slicer, state: u32, run: u64) -> c_int;
+    pub fn fmd_pulse_slicer_take(p: *mut fmd_pulse_slicer, packages: *mut fmd_pulse_package, cap: usize, n: *mut usize) -> c_int;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;
