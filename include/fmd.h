@@ -1469,7 +1469,8 @@ int fmd_modes_cpr_global(uint32_t lat_even, uint32_t lon_even, uint32_t lat_odd,
  * 1 <= pulse_cap <= 1024, n_streams = dev->n_channels >= 1.  Calls: as fmd_modes_run_*: nbytes % 8 != 0 is FMD_ERR_BAD_LENGTH,
  * nbytes > cap_bytes FMD_ERR_CAPACITY, cap_bytes % 4 != 0 or a d_iq that is not 4-byte aligned FMD_ERR_INVALID_ARG.  Stream lifetime
  * and completion points: as fmd_channelizer_* (fmd_pulses_check).  Out of scope: adaptive thresholds on the device, FSK pulse
- * detection, a peak or mean over the whole pulse, glitch merging below a minimum width, slicing on the device. */
+ * detection, a peak or mean over the whole pulse, glitch merging below a minimum width.  (Slicing on the device: the package bank,
+ * fmd_packages_*, below.) */
 typedef struct fmd_pulses fmd_pulses;
 typedef struct fmd_pulses_config {
     uint32_t W;           /* 1 .. 64 */
@@ -1541,6 +1542,69 @@ int fmd_pulse_slicer_push(fmd_pulse_slicer *p, const fmd_pulses_rec *recs, size_
 int fmd_pulse_slicer_idle(fmd_pulse_slicer *p, uint32_t state, uint64_t run);
 /* Moves the oldest min(waiting, cap) closed packages into packages[cap]; *n is how many. */
 int fmd_pulse_slicer_take(fmd_pulse_slicer *p, fmd_pulse_package *packages, size_t cap, size_t *n);
+
+/* ---- Package bank: the pulse records of every stream sliced into PWM / PPM bit packages on the device -------------------- */
+/* NEW SURFACE: the host slicer above, one per stream of a pulse bank, on the device.  Definition (tests/packages_ref.py): for any
+ * number of streams and any cutting into calls, stream s behaves as an fmd_pulse_slicer(modulation, short_w, long_w, tol, reset) of
+ * its own that, per call, is pushed the first min(count_s, rec_cap) records with pos_s = samples_s - n_samples (u64; samples_s the
+ * stream's fmd_pulses_totals.samples after the call), is then given idle(state_s, run_s), and has room for every package: the host
+ * ring of 64 has no counterpart.  A call leaves per stream
+ *   count  the delivered packages that closed in this call, all of them: the closes by a record with gap >= reset in record order,
+ *          the close by idle last;
+ *   pkgs   the first min(count, pkg_cap) of them as fmd_pulse_package: bits zero behind (n_bits + 7) / 8 bytes, rsv 0, start as
+ *          the host slicer computes it (fall = pos + (int64) k_rel; start = fall >= width ? fall - width : 0);
+ *   info   fmd_packages_totals, cumulative since creation or reset.
+ * min_bits (0 ... 256) is the one addition over the host slicer: a closed package with n_bits < min_bits counts in `packages` and
+ * `skipped`, takes no slot and is not in `count` (noise gives many one-pulse packages); min_bits = 0 is the host slicer exactly.
+ * A call of R records read closes at most R + 1 packages (the carried one at record 0, each record's own at the next record, the
+ * last by idle), so pkg_cap = rec_cap + 1 holds every package of a call: fmd_packages_max.  n_pulses saturates at 2^32 - 1.
+ * Domain (else FMD_ERR_UNSUPPORTED with a text, decided before a device is queried), in this order: the host slicer's tests with
+ * its texts; min_bits <= 256; 1 <= pkg_cap <= 1025; n_streams = dev->n_channels >= 1; per call 1 <= rec_cap <= 1024.
+ * n_samples == 0 launches nothing and leaves the last call's results.  A count above rec_cap reads rec_cap records; whatever lies
+ * behind a stream's min(count, rec_cap) records is never read.  Stream lifetime and completion points: as fmd_channelizer_*
+ * (fmd_packages_check).  Reset: every stream as new. */
+typedef struct fmd_packages fmd_packages;
+struct fmd_packages_config {                                                    /* 28 bytes */
+    fmd_pulse_slicer_config slicer;
+    uint32_t min_bits;    /* 0 .. 256 */
+    uint32_t pkg_cap;     /* 1 .. 1025 */
+};
+typedef struct fmd_packages_config fmd_packages_config;
+/* (Read by fmd_packages_info; the struct goes by another name as fmd_pulses_totals does.) */
+typedef struct fmd_packages_totals {                                            /* 40 bytes */
+    uint64_t records;     /* records taken */
+    uint64_t packages;    /* packages closed, delivered or not */
+    uint64_t skipped;     /* of them, closed with n_bits < min_bits */
+    uint64_t bad;         /* of them, closed with FMD_PULSE_BAD */
+    uint32_t open;        /* 1 if a package is open */
+    uint32_t open_pulses; /* the open package's n_pulses */
+} fmd_packages_totals;
+
+int fmd_packages_new(const fmd_packages_config *cfg, const fmd_device_config *dev, fmd_packages **out);   /* n_streams = dev->n_channels */
+void fmd_packages_free(fmd_packages *h);
+int fmd_packages_reset(fmd_packages *h);
+/* HOST arrays counts [n_streams], recs [n_streams][rec_cap] and totals [n_streams], as the pulse bank's accessors give them after a
+ * call of n_samples samples per stream.  Returns when the call has completed. */
+int fmd_packages_run_batch(fmd_packages *h, const uint32_t *counts, const fmd_pulses_rec *recs, size_t rec_cap,
+                           const fmd_pulses_totals *totals, size_t n_samples);
+/* What `bank`'s last call that launched left, where it lies on the device: counts, records, state and that call's sample count.
+ * Enqueued on `stream` without synchronising; nothing visits the host.  A bank on another device or with another n_streams is
+ * FMD_ERR_INVALID_ARG, one that has not launched since creation or reset FMD_ERR_BAD_STATE.  The bank's results must still be
+ * those of that call when the kernel runs: enqueue the bank's next call but one behind this one. */
+int fmd_packages_run_bank(fmd_packages *h, fmd_pulses *bank, void *stream);
+/* A call of no records whose idle test passes for every stream: the end of an input.  Its results are a call's results. */
+int fmd_packages_flush(fmd_packages *h, void *stream);
+int fmd_packages_check(fmd_packages *h);
+/* The last call's results, behind a synchronisation.  counts: host array [n_streams] (all 0 before the first call and after reset).
+ * pkgs: host array [n_sel][pkg_cap] for the streams listed in `streams` only, in the order listed, zero behind each one's
+ * min(count, pkg_cap); an index at or beyond n_streams is FMD_ERR_INVALID_ARG, with nothing written.  info: host array [n_streams]. */
+int fmd_packages_counts(fmd_packages *h, uint32_t *counts);
+int fmd_packages_pkgs(fmd_packages *h, const uint32_t *streams, size_t n_sel, fmd_pulse_package *pkgs);
+int fmd_packages_info(fmd_packages *h, fmd_packages_totals *info);
+/* Name of the kernel, as `rocprofv3 --kernel-trace` prints it. */
+int fmd_packages_kernel_name(const fmd_packages *h, char *name, size_t cap);
+/* The packages a call of n_records records read can close at most: n_records + 1.  Host only. */
+size_t fmd_packages_max(size_t n_records);
 
 /* ---- pipelined, multi-GPU sink for read_sync buffers ------------------------------------------------------- */
 /* NEW SURFACE (the reference has no asynchronous reader).  It mirrors the hand-off the example

@@ -30,8 +30,9 @@ from .pocsag import (FskDemod, Pager, PocsagDecoder, decode_pages, decode_pages_
 from .modes import (ModeSBank, cpr_global, modes_dedupe, modes_df11, modes_encode, modes_fields, modes_frame, modes_syndrome,
                     modes_table, modes_tile)
 from .pulses import PulseBank, PulseSlicer, ook_encode, package_bits, pulse_thresholds, pulses_tile
+from .packages import PackageBank, packages_max, sliced
 from . import shard, synth
 
-__all__ = ["DEFAULT_BUF_LENGTH", "Demod", "DemodBank", "PinnedBuffer", "FirBank", "Sink", "pump", "FirDemodBank", "auto_shift", "StationBank", "phase_inc", "stations_auto_shift", "Channelizer", "as_complex", "StereoBank", "stereo_taps", "RdsBank", "RdsDecoder", "decode_stations", "rds_taps", "ReceiverBank", "receive_stations", "NarrowBank", "narrow_taps", "narrow_auto_shift", "Spectrum", "find_stations", "hann_window", "UniformChannelizer", "uniform_auto_shift", "uniform_channel_inc", "uniform_channel_offsets", "uniform_taps", "BandPlanBank", "bandplan_auto_shifts", "Resampler", "bank_rate", "fixed_rate", "resample_ratio", "resample_taps", "Agc", "leveled", "CTCSS_TONES", "ToneSquelch", "tone_squelched", "tone_table", "DCS_CODES", "CodeSquelch", "code_squelched", "dcs_codeword", "dcs_design", "dcs_word", "AfskDemod", "Ax25Decoder", "afsk_stride", "afsk_table", "ax25_text", "decode_rows", "packets", "Ax25Framer", "ax25_max_frames", "decode_rows_gpu", "framed", "FskDemod", "PocsagDecoder", "decode_pages", "fsk_design", "pages", "pocsag_alpha", "pocsag_encode", "pocsag_numeric", "pocsag_text", "Pager", "decode_pages_gpu", "paged", "pocsag_max_messages", "ModeSBank", "cpr_global", "modes_dedupe", "modes_df11", "modes_encode", "modes_fields", "modes_frame", "modes_syndrome", "modes_table", "modes_tile", "PulseBank", "PulseSlicer", "ook_encode", "package_bits", "pulse_thresholds", "pulses_tile", "DemodConfig", "DemodState", "DeviceConfig", "FmdError",
+__all__ = ["DEFAULT_BUF_LENGTH", "Demod", "DemodBank", "PinnedBuffer", "FirBank", "Sink", "pump", "FirDemodBank", "auto_shift", "StationBank", "phase_inc", "stations_auto_shift", "Channelizer", "as_complex", "StereoBank", "stereo_taps", "RdsBank", "RdsDecoder", "decode_stations", "rds_taps", "ReceiverBank", "receive_stations", "NarrowBank", "narrow_taps", "narrow_auto_shift", "Spectrum", "find_stations", "hann_window", "UniformChannelizer", "uniform_auto_shift", "uniform_channel_inc", "uniform_channel_offsets", "uniform_taps", "BandPlanBank", "bandplan_auto_shifts", "Resampler", "bank_rate", "fixed_rate", "resample_ratio", "resample_taps", "Agc", "leveled", "CTCSS_TONES", "ToneSquelch", "tone_squelched", "tone_table", "DCS_CODES", "CodeSquelch", "code_squelched", "dcs_codeword", "dcs_design", "dcs_word", "AfskDemod", "Ax25Decoder", "afsk_stride", "afsk_table", "ax25_text", "decode_rows", "packets", "Ax25Framer", "ax25_max_frames", "decode_rows_gpu", "framed", "FskDemod", "PocsagDecoder", "decode_pages", "fsk_design", "pages", "pocsag_alpha", "pocsag_encode", "pocsag_numeric", "pocsag_text", "Pager", "decode_pages_gpu", "paged", "pocsag_max_messages", "ModeSBank", "cpr_global", "modes_dedupe", "modes_df11", "modes_encode", "modes_fields", "modes_frame", "modes_syndrome", "modes_table", "modes_tile", "PulseBank", "PulseSlicer", "ook_encode", "package_bits", "pulse_thresholds", "pulses_tile", "PackageBank", "packages_max", "sliced", "DemodConfig", "DemodState", "DeviceConfig", "FmdError",
            "RadioConfig", "SynthParams", "build", "check", "lib", "device_count", "optimal_settings", "out_cap",
            "shard", "synth"]

@@ -347,6 +347,18 @@ PROTOTYPES = {
     "fmd_pulse_slicer_push": (C.c_int, [_vp, _vp, _sz, C.c_uint64]),
     "fmd_pulse_slicer_idle": (C.c_int, [_vp, C.c_uint32, C.c_uint64]),
     "fmd_pulse_slicer_take": (C.c_int, [_vp, _vp, _sz, C.POINTER(C.c_size_t)]),
+    "fmd_packages_new": (C.c_int, [_vp, C.POINTER(DeviceConfig), C.POINTER(_vp)]),
+    "fmd_packages_free": (None, [_vp]),
+    "fmd_packages_reset": (C.c_int, [_vp]),
+    "fmd_packages_run_batch": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz]),
+    "fmd_packages_run_bank": (C.c_int, [_vp, _vp, _vp]),
+    "fmd_packages_flush": (C.c_int, [_vp, _vp]),
+    "fmd_packages_check": (C.c_int, [_vp]),
+    "fmd_packages_counts": (C.c_int, [_vp, _vp]),
+    "fmd_packages_pkgs": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmd_packages_info": (C.c_int, [_vp, _vp]),
+    "fmd_packages_kernel_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "fmd_packages_max": (_sz, [_sz]),
     "fmd_sink_new": (C.c_int, [C.POINTER(DemodConfig), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "fmd_sink_free": (None, [_vp]),
     "fmd_sink_acquire": (C.c_int, [_vp, C.POINTER(_vp)]),

@@ -1546,10 +1546,63 @@ public:
         return i;
     }
     uint32_t pulse_cap() const { return cap_; }
+    uint32_t n_streams() const { return n_streams_; }
+    fmd_pulses* handle() { return h_; }                       // (for PackageBank::run_bank)
 
 private:
     uint32_t n_streams_, cap_;
     Owned<fmd_pulses, fmd_pulses_free> h_;
+};
+
+// The package bank (fmd_packages_*): the slicer below for every stream of a pulse bank, on the device.  run_bank() takes what the
+// pulse bank's last call left on the device, flush() ends the input; behind either counts() gives every stream's delivered packages
+// of the call, packages(streams) the first min(count, pkg_cap) of each listed stream in the order they closed, info() the streams'
+// cumulative counters.  Both calls are enqueued on the default stream; the accessors synchronise.
+class PackageBank {
+public:
+    explicit PackageBank(const fmd_packages_config& cfg, uint32_t n_streams = 1, int32_t device_id = -1) : n_streams_(n_streams), cap_(cfg.pkg_cap)
+    {
+        fmd_device_config dev{n_streams, device_id, 0};
+        check(fmd_packages_new(&cfg, &dev, h_.out()));
+    }
+    // matched to a pulse bank: its streams, and room for every package a call of it can close
+    PackageBank(PulseBank& bank, const fmd_pulse_slicer_config& slicer, uint32_t min_bits = 0, int32_t device_id = -1)
+        : PackageBank(fmd_packages_config{slicer, min_bits, (uint32_t)fmd_packages_max(bank.pulse_cap())}, bank.n_streams(), device_id) {}
+
+    void run(const uint32_t* counts, const fmd_pulses_rec* recs, size_t rec_cap, const fmd_pulses_totals* totals, size_t n_samples)
+    {
+        check(fmd_packages_run_batch(h_, counts, recs, rec_cap, totals, n_samples));
+    }
+    void run_bank(PulseBank& bank, void* stream = nullptr) { check(fmd_packages_run_bank(h_, bank.handle(), stream)); }
+    void flush(void* stream = nullptr) { check(fmd_packages_flush(h_, stream)); }
+    void reset() { check(fmd_packages_reset(h_)); }
+    std::vector<uint32_t> counts()
+    {
+        std::vector<uint32_t> c(n_streams_);
+        check(fmd_packages_counts(h_, c.data()));
+        return c;
+    }
+    std::vector<std::vector<fmd_pulse_package>> packages(const std::vector<uint32_t>& streams)
+    {
+        const std::vector<uint32_t> c = counts();
+        std::vector<fmd_pulse_package> buf(std::max<size_t>(1, streams.size() * cap_));
+        check(fmd_packages_pkgs(h_, streams.data(), streams.size(), buf.data()));
+        std::vector<std::vector<fmd_pulse_package>> res(streams.size());
+        for (size_t s = 0; s < streams.size(); ++s)
+            res[s].assign(buf.begin() + s * cap_, buf.begin() + s * cap_ + std::min<size_t>(c[streams[s]], cap_));
+        return res;
+    }
+    std::vector<fmd_packages_totals> info()
+    {
+        std::vector<fmd_packages_totals> i(n_streams_);
+        check(fmd_packages_info(h_, i.data()));
+        return i;
+    }
+    uint32_t pkg_cap() const { return cap_; }
+
+private:
+    uint32_t n_streams_, cap_;
+    Owned<fmd_packages, fmd_packages_free> h_;
 };
 
 // The host slicer behind it (fmd_pulse_slicer_*): one stream's records in, its closed bit packages out.

@@ -374,6 +374,7 @@ struct fmd_pulses {
     FmdRowRecords recs;                                   // fmd_pulses_rec, pulse_cap per stream
     void* d_scratch = nullptr; size_t scratch_cap = 0;    // the tiles' summaries and kept falls of a call
     fmd_pulses_config cfg{};
+    uint32_t last_n = 0;                                  // samples per stream of the last call that launched
 };
 
 namespace {
@@ -408,10 +409,22 @@ int pl_enqueue(fmd_pulses* h, const void* d_iq, size_t nbytes, size_t cap_bytes,
     hipLaunchKernelGGL(fmd_pulses_gather_kernel, dim3(r.n_rows), dim3(64), 0, stream, L);
     FMD_DDC_TRY(hipGetLastError());
     fmd_ddc_commit(r.core, stream, n);
+    h->last_n = (uint32_t)n;
     return FMD_OK;
 }
 
 }  // namespace
+
+// (fmd_rows.h: what fmd_packages_run_bank reads; every call that launches takes samples, so pos == 0 is "none since reset")
+void fmd_pulses_last(fmd_pulses* h, FmdPulsesLast* out)
+{
+    const FmdDdcCore& c = h->rows.core;
+    out->device = c.device; out->n_streams = h->rows.n_rows; out->pulse_cap = h->cfg.pulse_cap;
+    out->launched = c.pos != 0; out->n_samples = h->last_n;
+    out->d_counts = reinterpret_cast<const uint32_t*>(h->recs.counts(c.cur)); out->d_recs = h->recs.records(c.cur);
+    out->d_state = h->state.in<uint32_t>(c.cur); out->state_dwords = fmd_pl::kState;
+    out->order = &h->rows.core.order;
+}
 
 extern "C" {
 

@@ -266,3 +266,20 @@ inline int fmd_rows_feed_batch(H* h, const int16_t* in, size_t n_in, size_t in_c
     FMD_DDC_TRY(e);
     return FMD_OK;
 }
+
+// ---- the pulse bank's results where they lie (fmd_pulses.hip), for the package bank that reads them there (fmd_packages.hip) --------
+
+// What the pulse bank's last call that launched left on the device.  `order` is the bank's own: a reader on another stream waits
+// behind it.  The pointers hold until the bank's next call but one.
+struct FmdPulsesLast {
+    int device = 0;
+    uint32_t n_streams = 0, pulse_cap = 0;
+    bool launched = false;                                // since creation or reset
+    uint32_t n_samples = 0;                               // per stream, of that call
+    const uint32_t* d_counts = nullptr;                   // [n_streams]
+    const uint8_t* d_recs = nullptr;                      // [n_streams][pulse_cap] fmd_pulses_rec
+    const uint32_t* d_state = nullptr;                    // [n_streams][state_dwords]: samples (u64) at dword 0, the run (u64) at 6, s at 8
+    uint32_t state_dwords = 0;
+    FmdStreamOrder* order = nullptr;
+};
+void fmd_pulses_last(fmd_pulses* h, FmdPulsesLast* out);

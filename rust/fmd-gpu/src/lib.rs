@@ -492,6 +492,33 @@ pub struct fmd_pulse_package {
     pub rsv: u32,
 }
 
+/// The package bank: the host slicer for every stream of a pulse bank, on the device.
+#[repr(C)]
+pub struct fmd_packages {
+    _private: [u8; 0],
+}
+
+/// `fmd_packages_config` of include/fmd.h.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_packages_config {
+    pub slicer: fmd_pulse_slicer_config,
+    pub min_bits: u32,
+    pub pkg_cap: u32,
+}
+
+/// `fmd_packages_totals` of include/fmd.h: a stream's cumulative counters and its open package.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fmd_packages_totals {
+    pub records: u64,
+    pub packages: u64,
+    pub skipped: u64,
+    pub bad: u64,
+    pub open: u32,
+    pub open_pulses: u32,
+}
+
 #[repr(C)]
 pub struct fmd_sink {
     _private: [u8; 0],
@@ -783,6 +810,18 @@ extern "C" {
     pub fn fmd_pulse_slicer_push(p: *mut fmd_pulse_slicer, recs: *const fmd_pulses_rec, n: usize, pos: u64) -> c_int;
     pub fn fmd_pulse_slicer_idle(p: *mut fmd_pulse_slicer, state: u32, run: u64) -> c_int;
     pub fn fmd_pulse_slicer_take(p: *mut fmd_pulse_slicer, packages: *mut fmd_pulse_package, cap: usize, n: *mut usize) -> c_int;
+    pub fn fmd_packages_new(cfg: *const fmd_packages_config, dev: *const DeviceConfig, out: *mut *mut fmd_packages) -> c_int;
+    pub fn fmd_packages_free(h: *mut fmd_packages);
+    pub fn fmd_packages_reset(h: *mut fmd_packages) -> c_int;
+    pub fn fmd_packages_run_batch(h: *mut fmd_packages, counts: *const u32, recs: *const fmd_pulses_rec, rec_cap: usize, totals: *const fmd_pulses_totals, n_samples: usize) -> c_int;
+    pub fn fmd_packages_run_bank(h: *mut fmd_packages, bank: *mut fmd_pulses, stream: *mut c_void) -> c_int;
+    pub fn fmd_packages_flush(h: *mut fmd_packages, stream: *mut c_void) -> c_int;
+    pub fn fmd_packages_check(h: *mut fmd_packages) -> c_int;
+    pub fn fmd_packages_counts(h: *mut fmd_packages, counts: *mut u32) -> c_int;
+    pub fn fmd_packages_pkgs(h: *mut fmd_packages, streams: *const u32, n_sel: usize, pkgs: *mut fmd_pulse_package) -> c_int;
+    pub fn fmd_packages_info(h: *mut fmd_packages, info: *mut fmd_packages_totals) -> c_int;
+    pub fn fmd_packages_kernel_name(h: *const fmd_packages, name: *mut c_char, cap: usize) -> c_int;
+    pub fn fmd_packages_max(n_records: usize) -> usize;
     pub fn fmd_sink_new(config: *const DemodConfig, n_channels: u32, device_ids: *const i32, n_devices: u32, nbytes: usize, depth: u32, callback: fmd_sink_callback, user: *mut c_void, out: *mut *mut fmd_sink) -> c_int;
     pub fn fmd_sink_free(s: *mut fmd_sink);
     pub fn fmd_sink_acquire(s: *mut fmd_sink, iq: *mut *mut u8) -> c_int;

@@ -24,7 +24,7 @@ DEFAULT = ["fmd_tile_lds_even.hip", "fmd_tile_lds_wide.hip", "fmd_tile_lds_odd.h
            "fmd_generic_kernel.hip", "fmd_fir.hip", "fmd_firdemod.hip", "fmd_stations.hip", "fmd_channelizer.hip", "fmd_spectrum.hip",
            "fmd_stereo.hip", "fmd_narrow.hip", "fmd_rds.hip", "fmd_receiver.hip", "fmd_uniform.hip", "fmd_bandplan.hip",
            "fmd_resample.hip", "fmd_agc.hip", "fmd_tonesq.hip", "fmd_dcs.hip", "fmd_afsk.hip", "fmd_fsk.hip", "fmd_hdlc.hip", "fmd_pager.hip",
-           "fmd_modes.hip", "fmd_pulses.hip"]
+           "fmd_modes.hip", "fmd_pulses.hip", "fmd_packages.hip"]
 
 
 def classify(op):
