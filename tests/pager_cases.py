@@ -80,10 +80,6 @@ def table(max_errors):
     return t
 
 
-def _mag(c):
-    return -c if c < 0 else c
-
-
 class Model:
     """One lane of fmd_pg::fmd_pager_kernel: the state of csrc/fmd_pager.hip under its names."""
 
@@ -107,6 +103,26 @@ class Model:
     def info(self):
         return {"messages": self.messages, "batches": self.batches, "bad_codewords": self.bad, "orphans": self.orph,
                 "locked": int(self.locked), "searching": int(not self.locked and self.window)}
+
+    # the step's arithmetic that a kernel could get wrong on its own: tests/test_pager_domain.py derives its wrong kernels from these
+    @staticmethod
+    def _mag(c):
+        return -c if c < 0 else c
+
+    def _n(self, n0, i):
+        return n0 + i
+
+    def _sum(self):
+        return self.rem + self.rd
+
+    def _inside(self, n):
+        return n <= self.kp + self.r
+
+    def _near(self, n):
+        return abs(n - self.kp) <= self.half
+
+    def _pol(self, hinv):
+        return hinv == self.inv
 
     def _close(self, out):
         if self.open:
@@ -146,7 +162,7 @@ class Model:
                     busy = False
                 else:
                     i, at = nx, True
-                    n = n0 + i
+                    n = self._n(n0, i)
                     while hk <= i:
                         if hk == i:
                             _, d, hcorr, hthr = hits[hi]
@@ -154,9 +170,9 @@ class Model:
                             if not self.locked:
                                 if not self.window:
                                     self.window, self.xinv, self.kp, self.xk, self.xthr, self.xcorr = True, hinv, n, n, hthr, hcorr
-                                elif n <= self.kp + self.r and _mag(hcorr) > _mag(self.xcorr):
+                                elif self._inside(n) and self._mag(hcorr) > self._mag(self.xcorr):
                                     self.xinv, self.xk, self.xthr, self.xcorr = hinv, n, hthr, hcorr
-                            elif abs(n - self.kp) <= self.half and hinv == self.inv and (not self.best or _mag(hcorr) > _mag(self.xcorr)):
+                            elif self._near(n) and self._pol(hinv) and (not self.best or self._mag(hcorr) > self._mag(self.xcorr)):
                                 self.best, self.xk, self.xthr, self.xcorr = True, n, hthr, hcorr
                         hi += 1
                         hk = hits[hi][0] if hi < cnt else NONE
@@ -164,7 +180,7 @@ class Model:
                         self.window, self.locked, self.inv = False, True, self.xinv
                         self._anchor(self.xk, self.xthr)
             if busy and at:
-                n = n0 + i
+                n = self._n(n0, i)
                 leave = False
                 if not self.locked:
                     leave = True
@@ -205,7 +221,7 @@ class Model:
                                 self.c_end = p
                             self.word = 0
                         self.nbm1 = nb
-                        t = self.rem + self.rd
+                        t = self._sum()
                         carry = t >= self.two_step
                         self.rem = t - self.two_step if carry else t
                         self.pnext += self.qd + int(carry)
